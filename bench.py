@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- ADMM iterations/sec of the MI355X loop, one JSON line on stdout.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload benchmark4|s10k|s100k|s6d]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload benchmark4|s10k|s100k|s6d] [--dump-outputs DIR]
 
 A "step" is one full ADMM iteration (vertex step, edge step, control: admm_solver_v3.py:655-733) on the resident state; K steps are
 enqueued back to back (no host round trip) between two synchronisation points.  The state is already in HBM when the timed region
@@ -23,6 +23,10 @@ path, the fan-out that replaces SolveInParallel at admm_solver_v3.py:490: BASELI
 row strips, the loop entirely behind the C ABI (gcsadmm_run_partitioned: RCCL halo exchange + 6-double all-reduce on one stream),
 `scaling: "strong"`, with the same lattice on one GPU measured beside it.  benchmark4 (42 vertices) does not shard; N independent
 replicas of it are a side field (`replicas_benchmark4`).
+
+--dump-outputs DIR: after the timed steps, what the timed loop computed in its last step (the state a caller of the loop receives,
+the control scalars and the K timed trace rows) as DIR/<name>.npy, at most 64 MB in all; the inputs are fixed (fixture, seeded
+lattices), so two builds run with the same arguments can be compared array for array.
 """
 import argparse
 import json
@@ -93,6 +97,45 @@ def time_window(dev, first, warmup, steps, enqueue=None, barrier=None):
     enqueue(steps)
     torch.cuda.synchronize()
     return time.perf_counter() - t0
+
+
+DUMP_CAP_BYTES = 64 << 20      # --dump-outputs: at most 64 MB in all
+
+
+def loop_outputs(dev, first, warmup, steps):
+    """What the timed loop hands its caller after its last step, as host arrays: the vertex solution (x_v, z_v, y_v), the edge
+    variables, the copies and the duals (pending mu scale applied) in incidence order -- the numbering that does not depend on the
+    state layout --, the control scalars after the last step and the trace rows of the K timed iterations (row it - 1 = iteration it)."""
+    import numpy as np
+    cb = dev.read_control()
+    host = lambda t: t.cpu().numpy()
+    E, col = dev.g.num_edges, dev.col_of
+    rows = slice(first + warmup, first + warmup + steps)
+    mu = host(dev.mu)[:, col]
+    return {"x_v": host(dev.xv), "z_v": host(dev.zv), "y_v": host(dev.yv), "z_edge": host(dev.zedge)[:, :E],
+            "copy": host(dev.copy)[:, col], "mu": mu * mu.dtype.type(cb.mu_scale),
+            "control": np.array([cb.it, cb.status, cb.rho, cb.mu_scale, cb.pri, cb.dual, cb.eps_pri, cb.eps_dual, cb.inner_failures],
+                                dtype=np.float64),
+            "trace": host(dev.trace[rows])}
+
+
+def dump_outputs(arrays, dirname, cap=DUMP_CAP_BYTES):
+    """DIR/<name>.npy for every array (float32 / float64 as computed).  Over `cap` bytes in all, every array of more than 1 MB keeps
+    the same share of its longest axis: a sorted sample drawn with a seed fixed by that axis' length, so that arrays sharing an axis
+    (copy and mu) keep the same columns and the same arguments give the same sample on every run."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    big = lambda a: a.nbytes > (1 << 20)
+    small = sum(a.nbytes for a in arrays.values() if not big(a)) + 4096 * len(arrays)      # (room for the .npy headers)
+    large = sum(a.nbytes for a in arrays.values() if big(a))
+    share = min(1.0, (cap - small) / large) if large else 1.0
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        if share < 1.0 and big(a):
+            ax = int(np.argmax(a.shape))
+            idx = np.sort(np.random.default_rng(a.shape[ax]).choice(a.shape[ax], max(int(a.shape[ax] * share), 1), replace=False))
+            a = np.take(a, idx, axis=ax)
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a))
 
 
 def kernel_shares(dev, first, warmup, steps):
@@ -389,9 +432,10 @@ def dry_launch(args):
     return 0
 
 
-def sharded_leg(args, rank, world, local, steps, warmup, out, with_single):
+def sharded_leg(args, rank, world, local, steps, warmup, out, with_single, dump=None):
     """BASELINE config 4: ONE 316 x 317 lattice in `world` row strips, the loop behind the C ABI (gcsadmm_run_partitioned).  Collective:
-    every rank calls it.  Returns (block, rank-0 extras) -- block is {} on ranks > 0."""
+    every rank calls it.  Returns (block, rank-0 extras) -- block is {} on ranks > 0.  `dump`: directory the timed loop's outputs
+    of this rank's strip are written to (dump_outputs, names suffixed with the rank, an equal share of the cap per rank)."""
     import numpy as np
     import torch
     import torch.distributed as dist
@@ -444,6 +488,9 @@ def sharded_leg(args, rank, world, local, steps, warmup, out, with_single):
         pel = time_window(pdev, pfirst, warmup, steps, enqueue=pdev.enqueue_partitioned, barrier=(dist.barrier if world > 1 else None))
         pcb = pdev.read_control()
         assert pcb.it == pfirst + warmup + steps + 1, (pcb.it, pcb.status)
+        if dump:
+            arrays = loop_outputs(pdev, pfirst, warmup, steps)
+            dump_outputs({f"{k}_rank{rank}": v for k, v in arrays.items()}, dump, cap=DUMP_CAP_BYTES // world)
         halo = float(sum(len(v) for v in part.send_idx.values()))
         # per-stage device time of THIS rank over a replay of the window (events serialise nothing here: one stream)
         pdev.reset(max_it=pfirst + warmup + steps + 1, eps_abs=0.0, eps_rel=0.0)
@@ -543,9 +590,13 @@ def main(argv=None):
                     help="only the timed loop and the per-kernel timing (no convergence runs, no CPU baseline): the "
                          "command to put under rocprofv3, so that its per-kernel averages cover the same launches as roofline.avg_launch_ms")
     ap.add_argument("--dry-launch", action="store_true", help="start the ranks and report what each one sees (RANK / WORLD_SIZE), no GPU work")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the timed loop computed in its last step as "
+                                                          "DIR/<name>.npy (at N > 1 every rank its own strip, <name>_rank<r>.npy)")
     args = ap.parse_args(argv)
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return launch_ranks(args, argv)
     if args.dry_launch:
@@ -576,6 +627,8 @@ def main(argv=None):
     cb = dev.read_control()
     assert cb.it == first + args.warmup + args.steps + 1, (cb.it, cb.status)
     its = args.steps / el
+    if args.dump_outputs:
+        dump_outputs(loop_outputs(dev, first, args.warmup, args.steps), args.dump_outputs)
 
     out = {"metric": "admm_iterations_per_sec", "value": its, "unit": "iterations/s", "n_gpus": 1,
            "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * el / args.steps,
@@ -681,7 +734,7 @@ def main_sharded(args, rank, world, local):
     out = {"metric": "admm_iterations_per_sec", "value": 0.0, "unit": "iterations/s", "n_gpus": world,
            "steps": args.steps, "warmup": args.warmup, "ms_per_step": 0.0, "higher_is_better": True, "scaling": "strong",
            "vs_baseline": None, "dtype": "f64 (interior point) on f32 state", "data": "synthetic"}
-    block = sharded_leg(args, rank, world, local, args.steps, args.warmup, out, with_single=True)
+    block = sharded_leg(args, rank, world, local, args.steps, args.warmup, out, with_single=True, dump=args.dump_outputs)
     rc = 0
     if rank == 0:
         if "error" in block:

@@ -120,3 +120,55 @@ def test_live_bench_line_holds_the_contract():
     assert d["cpu_baseline"]["window"] == {k: d["config"]["window"][k] for k in ("first_iteration", "last_iteration")}
     assert d["convergence"]["iterations_to_stop"] == 465 and d["convergence"]["inner_failures"] == 0
     assert d["partitioned_s100k"]["rccl_ranks"] == 1
+
+
+def test_dump_outputs_keeps_dtypes_and_samples_under_the_cap(tmp_path):
+    """--dump-outputs writes float32 / float64 as computed; over the cap every large array keeps the same seeded sample of its
+    longest axis (copy and mu the same columns), the same on every run, and the files stay under the cap"""
+    import numpy as np
+    import bench
+    rng = np.random.default_rng(1)
+    copy = rng.standard_normal((5, 400000)).astype(np.float32)
+    arrays = {"copy": copy, "mu": 2 * copy, "x_v": rng.standard_normal((100000, 4)), "control": np.arange(9.0)}
+    cap = 8 << 20
+    for d in ("a", "b"):
+        bench.dump_outputs(arrays, str(tmp_path / d), cap=cap)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["control.npy", "copy.npy", "mu.npy", "x_v.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= cap
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in files}
+    assert got["copy"].dtype == np.float32 and got["x_v"].dtype == np.float64
+    assert got["copy"].shape[0] == 5 and 0 < got["copy"].shape[1] < 400000 and got["x_v"].shape[1] == 4
+    assert np.array_equal(got["mu"], 2 * got["copy"]) and np.array_equal(got["control"], np.arange(9.0))
+    for f in files:
+        assert np.array_equal(got[f[:-4]], np.load(tmp_path / "b" / f))
+    bench.dump_outputs(arrays, str(tmp_path / "c"))          # under the default cap: written whole
+    assert np.array_equal(np.load(tmp_path / "c" / "copy.npy"), copy)
+
+
+@pytest.mark.gpu
+def test_dump_outputs_are_the_timed_loops_last_state(tmp_path):
+    """`--steps K --dump-outputs DIR`: K trace rows, the control block after iteration first + W + K, and the state a DeviceSolver
+    holds after the same window; a second run with the same arguments writes the same arrays"""
+    import numpy as np
+    import torch
+    import bench
+    from gcs_admm_amd.solver import DeviceSolver
+    steps, warmup = 7, 3
+    for d in ("a", "b"):
+        rc, line, err = _run_bench("--steps", str(steps), "--warmup", str(warmup), "--loop-only", "--dump-outputs", str(tmp_path / d))
+        assert rc == 0 and line["steps"] == steps, err[-3000:]
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")}
+    assert set(got) == {"x_v", "z_v", "y_v", "z_edge", "copy", "mu", "control", "trace"}
+    for k, v in got.items():
+        assert np.array_equal(v, np.load(tmp_path / "b" / f"{k}.npy")), k
+    first = bench.window_start("benchmark4", warmup, steps)
+    assert got["trace"].shape == (steps, 6) and got["control"][0] == first + warmup + steps + 1
+    g, dtype, _ = bench.make_workload("benchmark4")
+    dev = DeviceSolver(g, dtype, device=0)
+    bench.time_window(dev, first, warmup, steps)
+    torch.cuda.synchronize()
+    mine = bench.loop_outputs(dev, first, warmup, steps)
+    dev.close()
+    for k in ("x_v", "z_v", "y_v", "z_edge", "copy", "mu", "trace"):
+        assert mine[k].shape == got[k].shape and np.allclose(mine[k], got[k], rtol=1e-12, atol=1e-14), k
