@@ -11,7 +11,7 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 MAIN = os.path.join(CSRC, "gcsadmm.hip")
 WG = os.path.join(CSRC, "vertex_wg.hip")        # workgroup-cooperative vertex program (n = 2, 3, 6; own object)
-WGD = os.path.join(CSRC, "vertex_wg_dims.hip")  # the same program for n = 1, 4, 5 (own object: the builds run in parallel)
+WGD = os.path.join(CSRC, "vertex_wg_dims.hip")  # the same program for n = 1, 4, 5, 7, 8 (own object: the builds run in parallel)
 LP = os.path.join(CSRC, "polytope_lp.hip")      # batched tiny LPs for graph construction (own object, own dependencies)
 TERM = os.path.join(CSRC, "terminal_region.hip")  # x-update of terminals that are regions (own object)
 # (source, object name, extra flags)
@@ -21,11 +21,11 @@ UNITS = [(MAIN, "gcsadmm.o", []), (WG, "vertex_wg.o", []), (WG, "vertex_wg_t512.
          (LP, "polytope_lp.o", []), (TERM, "terminal_region.o", [])]
 HDR = os.path.join(ROOT, "include", "gcsadmm.h")
 _c = lambda *names: [os.path.join(CSRC, f) for f in names]
-DEPS = [MAIN, HDR] + _c("vertex_program.h", "vertex_program.inc", "vertex_kernel.h", "special_vertex.h", "vertex_wg_launch.h", "canonical_box.h", "warm_start.h", "terminal_launch.h")
+DEPS = [MAIN, HDR] + _c("vertex_program.h", "vertex_program.inc", "vertex_kernel.h", "special_vertex.h", "vertex_wg_launch.h", "canonical_box.h", "warm_start.h", "terminal_launch.h", "step_args.h", "gcs_math.h")
 UNIT_DEPS = {LP: [LP, HDR] + _c("polytope_lp_core.h"),
-             WG: [WG, HDR] + _c("vertex_wg.h", "vertex_wg_kernel.h", "vertex_wg_launch.h", "special_vertex.h", "gcs_math.h", "warm_start.h")}
+             WG: [WG, HDR] + _c("vertex_wg.h", "vertex_wg_kernel.h", "vertex_wg_launch.h", "special_vertex.h", "gcs_math.h", "warm_start.h", "step_args.h")}
 UNIT_DEPS[WGD] = [WGD] + UNIT_DEPS[WG][1:]
-UNIT_DEPS[TERM] = [TERM, HDR] + _c("terminal_region.h", "terminal_launch.h", "gcs_math.h")
+UNIT_DEPS[TERM] = [TERM, HDR] + _c("terminal_region.h", "terminal_launch.h", "gcs_math.h", "step_args.h")
 OUT = os.path.join(HERE, "libgcsadmm.so")
 
 

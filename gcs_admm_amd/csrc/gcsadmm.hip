@@ -504,21 +504,29 @@ template <class U> static hipError_t upload(U **dst, const U *src, size_t count)
 static VertexLaunchDesc make_launch_desc(gcsadmm_handle h, const gcsadmm_state *st);
 static void halo_free(gcsadmm_handle h);
 
+// the inputs every vertex-step launch shares (step_args.h)
+static StepDesc make_step(gcsadmm_handle h, const gcsadmm_state *st)
+{
+    StepDesc a;
+    a.inc_ptr = h->d_inc_ptr; a.deg_in = h->d_deg_in; a.inc_edge = h->d_inc_edge; a.poly_ptr = h->d_poly_ptr;
+    a.poly_A = h->d_poly_A; a.poly_bc = h->d_poly_bc; a.center = h->d_center;
+    a.E = h->E; a.NI = h->NI; a.edge_major = h->edge_major;
+    a.zedge = st->zedge; a.mu = st->mu; a.copy = st->copy; a.xv = st->xv; a.zv = st->zv; a.yv = st->yv;
+    a.counters = h->d_counters; a.cb = h->d_cb;
+    a.eps_edge = h->params.eps_edge; a.ipm_tol = h->params.ipm_tol; a.ipm_max_iter = h->params.ipm_max_iter;
+    a.warm = h->params.cold_start ? nullptr : h->d_warm; a.warm_ptr = h->d_warm_ptr;
+    return a;
+}
+
 // The generic vertices of a handle are split at create between the wavefront program (n = 2, degree <= 63: vertex_kernel.h)
 // and the workgroup program (everything else, and all vertices of small graphs: vertex_wg.hip); the closed-form vertices
 // ride in the trailing workgroups of whichever launch exists.
 static WgLaunchDesc make_wg_desc(gcsadmm_handle h, const gcsadmm_state *st, bool with_special)
 {
     WgLaunchDesc d;
+    d.step = make_step(h, st);
     d.n = h->n; d.dtype = h->dtype; d.n_vtx = h->n_wg; d.n_special = with_special ? h->n_special : 0; d.lds_bytes = h->wg_lds_bytes;
-    d.vtx = h->d_wg_vtx; d.special_vtx = h->d_special_vtx; d.special_kind = h->d_special_kind;
-    d.inc_ptr = h->d_inc_ptr; d.deg_in = h->d_deg_in; d.inc_edge = h->d_inc_edge; d.poly_ptr = h->d_poly_ptr;
-    d.poly_A = h->d_poly_A; d.poly_bc = h->d_poly_bc; d.center = h->d_center;
-    d.E = h->E; d.NI = h->NI; d.edge_major = h->edge_major; d.box = h->wg_box;
-    d.zedge = st->zedge; d.mu = st->mu; d.copy = st->copy; d.xv = st->xv; d.zv = st->zv; d.yv = st->yv;
-    d.counters = h->d_counters; d.cb = h->d_cb;
-    d.eps_edge = h->params.eps_edge; d.ipm_tol = h->params.ipm_tol; d.ipm_max_iter = h->params.ipm_max_iter;
-    d.warm = h->params.cold_start ? nullptr : h->d_warm; d.warm_ptr = h->d_warm_ptr;
+    d.vtx = h->d_wg_vtx; d.special_vtx = h->d_special_vtx; d.special_kind = h->d_special_kind; d.box = h->wg_box;
     d.order = h->d_wg_order; d.unit_iters = h->d_wg_iters;
     return d;
 }
@@ -528,17 +536,13 @@ static WgLaunchDesc make_wg_desc(gcsadmm_handle h, const gcsadmm_state *st, bool
 static gcsadmm_k::TermLaunchDesc make_term_desc(gcsadmm_handle h, const gcsadmm_state *st)
 {
     gcsadmm_k::TermLaunchDesc d;
-    d.n = h->n; d.dtype = h->dtype; d.count = h->n_term;
-    for (int i = 0; i < 2; ++i) { d.vtx[i] = h->term_vtx[i]; d.is_src[i] = h->term_is_src[i]; d.ws_off[i] = h->term_ws_off[i]; }
-    d.ws = h->d_term_ws; d.threads = h->term_threads; d.lds_doubles = h->term_lds_doubles;
-    d.rec = h->params.cold_start ? nullptr : h->d_term_rec;
-    for (int i = 0; i < 2; ++i) d.rec_off[i] = h->term_rec_off[i];
-    d.inc_ptr = h->d_inc_ptr; d.deg_in = h->d_deg_in; d.inc_edge = h->d_inc_edge; d.poly_ptr = h->d_poly_ptr;
-    d.poly_A = h->d_poly_A; d.poly_bc = h->d_poly_bc; d.center = h->d_center;
-    d.E = h->E; d.NI = h->NI; d.edge_major = h->edge_major;
-    d.zedge = st->zedge; d.mu = st->mu; d.copy = st->copy; d.xv = st->xv; d.zv = st->zv; d.yv = st->yv;
-    d.counters = h->d_counters; d.cb = h->d_cb;
-    d.eps_edge = h->params.eps_edge; d.ipm_tol = h->params.ipm_tol; d.ipm_max_iter = h->params.ipm_max_iter;
+    d.step = make_step(h, st);
+    d.n = h->n; d.dtype = h->dtype; d.count = h->n_term; d.threads = h->term_threads; d.lds_doubles = h->term_lds_doubles;
+    for (int i = 0; i < 2; ++i) {
+        d.t.vtx[i] = h->term_vtx[i]; d.t.is_src[i] = h->term_is_src[i]; d.t.ws_off[i] = h->term_ws_off[i]; d.t.rec_off[i] = h->term_rec_off[i];
+    }
+    d.t.ws = h->d_term_ws;
+    d.t.rec = h->params.cold_start ? nullptr : h->d_term_rec;
     return d;
 }
 
@@ -636,15 +640,10 @@ static bool state_ok(gcsadmm_handle h, const gcsadmm_state *st)
 static VertexLaunchDesc make_launch_desc(gcsadmm_handle h, const gcsadmm_state *st)
 {
     VertexLaunchDesc d;
-    d.n_waves = h->n_waves; d.n_special = h->n_special; d.all_m4 = h->all_m4; d.lds_bytes = h->lds_bytes; d.align_rows = h->align_rows; d.store_dl = h->store_dl;
+    d.step = make_step(h, st);
+    d.n_waves = h->n_waves; d.n_special = h->n_special; d.all_m4 = h->all_m4; d.lds_bytes = h->lds_bytes; d.align_rows = h->align_rows;
+    d.store_dl = h->store_dl; d.MM = h->MM;
     d.wave_slot_ptr = h->d_wave_slot_ptr; d.wave_vtx = h->d_wave_vtx; d.special_vtx = h->d_special_vtx; d.special_kind = h->d_special_kind;
-    d.inc_ptr = h->d_inc_ptr; d.deg_in = h->d_deg_in; d.inc_edge = h->d_inc_edge; d.poly_ptr = h->d_poly_ptr;
-    d.poly_A = h->d_poly_A; d.poly_bc = h->d_poly_bc; d.center = h->d_center;
-    d.E = h->E; d.NI = h->NI; d.MM = h->MM; d.edge_major = h->edge_major;
-    d.zedge = st->zedge; d.mu = st->mu; d.copy = st->copy; d.xv = st->xv; d.zv = st->zv; d.yv = st->yv;
-    d.counters = h->d_counters; d.cb = h->d_cb;
-    d.eps_edge = h->params.eps_edge; d.ipm_tol = h->params.ipm_tol; d.ipm_max_iter = h->params.ipm_max_iter;
-    d.warm = h->params.cold_start ? nullptr : h->d_warm; d.warm_ptr = h->d_warm_ptr;
     d.wave_order = h->d_wave_order; d.wave_iters = h->d_wave_iters;
     return d;
 }
@@ -1010,11 +1009,11 @@ gcsadmm_status gcsadmm_create(const gcsadmm_graph_desc *g, gcsadmm_handle *out)
     h->col_owned.assign((size_t)std::max<int64_t>(g->num_incidences, 1), 0);
     for (int v = 0; v < V; ++v)
         for (int k = g->inc_ptr[v]; k < g->inc_ptr[v + 1]; ++k)
-            h->col_owned[h->edge_major ? g->inc_edge[k] + (g->inc_out[k] ? 0 : E) : k] = 1;
+            h->col_owned[state_column(h->edge_major, E, 0, k, g->inc_edge[k], g->inc_out[k])] = 1;
     h->col_vertex.assign((size_t)std::max<int64_t>(g->num_incidences, 1), -1);
     for (int v = 0; v < V; ++v)
         for (int k = g->inc_ptr[v]; k < g->inc_ptr[v + 1]; ++k)
-            h->col_vertex[h->edge_major ? g->inc_edge[k] + (g->inc_out[k] ? 0 : E) : k] = v;
+            h->col_vertex[state_column(h->edge_major, E, 0, k, g->inc_edge[k], g->inc_out[k])] = v;
     h->h_wave_slot_ptr = wave_slot_ptr; h->h_wave_vtx = wave_vtx;
     h->dtype = g->state_dtype; h->device = g->device;
     h->n_waves = n_waves; h->n_special = (int)special_vtx.size();
@@ -1422,9 +1421,10 @@ gcsadmm_status gcsadmm_vertex_prox(gcsadmm_handle h, const double *q_dev, const 
     HIPCHK(h, hipMemsetAsync(h->d_prox_counters, 0, 2 * sizeof(int), s));
     WgLaunchDesc d{};
     d.n = h->n; d.dtype = GCSADMM_F64; d.n_vtx = h->n_prox; d.lds_bytes = h->prox_lds_bytes; d.vtx = h->d_prox_vtx;
-    d.inc_ptr = h->d_inc_ptr; d.deg_in = h->d_deg_in; d.inc_edge = h->d_inc_edge; d.poly_ptr = h->d_poly_ptr;
-    d.poly_A = h->d_poly_A; d.poly_bc = h->d_poly_bc; d.center = h->d_center;
-    d.xv = xv_dev; d.zv = zv_dev; d.yv = yv_dev; d.counters = h->d_prox_counters; d.ipm_tol = ipm_tol; d.ipm_max_iter = ipm_max_iter;
+    StepDesc &p = d.step;     // the ADMM state, the edge tolerance and the warm start stay unset: the PROX solve reads none of them
+    p.inc_ptr = h->d_inc_ptr; p.deg_in = h->d_deg_in; p.inc_edge = h->d_inc_edge; p.poly_ptr = h->d_poly_ptr;
+    p.poly_A = h->d_poly_A; p.poly_bc = h->d_poly_bc; p.center = h->d_center;
+    p.xv = xv_dev; p.zv = zv_dev; p.yv = yv_dev; p.counters = h->d_prox_counters; p.ipm_tol = ipm_tol; p.ipm_max_iter = ipm_max_iter;
     gcsadmm_wg_launch_prox(d, q_dev, c_dev, h->src, h->dst, s);
     HIPCHK(h, hipGetLastError());
     if (failures_host) {      // optional: synchronises the stream

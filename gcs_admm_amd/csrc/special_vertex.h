@@ -3,6 +3,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "step_args.h"
+
 namespace gcsadmm_k {
 
 constexpr int MAX_SPECIAL_DEG = 256;
@@ -12,32 +14,24 @@ constexpr int MAX_SPECIAL_DEG = 256;
 // collapses to a separable quadratic over the simplex of the live side; a vertex with no incoming or
 // no outgoing edge carries no flow.  One thread per vertex.
 // -------------------------------------------------------------------------------------------------
-template <class T> struct SpecialArgs {
+struct SpecialArgs {
     int count;
     const int *vtx;     // vertex ids
     const int *kind;    // 1 = source, 2 = target, 0 = no-flow
-    const int *inc_ptr, *deg_in, *inc_edge;
-    const double *center;
-    int E, NI;
-    const T *zedge, *mu;
-    T *copy;
-    double *xv, *zv, *yv;
-    double eps_edge;
-    int edge_major = 0;     // 1: state columns numbered by edge (tail side e, head side E + e) instead of by incidence
 };
 
 // vals / u: work arrays of MAX_SPECIAL_DEG doubles each, used by the source and the target only
 template <int N, class T>
-__device__ void special_body(const SpecialArgs<T> &a, int i, double rho, double mu_scale, double *vals, double *u)
+__device__ void special_body(const StepArgs<T> &a, const SpecialArgs &sp, int i, double rho, double mu_scale, double *vals, double *u)
 {
-    const int v = a.vtx[i], kind = a.kind[i];
+    const int v = sp.vtx[i], kind = sp.kind[i];
     const int lo = a.inc_ptr[v], d = a.inc_ptr[v + 1] - lo, d_in = a.deg_in[v];
     double cen[N];
 #pragma unroll
     for (int k = 0; k < N; ++k) cen[k] = a.center[(size_t)v * N + k];
     auto target = [&](int w, int k) -> double {
-        const int e = a.inc_edge[lo + k], inc = a.edge_major ? e + (k >= d_in ? 0 : a.E) : lo + k;
-        return (double)a.zedge[(size_t)w * a.E + e] - mu_scale * (double)a.mu[(size_t)w * a.NI + inc];
+        const int e = a.inc_edge[lo + k], inc = state_column(a, lo, k, e, k >= d_in);
+        return consensus_target(a, w, e, inc, mu_scale);
     };
     const bool is_src = kind == 1, is_dst = kind == 2;
     const int live_lo = is_src ? d_in : 0, live_hi = is_src ? d : (is_dst ? d_in : 0);
@@ -73,7 +67,7 @@ __device__ void special_body(const SpecialArgs<T> &a, int i, double rho, double 
         double ye = 0.0;
         if (live) { ye = vals[e - live_lo] - tau; ye = ye > 0 ? ye : 0.0; }
         const bool outgoing = e >= d_in;
-        const int inc = a.edge_major ? a.inc_edge[lo + e] + (outgoing ? 0 : a.E) : lo + e;
+        const int inc = state_column(a, lo, e, a.inc_edge + lo, outgoing);
 #pragma unroll
         for (int k = 0; k < N; ++k) {
             const double yc = (kind != 0) ? ye * cen[k] : 0.0;

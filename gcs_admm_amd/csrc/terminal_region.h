@@ -26,6 +26,7 @@
 #include <stdint.h>
 
 #include "gcs_math.h"
+#include "step_args.h"
 
 namespace gcs_term {
 
@@ -77,12 +78,12 @@ template <class T> struct TermProblem {
 template <int N, class T>
 GCS_HD int state_column(const TermProblem<T> &P, int k)
 {
-    return P.edge_major ? P.inc_edge[k] + (k >= P.d_in ? 0 : P.E) : P.inc_lo + k;
+    return gcsadmm_k::state_column(P, P.inc_lo, k, P.inc_edge, k >= P.d_in);
 }
 template <int N, class T>
 GCS_HD double target(const TermProblem<T> &P, int word, int k)
 {
-    return (double)P.zedge[(size_t)word * P.E + P.inc_edge[k]] - P.mu_scale * (double)P.mu[(size_t)word * P.NI + state_column<N, T>(P, k)];
+    return gcsadmm_k::consensus_target(P, word, P.inc_edge[k], state_column<N, T>(P, k), P.mu_scale);
 }
 
 template <int Q> GCS_HD void soc_prod(const double *a, const double *b, double *o)

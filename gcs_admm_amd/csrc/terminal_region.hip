@@ -54,44 +54,39 @@ struct TermExec {
 
 // LDSWS: the work arrays live in dynamic LDS (its own instantiation, so that the compiler addresses them as LDS rather than through flat pointers)
 template <int N, class T, bool LDSWS>
-__global__ __launch_bounds__(TERM_THREADS) void terminal_region_kernel(TermLaunchDesc d)
+__global__ __launch_bounds__(TERM_THREADS) void terminal_region_kernel(StepArgs<T> a, TermBlock t, const gcsadmm_control_block *cb)
 {
     extern __shared__ __attribute__((aligned(16))) double term_lds[];
-    if (d.cb->status != GCSADMM_RUNNING) return;
+    if (cb->status != GCSADMM_RUNNING) return;
     __shared__ gcs_term::TermShared<N> sh;
     __shared__ double red[12];
-    const int ti = (int)blockIdx.x, v = d.vtx[ti];
+    const int ti = (int)blockIdx.x, v = t.vtx[ti];
     gcs_term::TermProblem<T> P;
-    const int p0 = d.poly_ptr[v], lo = d.inc_ptr[v];
-    P.m = d.poly_ptr[v + 1] - p0; P.d = d.inc_ptr[v + 1] - lo; P.d_in = d.deg_in[v]; P.is_src = d.is_src[ti];
-    P.A = d.poly_A + (size_t)p0 * N; P.bc = d.poly_bc + p0; P.cen = d.center + (size_t)v * N;
-    P.inc_edge = d.inc_edge + lo; P.inc_lo = lo;
-    P.E = d.E; P.NI = d.NI; P.edge_major = d.edge_major;
-    P.zedge = (const T *)d.zedge; P.mu = (const T *)d.mu; P.copy = (T *)d.copy;
-    P.xv = d.xv + (size_t)v * 2 * N; P.zv = d.zv + (size_t)v * 2 * N; P.yv = d.yv + v;
-    P.rho = d.cb->rho; P.mu_scale = d.cb->mu_scale; P.eps_edge = d.eps_edge; P.ipm_tol = d.ipm_tol; P.ipm_max_iter = d.ipm_max_iter;
-    P.warm = d.rec ? d.rec + d.rec_off[ti] : nullptr;
+    const int p0 = a.poly_ptr[v], lo = a.inc_ptr[v];
+    P.m = a.poly_ptr[v + 1] - p0; P.d = a.inc_ptr[v + 1] - lo; P.d_in = a.deg_in[v]; P.is_src = t.is_src[ti];
+    P.A = a.poly_A + (size_t)p0 * N; P.bc = a.poly_bc + p0; P.cen = a.center + (size_t)v * N;
+    P.inc_edge = a.inc_edge + lo; P.inc_lo = lo;
+    P.E = a.E; P.NI = a.NI; P.edge_major = a.edge_major;
+    P.zedge = a.zedge; P.mu = a.mu; P.copy = a.copy;
+    P.xv = a.xv + (size_t)v * 2 * N; P.zv = a.zv + (size_t)v * 2 * N; P.yv = a.yv + v;
+    P.rho = cb->rho; P.mu_scale = cb->mu_scale; P.eps_edge = a.eps_edge; P.ipm_tol = a.ipm_tol; P.ipm_max_iter = a.ipm_max_iter;
+    P.warm = t.rec ? t.rec + t.rec_off[ti] : nullptr;
     TermExec ex{red};
-    // work arrays: LDS when the launch was given room for the larger of the terminals (d.lds_doubles), the HBM workspace otherwise
+    // work arrays: LDS when the launch was given room for the larger of the terminals (lds_doubles), the HBM workspace otherwise
     int r;
     if constexpr (LDSWS) r = gcs_term::terminal_region_solve<N, T>(ex, P, term_lds, sh);
-    else r = gcs_term::terminal_region_solve<N, T>(ex, P, d.ws + d.ws_off[ti], sh);
+    else r = gcs_term::terminal_region_solve<N, T>(ex, P, t.ws + t.ws_off[ti], sh);
     if (threadIdx.x == 0) {
-        if (r < 0) atomicAdd(&d.counters[0], 1);
-        else atomicAdd(&d.counters[1], r);
+        if (r < 0) atomicAdd(&a.counters[0], 1);
+        else atomicAdd(&a.counters[1], r);
     }
 }
 
-template <int N> static void launch_n(const TermLaunchDesc &d, hipStream_t s)
+template <int N, class T> static void launch_n(const TermLaunchDesc &d, hipStream_t s)
 {
     const size_t lds = (size_t)d.lds_doubles * sizeof(double);
-    if (d.dtype == GCSADMM_F64) {
-        if (lds) hipLaunchKernelGGL((terminal_region_kernel<N, double, true>), dim3(d.count), dim3(d.threads), lds, s, d);
-        else hipLaunchKernelGGL((terminal_region_kernel<N, double, false>), dim3(d.count), dim3(d.threads), 0, s, d);
-    } else {
-        if (lds) hipLaunchKernelGGL((terminal_region_kernel<N, float, true>), dim3(d.count), dim3(d.threads), lds, s, d);
-        else hipLaunchKernelGGL((terminal_region_kernel<N, float, false>), dim3(d.count), dim3(d.threads), 0, s, d);
-    }
+    if (lds) hipLaunchKernelGGL((terminal_region_kernel<N, T, true>), dim3(d.count), dim3(d.threads), lds, s, d.step.typed<T>(), d.t, d.step.cb);
+    else hipLaunchKernelGGL((terminal_region_kernel<N, T, false>), dim3(d.count), dim3(d.threads), 0, s, d.step.typed<T>(), d.t, d.step.cb);
 }
 
 }  // namespace gcsadmm_k
@@ -112,15 +107,9 @@ void gcsadmm_terminal_launch(const gcsadmm_k::TermLaunchDesc &d, hipStream_t s)
 {
     using namespace gcsadmm_k;
     if (d.count <= 0) return;
-    switch (d.n) {
-    case 1: launch_n<1>(d, s); break;
-    case 2: launch_n<2>(d, s); break;
-    case 3: launch_n<3>(d, s); break;
-    case 4: launch_n<4>(d, s); break;
-    case 5: launch_n<5>(d, s); break;
-    case 6: launch_n<6>(d, s); break;
-    case 7: launch_n<7>(d, s); break;
-    case 8: launch_n<8>(d, s); break;
-    default: break;
-    }
+    dispatch_dim<1, 2, 3, 4, 5, 6, 7, 8>(d.n, [&](auto n) {
+        constexpr int N = decltype(n)::value;
+        if (d.dtype == GCSADMM_F64) launch_n<N, double>(d, s);
+        else launch_n<N, float>(d, s);
+    });
 }

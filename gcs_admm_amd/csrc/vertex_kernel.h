@@ -14,21 +14,11 @@ namespace gcsadmm_k {
 
 using gcs::WAVE;
 
-// everything a vertex-step launch needs, as plain pointers (device) and scalars
+// everything a vertex-step launch of the wavefront program needs, as plain pointers (device) and scalars
 struct VertexLaunchDesc {
-    int n_waves, n_special, all_m4, lds_bytes, align_rows, store_dl;
+    StepDesc step;
+    int n_waves, n_special, all_m4, lds_bytes, align_rows, store_dl, MM;
     const int *wave_slot_ptr, *wave_vtx, *special_vtx, *special_kind;
-    const int *inc_ptr, *deg_in, *inc_edge, *poly_ptr;
-    const double *poly_A, *poly_bc, *center;
-    int E, NI, MM, edge_major;
-    void *zedge, *mu, *copy;
-    double *xv, *zv, *yv;
-    int *counters;
-    const gcsadmm_control_block *cb;
-    double eps_edge, ipm_tol;
-    int ipm_max_iter;
-    double *warm;                   // warm-start records of the handle (warm_start.h), warm + warm_ptr[v]; nullptr: cold solves
-    const long long *warm_ptr;
     const int *wave_order;          // slowest-first dispatch (reorder_kernel): workgroup b runs wavefront wave_order[b]; may be null
     int *wave_iters;                // [n_waves] Newton iterations of each wavefront's last launch; may be null
 };
@@ -162,7 +152,7 @@ struct ProgBox {       // every polytope an axis-aligned box in canonical facet 
 // SDL = 1: the LDS allocation has room for the final dual directions of the facet rows (lds_doubles(.., 1)); the
 // update pass applies them instead of recomputing the rows.  Chosen by the host when it does not cost occupancy.
 template <class PROG, int N, class T, int RMODE, int SDL>
-__global__ __launch_bounds__(WAVE) void vertex_kernel(typename PROG::template Args<T> a, SpecialArgs<T> sp, const gcsadmm_control_block *cb)
+__global__ __launch_bounds__(WAVE) void vertex_kernel(typename PROG::template Args<T> a, SpecialArgs sp, const gcsadmm_control_block *cb)
 {
     extern __shared__ __attribute__((aligned(16))) double smem[];
     if (cb->status != GCSADMM_RUNNING) return;
@@ -171,7 +161,7 @@ __global__ __launch_bounds__(WAVE) void vertex_kernel(typename PROG::template Ar
         const int i = ((int)blockIdx.x - a.n_waves) * WAVE + (int)threadIdx.x;
         if (i < sp.count) {
             double *vals = smem + (sp.kind[i] == 2 ? 2 * MAX_SPECIAL_DEG : 0);   // source and target: own work arrays in LDS
-            special_body<N, T>(sp, i, rho, mu_scale, vals, vals + MAX_SPECIAL_DEG);
+            special_body<N, T>(a, sp, i, rho, mu_scale, vals, vals + MAX_SPECIAL_DEG);
         }
         return;
     }
@@ -198,22 +188,13 @@ __global__ __launch_bounds__(WAVE) void vertex_kernel(typename PROG::template Ar
 template <class PROG, int N, class T> static void launch_vertex_prog(const VertexLaunchDesc &d, hipStream_t s)
 {
     typename PROG::template Args<T> a;
-    a.n_waves = d.n_waves; a.wave_slot_ptr = d.wave_slot_ptr; a.wave_vtx = d.wave_vtx; a.align_rows = d.align_rows;
-    a.inc_ptr = d.inc_ptr; a.deg_in = d.deg_in; a.inc_edge = d.inc_edge; a.poly_ptr = d.poly_ptr;
-    a.poly_A = d.poly_A; a.poly_bc = d.poly_bc; a.center = d.center;
-    a.E = d.E; a.NI = d.NI; a.MM = d.MM;
-    a.zedge = (const T *)d.zedge; a.mu = (const T *)d.mu; a.copy = (T *)d.copy;
-    a.xv = d.xv; a.zv = d.zv; a.yv = d.yv; a.counters = d.counters;
-    a.eps_edge = d.eps_edge; a.ipm_tol = d.ipm_tol; a.ipm_max_iter = d.ipm_max_iter; a.edge_major = d.edge_major;
-    a.warm = d.warm; a.warm_ptr = d.warm_ptr; a.wave_order = d.wave_order; a.wave_iters = d.wave_iters;
-    SpecialArgs<T> sp;
-    sp.count = d.n_special; sp.vtx = d.special_vtx; sp.kind = d.special_kind;
-    sp.inc_ptr = d.inc_ptr; sp.deg_in = d.deg_in; sp.inc_edge = d.inc_edge; sp.center = d.center;
-    sp.E = d.E; sp.NI = d.NI; sp.zedge = (const T *)d.zedge; sp.mu = (const T *)d.mu; sp.copy = (T *)d.copy;
-    sp.xv = d.xv; sp.zv = d.zv; sp.yv = d.yv; sp.eps_edge = d.eps_edge; sp.edge_major = d.edge_major;
+    static_cast<StepArgs<T> &>(a) = d.step.typed<T>();
+    a.n_waves = d.n_waves; a.align_rows = d.align_rows; a.wave_slot_ptr = d.wave_slot_ptr; a.wave_vtx = d.wave_vtx; a.MM = d.MM;
+    a.wave_order = d.wave_order; a.wave_iters = d.wave_iters;
+    const SpecialArgs sp{d.n_special, d.special_vtx, d.special_kind};
     const unsigned grid = (unsigned)(d.n_waves + (d.n_special + WAVE - 1) / WAVE);
     const int lds = std::max(d.lds_bytes, (int)(4 * MAX_SPECIAL_DEG * sizeof(double)));   // room for the special work arrays
-#define GCS_LAUNCH(RM, DL) hipLaunchKernelGGL((vertex_kernel<PROG, N, T, RM, DL>), dim3(grid), dim3(WAVE), lds, s, a, sp, d.cb)
+#define GCS_LAUNCH(RM, DL) hipLaunchKernelGGL((vertex_kernel<PROG, N, T, RM, DL>), dim3(grid), dim3(WAVE), lds, s, a, sp, d.step.cb)
     if constexpr (N == 2) {   // dense packing + wave shifts, and the stored dual directions, exist for the tuned dimension only
         if (!d.align_rows) { if (d.store_dl) GCS_LAUNCH(1, 1); else GCS_LAUNCH(1, 0); }
         else { if (d.store_dl) GCS_LAUNCH(0, 1); else GCS_LAUNCH(0, 0); }

@@ -20,13 +20,8 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "step_args.h"
 #include "warm_start.h"
-
-#if defined(__HIPCC__)
-#define GCS_HD __host__ __device__ __forceinline__
-#else
-#define GCS_HD inline
-#endif
 
 // diagnostic builds (-DGCS_DUP=k): part k of the border factorisation is executed twice; the kernel time added
 // is the cost of that part in place (tools/variant_time.py)
@@ -1475,29 +1470,12 @@ GCS_HD int group_base(int cur, int d, int d_in, int align)
     return -1;
 }
 
-template <class T> struct VertexArgs {
+template <class T> struct VertexArgs : gcsadmm_k::StepArgs<T> {
     int n_waves;
     int align_rows;             // groups placed by group_base(.., align = 1)
     const int *wave_slot_ptr;   // [n_waves+1] into wave_vtx
     const int *wave_vtx;        // vertex ids, grouped per wave
-    const int *inc_ptr;         // [V+1]
-    const int *deg_in;          // [V]
-    const int *inc_edge;        // [NI_owned]
-    const int *poly_ptr;        // [V+1]
-    const double *poly_A;       // [sum m][n]
-    const double *poly_bc;      // [sum m] centred: b - A c
-    const double *center;       // [V][n]
-    int E, NI, MM;
-    const T *zedge, *mu;
-    T *copy;
-    double *xv, *zv, *yv;
-    int *counters;              // [0] inner failures, [1] inner iterations
-    double eps_edge, ipm_tol;
-    int ipm_max_iter;
-    int edge_major = 0;         // 1: state columns numbered by edge (tail side e, head side E + e) instead of by incidence
-    // warm start (warm_start.h): the records of the handle's workspace, warm + warm_ptr[v]; nullptr = every solve starts cold
-    double *warm = nullptr;
-    const long long *warm_ptr = nullptr;
+    int MM;
     // slowest-first dispatch (gcsadmm.hip reorder_kernel): workgroup b of the launch runs wavefront wave_order[b]; every wavefront
     // leaves the number of Newton iterations it ran in wave_iters (both may be null: identity order, nothing recorded)
     const int *wave_order = nullptr;
@@ -1511,9 +1489,9 @@ GCS_HD void lane_ids(const Lane<N> &L, int wave, const VertexArgs<T> &a, int &v,
     v = a.wave_vtx[a.wave_slot_ptr[wave] + L.slot];
     inc = 0; edge = 0;
     if (L.role == BLOCK) {
-        inc = a.inc_ptr[v] + L.glane - 1;
-        edge = a.inc_edge[inc];
-        if (a.edge_major) inc = edge + (L.out ? 0 : a.E);      // state column of this incidence (gcsadmm_graph_desc.edge_major_columns)
+        const int lo = a.inc_ptr[v];
+        edge = a.inc_edge[lo + L.glane - 1];
+        inc = gcsadmm_k::state_column(a, lo, L.glane - 1, edge, L.out);
     }
 }
 
@@ -1640,7 +1618,7 @@ GCS_HD void phase_targets(Lane<N> &L, int lane, int wave, const VertexArgs<T> &a
     double Tw[D::NW];
 #pragma unroll
     for (int w = 0; w < D::NW; ++w)
-        Tw[w] = (double)a.zedge[(size_t)w * a.E + edge] - mu_scale * (double)a.mu[(size_t)w * a.NI + inc];
+        Tw[w] = gcsadmm_k::consensus_target(a, w, edge, inc, mu_scale);
 #pragma unroll
     for (int k = 0; k < N; ++k) {
         L.T1[k] = L.out ? Tw[k] : Tw[N + k];
@@ -1846,7 +1824,7 @@ GCS_HD void run_vertex_program(EX &ex, int wave, const VertexArgs<T> &a, const W
             for (int k = 0; k < N; ++k) {
                 const double o1 = L.p[k] + L.yy * cen[k], o2 = L.p[N + k] + L.yy * cen[k];
                 // incoming block: the first coupled word is only penalised, the copy keeps its target (read again here)
-                const double tfree = L.out ? 0.0 : (double)a.zedge[(size_t)k * a.E + edge] - mu_scale * (double)a.mu[(size_t)k * a.NI + inc];
+                const double tfree = L.out ? 0.0 : gcsadmm_k::consensus_target(a, k, edge, inc, mu_scale);
                 a.copy[(size_t)k * a.NI + inc] = (T)(L.out ? o1 : tfree);
                 a.copy[(size_t)(N + k) * a.NI + inc] = (T)(L.out ? o2 : o1);
             }

@@ -23,6 +23,7 @@
 #include <type_traits>
 
 #include "gcs_math.h"
+#include "step_args.h"
 #include "warm_start.h"
 
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -239,31 +240,13 @@ inline int wg_lds_doubles_n(int n, int U, int m, bool box = false)
 
 struct alignas(8) WgF2 { float a, b; };      // two row duals of a warm-start record (warm_start.h: f32)
 
-template <class T> struct WgArgs {
+template <class T> struct WgArgs : gcsadmm_k::StepArgs<T> {
     int n_vtx;                  // generic vertices handled by this launch, one workgroup each
     const int *vtx;             // [n_vtx] vertex ids, heaviest first
-    const int *inc_ptr;         // [V+1]
-    const int *deg_in;          // [V]
-    const int *inc_edge;        // [NI_owned]
-    const int *poly_ptr;        // [V+1]
-    const double *poly_A;       // [sum m][n]
-    const double *poly_bc;      // [sum m] centred: b - A c
-    const double *center;       // [V][n]
-    int E, NI;
-    const T *zedge, *mu;
-    T *copy;
-    double *xv, *zv, *yv;
-    int *counters;              // [0] inner failures, [1] inner iterations
-    double eps_edge, ipm_tol;
-    int ipm_max_iter;
     // PROX configuration (the x-update of the reference's vertex-edge splits, admm_solver_v1.py:334-383):
     // no edge blocks; a separable quadratic 1/2 sum_k q_k (u_k - c_k)^2 on the border unknowns u = (x_v, z_v, y_v) instead of
     // the consensus penalty.  [V][4n+1] each, order x (2n), z (2n), y; nullptr = the ADMM vertex step of the v3 solver.
     const double *prox_q = nullptr, *prox_c = nullptr;
-    int edge_major = 0;         // 1: state columns numbered by edge (tail side e, head side E + e) instead of by incidence
-    // warm start (warm_start.h): the records of the handle's workspace, warm + warm_ptr[v]; nullptr = every solve starts cold
-    double *warm = nullptr;
-    const long long *warm_ptr = nullptr;
     // slowest-first dispatch (gcsadmm.hip reorder_kernel): workgroup b of the launch solves vtx[order[b]] and leaves its Newton
     // iteration count in unit_iters[order[b]] (both may be null: the static heaviest-first order of vtx, nothing recorded)
     const int *order = nullptr;
@@ -615,9 +598,9 @@ GCS_HD void wg_solve_vertex(const WgArgs<T> &a, int v, double rho, double mu_sca
     WG_FOR_AT(t, d * NW, pl0.at(d * NW)) {
         const int e = t / NW, w = t - e * NW, edge = a.inc_edge[lo + e];
         const bool out = e >= d_in;
-        const int inc = a.edge_major ? edge + (out ? 0 : a.E) : lo + e;      // state column of this incidence
+        const int inc = gcsadmm_k::state_column(a, lo, e, edge, out);
         double *un = UN(e + 1);
-        const double Tw = (double)a.zedge[(size_t)w * a.E + edge] - mu_scale * (double)a.mu[(size_t)w * a.NI + inc];
+        const double Tw = gcsadmm_k::consensus_target(a, w, edge, inc, mu_scale);
         // block targets: T1 (of O[:n]), T2 (of O[n:], outgoing only), Ty; the first word of an incoming edge is free
         int slot = -1;        // position of a PENALISED word in the unit's target array
         if (w == 2 * N) slot = 2 * N;
@@ -1719,7 +1702,7 @@ GCS_HD void wg_solve_vertex(const WgArgs<T> &a, int v, double rho, double mu_sca
     WG_FOR_AT(t, d * NW, plo.at(d * NW)) {
         const int e = t / NW, w = t - e * NW;
         const bool out = e >= d_in;
-        const int inc = a.edge_major ? a.inc_edge[lo + e] + (out ? 0 : a.E) : lo + e;
+        const int inc = gcsadmm_k::state_column(a, lo, e, a.inc_edge + lo, out);
         const double *un = UN(e + 1), *p = un + W::P;
         const double yy = p[2 * N];
         double val;

@@ -1,6 +1,6 @@
 // vertex_wg.hip -- gfx950 kernel of the workgroup-cooperative vertex program (vertex_wg.h): one 256-thread workgroup
 // per generic vertex, any degree and facet count that fits the CU's 160 KB of LDS.  Trailing workgroups of the launch take the
-// closed-form vertices (special_vertex.h).  This object instantiates the program for n = 2, 3, 6 and dispatches; n = 1, 4, 5 are in
+// closed-form vertices (special_vertex.h).  This object instantiates the program for n = 2, 3, 6 and dispatches; n = 1, 4, 5, 7, 8 are in
 // vertex_wg_dims.hip (same templates, vertex_wg_kernel.h).
 // Replaces admm_solver_v3.py:469-540 (one MOSEK solve per vertex through SolveInParallel) for the vertices routed here
 // by gcsadmm_create: small graphs, n != 2, degree > 63.
@@ -26,28 +26,20 @@ bool GCS_WG_SYM(gcsadmm_wg_has_box)(int n) { return gcs_wg::wg_has_box(n); }
 
 hipError_t GCS_WG_SYM(gcsadmm_wg_set_lds)(int n, int dtype, int lds_bytes)
 {
-    const bool f64 = dtype == GCSADMM_F64;
-    if (n == 2) return f64 ? set_lds<2, double>(lds_bytes) : set_lds<2, float>(lds_bytes);
-    if (n == 3) return f64 ? set_lds<3, double>(lds_bytes) : set_lds<3, float>(lds_bytes);
-    if (n == 6) return f64 ? set_lds<6, double>(lds_bytes) : set_lds<6, float>(lds_bytes);
+    hipError_t e = hipSuccess;
+    if (dispatch_dim<2, 3, 6>(n, [&](auto nn) { e = set_lds_n<decltype(nn)::value>(dtype, lds_bytes); })) return e;
     return GCS_WG_SYM(gcsadmm_wg_set_lds_dims)(n, dtype, lds_bytes);
 }
 
 void GCS_WG_SYM(gcsadmm_wg_launch)(const WgLaunchDesc &d, hipStream_t s)
 {
-    const bool f64 = d.dtype == GCSADMM_F64;
-    if (d.n == 2) { if (f64) launch<2, double>(d, s); else launch<2, float>(d, s); }
-    else if (d.n == 3) { if (f64) launch<3, double>(d, s); else launch<3, float>(d, s); }
-    else if (d.n == 6) { if (f64) launch<6, double>(d, s); else launch<6, float>(d, s); }
-    else GCS_WG_SYM(gcsadmm_wg_launch_dims)(d, s);
+    if (!dispatch_dim<2, 3, 6>(d.n, [&](auto nn) { launch_n<decltype(nn)::value>(d, s); })) GCS_WG_SYM(gcsadmm_wg_launch_dims)(d, s);
 }
 
 void GCS_WG_SYM(gcsadmm_wg_launch_prox)(const WgLaunchDesc &d, const double *q, const double *c, int src, int dst, hipStream_t s)
 {
-    if (d.n == 2) launch_prox<2>(d, q, c, src, dst, s);
-    else if (d.n == 3) launch_prox<3>(d, q, c, src, dst, s);
-    else if (d.n == 6) launch_prox<6>(d, q, c, src, dst, s);
-    else GCS_WG_SYM(gcsadmm_wg_launch_prox_dims)(d, q, c, src, dst, s);
+    if (!dispatch_dim<2, 3, 6>(d.n, [&](auto nn) { launch_prox<decltype(nn)::value>(d, q, c, src, dst, s); }))
+        GCS_WG_SYM(gcsadmm_wg_launch_prox_dims)(d, q, c, src, dst, s);
 }
 
 #ifdef GCS_WG_TIMING

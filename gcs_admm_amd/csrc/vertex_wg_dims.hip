@@ -12,30 +12,17 @@ using namespace gcsadmm_k;
 
 hipError_t GCS_WG_SYM(gcsadmm_wg_set_lds_dims)(int n, int dtype, int lds_bytes)
 {
-    const bool f64 = dtype == GCSADMM_F64;
-    if (n == 1) return f64 ? set_lds<1, double>(lds_bytes) : set_lds<1, float>(lds_bytes);
-    if (n == 4) return f64 ? set_lds<4, double>(lds_bytes) : set_lds<4, float>(lds_bytes);
-    if (n == 5) return f64 ? set_lds<5, double>(lds_bytes) : set_lds<5, float>(lds_bytes);
-    if (n == 7) return f64 ? set_lds<7, double>(lds_bytes) : set_lds<7, float>(lds_bytes);
-    if (n == 8) return f64 ? set_lds<8, double>(lds_bytes) : set_lds<8, float>(lds_bytes);
-    return hipErrorInvalidValue;
+    hipError_t e = hipErrorInvalidValue;
+    dispatch_dim<1, 4, 5, 7, 8>(n, [&](auto nn) { e = set_lds_n<decltype(nn)::value>(dtype, lds_bytes); });
+    return e;
 }
 
 void GCS_WG_SYM(gcsadmm_wg_launch_dims)(const WgLaunchDesc &d, hipStream_t s)
 {
-    const bool f64 = d.dtype == GCSADMM_F64;
-    if (d.n == 1) { if (f64) launch<1, double>(d, s); else launch<1, float>(d, s); }
-    else if (d.n == 4) { if (f64) launch<4, double>(d, s); else launch<4, float>(d, s); }
-    else if (d.n == 5) { if (f64) launch<5, double>(d, s); else launch<5, float>(d, s); }
-    else if (d.n == 7) { if (f64) launch<7, double>(d, s); else launch<7, float>(d, s); }
-    else if (d.n == 8) { if (f64) launch<8, double>(d, s); else launch<8, float>(d, s); }
+    dispatch_dim<1, 4, 5, 7, 8>(d.n, [&](auto nn) { launch_n<decltype(nn)::value>(d, s); });
 }
 
 void GCS_WG_SYM(gcsadmm_wg_launch_prox_dims)(const WgLaunchDesc &d, const double *q, const double *c, int src, int dst, hipStream_t s)
 {
-    if (d.n == 1) launch_prox<1>(d, q, c, src, dst, s);
-    else if (d.n == 4) launch_prox<4>(d, q, c, src, dst, s);
-    else if (d.n == 5) launch_prox<5>(d, q, c, src, dst, s);
-    else if (d.n == 7) launch_prox<7>(d, q, c, src, dst, s);
-    else if (d.n == 8) launch_prox<8>(d, q, c, src, dst, s);
+    dispatch_dim<1, 4, 5, 7, 8>(d.n, [&](auto nn) { launch_prox<decltype(nn)::value>(d, q, c, src, dst, s); });
 }

@@ -1,6 +1,6 @@
 // vertex_wg_kernel.h -- the kernel templates of the workgroup-cooperative vertex program and their launch helpers, shared by the two
 // translation units that instantiate them: vertex_wg.hip (n = 2, 3, 6: the dimensions of BASELINE.json's configs) and
-// vertex_wg_dims.hip (n = 1, 4, 5: the program is dimension-generic, as the reference's sub-problem is -- admm_solver_v3.py:363-377
+// vertex_wg_dims.hip (n = 1, 4, 5, 7, 8: the program is dimension-generic, as the reference's sub-problem is -- admm_solver_v3.py:363-377
 // takes any n; a second object keeps the builds parallel).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -39,7 +39,7 @@ __device__ unsigned long long g_wg_block_ticks[64], g_wg_block_iters[64];
 // the allocator spill 56 B, tests/test_build.py checks both.)
 template <int N, bool BOX> constexpr int wg_min_blocks() { return GCS_WG_MIN_BLOCKS == 1 ? 1 : (N <= 3 ? 4 : 2); }
 template <int N, class T, bool BOX>
-__global__ __launch_bounds__(WG_THREADS, (wg_min_blocks<N, BOX>())) void vertex_wg_kernel(gcs_wg::WgArgs<T> a, SpecialArgs<T> sp, const gcsadmm_control_block *cb)
+__global__ __launch_bounds__(WG_THREADS, (wg_min_blocks<N, BOX>())) void vertex_wg_kernel(gcs_wg::WgArgs<T> a, SpecialArgs sp, const gcsadmm_control_block *cb)
 {
     extern __shared__ __attribute__((aligned(16))) double smem[];
     if (cb->status != GCSADMM_RUNNING) return;
@@ -48,7 +48,7 @@ __global__ __launch_bounds__(WG_THREADS, (wg_min_blocks<N, BOX>())) void vertex_
         const int i = ((int)blockIdx.x - a.n_vtx) * WG_THREADS + (int)threadIdx.x;
         if (i < sp.count) {
             double *vals = smem + (sp.kind[i] == 2 ? 2 * MAX_SPECIAL_DEG : 0);   // source and target: own work arrays in LDS
-            special_body<N, T>(sp, i, rho, mu_scale, vals, vals + MAX_SPECIAL_DEG);
+            special_body<N, T>(a, sp, i, rho, mu_scale, vals, vals + MAX_SPECIAL_DEG);
         }
         return;
     }
@@ -74,28 +74,25 @@ __global__ __launch_bounds__(WG_THREADS, (wg_min_blocks<N, BOX>())) void vertex_
 template <int N, class T> void launch(const WgLaunchDesc &d, hipStream_t s)
 {
     gcs_wg::WgArgs<T> a;
-    a.n_vtx = d.n_vtx; a.vtx = d.vtx;
-    a.inc_ptr = d.inc_ptr; a.deg_in = d.deg_in; a.inc_edge = d.inc_edge; a.poly_ptr = d.poly_ptr;
-    a.poly_A = d.poly_A; a.poly_bc = d.poly_bc; a.center = d.center;
-    a.E = d.E; a.NI = d.NI;
-    a.zedge = (const T *)d.zedge; a.mu = (const T *)d.mu; a.copy = (T *)d.copy;
-    a.xv = d.xv; a.zv = d.zv; a.yv = d.yv; a.counters = d.counters;
-    a.eps_edge = d.eps_edge; a.ipm_tol = d.ipm_tol; a.ipm_max_iter = d.ipm_max_iter; a.edge_major = d.edge_major;
-    a.warm = d.warm; a.warm_ptr = d.warm_ptr; a.order = d.order; a.unit_iters = d.unit_iters;
-    SpecialArgs<T> sp;
-    sp.count = d.n_special; sp.vtx = d.special_vtx; sp.kind = d.special_kind;
-    sp.inc_ptr = d.inc_ptr; sp.deg_in = d.deg_in; sp.inc_edge = d.inc_edge; sp.center = d.center;
-    sp.E = d.E; sp.NI = d.NI; sp.zedge = (const T *)d.zedge; sp.mu = (const T *)d.mu; sp.copy = (T *)d.copy;
-    sp.xv = d.xv; sp.zv = d.zv; sp.yv = d.yv; sp.eps_edge = d.eps_edge; sp.edge_major = d.edge_major;
+    static_cast<StepArgs<T> &>(a) = d.step.typed<T>();
+    a.n_vtx = d.n_vtx; a.vtx = d.vtx; a.order = d.order; a.unit_iters = d.unit_iters;
+    const SpecialArgs sp{d.n_special, d.special_vtx, d.special_kind};
     const unsigned grid = (unsigned)(d.n_vtx + (d.n_special + WG_THREADS - 1) / WG_THREADS);
     if (grid == 0) return;
     const int lds = std::max(d.lds_bytes, (int)(4 * MAX_SPECIAL_DEG * sizeof(double)));
     // the BOX instantiation pays from n = 3 (n = 6: -9 % per Newton iteration); at n = 2 the loops it shortens are two terms long and
     // it measured 1 % slower, so n = 2 has none
     if constexpr (N == 3 || N == 6) {
-        if (d.box) { hipLaunchKernelGGL((vertex_wg_kernel<N, T, true>), dim3(grid), dim3(WG_THREADS), lds, s, a, sp, d.cb); return; }
+        if (d.box) { hipLaunchKernelGGL((vertex_wg_kernel<N, T, true>), dim3(grid), dim3(WG_THREADS), lds, s, a, sp, d.step.cb); return; }
     }
-    hipLaunchKernelGGL((vertex_wg_kernel<N, T, false>), dim3(grid), dim3(WG_THREADS), lds, s, a, sp, d.cb);
+    hipLaunchKernelGGL((vertex_wg_kernel<N, T, false>), dim3(grid), dim3(WG_THREADS), lds, s, a, sp, d.step.cb);
+}
+
+// the state type of the launch (d.dtype)
+template <int N> void launch_n(const WgLaunchDesc &d, hipStream_t s)
+{
+    if (d.dtype == GCSADMM_F64) launch<N, double>(d, s);
+    else launch<N, float>(d, s);
 }
 
 // PROX configuration (admm_solver_v1.py:334-383): one workgroup per vertex, no edge blocks; the two trailing
@@ -138,11 +135,8 @@ __global__ __launch_bounds__(WG_THREADS, 2) void vertex_prox_kernel(gcs_wg::WgAr
 template <int N> void launch_prox(const WgLaunchDesc &d, const double *q, const double *c, int src, int dst, hipStream_t s)
 {
     gcs_wg::WgArgs<double> a{};
-    a.n_vtx = d.n_vtx; a.vtx = d.vtx;
-    a.inc_ptr = d.inc_ptr; a.deg_in = d.deg_in; a.inc_edge = d.inc_edge; a.poly_ptr = d.poly_ptr;
-    a.poly_A = d.poly_A; a.poly_bc = d.poly_bc; a.center = d.center;
-    a.xv = d.xv; a.zv = d.zv; a.yv = d.yv; a.counters = d.counters;
-    a.ipm_tol = d.ipm_tol; a.ipm_max_iter = d.ipm_max_iter; a.prox_q = q; a.prox_c = c;
+    static_cast<StepArgs<double> &>(a) = d.step.typed<double>();
+    a.n_vtx = d.n_vtx; a.vtx = d.vtx; a.prox_q = q; a.prox_c = c;
     if (d.lds_bytes > 48 * 1024)
         (void)hipFuncSetAttribute((const void *)vertex_prox_kernel<N>, hipFuncAttributeMaxDynamicSharedMemorySize, d.lds_bytes);
     hipLaunchKernelGGL((vertex_prox_kernel<N>), dim3(d.n_vtx + 1), dim3(WG_THREADS), d.lds_bytes, s, a, src, dst);
@@ -154,6 +148,11 @@ template <int N, class T> hipError_t set_lds(int lds_bytes)
     if constexpr (N == 3 || N == 6)
         if (e == hipSuccess) e = hipFuncSetAttribute((const void *)vertex_wg_kernel<N, T, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
     return e;
+}
+
+template <int N> hipError_t set_lds_n(int dtype, int lds_bytes)
+{
+    return dtype == GCSADMM_F64 ? set_lds<N, double>(lds_bytes) : set_lds<N, float>(lds_bytes);
 }
 
 }  // namespace

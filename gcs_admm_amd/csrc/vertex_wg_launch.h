@@ -4,26 +4,17 @@
 #include <hip/hip_runtime.h>
 
 #include "gcsadmm.h"
+#include "step_args.h"
 
 namespace gcsadmm_k {
 
 struct WgLaunchDesc {
-    int n, dtype;                   // space dimension (2, 3, 6), GCSADMM_F64 / GCSADMM_F32
+    StepDesc step;
+    int n, dtype;                   // space dimension 1 .. 8, GCSADMM_F64 / GCSADMM_F32
     int n_vtx, n_special, lds_bytes;
     const int *vtx;                 // [n_vtx] generic vertices of this launch, one workgroup each
     const int *special_vtx, *special_kind;   // trailing workgroups (may be empty: n_special = 0)
-    const int *inc_ptr, *deg_in, *inc_edge, *poly_ptr;
-    const double *poly_A, *poly_bc, *center;
-    int E, NI, edge_major;
     int box;                        // every vertex of the launch is a canonical axis-aligned box (canonical_box.h): BOX instantiation
-    void *zedge, *mu, *copy;
-    double *xv, *zv, *yv;
-    int *counters;
-    const gcsadmm_control_block *cb;
-    double eps_edge, ipm_tol;
-    int ipm_max_iter;
-    double *warm;                   // warm-start records of the handle (warm_start.h), warm + warm_ptr[v]; nullptr: cold solves
-    const long long *warm_ptr;
     const int *order;               // slowest-first dispatch (reorder_kernel): workgroup b solves vtx[order[b]]; may be null
     int *unit_iters;                // [n_vtx] Newton iterations of each vertex's last solve; may be null
 };

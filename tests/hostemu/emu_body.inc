@@ -68,12 +68,12 @@ extern "C" int EMU_NAME(int n, int V, int E, int NI, const int *inc_ptr, const i
     if ((int)wave_vtx.size() > wave_slot_ptr.back()) wave_slot_ptr.push_back((int)wave_vtx.size());
     const int n_waves = (int)wave_slot_ptr.size() - 1;
     VertexArgs<double> a;
-    a.n_waves = n_waves; a.wave_slot_ptr = wave_slot_ptr.data(); a.wave_vtx = wave_vtx.data(); a.align_rows = align_rows;
-    a.inc_ptr = inc_ptr; a.deg_in = deg_in.data(); a.inc_edge = inc_edge; a.poly_ptr = poly_ptr;
-    a.poly_A = poly_A; a.poly_bc = bc.data(); a.center = center; a.E = E; a.NI = NI; a.MM = MM;
-    a.zedge = zedge; a.mu = mu; a.copy = copy; a.xv = xv; a.zv = zv; a.yv = yv; a.counters = counters;
-    a.eps_edge = eps_edge; a.ipm_tol = ipm_tol; a.ipm_max_iter = ipm_max_iter;
-    a.warm = g_warm; a.warm_ptr = g_warm_ptr;
+    a.n_waves = n_waves; a.wave_slot_ptr = wave_slot_ptr.data(); a.wave_vtx = wave_vtx.data(); a.align_rows = align_rows; a.MM = MM;
+    gcsadmm_k::StepArgs<double> &s = a;     // the inputs every vertex-step program shares (step_args.h)
+    s.inc_ptr = inc_ptr; s.deg_in = deg_in.data(); s.inc_edge = inc_edge; s.poly_ptr = poly_ptr;
+    s.poly_A = poly_A; s.poly_bc = bc.data(); s.center = center; s.E = E; s.NI = NI;
+    s.zedge = zedge; s.mu = mu; s.copy = copy; s.xv = xv; s.zv = zv; s.yv = yv; s.counters = counters;
+    s.eps_edge = eps_edge; s.ipm_tol = ipm_tol; s.ipm_max_iter = ipm_max_iter; s.warm = g_warm; s.warm_ptr = g_warm_ptr;
     std::vector<double> smem(lds_doubles(n, MM, MAX_SLOTS, STORE_DL));
     auto run_all = [&](auto *ex, auto ntag) {
         constexpr int NN = decltype(ntag)::value;

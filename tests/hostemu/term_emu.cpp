@@ -41,14 +41,11 @@ extern "C" int term_emu_solve(int n, int m, const double *A, const double *b_raw
                               const double *T, double rho, double eps_edge, double ipm_tol, int ipm_max_iter, double *copy, double *xv,
                               double *zv, double *yv, double *warm)
 {
-    switch (n) {
-    case 1: return run<1>(m, A, b_raw, cen, d, d_in, is_src, T, rho, eps_edge, ipm_tol, ipm_max_iter, copy, xv, zv, yv, warm);
-    case 2: return run<2>(m, A, b_raw, cen, d, d_in, is_src, T, rho, eps_edge, ipm_tol, ipm_max_iter, copy, xv, zv, yv, warm);
-    case 3: return run<3>(m, A, b_raw, cen, d, d_in, is_src, T, rho, eps_edge, ipm_tol, ipm_max_iter, copy, xv, zv, yv, warm);
-    case 6: return run<6>(m, A, b_raw, cen, d, d_in, is_src, T, rho, eps_edge, ipm_tol, ipm_max_iter, copy, xv, zv, yv, warm);
-    case 8: return run<8>(m, A, b_raw, cen, d, d_in, is_src, T, rho, eps_edge, ipm_tol, ipm_max_iter, copy, xv, zv, yv, warm);
-    default: return -100;
-    }
+    int r = -100;
+    gcsadmm_k::dispatch_dim<1, 2, 3, 6, 8>(n, [&](auto nn) {
+        r = run<decltype(nn)::value>(m, A, b_raw, cen, d, d_in, is_src, T, rho, eps_edge, ipm_tol, ipm_max_iter, copy, xv, zv, yv, warm);
+    });
+    return r;
 }
 
 // doubles of a terminal's warm-start record (zeroed by the caller: no record yet)

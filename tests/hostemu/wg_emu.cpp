@@ -77,22 +77,13 @@ extern "C" int EMU_FN(int n, int V, int E, int NI, const int *inc_ptr, const int
         }
     gcs_wg::WgArgs<double> a;
     a.n_vtx = (int)vtx.size(); a.vtx = vtx.data();
-    a.inc_ptr = inc_ptr; a.deg_in = deg_in.data(); a.inc_edge = inc_edge; a.poly_ptr = poly_ptr;
-    a.poly_A = poly_A; a.poly_bc = bc.data(); a.center = center; a.E = E; a.NI = NI;
-    a.zedge = zedge; a.mu = mu; a.copy = copy; a.xv = xv; a.zv = zv; a.yv = yv; a.counters = counters;
-    a.eps_edge = eps_edge; a.ipm_tol = ipm_tol; a.ipm_max_iter = ipm_max_iter;
-    a.warm = g_emu_warm; a.warm_ptr = g_emu_warm_ptr;
-    switch (n) {
-    case 1: run_all<1>(a, rho, mu_scale, lds, status, iters); break;
-    case 2: run_all<2>(a, rho, mu_scale, lds, status, iters); break;
-    case 3: run_all<3>(a, rho, mu_scale, lds, status, iters); break;
-    case 4: run_all<4>(a, rho, mu_scale, lds, status, iters); break;
-    case 5: run_all<5>(a, rho, mu_scale, lds, status, iters); break;
-    case 6: run_all<6>(a, rho, mu_scale, lds, status, iters); break;
-    case 7: run_all<7>(a, rho, mu_scale, lds, status, iters); break;
-    default: run_all<8>(a, rho, mu_scale, lds, status, iters);
-    }
-    return 0;
+    gcsadmm_k::StepArgs<double> &s = a;     // the inputs every vertex-step program shares (step_args.h)
+    s.inc_ptr = inc_ptr; s.deg_in = deg_in.data(); s.inc_edge = inc_edge; s.poly_ptr = poly_ptr;
+    s.poly_A = poly_A; s.poly_bc = bc.data(); s.center = center; s.E = E; s.NI = NI;
+    s.zedge = zedge; s.mu = mu; s.copy = copy; s.xv = xv; s.zv = zv; s.yv = yv; s.counters = counters;
+    s.eps_edge = eps_edge; s.ipm_tol = ipm_tol; s.ipm_max_iter = ipm_max_iter; s.warm = g_emu_warm; s.warm_ptr = g_emu_warm_ptr;
+    const bool ran = gcsadmm_k::dispatch_dim<1, 2, 3, 4, 5, 6, 7, 8>(n, [&](auto nn) { run_all<decltype(nn)::value>(a, rho, mu_scale, lds, status, iters); });
+    return ran ? 0 : 1;
 }
 
 #ifdef GCS_WG_REVERSE
@@ -123,13 +114,11 @@ extern "C" int EMU_PROX(int n, int V, const int *poly_ptr, const double *poly_A,
             bc[j] = s;
         }
     gcs_wg::WgArgs<double> a{};
-    a.n_vtx = (int)vtx.size(); a.vtx = vtx.data();
-    a.inc_ptr = zero.data(); a.deg_in = zero.data(); a.inc_edge = zero.data(); a.poly_ptr = poly_ptr;
-    a.poly_A = poly_A; a.poly_bc = bc.data(); a.center = center; a.E = 0; a.NI = 0;
-    a.zedge = nullptr; a.mu = nullptr; a.copy = nullptr; a.xv = xv; a.zv = zv; a.yv = yv; a.counters = counters;
-    a.eps_edge = 0.0; a.ipm_tol = ipm_tol; a.ipm_max_iter = ipm_max_iter; a.prox_q = q; a.prox_c = c;
-    if (n == 2) run_all<2>(a, 1.0, 1.0, lds, status, iters);
-    else if (n == 3) run_all<3>(a, 1.0, 1.0, lds, status, iters);
-    else run_all<6>(a, 1.0, 1.0, lds, status, iters);
-    return 0;
+    a.n_vtx = (int)vtx.size(); a.vtx = vtx.data(); a.prox_q = q; a.prox_c = c;
+    gcsadmm_k::StepArgs<double> &s = a;     // no edge blocks: empty incidences, no ADMM state
+    s.inc_ptr = zero.data(); s.deg_in = zero.data(); s.inc_edge = zero.data(); s.poly_ptr = poly_ptr;
+    s.poly_A = poly_A; s.poly_bc = bc.data(); s.center = center;
+    s.xv = xv; s.zv = zv; s.yv = yv; s.counters = counters; s.ipm_tol = ipm_tol; s.ipm_max_iter = ipm_max_iter;
+    const bool ran = gcsadmm_k::dispatch_dim<2, 3, 6>(n, [&](auto nn) { run_all<decltype(nn)::value>(a, 1.0, 1.0, lds, status, iters); });
+    return ran ? 0 : 1;
 }

@@ -26,7 +26,7 @@ def emu():
     src = os.path.join(HERE, "hostemu", "emu.cpp")
     out = os.path.join(HERE, "hostemu", "libemu.so")
     hdr = os.path.join(ROOT, "gcs_admm_amd", "csrc", "vertex_program.h")
-    deps = [src, hdr, os.path.join(HERE, "hostemu", "emu_body.inc")] + [os.path.join(os.path.dirname(hdr), f) for f in ("vertex_program.inc", "warm_start.h")]
+    deps = [src, hdr, os.path.join(HERE, "hostemu", "emu_body.inc")] + [os.path.join(os.path.dirname(hdr), f) for f in ("vertex_program.inc", "warm_start.h", "step_args.h", "gcs_math.h")]
     if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(d) for d in deps):
         subprocess.check_call(["g++", "-O1", "-std=c++17", "-fPIC", "-shared", "-I" + os.path.dirname(hdr), src, "-o", out])
     return C.CDLL(out)

@@ -23,7 +23,7 @@ CSRC = os.path.join(ROOT, "gcs_admm_amd", "csrc")
 @pytest.fixture(scope="module")
 def libs():
     src = os.path.join(HERE, "hostemu", "wg_emu.cpp")
-    deps = [src] + [os.path.join(CSRC, f) for f in ("vertex_wg.h", "gcs_math.h", "warm_start.h")]      # (rebuilt when the program changes)
+    deps = [src] + [os.path.join(CSRC, f) for f in ("vertex_wg.h", "gcs_math.h", "warm_start.h", "step_args.h")]      # (rebuilt when the program changes)
     out = []
     for name, flags in (("libwgemu.so", []), ("libwgemu_rev.so", ["-DGCS_WG_REVERSE"])):
         so = os.path.join(HERE, "hostemu", name)

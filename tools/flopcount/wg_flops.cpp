@@ -121,15 +121,14 @@ extern "C" int wg_count_vertex_step(int n, int V, int E, int NI, const int *inc_
     int counters[2] = {0, 0};
     gcs_wg::WgArgs<counted> a;
     a.n_vtx = (int)vtx.size(); a.vtx = vtx.data();
-    a.inc_ptr = inc_ptr; a.deg_in = deg_in.data(); a.inc_edge = inc_edge; a.poly_ptr = poly_ptr;
-    a.poly_A = A.data(); a.poly_bc = bc.data(); a.center = cen.data(); a.E = E; a.NI = NI;
-    a.zedge = ze.data(); a.mu = m_.data(); a.copy = copy.data(); a.xv = xv.data(); a.zv = zv.data(); a.yv = yv.data();
-    a.counters = counters; a.eps_edge = counted(eps_edge); a.ipm_tol = counted(ipm_tol); a.ipm_max_iter = ipm_max_iter;
+    gcsadmm_k::StepArgs<counted> &s = a;    // the inputs every vertex-step program shares (step_args.h)
+    s.inc_ptr = inc_ptr; s.deg_in = deg_in.data(); s.inc_edge = inc_edge; s.poly_ptr = poly_ptr;
+    s.poly_A = A.data(); s.poly_bc = bc.data(); s.center = cen.data(); s.E = E; s.NI = NI;
+    s.zedge = ze.data(); s.mu = m_.data(); s.copy = copy.data(); s.xv = xv.data(); s.zv = zv.data(); s.yv = yv.data();
+    s.counters = counters; s.eps_edge = counted(eps_edge); s.ipm_tol = counted(ipm_tol); s.ipm_max_iter = ipm_max_iter;
     g_flops = g_div = g_sqrt = 0;
     long long iters = 0;
-    if (n == 2) run_all<2>(a, counted(rho), counted(mu_scale), lds, &iters);
-    else if (n == 3) run_all<3>(a, counted(rho), counted(mu_scale), lds, &iters);
-    else run_all<6>(a, counted(rho), counted(mu_scale), lds, &iters);
+    if (!gcsadmm_k::dispatch_dim<2, 3, 6>(n, [&](auto nn) { run_all<decltype(nn)::value>(a, counted(rho), counted(mu_scale), lds, &iters); })) return 1;
     counts[0] = g_flops; counts[1] = g_div; counts[2] = g_sqrt; counts[3] = iters; counts[4] = (long long)vtx.size();
     return 0;
 }

@@ -15,7 +15,7 @@ LIB = os.path.join(HERE, "libwgflops.so")
 
 def build(force=False):
     src = os.path.join(HERE, "wg_flops.cpp")
-    deps = [src, os.path.join(CSRC, "vertex_wg.h"), os.path.join(CSRC, "gcs_math.h")]
+    deps = [src, os.path.join(CSRC, "vertex_wg.h"), os.path.join(CSRC, "gcs_math.h"), os.path.join(CSRC, "step_args.h")]
     if force or not os.path.exists(LIB) or os.path.getmtime(LIB) < max(os.path.getmtime(d) for d in deps):
         subprocess.check_call(["g++", "-O1", "-std=c++17", "-fPIC", "-shared", "-I" + CSRC, src, "-o", LIB])
     return LIB
