@@ -47,13 +47,12 @@ __device__ __forceinline__ void gcs_stamp(int k)
 #include "vertex_wg_launch.h"
 #include "warm_start.h"
 #include "canonical_box.h"
+#include "create_plan.h"
 
 namespace {
 
 using namespace gcs;
 using namespace gcsadmm_k;
-
-constexpr int EDGE_BLOCK = 256;
 
 // -------------------------------------------------------------------------------------------------
 // edge kernel: one thread per directed edge, all c coupled words
@@ -120,14 +119,9 @@ __global__ void control_kernel(gcsadmm_control_block *cb, const double *sums, Co
     control_body(cb, sums, p, counters, trace, global_fails);
 }
 
-// edges a thread of the edge kernel has in flight at once on LARGE graphs (registers: U x 5C words); graphs that would not fill
-// the chip with such tiles (fewer than 256 workgroups: one per CU) keep one edge per thread
+// edges a thread of the edge kernel has in flight at once on LARGE graphs (registers: U x 5C words); which graphs use it:
+// edge_unroll_rt (create_plan.h)
 template <class T, int C> __host__ __device__ constexpr int edge_unroll() { return sizeof(T) == 4 ? (C <= 7 ? 4 : 2) : (C <= 7 ? 2 : 1); }
-static int edge_unroll_rt(int dtype, int c, int E)
-{
-    const int u = dtype == GCSADMM_F32 ? (c <= 7 ? 4 : 2) : (c <= 7 ? 2 : 1);
-    return (E + EDGE_BLOCK * u - 1) / (EDGE_BLOCK * u) >= 256 ? u : 1;
-}
 
 // MODE 0: partial sums per workgroup only (gcsadmm_edge_step: the caller all-reduces / finalizes);
 // MODE 1: single workgroup (at most EDGE_BLOCK edges, gcsadmm_run on small graphs): the workgroup also does the final
@@ -249,7 +243,7 @@ __global__ __launch_bounds__(EDGE_BLOCK) void edge_kernel(EdgeArgs<T> a, gcsadmm
 // wavefront that happens to start in the second round ends the launch at 21 iteration times instead of 17.  Every few ADMM
 // iterations the units (wavefronts / workgroups) are re-ordered by the Newton iterations of their last launch, descending: a
 // counting sort by one workgroup.  The order among equal counts is arbitrary (atomics); it affects scheduling only, never results.
-constexpr int REORDER_BINS = 64, REORDER_THREADS = 1024, REORDER_EVERY = 8, REORDER_MIN_UNITS = 512;
+constexpr int REORDER_BINS = 64, REORDER_THREADS = 1024, REORDER_EVERY = 8;     // (REORDER_MIN_UNITS: create_plan.h)
 // ids (may be null): the units to order are ids[0 .. n) instead of 0 .. n (the boundary / interior subsets of a partition's overlapped loop)
 __global__ __launch_bounds__(REORDER_THREADS) void reorder_kernel(int n, const int *iters, int *order, const gcsadmm_control_block *cb, const int *ids = nullptr)
 {
@@ -815,227 +809,29 @@ gcsadmm_status gcsadmm_create(const gcsadmm_graph_desc *g, gcsadmm_handle *out)
 {
     if (out) *out = nullptr;
     auto fail = [&](gcsadmm_status st, const std::string &msg) { g_create_error = msg; return st; };
-    if (!g || !out) return fail(GCSADMM_ERR_BAD_ARG, "null descriptor or output pointer");
-    if (g->n < 1 || g->n > 8) return fail(GCSADMM_ERR_UNSUPPORTED, "the vertex kernels are instantiated for n = 1 .. 8");
-    if (g->num_vertices < 0 || g->num_edges < 0) return fail(GCSADMM_ERR_BAD_ARG, "negative size");
-    if (!g->inc_ptr || !g->poly_ptr || (g->num_edges > 0 && (!g->inc_edge || !g->inc_out || !g->edge_inc_tail || !g->edge_inc_head)) ||
-        (g->num_vertices > 0 && (!g->poly_A || !g->poly_b || !g->center)))
-        return fail(GCSADMM_ERR_BAD_ARG, "null graph array");
-    if (g->state_dtype != GCSADMM_F64 && g->state_dtype != GCSADMM_F32) return fail(GCSADMM_ERR_BAD_ARG, "bad state_dtype");
-    const int V = g->num_vertices, E = g->num_edges, n = g->n;
-    const int NIo = g->inc_ptr[V];
-    if (g->inc_ptr[0] != 0 || NIo < 0 || g->num_incidences < NIo) return fail(GCSADMM_ERR_BAD_ARG, "inconsistent incidence CSR");
+    std::string msg;
+    gcsadmm_status st;
+    if (!out) return fail(GCSADMM_ERR_BAD_ARG, "null descriptor or output pointer");
+    if ((st = check_graph_desc(g, msg)) != GCSADMM_OK) return fail(st, msg);
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(GCSADMM_ERR_NO_DEVICE, "no HIP device");
     if (g->device < 0 || g->device >= ndev) return fail(GCSADMM_ERR_BAD_ARG, "device ordinal out of range");
+    CreatePlan p;
+    if ((st = make_create_plan(*g, p, msg)) != GCSADMM_OK) return fail(st, msg);
 
-    // validate CSR, derive deg_in, facet maximum
-    std::vector<int> deg_in(V, 0);
-    int MM = 1;
-    for (int v = 0; v < V; ++v) {
-        const int lo = g->inc_ptr[v], hi = g->inc_ptr[v + 1];
-        if (hi < lo) return fail(GCSADMM_ERR_BAD_ARG, "inc_ptr not monotone");
-        bool seen_out = false;
-        for (int k = lo; k < hi; ++k) {
-            if (g->inc_edge[k] < 0 || g->inc_edge[k] >= E) return fail(GCSADMM_ERR_BAD_ARG, "inc_edge out of range");
-            if (g->inc_out[k]) seen_out = true;
-            else { if (seen_out) return fail(GCSADMM_ERR_BAD_ARG, "incoming incidences must precede outgoing ones"); deg_in[v]++; }
-        }
-        const int m = g->poly_ptr[v + 1] - g->poly_ptr[v];
-        if (m < n + 1) return fail(GCSADMM_ERR_BAD_ARG, "polytope with fewer than n+1 facets cannot be bounded");
-        MM = std::max(MM, m);
-    }
-    for (int e = 0; e < E; ++e)
-        if (g->edge_inc_tail[e] < 0 || g->edge_inc_tail[e] >= g->num_incidences || g->edge_inc_head[e] < 0 ||
-            g->edge_inc_head[e] >= g->num_incidences)
-            return fail(GCSADMM_ERR_BAD_ARG, "edge incidence slot out of range");
-    if (g->edge_major_columns != 0 && g->edge_major_columns != 1) return fail(GCSADMM_ERR_BAD_ARG, "edge_major_columns must be 0 or 1");
-    if (g->edge_major_columns) {
-        if (g->num_incidences != 2 * (int64_t)E) return fail(GCSADMM_ERR_BAD_ARG, "edge-major columns: num_incidences must be 2 num_edges");
-        for (int e = 0; e < E; ++e)
-            if (g->edge_inc_tail[e] != e || g->edge_inc_head[e] != E + e)
-                return fail(GCSADMM_ERR_BAD_ARG, "edge-major columns: edge_inc_tail[e] must be e and edge_inc_head[e] num_edges + e");
-    }
-
-    // centred right-hand sides b - A c
-    const int MT = g->poly_ptr[V];
-    std::vector<double> bc(MT > 0 ? MT : 1);
-    for (int v = 0; v < V; ++v)
-        for (int j = g->poly_ptr[v]; j < g->poly_ptr[v + 1]; ++j) {
-            double s = g->poly_b[j];
-            for (int k = 0; k < n; ++k) s -= g->poly_A[(size_t)j * n + k] * g->center[(size_t)v * n + k];
-            bc[j] = s;
-            if (v != g->src && v != g->dst && !(s > 0.0)) return fail(GCSADMM_ERR_BAD_ARG, "center is not strictly inside its polytope");
-        }
-
-    // ---- classify the vertices ----
-    // closed form: s, t (points) and vertices no flow can cross; generic: an interior-point solve each.  A generic vertex
-    // goes to the WORKGROUP program (vertex_wg.hip) when the wavefront program cannot take it (n != 2, more than 63
-    // incident edges) or when the graph is small enough that latency, not throughput, decides (or on request).
-    // s / t: the reference builds them as points (utils.py:12-28, boxes of half-width 1e-6) -> closed form (special_vertex.h).  A terminal
-    // whose polytope has an extent is a REGION: its sub-problem is the reference's with delta_sv / delta_tv (admm_solver_v3.py:450-464),
-    // solved by terminal_region.h.  Extent = the widest distance from `center` to a facet; the rule the oracle uses (terminal_extent).
-    int term_vtx[2] = {-1, -1}, term_is_src[2] = {0, 0}, n_term = 0;
-    for (int term : {g->src, g->dst}) {
-        if (term < 0 || term >= V) continue;
-        double ext = 0;
-        for (int j = g->poly_ptr[term]; j < g->poly_ptr[term + 1]; ++j) {
-            double nrm = 0;
-            for (int k = 0; k < n; ++k) nrm += g->poly_A[(size_t)j * n + k] * g->poly_A[(size_t)j * n + k];
-            ext = std::max(ext, std::fabs(bc[j]) / std::sqrt(nrm > 0 ? nrm : 1.0));
-        }
-        if (ext > 1e-5) {
-            const int d = g->inc_ptr[term + 1] - g->inc_ptr[term], din = deg_in[term];
-            if (g->src == g->dst) return fail(GCSADMM_ERR_UNSUPPORTED, "source and target are the same region");
-            if ((term == g->src ? d - din : din) < 1)
-                return fail(GCSADMM_ERR_UNSUPPORTED, "a terminal that is a region needs an edge on its live side (outgoing for the source, incoming for the target)");
-            term_vtx[n_term] = term; term_is_src[n_term] = term == g->src; ++n_term;
-        }
-    }
-    auto is_region_terminal = [&](int v) { return (n_term > 0 && v == term_vtx[0]) || (n_term > 1 && v == term_vtx[1]); };
-    auto is_special = [&](int v) {
-        if (is_region_terminal(v)) return false;
-        const int d = g->inc_ptr[v + 1] - g->inc_ptr[v], din = deg_in[v];
-        return v == g->src || v == g->dst || din == 0 || d - din == 0;
-    };
-    int n_generic = 0;
-    for (int v = 0; v < V; ++v) n_generic += !is_special(v) && !is_region_terminal(v);
-    // Crossover of the two programs on n = 2 (measured on box lattices, profiles/r02/README.md: 1 024 vertices 3 570 vs 3 030 it/s,
-    // 1 444 vertices 2 410 vs 3 060): the workgroup program holds 4 workgroups per CU (102 registers), i.e. 1 024 vertices in one
-    // round of ~0.28 ms; the wavefront program packs up to 7 vertices per wavefront and serves up to ~7 000 in one round of 0.33 ms.
-    constexpr int WG_AUTO_MAX = 1024;
-    if (g->vertex_program < 0 || g->vertex_program > 3) return fail(GCSADMM_ERR_BAD_ARG, "vertex_program must be 0, 1, 2 or 3");
-    const bool prefer_wg = g->vertex_program >= 2 || (g->vertex_program == 0 && n_generic <= WG_AUTO_MAX);
-    std::vector<int> special_vtx, special_kind, wave_slot_ptr{0}, wave_vtx, wg_vtx;
-    std::vector<char> on_wave(V, 0);
-    int wg_lds = 0, MMw = 1;
-    int wg_lds_box = 0;       // LDS per workgroup under the BOX instantiation's layout (used when every vertex turns out to be a box)
-    bool wg_all_box = g->wave_generic_rows == 0 && gcsadmm_wg_has_box(n);      // (the knob that forces the generic wavefront variants forces this one too)
-    bool all_m4 = (n == 2) && g->wave_generic_rows != 1, all_box = all_m4 && g->wave_generic_rows != 2;
-    for (int v = 0; v < V; ++v) {
-        const int d = g->inc_ptr[v + 1] - g->inc_ptr[v];
-        const int m = g->poly_ptr[v + 1] - g->poly_ptr[v];
-        if (is_region_terminal(v)) continue;      // its own kernel
-        if (is_special(v)) {
-            if (d > MAX_SPECIAL_DEG) return fail(GCSADMM_ERR_UNSUPPORTED, "terminal vertex degree above 256");
-            special_vtx.push_back(v);
-            special_kind.push_back(v == g->src ? 1 : (v == g->dst ? 2 : 0));
-        } else if (n != 2 || d + 1 > WAVE || prefer_wg) {
-            wg_vtx.push_back(v);
-            wg_lds = std::max(wg_lds, gcsadmm_wg_lds_bytes(n, d + 1, m));
-            wg_lds_box = std::max(wg_lds_box, gcsadmm_wg_lds_bytes(n, d + 1, m, true));
-            if (wg_all_box && !canonical_box(n, m, g->poly_A + (size_t)g->poly_ptr[v] * n)) wg_all_box = false;
-        } else {
-            on_wave[v] = 1;
-            MMw = std::max(MMw, m);
-            if (m != 4) all_m4 = false;
-            if (all_m4 && all_box && !canonical_box(2, m, g->poly_A + (size_t)g->poly_ptr[v] * 2)) all_box = false;   // [+e0, +e1, -e0, -e1]
-        }
-    }
-    // threads per workgroup: 512 while every workgroup of the launch has a CU to itself (vertex_wg_launch.h), 256 otherwise
-    const bool wg_t512 = !wg_vtx.empty() && g->vertex_program != 3 && wg_vtx.size() + 1 <= 256;
-    if (wg_t512) {
-        wg_lds = wg_lds_box = 0;
-        for (int v : wg_vtx) {
-            const int d = g->inc_ptr[v + 1] - g->inc_ptr[v], m = g->poly_ptr[v + 1] - g->poly_ptr[v];
-            wg_lds = std::max(wg_lds, gcsadmm_wg_lds_bytes_t512(n, d + 1, m));
-            wg_lds_box = std::max(wg_lds_box, gcsadmm_wg_lds_bytes_t512(n, d + 1, m, true));
-        }
-    }
-    if (wg_all_box && n > 2 && !wg_vtx.empty()) wg_lds = wg_lds_box;      // the BOX instantiation (n > 2) and its structured unit layout
-    if (wg_lds > 160 * 1024) return fail(GCSADMM_ERR_UNSUPPORTED, "a vertex sub-problem (degree x facets) does not fit the 160 KB of LDS of a CU");
-    // heaviest sub-problems first: the launch ends when its slowest workgroup does
-    std::stable_sort(wg_vtx.begin(), wg_vtx.end(), [&](int a, int b) {
-        const long ca = (long)(g->inc_ptr[a + 1] - g->inc_ptr[a] + 1) * (g->poly_ptr[a + 1] - g->poly_ptr[a]);
-        const long cb = (long)(g->inc_ptr[b + 1] - g->inc_ptr[b] + 1) * (g->poly_ptr[b + 1] - g->poly_ptr[b]);
-        return ca > cb;
-    });
-    MM = MMw;   // facet maximum over the wavefront program's vertices only (sizes its LDS)
-
-    // ---- wavefront program: pack its vertices into wavefronts, d+1 lanes each ----
-    // LDS per wavefront with / without room for the final dual directions (kernel template SDL): they save the
-    // update pass its facet rows (10k lattice +5 %) but must not cost a resident wavefront: kept only while four
-    // wavefronts still fit a CU's 160 KB
-    int store_dl = 0;
-    auto lds_need = [&](int slots) { return (size_t)((all_m4 && all_box) ? gcs_box::lds_doubles(n, MM, slots, store_dl) : gcs::lds_doubles(n, MM, slots, store_dl)) * 8; };
-    int slots_cap = MAX_SLOTS;
-    int n_on_wave = 0;
-    for (int v = 0; v < V; ++v) n_on_wave += on_wave[v];
-    if (n_on_wave > 0) {
-        while (slots_cap > 1 && lds_need(slots_cap) > 160 * 1024) --slots_cap;
-        if (lds_need(slots_cap) > 160 * 1024) return fail(GCSADMM_ERR_UNSUPPORTED, "facet count too large for LDS");
-        const int lds_cap = slots_cap;
-        // fewer vertices than wave slots: one vertex per wavefront (a wavefront runs as long as its slowest vertex)
-        const int want = std::max(1, (n_on_wave + 1023) / 1024);
-        slots_cap = std::min(slots_cap, want);
-        if (g->wave_slots > 0) slots_cap = std::max(1, std::min(lds_cap, (int)g->wave_slots));
-    }
-    // Group placement (vertex_program.inc group_base).  Aligned: no side segment straddles a 16-lane row, the
-    // reductions use DPP row shifts (kernel RMODE 0).  Dense: groups back to back, more vertices per wavefront,
-    // reductions by chained wave shifts (RMODE 1).  Aligned wins while the wavefronts fit the chip in
-    // two rounds (2 x 1024 one-wave-per-SIMD slots); beyond that throughput is per wavefront and dense wins
-    // (10k lattice: 1 490 vs 1 440 it/s; 100k lattice: 241 vs 264 it/s).
-    int max_slots_used = 0;
-    auto pack = [&](int align) {
-        wave_slot_ptr.assign(1, 0); wave_vtx.clear(); max_slots_used = 0;
-        int lanes = 0, slots = 0;
-        for (int v = 0; v < V; ++v) {
-            if (!on_wave[v]) continue;
-            const int d = g->inc_ptr[v + 1] - g->inc_ptr[v], din = deg_in[v];
-            int base = gcs::group_base(lanes, d, din, align);
-            if (base < 0 || slots + 1 > slots_cap) {
-                wave_slot_ptr.push_back((int)wave_vtx.size());
-                slots = 0;
-                base = gcs::group_base(0, d, din, align);
-            }
-            wave_vtx.push_back(v);
-            lanes = base + d + 1; slots += 1;
-            max_slots_used = std::max(max_slots_used, slots);
-        }
-        if ((int)wave_vtx.size() > wave_slot_ptr.back()) wave_slot_ptr.push_back((int)wave_vtx.size());
-    };
-    int align_rows = 1;
-    pack(1);
-    if (g->wave_align == 1) align_rows = 1;
-    else if (g->wave_align == 2) align_rows = 0;
-    else if ((int)wave_slot_ptr.size() - 1 > 2048) align_rows = 0;
-    if (!align_rows) pack(0);
-    const int n_waves = (int)wave_slot_ptr.size() - 1;
-
+    const int V = g->num_vertices, E = g->num_edges, n = g->n, NIo = g->inc_ptr[V], MT = g->poly_ptr[V];
     auto *h = new (std::nothrow) gcsadmm_handle_s;
     if (!h) return fail(GCSADMM_ERR_HIP, "out of host memory");
-    h->n = n; h->V = V; h->E = E; h->NI = g->num_incidences; h->NI_owned = NIo; h->c = 2 * n + 1; h->MM = MM;
+    h->n = n; h->V = V; h->E = E; h->NI = g->num_incidences; h->NI_owned = NIo; h->c = 2 * n + 1; h->MM = p.wave_mm;
     h->edge_major = g->edge_major_columns;
-    h->col_owned.assign((size_t)std::max<int64_t>(g->num_incidences, 1), 0);
-    for (int v = 0; v < V; ++v)
-        for (int k = g->inc_ptr[v]; k < g->inc_ptr[v + 1]; ++k)
-            h->col_owned[state_column(h->edge_major, E, 0, k, g->inc_edge[k], g->inc_out[k])] = 1;
-    h->col_vertex.assign((size_t)std::max<int64_t>(g->num_incidences, 1), -1);
-    for (int v = 0; v < V; ++v)
-        for (int k = g->inc_ptr[v]; k < g->inc_ptr[v + 1]; ++k)
-            h->col_vertex[state_column(h->edge_major, E, 0, k, g->inc_edge[k], g->inc_out[k])] = v;
-    h->h_wave_slot_ptr = wave_slot_ptr; h->h_wave_vtx = wave_vtx;
+    h->col_owned = std::move(p.col_owned); h->col_vertex = std::move(p.col_vertex);
+    h->h_wave_slot_ptr = p.wave_slot_ptr; h->h_wave_vtx = p.wave_vtx;
     h->dtype = g->state_dtype; h->device = g->device;
-    h->n_waves = n_waves; h->n_special = (int)special_vtx.size();
-    h->slots_cap = std::max(1, max_slots_used);
-    h->all_m4 = (all_m4 && all_box) ? 2 : 0; h->align_rows = align_rows;
-    if (n_waves > 0) {
-        store_dl = 1;
-        if (lds_need(h->slots_cap) > 40 * 1024) store_dl = 0;
-        if (g->wave_store_dl == 1) store_dl = 1;
-        else if (g->wave_store_dl == 2) store_dl = 0;
-        if (store_dl && lds_need(h->slots_cap) > 160 * 1024) store_dl = 0;
-    }
-    h->store_dl = store_dl;
-    h->lds_bytes = n_waves > 0 ? (int)lds_need(h->slots_cap) : 0;
-    h->n_wg = (int)wg_vtx.size(); h->wg_lds_bytes = wg_lds; h->wg_box = (wg_all_box && !wg_vtx.empty()) ? 1 : 0; h->wg_t512 = wg_t512 ? 1 : 0;
-    h->nx = g->nx_global > 0 ? g->nx_global : (4.0 * n + 1) * (V + 2.0 * E);
-    h->nmu = g->nmu_global > 0 ? g->nmu_global : (4.0 * n + 2) * E;
-    {
-        h->edge_unroll = edge_unroll_rt(h->dtype, h->c, E);
-        const int tile = EDGE_BLOCK * h->edge_unroll;     // edges per workgroup and pass
-        h->edge_blocks = std::max(1, std::min((E + tile - 1) / tile, 2048));
-    }
+    h->n_waves = p.n_waves(); h->n_special = (int)p.special_vtx.size();
+    h->slots_cap = p.slots_cap; h->all_m4 = p.all_m4; h->align_rows = p.align_rows; h->store_dl = p.store_dl; h->lds_bytes = p.lds_bytes;
+    h->n_wg = (int)p.wg_vtx.size(); h->wg_lds_bytes = p.wg_lds_bytes; h->wg_box = p.wg_box; h->wg_t512 = p.wg_t512;
+    h->nx = p.nx; h->nmu = p.nmu;
+    h->edge_unroll = p.edge_unroll; h->edge_blocks = p.edge_blocks;
     auto bail = [&](hipError_t e, const char *what) {
         g_create_error = std::string(what) + ": " + hipGetErrorString(e);
         gcsadmm_destroy(h);
@@ -1046,18 +842,18 @@ gcsadmm_status gcsadmm_create(const gcsadmm_graph_desc *g, gcsadmm_handle *out)
     if ((e = device_guard_.err) != hipSuccess) return bail(e, "hipSetDevice");
 #define UP(dst, src, cnt) if ((e = upload(&h->dst, src, (size_t)(cnt))) != hipSuccess) return bail(e, "upload " #dst)
     UP(d_inc_ptr, g->inc_ptr, V + 1);
-    UP(d_deg_in, deg_in.data(), V);
+    UP(d_deg_in, p.deg_in.data(), V);
     UP(d_inc_edge, g->inc_edge, NIo);
     UP(d_poly_ptr, g->poly_ptr, V + 1);
     UP(d_edge_inc_tail, g->edge_inc_tail, E);
     UP(d_edge_inc_head, g->edge_inc_head, E);
-    UP(d_wave_slot_ptr, wave_slot_ptr.data(), wave_slot_ptr.size());
-    UP(d_wave_vtx, wave_vtx.data(), wave_vtx.size());
-    UP(d_special_vtx, special_vtx.data(), special_vtx.size());
-    UP(d_special_kind, special_kind.data(), special_kind.size());
-    UP(d_wg_vtx, wg_vtx.data(), wg_vtx.size());
+    UP(d_wave_slot_ptr, p.wave_slot_ptr.data(), p.wave_slot_ptr.size());
+    UP(d_wave_vtx, p.wave_vtx.data(), p.wave_vtx.size());
+    UP(d_special_vtx, p.special_vtx.data(), p.special_vtx.size());
+    UP(d_special_kind, p.special_kind.data(), p.special_kind.size());
+    UP(d_wg_vtx, p.wg_vtx.data(), p.wg_vtx.size());
     UP(d_poly_A, g->poly_A, (size_t)MT * n);
-    UP(d_poly_bc, bc.data(), MT);
+    UP(d_poly_bc, p.bc.data(), MT);
     UP(d_center, g->center, (size_t)V * n);
     if (g->inc_counted) UP(d_inc_counted, g->inc_counted, g->num_incidences);
     if (g->edge_counted) UP(d_edge_counted, g->edge_counted, E);
@@ -1066,55 +862,32 @@ gcsadmm_status gcsadmm_create(const gcsadmm_graph_desc *g, gcsadmm_handle *out)
     UP(d_partials, (const double *)nullptr, (size_t)h->edge_blocks * 5);
     UP(d_sums, (const double *)nullptr, 5);
     UP(d_ticket, (const unsigned *)nullptr, 1);
-    if (n_term > 0) {       // region terminals: workspace, an auxiliary stream and the fork / join events
-        long long off = 0, largest = 0, roff = 0;
-        int rows = 0;
-        for (int i = 0; i < n_term; ++i) {
-            const int v = term_vtx[i], d = g->inc_ptr[v + 1] - g->inc_ptr[v], din = deg_in[v], live = term_is_src[i] ? d - din : din;
-            const long long need = gcsadmm_terminal_ws_doubles(n, g->poly_ptr[v + 1] - g->poly_ptr[v], live);
-            h->term_vtx[i] = v; h->term_is_src[i] = term_is_src[i]; h->term_ws_off[i] = off;
-            off += need; largest = std::max(largest, need);
-            h->term_rec_off[i] = roff; roff += gcsadmm_terminal_record_doubles(n, g->poly_ptr[v + 1] - g->poly_ptr[v], live);
-            rows = std::max(rows, live * 2 * (g->poly_ptr[v + 1] - g->poly_ptr[v]));
+    if (p.n_term > 0) {       // region terminals: workspace, an auxiliary stream and the fork / join events
+        h->n_term = p.n_term;
+        for (int i = 0; i < p.n_term; ++i) {
+            h->term_vtx[i] = p.term_vtx[i]; h->term_is_src[i] = p.term_is_src[i];
+            h->term_ws_off[i] = p.term_ws_off[i]; h->term_rec_off[i] = p.term_rec_off[i];
         }
-        h->n_term = n_term;
-        // the solve is latency-bound: work arrays in LDS while they fit 48 KB, one wavefront (barriers and reductions stay inside it)
-        // while no phase has more than four passes over its rows
-        h->term_lds_doubles = largest * 8 <= 48 * 1024 ? (int)largest : 0;
-        h->term_threads = rows <= 256 ? 64 : 256;
-        UP(d_term_ws, (const double *)nullptr, (size_t)off);
-        h->term_rec_doubles = (size_t)roff;
-        UP(d_term_rec, (const double *)nullptr, (size_t)roff);
+        h->term_lds_doubles = p.term_lds_doubles; h->term_threads = p.term_threads;
+        UP(d_term_ws, (const double *)nullptr, (size_t)p.term_ws_doubles);
+        h->term_rec_doubles = (size_t)p.term_rec_doubles;
+        UP(d_term_rec, (const double *)nullptr, h->term_rec_doubles);
         if ((e = hipStreamCreateWithFlags(&h->term_stream, hipStreamNonBlocking)) != hipSuccess) return bail(e, "hipStreamCreate");
         if ((e = hipEventCreateWithFlags(&h->ev_term_fork, hipEventDisableTiming)) != hipSuccess) return bail(e, "hipEventCreate");
         if ((e = hipEventCreateWithFlags(&h->ev_term_join, hipEventDisableTiming)) != hipSuccess) return bail(e, "hipEventCreate");
     }
-    {   // warm-start workspace: one record per generic vertex (either program), none for the closed-form ones; zero = no record
-        std::vector<long long> wp(V + 1, 0);
-        for (int v = 0; v < V; ++v)
-            wp[v + 1] = wp[v] + ((is_special(v) || is_region_terminal(v)) ? 0 : gcs_ws::warm_record_doubles(n, g->poly_ptr[v + 1] - g->poly_ptr[v], g->inc_ptr[v + 1] - g->inc_ptr[v]));
-        h->warm_doubles = (size_t)wp[V];
-        UP(d_warm_ptr, wp.data(), V + 1);
-        UP(d_warm, (const double *)nullptr, h->warm_doubles);
-    }
+    h->warm_doubles = (size_t)p.warm_ptr[V];
+    UP(d_warm_ptr, p.warm_ptr.data(), V + 1);
+    UP(d_warm, (const double *)nullptr, h->warm_doubles);
     {   // slowest-first dispatch: only where a launch needs more than one round of the chip (small graphs run all at once)
-        std::vector<int> iota(std::max(std::max(n_waves, (int)wg_vtx.size()), 1));
+        std::vector<int> iota(std::max(std::max(h->n_waves, h->n_wg), 1));
         for (size_t i = 0; i < iota.size(); ++i) iota[i] = (int)i;
-        if (n_waves >= REORDER_MIN_UNITS) { UP(d_wave_iters, (const int *)nullptr, n_waves); UP(d_wave_order, iota.data(), n_waves); }
-        if ((int)wg_vtx.size() >= REORDER_MIN_UNITS) { UP(d_wg_iters, (const int *)nullptr, wg_vtx.size()); UP(d_wg_order, iota.data(), wg_vtx.size()); }
+        if (p.wave_reorder) { UP(d_wave_iters, (const int *)nullptr, h->n_waves); UP(d_wave_order, iota.data(), h->n_waves); }
+        if (p.wg_reorder) { UP(d_wg_iters, (const int *)nullptr, h->n_wg); UP(d_wg_order, iota.data(), h->n_wg); }
     }
-    {
-        std::vector<int> pv;
-        int mm_all = 1;
-        for (int v = 0; v < V; ++v) {
-            if (v != g->src && v != g->dst) pv.push_back(v);
-            mm_all = std::max(mm_all, g->poly_ptr[v + 1] - g->poly_ptr[v]);
-        }
-        h->n_prox = (int)pv.size(); h->src = g->src; h->dst = g->dst;
-        h->prox_lds_bytes = gcsadmm_wg_lds_bytes(n, 1, mm_all);
-        UP(d_prox_vtx, pv.data(), pv.size());
-        UP(d_prox_counters, (const int *)nullptr, 2);
-    }
+    h->n_prox = (int)p.prox_vtx.size(); h->src = g->src; h->dst = g->dst; h->prox_lds_bytes = p.prox_lds_bytes;
+    UP(d_prox_vtx, p.prox_vtx.data(), p.prox_vtx.size());
+    UP(d_prox_counters, (const int *)nullptr, 2);
 #undef UP
     if (h->lds_bytes > 48 * 1024) {
         e = h->dtype == GCSADMM_F64 ? set_lds_attr<2, double>(h->all_m4, h->lds_bytes) : set_lds_attr<2, float>(h->all_m4, h->lds_bytes);

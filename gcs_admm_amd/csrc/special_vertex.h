@@ -7,8 +7,6 @@
 
 namespace gcsadmm_k {
 
-constexpr int MAX_SPECIAL_DEG = 256;
-
 // -------------------------------------------------------------------------------------------------
 // special vertices: s / t are points (utils.py:12-28, boxes of half-width 1e-6) -> the sub-problem
 // collapses to a separable quadratic over the simplex of the live side; a vertex with no incoming or

@@ -11,6 +11,8 @@ struct gcsadmm_control_block;
 
 namespace gcsadmm_k {
 
+constexpr int MAX_SPECIAL_DEG = 256;   // degree limit of the closed-form vertices (special_vertex.h): their work arrays are this long
+
 struct StepArgsBase {
     const int *inc_ptr;         // [V+1]
     const int *deg_in;          // [V]

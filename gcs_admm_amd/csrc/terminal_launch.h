@@ -27,6 +27,5 @@ struct TermLaunchDesc {
 
 }  // namespace gcsadmm_k
 
-long long gcsadmm_terminal_ws_doubles(int n, int facets, int live_edges);
-long long gcsadmm_terminal_record_doubles(int n, int facets, int live_edges);
+// (work-array and record sizes, gcsadmm_terminal_ws_doubles / gcsadmm_terminal_record_doubles: create_plan.h, which is host-only)
 void gcsadmm_terminal_launch(const gcsadmm_k::TermLaunchDesc &d, hipStream_t s);

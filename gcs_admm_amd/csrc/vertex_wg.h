@@ -219,7 +219,7 @@ template <int N> struct WLBox {
     static GCS_HD int total(int U, int m) { return FIXED + pad2(U * unit_stride(m)) + pad2(m * N) + pad2(m); }
 };
 template <int N> GCS_HD int wg_lds_doubles(int U, int m, bool box = false) { return box ? WLBox<N>::total(U, m) : WL<N>::total(U, m); }
-// the program is dimension-generic (admm_solver_v3.py:363-377 takes any n): instantiated for n = 1 .. 6; the BOX instantiation and
+// the program is dimension-generic (admm_solver_v3.py:363-377 takes any n): instantiated for n = 1 .. WG_MAX_N; the BOX instantiation and
 // its layout exist for the two dimensions that are tuned for it, n = 3 and 6
 constexpr int WG_MAX_N = 8;
 inline bool wg_has_box(int n) { return n == 3 || n == 6; }

@@ -21,16 +21,13 @@ struct WgLaunchDesc {
 
 }  // namespace gcsadmm_k
 
-// LDS bytes one workgroup needs for a vertex with `units` = degree + 1 and `facets` facets
-int gcsadmm_wg_lds_bytes(int n, int units, int facets, bool box = false);     // box: the BOX instantiation's structured layout
-bool gcsadmm_wg_has_box(int n);                                                // the BOX instantiation exists for this dimension (3, 6)
+// (LDS sizes of the program, gcsadmm_wg_lds_bytes / _t512 and gcsadmm_wg_has_box: create_plan.h, which is host-only)
 // raise the dynamic-LDS limit of the instantiation (needed above 48 KB)
 hipError_t gcsadmm_wg_set_lds(int n, int dtype, int lds_bytes);
 void gcsadmm_wg_launch(const gcsadmm_k::WgLaunchDesc &d, hipStream_t s);
 
 // the same program built with 512 threads per workgroup (second objects of vertex_wg.hip and vertex_wg_dims.hip): 3-10 % faster while every
 // workgroup has a CU to itself (benchmark3 5 656 -> 6 244 it/s, benchmark4 7 590 -> 7 955), slower beyond (1 026 vertices: 5 763 -> 3 932)
-int gcsadmm_wg_lds_bytes_t512(int n, int units, int facets, bool box = false);
 hipError_t gcsadmm_wg_set_lds_t512(int n, int dtype, int lds_bytes);
 void gcsadmm_wg_launch_t512(const gcsadmm_k::WgLaunchDesc &d, hipStream_t s);
 

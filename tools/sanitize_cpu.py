@@ -72,3 +72,21 @@ for n, seed in [(2, 0), (2, 1), (1, 4), (3, 5), (6, 7)]:
                                   C.byref(ip), p(copy), p(xv), p(zv), p(yv), None)
     assert r >= 0 and np.abs(copy - e[0]).max() < 2e-5
     print('region terminal n =', n, 'ok')
+
+# ---- gcsadmm_create's plan (create_plan.h): every case of tests/test_create_plan.py on the sanitized build of its shim
+import test_create_plan as CP
+from conftest import BENCHMARKS
+plan = CP.load('/tmp/libplanemu_asan.so')
+for name in BENCHMARKS:
+    CP.test_benchmarks_run_the_512_thread_workgroup_program(plan, name)
+g10k = lattice_boxes(100, 100, seed=0)
+for t in (CP.test_lattice_10k_runs_the_aligned_box_wavefront_program, CP.test_more_than_2048_wavefronts_pack_dense, CP.test_vertex_program_knob,
+          CP.test_wave_knobs):
+    t(plan, g10k)
+for n in (3, 6):
+    CP.test_box_lattices_use_the_box_workgroup_instantiation(plan, n)
+CP.test_degree_above_63_goes_to_the_workgroup_program(plan)
+for case in ('row', 'star3', 'star6'):
+    CP.test_region_terminals(plan, case)
+CP.test_refusals(plan)
+print('create plan ok')
