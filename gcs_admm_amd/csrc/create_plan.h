@@ -48,6 +48,12 @@ struct CreatePlan {
     // workgroup program (vertex_wg.hip), heaviest sub-problem first
     std::vector<int> wg_vtx;
     int wg_lds_bytes = 0, wg_box = 0, wg_t512 = 0;
+    // its split form (gcsadmm_graph_desc.vertex_workspace), 256 threads, same BOX choice: split_vtx[i] has its units at
+    // split_off[i] doubles into a device workspace of split_doubles, 256-byte aligned slabs; heaviest first
+    std::vector<int> split_vtx;
+    std::vector<long long> split_off;
+    long long split_doubles = 0;
+    int split_lds_bytes = 0;
     // wavefront program (vertex_program.inc): wavefront w holds wave_vtx[wave_slot_ptr[w] .. wave_slot_ptr[w + 1])
     std::vector<int> wave_slot_ptr{0}, wave_vtx;
     int slots_cap = 1, align_rows = 0, store_dl = 0, all_m4 = 0;
@@ -160,6 +166,8 @@ inline gcsadmm_status make_create_plan(const gcsadmm_graph_desc &g, CreatePlan &
     // round of ~0.28 ms; the wavefront program packs up to 7 vertices per wavefront and serves up to ~7 000 in one round of 0.33 ms.
     constexpr int WG_AUTO_MAX = 1024;
     if (g.vertex_program < 0 || g.vertex_program > 3) return fail(GCSADMM_ERR_BAD_ARG, "vertex_program must be 0, 1, 2 or 3");
+    if (g.vertex_workspace < 0 || g.vertex_workspace > 2) return fail(GCSADMM_ERR_BAD_ARG, "vertex_workspace must be 0, 1 or 2");
+    const int ws_mode = g.vertex_workspace;
     const bool prefer_wg = g.vertex_program >= 2 || (g.vertex_program == 0 && n_generic <= WG_AUTO_MAX);
     // box instantiations: the workgroup program's where it has one (n = 3, 6), the wavefront program's at n = 2 (facets
     // [+e0, +e1, -e0, -e1]); wave_generic_rows forces the generic variants of both
@@ -177,7 +185,9 @@ inline gcsadmm_status make_create_plan(const gcsadmm_graph_desc &g, CreatePlan &
             continue;
         }
         p.warm_ptr[v + 1] += gcs_ws::warm_record_doubles(n, fac[v], deg[v]);
-        if (n != 2 || deg[v] + 1 > gcs::WAVE || prefer_wg) {
+        // (vertex_workspace 1: an n = 2 vertex the wavefront program cannot hold even alone in a wavefront goes to the workgroup program)
+        const bool wave_too_small = ws_mode == 1 && n == 2 && (size_t)gcs::lds_doubles(n, fac[v], 1, 0) * 8 > (size_t)LDS_CU_BYTES;
+        if (n != 2 || deg[v] + 1 > gcs::WAVE || prefer_wg || wave_too_small) {
             p.wg_vtx.push_back(v);
             if (wg_box && !canonical_box(n, fac[v], poly_A(v))) wg_box = false;
         } else {
@@ -191,13 +201,28 @@ inline gcsadmm_status make_create_plan(const gcsadmm_graph_desc &g, CreatePlan &
     // threads per workgroup: 512 while every workgroup of the launch has a CU to itself (vertex_wg_launch.h), 256 otherwise
     const int n_wg = (int)p.wg_vtx.size();
     p.wg_t512 = n_wg > 0 && g.vertex_program != 3 && n_wg + 1 <= 256;
-    p.wg_box = n_wg > 0 && wg_box;
-    for (int v : p.wg_vtx)
-        p.wg_lds_bytes = std::max(p.wg_lds_bytes, p.wg_t512 ? gcsadmm_wg_lds_bytes_t512(n, deg[v] + 1, fac[v], wg_box)
-                                                            : gcsadmm_wg_lds_bytes(n, deg[v] + 1, fac[v], wg_box));
+    p.wg_box = n_wg > 0 && wg_box;      // (n_wg: before the split below; both launches take this choice)
+    auto wg_bytes = [&](int v) { return p.wg_t512 ? gcsadmm_wg_lds_bytes_t512(n, deg[v] + 1, fac[v], wg_box)
+                                                  : gcsadmm_wg_lds_bytes(n, deg[v] + 1, fac[v], wg_box); };
+    if (ws_mode > 0) {      // split form: the vertices that do not fit (1) or all of them (2) leave the in-LDS launch
+        std::vector<int> keep;
+        for (int v : p.wg_vtx) (ws_mode == 2 || wg_bytes(v) > LDS_CU_BYTES ? p.split_vtx : keep).push_back(v);
+        p.wg_vtx.swap(keep);
+    }
+    for (int v : p.wg_vtx) p.wg_lds_bytes = std::max(p.wg_lds_bytes, wg_bytes(v));
     if (p.wg_lds_bytes > LDS_CU_BYTES) return fail(GCSADMM_ERR_UNSUPPORTED, "a vertex sub-problem (degree x facets) does not fit the 160 KB of LDS of a CU");
     // heaviest sub-problems first: the launch ends when its slowest workgroup does
-    std::stable_sort(p.wg_vtx.begin(), p.wg_vtx.end(), [&](int a, int b) { return (long)(deg[a] + 1) * fac[a] > (long)(deg[b] + 1) * fac[b]; });
+    auto heavier = [&](int a, int b) { return (long)(deg[a] + 1) * fac[a] > (long)(deg[b] + 1) * fac[b]; };
+    std::stable_sort(p.wg_vtx.begin(), p.wg_vtx.end(), heavier);
+    // split form (256-thread build): LDS = the layout without units, total(0, m); slab = what the units add, rounded to 256 bytes
+    std::stable_sort(p.split_vtx.begin(), p.split_vtx.end(), heavier);
+    for (int v : p.split_vtx) {
+        const int lds = gcsadmm_wg_lds_bytes(n, 0, fac[v], wg_box);
+        if (lds > LDS_CU_BYTES) return fail(GCSADMM_ERR_UNSUPPORTED, "a vertex's border system and polytope do not fit the 160 KB of LDS of a CU");
+        p.split_lds_bytes = std::max(p.split_lds_bytes, lds);
+        p.split_off.push_back(p.split_doubles);
+        p.split_doubles += ((gcsadmm_wg_lds_bytes(n, deg[v] + 1, fac[v], wg_box) - lds) / 8 + 31) / 32 * 32;
+    }
 
     // ---- wavefront program: pack its vertices into wavefronts, d+1 lanes each ----
     // LDS per wavefront with / without room for the final dual directions (kernel template SDL): they save the

@@ -5,6 +5,7 @@
 //                        per wavefront, program in vertex_program.h     (admm_solver_v3.py:352-540)
 //   vertex_wg_kernel<N,T> (vertex_wg.hip) x-update, workgroup program: one 256-thread workgroup per vertex, any n / degree
 //                        trailing workgroups of either launch: x-update of s, t (closed form) and of vertices no flow can cross
+//   vertex_wg_split_kernel<N,T> (vertex_wg.hip) the same program for vertices too large for LDS, edge blocks in a device workspace
 //   edge_kernel<T,MODE,C> z-update, dual update, five partial norms     (admm_solver_v3.py:543-614); in gcsadmm_run the last
 //                        workgroup to finish also does the final reduction and the control step (one launch per edge step)
 //   finalize_kernel / control_kernel   deterministic final reduction; residuals, rho adaptation, stop test,
@@ -339,6 +340,12 @@ struct gcsadmm_handle_s {
     int n_wg = 0, wg_lds_bytes = 0;   // vertices solved by the workgroup program (vertex_wg.hip), LDS per workgroup
     int wg_box = 0;           // every workgroup-program vertex is a canonical box: BOX instantiation of that program
     int wg_t512 = 0;          // the launch uses the 512-thread build of the workgroup program (at most one workgroup per CU)
+    // split form of the workgroup program (gcsadmm_graph_desc.vertex_workspace): vertices, LDS per workgroup, their units' slabs
+    int n_split = 0, split_lds_bytes = 0;
+    int *d_split_vtx = nullptr;
+    long long *d_split_off = nullptr;
+    double *d_split_ws = nullptr;
+    size_t split_doubles = 0;
     int edge_unroll = 1;      // edges in flight per thread of the edge kernel
     int edge_major = 0;       // state columns numbered by edge (gcsadmm_graph_desc.edge_major_columns)
     std::vector<char> col_owned;   // [NI] 1: the column of an incidence of this handle's vertices, 0: a ghost column
@@ -576,6 +583,11 @@ template <class T> static gcsadmm_status launch_vertex(gcsadmm_handle h, const g
         if (h->wg_t512) gcsadmm_wg_launch_t512(make_wg_desc(h, st, !special_on_wave), s);
         else gcsadmm_wg_launch(make_wg_desc(h, st, !special_on_wave), s);
     }
+    if (h->n_split > 0) {      // the vertices too large for LDS: the split form, units in the handle's workspace
+        WgLaunchDesc d = make_wg_desc(h, st, false);
+        d.n_vtx = h->n_split; d.vtx = h->d_split_vtx; d.lds_bytes = h->split_lds_bytes; d.order = nullptr; d.unit_iters = nullptr;
+        gcsadmm_wg_launch_split(d, WgSplitArgs{h->d_split_ws, h->d_split_off}, s);
+    }
     if (++h->vertex_steps % REORDER_EVERY == 0) {      // slowest-first dispatch of the following launches (graphs that need more than one round)
         if (h->d_wave_order) hipLaunchKernelGGL(reorder_kernel, dim3(1), dim3(REORDER_THREADS), 0, s, h->n_waves, h->d_wave_iters, h->d_wave_order, h->d_cb);
         if (h->d_wg_order) hipLaunchKernelGGL(reorder_kernel, dim3(1), dim3(REORDER_THREADS), 0, s, h->n_wg, h->d_wg_iters, h->d_wg_order, h->d_cb);
@@ -681,7 +693,7 @@ static void overlap_free(gcsadmm_handle h)
 static gcsadmm_status overlap_setup(gcsadmm_handle h, const gcsadmm_halo_desc *hd)
 {
     overlap_free(h);
-    if (h->overlap_mode == 2 || h->n_waves < 2 || h->n_wg > 0) return GCSADMM_OK;
+    if (h->overlap_mode == 2 || h->n_waves < 2 || h->n_wg > 0 || h->n_split > 0) return GCSADMM_OK;
     const int n_send = (hd && hd->num_peers > 0) ? hd->send_ptr[hd->num_peers] : 0;
     if (n_send == 0 && h->overlap_mode != 1) return GCSADMM_OK;
     std::vector<char> vb((size_t)std::max(h->V, 1), 0);
@@ -790,7 +802,8 @@ void gcsadmm_destroy(gcsadmm_handle h)
     void *ptrs[] = {h->d_inc_ptr, h->d_deg_in, h->d_inc_edge, h->d_poly_ptr, h->d_edge_inc_tail, h->d_edge_inc_head,
                     h->d_wave_slot_ptr, h->d_wave_vtx, h->d_special_vtx, h->d_special_kind, h->d_wg_vtx, h->d_poly_A, h->d_poly_bc,
                     h->d_center, h->d_inc_counted, h->d_edge_counted, h->d_cb, h->d_counters, h->d_partials, h->d_sums, h->d_ticket, h->d_prox_vtx, h->d_prox_counters,
-                    h->d_warm, h->d_warm_ptr, h->d_wave_iters, h->d_wave_order, h->d_wg_iters, h->d_wg_order};
+                    h->d_warm, h->d_warm_ptr, h->d_wave_iters, h->d_wave_order, h->d_wg_iters, h->d_wg_order, h->d_split_vtx,
+                    h->d_split_off, h->d_split_ws};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     halo_free(h);
@@ -830,6 +843,7 @@ gcsadmm_status gcsadmm_create(const gcsadmm_graph_desc *g, gcsadmm_handle *out)
     h->n_waves = p.n_waves(); h->n_special = (int)p.special_vtx.size();
     h->slots_cap = p.slots_cap; h->all_m4 = p.all_m4; h->align_rows = p.align_rows; h->store_dl = p.store_dl; h->lds_bytes = p.lds_bytes;
     h->n_wg = (int)p.wg_vtx.size(); h->wg_lds_bytes = p.wg_lds_bytes; h->wg_box = p.wg_box; h->wg_t512 = p.wg_t512;
+    h->n_split = (int)p.split_vtx.size(); h->split_lds_bytes = p.split_lds_bytes; h->split_doubles = (size_t)p.split_doubles;
     h->nx = p.nx; h->nmu = p.nmu;
     h->edge_unroll = p.edge_unroll; h->edge_blocks = p.edge_blocks;
     auto bail = [&](hipError_t e, const char *what) {
@@ -852,6 +866,11 @@ gcsadmm_status gcsadmm_create(const gcsadmm_graph_desc *g, gcsadmm_handle *out)
     UP(d_special_vtx, p.special_vtx.data(), p.special_vtx.size());
     UP(d_special_kind, p.special_kind.data(), p.special_kind.size());
     UP(d_wg_vtx, p.wg_vtx.data(), p.wg_vtx.size());
+    if (h->n_split > 0) {
+        UP(d_split_vtx, p.split_vtx.data(), p.split_vtx.size());
+        UP(d_split_off, p.split_off.data(), p.split_off.size());
+        UP(d_split_ws, (const double *)nullptr, h->split_doubles);
+    }
     UP(d_poly_A, g->poly_A, (size_t)MT * n);
     UP(d_poly_bc, p.bc.data(), MT);
     UP(d_center, g->center, (size_t)V * n);
@@ -896,6 +915,8 @@ gcsadmm_status gcsadmm_create(const gcsadmm_graph_desc *g, gcsadmm_handle *out)
     if (h->wg_lds_bytes > 48 * 1024 && (e = h->wg_t512 ? gcsadmm_wg_set_lds_t512(h->n, h->dtype, h->wg_lds_bytes)
                                                         : gcsadmm_wg_set_lds(h->n, h->dtype, h->wg_lds_bytes)) != hipSuccess)
         return bail(e, "hipFuncSetAttribute(MaxDynamicSharedMemorySize, workgroup program)");
+    if (h->split_lds_bytes > 48 * 1024 && (e = gcsadmm_wg_set_split_lds(h->n, h->dtype, h->split_lds_bytes)) != hipSuccess)
+        return bail(e, "hipFuncSetAttribute(MaxDynamicSharedMemorySize, split workgroup program)");
     *out = h;
     return GCSADMM_OK;
 }
@@ -1286,6 +1307,15 @@ gcsadmm_status gcsadmm_query(gcsadmm_handle h, int32_t *num_waves, int32_t *lds_
     if (num_special) *num_special = h->n_special;
     if (num_workgroup_vertices) *num_workgroup_vertices = h->n_wg;
     if (workgroup_lds_bytes) *workgroup_lds_bytes = h->wg_lds_bytes;
+    return GCSADMM_OK;
+}
+
+gcsadmm_status gcsadmm_query_workspace(gcsadmm_handle h, int32_t *num_split_vertices, int32_t *split_lds_bytes, int64_t *workspace_bytes)
+{
+    if (!h) return GCSADMM_ERR_BAD_ARG;
+    if (num_split_vertices) *num_split_vertices = h->n_split;
+    if (split_lds_bytes) *split_lds_bytes = h->split_lds_bytes;
+    if (workspace_bytes) *workspace_bytes = (int64_t)(h->split_doubles * sizeof(double));
     return GCSADMM_OK;
 }
 

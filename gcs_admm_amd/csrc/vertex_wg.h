@@ -48,7 +48,24 @@ constexpr int WG_ITEM_WAVES = WG_WAVES > 1 ? WG_WAVES - 1 : 1;   // wavefronts t
 constexpr double CHOL_SKIP = 1e-12;
 constexpr double REG_DELTA = 1e-7;   // Tikhonov term on every centred unknown except t (oracle/gcs_oracle.c REG_DELTA)
 
+// WG_VM: the units of the sub-problem are in DEVICE memory (the split form of wg_solve_vertex, which shadows this name with its
+// template flag).  Then a barrier, or a hand-off inside a wavefront, must also wait for the wavefront's global stores and loads:
+// __syncthreads() does not -- its workgroup-scope fence is a bare s_barrier for global memory on this target (no TgSplit mode; the
+// disassembly shows global stores still in flight at the s_barrier) -- so s_waitcnt vmcnt(0) goes before it.  The in-LDS form
+// (WG_VM false) is unchanged.
+constexpr bool WG_VM = false;
 #if WG_DEVICE
+template <bool VM> __device__ __forceinline__ void wg_barrier()
+{
+    if constexpr (VM) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+}
+// a wavefront's LDS operations complete in order: waiting for them is enough to hand data to the next item loop of a wave-local pipeline
+template <bool VM> __device__ __forceinline__ void wg_wave_sync()
+{
+    if constexpr (VM) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    else asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+}
 // The thread id is made opaque at the head of every region: a thread's first task of a region (and its decode into
 // unit / row / column, base pointers, ...) is invariant across the Newton loop, and hoisting all of that out of the loop
 // costs hundreds of live registers (scratch spills) for no gain.
@@ -62,7 +79,7 @@ __device__ __forceinline__ int wg_tid()
 // the same with task 0 on thread `start`: a region with several KINDS of task starts each kind on its own wavefront
 // (Place, below); with every kind starting at thread 0 the first wavefront runs all kinds back to back while the others idle
 #define WG_FOR_AT(i, cnt, start) for (int i = (gcs_wg::wg_tid() - (start)) & (gcs_wg::WG_THREADS - 1), i##_end = (cnt); i < i##_end; i += gcs_wg::WG_THREADS)
-#define WG_SYNC() __syncthreads()
+#define WG_SYNC() gcs_wg::wg_barrier<WG_VM>()
 #define WG_ONE() if (gcs_wg::wg_tid() == 0)
 // the serial cone algebra runs on the LAST thread: wave 3 has the fewest row / entry tasks in every region
 #define WG_CONE() if (gcs_wg::wg_tid() == gcs_wg::WG_THREADS - 1)
@@ -88,7 +105,7 @@ __device__ __forceinline__ int wg_tid()
         if (const int qq_ = l_ / (PER), i = l_ - qq_ * (PER), q = w_ + gcs_wg::WG_ITEM_WAVES * qq_; true)
 // a small step EVERY item wavefront repeats for itself (same values to the same words) instead of waiting at a barrier for one
 #define WG_REPL_FOR(i, cnt) for (int i = (gcs_wg::wg_tid() >> 6) < gcs_wg::WG_ITEM_WAVES ? (gcs_wg::wg_tid() & 63) : (cnt), i##_end = (cnt); i < i##_end; i += 64)
-#define WG_WAVE_SYNC() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
+#define WG_WAVE_SYNC() gcs_wg::wg_wave_sync<WG_VM>()
 #define WG_FENCE() asm volatile("" ::: "memory")
 #else
 #define WG_FENCE() do { } while (0)
@@ -197,6 +214,9 @@ template <int N> struct WL {
     // banks; with the natural even stride (e.g. 216 doubles at n = 2, m = 7) units 4 apart collide: 4-way conflicts
     static GCS_HD int unit_stride(int m) { return (ROWS + 12 * m) | 1; }
     static GCS_HD int total(int U, int m) { return FIXED + pad2(U * unit_stride(m)) + pad2(m * N) + pad2(m); }
+    // SPLIT form (wg_solve_vertex<..., true>): the units in a device-memory slab of units_doubles, LDS holds [ fixed block | A | bc ] =
+    // total(0, m)
+    static GCS_HD int units_doubles(int U, int m) { return pad2(U * unit_stride(m)); }
 };
 // The same for the BOX instantiation (canonical axis-aligned boxes, wg_solve_vertex<N, T, true>): the fixed block is WL<N>'s; a unit
 // holds K_e, X_e and B_e = K_e^{-1} in their STRUCTURED forms instead of three dense matrices (86 instead of 496 doubles at n = 6):
@@ -217,6 +237,7 @@ template <int N> struct WLBox {
                          BD = XY + pad2(NX), BW = BD + pad2(NX), BRS = BW + pad2(NW), BQ = BRS + 2, ROWS = BQ + pad2(NX);
     static GCS_HD int unit_stride(int m) { return (ROWS + 12 * m) | 1; }
     static GCS_HD int total(int U, int m) { return FIXED + pad2(U * unit_stride(m)) + pad2(m * N) + pad2(m); }
+    static GCS_HD int units_doubles(int U, int m) { return pad2(U * unit_stride(m)); }
 };
 template <int N> GCS_HD int wg_lds_doubles(int U, int m, bool box = false) { return box ? WLBox<N>::total(U, m) : WL<N>::total(U, m); }
 // the program is dimension-generic (admm_solver_v3.py:363-377 takes any n): instantiated for n = 1 .. WG_MAX_N; the BOX instantiation and
@@ -291,7 +312,7 @@ GCS_HD int wg_uniform(int x)
 #endif
 }
 
-GCS_HD Red3 wg_reduce(Red3 v, double *red, int &phase)
+template <bool VM = false> GCS_HD Red3 wg_reduce(Red3 v, double *red, int &phase)
 {
 #if WG_DEVICE
     // rows of 16 lanes with DPP shifts (lane 15 of a row ends up with the row's result), then the four row results
@@ -308,7 +329,7 @@ GCS_HD Red3 wg_reduce(Red3 v, double *red, int &phase)
     phase = phase == 2 ? 0 : phase + 1;
     const int wave = (int)threadIdx.x >> 6;
     if (((int)threadIdx.x & 63) == 0) { buf[wave * 3 + 0] = w.mn; buf[wave * 3 + 1] = w.s1; buf[wave * 3 + 2] = w.s2; }
-    __syncthreads();
+    wg_barrier<VM>();
     Red3 r{buf[0], buf[1], buf[2]};
 #pragma unroll
     for (int q = 1; q < WG_WAVES; ++q) { r.mn = fmin(r.mn, buf[3 * q]); r.s1 += buf[3 * q + 1]; r.s2 += buf[3 * q + 2]; }
@@ -557,8 +578,16 @@ template <int Q> GCS_HD void soc_apply_W2(const double *wb, double eta, const do
 // k_j = j mod N: every facet-row dot product is one term, K_h and the x-coupling X_e of a unit are DIAGONAL (plus the y row /
 // column), and the loops over facets / coordinates below shrink accordingly.  Same algorithm, same operation order on the terms
 // that remain (the dropped terms are exact zeros), so results agree with the generic instantiation to rounding of -0.0 + x.
-template <int N, class T, bool BOX = false>
-GCS_HD void wg_solve_vertex(const WgArgs<T> &a, int v, double rho, double mu_scale, double *sm, int &status_out, int &iters_out)
+//
+// SPLIT: the units live in `units` (device memory: a slab of W::units_doubles(d + 1, m), the handle's workspace) instead of LDS, which
+// then holds the fixed block and the polytope only, [ fixed block | A | bc ] -- for sub-problems whose full layout does not fit a CU's
+// LDS (gcsadmm_graph_desc.vertex_workspace).  Same unit layout, same arithmetic in the same order: the results are bitwise those of the
+// in-LDS form.  What changes is the ordering of the unit accesses: every barrier of a region, and every hand-off between the item
+// loops of a wave-local pipeline, first waits for the wavefront's global accesses (s_waitcnt vmcnt(0): WG_VM, above), so that the
+// units are ordered at workgroup scope as LDS is.
+template <int N, class T, bool BOX = false, bool SPLIT = false>
+GCS_HD void wg_solve_vertex(const WgArgs<T> &a, int v, double rho, double mu_scale, double *sm, int &status_out, int &iters_out,
+                            double *units = nullptr)
 {
     using D = WD<N>;
     using SO = WSoc<N>;
@@ -576,9 +605,11 @@ GCS_HD void wg_solve_vertex(const WgArgs<T> &a, int v, double rho, double mu_sca
     const int U = d + 1, R = 4 * m, m2 = 2 * m;
     const int US = W::unit_stride(m);
     const float inv_m2 = 1.0f / (float)m2;
-    auto UN = [&](int u) -> double * { return sm + W::FIXED + u * US; };       // base of unit u
+    double *const UB = SPLIT ? units : sm + W::FIXED;
+    auto UN = [&](int u) -> double * { return UB + u * US; };       // base of unit u
+    constexpr bool WG_VM = SPLIT;      // (WG_SYNC, WG_WAVE_SYNC and wg_reduce wait for the units' global accesses)
     const int oLAM = W::ROWS, oR1 = W::ROWS + R, oR2 = W::ROWS + 2 * R;   // facet-row arrays of a unit: duals, two work arrays
-    double *const PA = sm + W::FIXED + pad2(U * US);
+    double *const PA = sm + W::FIXED + (SPLIT ? 0 : pad2(U * US));
     const double *A = PA, *BC = PA + pad2(m * N), *CEN = sm + W::CEN;
     double *SOC = sm + W::SOC, *SC = sm + W::SC;
     int red_phase = 0;
@@ -626,7 +657,7 @@ GCS_HD void wg_solve_vertex(const WgArgs<T> &a, int v, double rho, double mu_sca
     bool use_warm = false;
     double mu_ref = gcs_ws::WS_COLD_REF, ws_dT = -1.0;      // ws_dT < 0: no comparable record
     if (wrec) {      // (workgroup-uniform; the reduction's barrier also publishes the loads above)
-        const Red3 rt = wg_reduce(Red3{-dtm, 0.0, 0.0}, sm + W::RED, red_phase);
+        const Red3 rt = wg_reduce<WG_VM>(Red3{-dtm, 0.0, 0.0}, sm + W::RED, red_phase);
         const bool comparable = wg_uniform((int)(wrec[0] == 1.0 && wrec[1] == rho)) != 0;
         ws_dT = wg_uniform(comparable ? -rt.mn * rho : -1.0);
         use_warm = wg_uniform((int)(comparable && ws_dT <= gcs_ws::ws_theta(wrec))) != 0;
@@ -1003,7 +1034,7 @@ GCS_HD void wg_solve_vertex(const WgArgs<T> &a, int v, double rho, double mu_sca
             if (!gcs_math::soc_interior<Q>(SOC + SO::SS)) bad = 1;
         }
         WG_ARRIVE(1);
-        const Red3 r0 = wg_reduce(Red3{bad ? -1.0 : 1.0, acc, 0.0}, sm + W::RED, red_phase);
+        const Red3 r0 = wg_reduce<WG_VM>(Red3{bad ? -1.0 : 1.0, acc, 0.0}, sm + W::RED, red_phase);
         WG_STAMP(1);
         // (workgroup-uniform scalars go to scalar registers: the branches on them are then scalar branches, not EXEC-masked regions)
         const double gap = wg_uniform(r0.s1);
@@ -1535,7 +1566,7 @@ GCS_HD void wg_solve_vertex(const WgArgs<T> &a, int v, double rho, double mu_sca
         // the cone's share (step bounds, mu_aff sums) was computed by the cone lanes inside the solve (solve_tail)
         WG_CONE() { amax_cone = fmin(SC[SC_AMAXC], SC[SC_AMAXC2]); c1 += SC[SC_C1C]; c2 += SC[SC_C2C]; }
         WG_ARRIVE(14);
-        const Red3 rb = wg_reduce(Red3{fmin(rmax > 0.0 ? rcp1(rmax) : 1e300, amax_cone), c1, c2}, sm + W::RED, red_phase);
+        const Red3 rb = wg_reduce<WG_VM>(Red3{fmin(rmax > 0.0 ? rcp1(rmax) : 1e300, amax_cone), c1, c2}, sm + W::RED, red_phase);
         WG_STAMP(14);
         {
             const double al = fmin(1.0, rb.mn);
@@ -1639,7 +1670,7 @@ GCS_HD void wg_solve_vertex(const WgArgs<T> &a, int v, double rho, double mu_sca
         amax_cone = 1e300;
         WG_CONE() amax_cone = fmin(SC[SC_AMAXC], SC[SC_AMAXC2]);
         WG_ARRIVE(19);
-        const Red3 rd = wg_reduce(Red3{fmin(rmax > 0.0 ? rcp1(rmax) : 1e300, amax_cone), 0.0, 0.0}, sm + W::RED, red_phase);
+        const Red3 rd = wg_reduce<WG_VM>(Red3{fmin(rmax > 0.0 ? rcp1(rmax) : 1e300, amax_cone), 0.0, 0.0}, sm + W::RED, red_phase);
         WG_STAMP(19);
         WG_CONE() {      // step length with the cone guard (round-off must not push either cone point outside)
             double al = fmin(1.0, 0.99 * rd.mn);

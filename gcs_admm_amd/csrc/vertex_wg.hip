@@ -42,6 +42,24 @@ void GCS_WG_SYM(gcsadmm_wg_launch_prox)(const WgLaunchDesc &d, const double *q, 
         GCS_WG_SYM(gcsadmm_wg_launch_prox_dims)(d, q, c, src, dst, s);
 }
 
+#if GCS_WG_THREADS == 256
+// the split form (units in device memory), 256-thread build only
+hipError_t gcsadmm_wg_set_split_lds_dims(int n, int dtype, int lds_bytes);
+void gcsadmm_wg_launch_split_dims(const WgLaunchDesc &d, const WgSplitArgs &w, hipStream_t s);
+
+hipError_t gcsadmm_wg_set_split_lds(int n, int dtype, int lds_bytes)
+{
+    hipError_t e = hipSuccess;
+    if (dispatch_dim<2, 3, 6>(n, [&](auto nn) { e = set_split_lds_n<decltype(nn)::value>(dtype, lds_bytes); })) return e;
+    return gcsadmm_wg_set_split_lds_dims(n, dtype, lds_bytes);
+}
+
+void gcsadmm_wg_launch_split(const WgLaunchDesc &d, const WgSplitArgs &w, hipStream_t s)
+{
+    if (!dispatch_dim<2, 3, 6>(d.n, [&](auto nn) { launch_split_n<decltype(nn)::value>(d, w, s); })) gcsadmm_wg_launch_split_dims(d, w, s);
+}
+#endif
+
 #ifdef GCS_WG_TIMING
 extern "C" int gcsadmm_debug_wg_cycles(unsigned long long *cycles64, unsigned long long *counts64)
 {

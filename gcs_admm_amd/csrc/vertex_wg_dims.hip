@@ -26,3 +26,17 @@ void GCS_WG_SYM(gcsadmm_wg_launch_prox_dims)(const WgLaunchDesc &d, const double
 {
     dispatch_dim<1, 4, 5, 7, 8>(d.n, [&](auto nn) { launch_prox<decltype(nn)::value>(d, q, c, src, dst, s); });
 }
+
+#if GCS_WG_THREADS == 256
+hipError_t gcsadmm_wg_set_split_lds_dims(int n, int dtype, int lds_bytes)
+{
+    hipError_t e = hipErrorInvalidValue;
+    dispatch_dim<1, 4, 5, 7, 8>(n, [&](auto nn) { e = set_split_lds_n<decltype(nn)::value>(dtype, lds_bytes); });
+    return e;
+}
+
+void gcsadmm_wg_launch_split_dims(const WgLaunchDesc &d, const WgSplitArgs &w, hipStream_t s)
+{
+    dispatch_dim<1, 4, 5, 7, 8>(d.n, [&](auto nn) { launch_split_n<decltype(nn)::value>(d, w, s); });
+}
+#endif

@@ -71,6 +71,26 @@ __global__ __launch_bounds__(WG_THREADS, (wg_min_blocks<N, BOX>())) void vertex_
     }
 }
 
+// SPLIT form of the same program (wg_solve_vertex<N, T, BOX, true>): workgroup b solves vtx[b] with its units in the device-memory slab
+// units + unit_off[b] and only the fixed block and the polytope in LDS.  No closed-form vertices (they ride in the launch above), no
+// slowest-first dispatch, no per-vertex iteration record: the launch holds the few vertices too large for the in-LDS form.  Built in the
+// 256-thread objects only.  Its 64-bit unit addresses cost registers: at n = 8 the in-LDS bound (two waves per SIMD, 256 registers) spilled
+// 36 bytes, so n = 7, 8 take one wave per SIMD (the vertices of this launch are few, and their LDS alone rarely leaves room for a second).
+template <int N, bool BOX> constexpr int wg_split_min_blocks() { return N >= 7 ? 1 : wg_min_blocks<N, BOX>(); }
+template <int N, class T, bool BOX>
+__global__ __launch_bounds__(WG_THREADS, (wg_split_min_blocks<N, BOX>())) void vertex_wg_split_kernel(gcs_wg::WgArgs<T> a, WgSplitArgs w,
+                                                                                              const gcsadmm_control_block *cb)
+{
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    if (cb->status != GCSADMM_RUNNING) return;
+    int status = 0, iters = 0;
+    gcs_wg::wg_solve_vertex<N, T, BOX, true>(a, a.vtx[blockIdx.x], cb->rho, cb->mu_scale, smem, status, iters, w.units + w.unit_off[blockIdx.x]);
+    if (threadIdx.x == 0) {
+        if (status != 0) atomicAdd(&a.counters[0], 1);
+        atomicAdd(&a.counters[1], iters);
+    }
+}
+
 template <int N, class T> void launch(const WgLaunchDesc &d, hipStream_t s)
 {
     gcs_wg::WgArgs<T> a;
@@ -93,6 +113,37 @@ template <int N> void launch_n(const WgLaunchDesc &d, hipStream_t s)
 {
     if (d.dtype == GCSADMM_F64) launch<N, double>(d, s);
     else launch<N, float>(d, s);
+}
+
+template <int N, class T> void launch_split(const WgLaunchDesc &d, const WgSplitArgs &w, hipStream_t s)
+{
+    if (d.n_vtx <= 0) return;
+    gcs_wg::WgArgs<T> a;
+    static_cast<StepArgs<T> &>(a) = d.step.typed<T>();
+    a.n_vtx = d.n_vtx; a.vtx = d.vtx;
+    if constexpr (N == 3 || N == 6) {
+        if (d.box) { hipLaunchKernelGGL((vertex_wg_split_kernel<N, T, true>), dim3(d.n_vtx), dim3(WG_THREADS), d.lds_bytes, s, a, w, d.step.cb); return; }
+    }
+    hipLaunchKernelGGL((vertex_wg_split_kernel<N, T, false>), dim3(d.n_vtx), dim3(WG_THREADS), d.lds_bytes, s, a, w, d.step.cb);
+}
+
+template <int N> void launch_split_n(const WgLaunchDesc &d, const WgSplitArgs &w, hipStream_t s)
+{
+    if (d.dtype == GCSADMM_F64) launch_split<N, double>(d, w, s);
+    else launch_split<N, float>(d, w, s);
+}
+
+template <int N, class T> hipError_t set_split_lds(int lds_bytes)
+{
+    hipError_t e = hipFuncSetAttribute((const void *)vertex_wg_split_kernel<N, T, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
+    if constexpr (N == 3 || N == 6)
+        if (e == hipSuccess) e = hipFuncSetAttribute((const void *)vertex_wg_split_kernel<N, T, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
+    return e;
+}
+
+template <int N> hipError_t set_split_lds_n(int dtype, int lds_bytes)
+{
+    return dtype == GCSADMM_F64 ? set_split_lds<N, double>(lds_bytes) : set_split_lds<N, float>(lds_bytes);
 }
 
 // PROX configuration (admm_solver_v1.py:334-383): one workgroup per vertex, no edge blocks; the two trailing

@@ -19,6 +19,12 @@ struct WgLaunchDesc {
     int *unit_iters;                // [n_vtx] Newton iterations of each vertex's last solve; may be null
 };
 
+// the split form's device-memory workspace: the units of vtx[b] of the launch at units + unit_off[b] (256-byte aligned slabs)
+struct WgSplitArgs {
+    double *units;
+    const long long *unit_off;      // [n_vtx] offsets in doubles
+};
+
 }  // namespace gcsadmm_k
 
 // (LDS sizes of the program, gcsadmm_wg_lds_bytes / _t512 and gcsadmm_wg_has_box: create_plan.h, which is host-only)
@@ -30,6 +36,12 @@ void gcsadmm_wg_launch(const gcsadmm_k::WgLaunchDesc &d, hipStream_t s);
 // workgroup has a CU to itself (benchmark3 5 656 -> 6 244 it/s, benchmark4 7 590 -> 7 955), slower beyond (1 026 vertices: 5 763 -> 3 932)
 hipError_t gcsadmm_wg_set_lds_t512(int n, int dtype, int lds_bytes);
 void gcsadmm_wg_launch_t512(const gcsadmm_k::WgLaunchDesc &d, hipStream_t s);
+
+// the split form (vertex_wg_split_kernel; 256-thread objects only): d.vtx / d.n_vtx are the split vertices, d.lds_bytes the LDS of the
+// fixed block and the polytope (at least 48 KB needs the attribute below), d.box as for the in-LDS launch; d.n_special, d.order and
+// d.unit_iters are unused
+hipError_t gcsadmm_wg_set_split_lds(int n, int dtype, int lds_bytes);
+void gcsadmm_wg_launch_split(const gcsadmm_k::WgLaunchDesc &d, const gcsadmm_k::WgSplitArgs &w, hipStream_t s);
 
 // PROX configuration of the workgroup program (gcsadmm_vertex_prox): every vertex of `vtx` solves the border-only problem with
 // the separable quadratic (q, c) [V][4n+1]; the two terminals (points) are closed form.  zedge / mu / copy of `d` are unused.

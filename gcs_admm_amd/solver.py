@@ -25,7 +25,7 @@ STATUS_NAME = {RUNNING: "running", CONVERGED: "converged", MAX_IT: "max_it", DIV
 
 EXPORTS = ["gcsadmm_create", "gcsadmm_destroy", "gcsadmm_last_error", "gcsadmm_reset", "gcsadmm_vertex_step",
            "gcsadmm_edge_step", "gcsadmm_control", "gcsadmm_run", "gcsadmm_run_timed", "gcsadmm_read_control",
-           "gcsadmm_cost", "gcsadmm_query", "gcsadmm_unit_iterations", "gcsadmm_vertex_prox",
+           "gcsadmm_cost", "gcsadmm_query", "gcsadmm_query_workspace", "gcsadmm_unit_iterations", "gcsadmm_vertex_prox",
            # vertex partitions across GPUs (RCCL)
            "gcsadmm_comm_unique_id", "gcsadmm_check_halo", "gcsadmm_attach_comm", "gcsadmm_run_partitioned", "gcsadmm_halo_pack", "gcsadmm_halo_unpack",
            "gcsadmm_halo_exchange", "gcsadmm_halo_buffers", "gcsadmm_run_partitioned_timed", "gcsadmm_comm_count", "gcsadmm_set_overlap",
@@ -43,7 +43,9 @@ class GraphDesc(C.Structure):
                 ("nx_global", C.c_double), ("nmu_global", C.c_double),
                 # schedule of the vertex step (0 = automatic): see include/gcsadmm.h
                 ("vertex_program", C.c_int32), ("wave_slots", C.c_int32), ("wave_align", C.c_int32),
-                ("wave_store_dl", C.c_int32), ("wave_generic_rows", C.c_int32), ("edge_major_columns", C.c_int32)]
+                ("wave_store_dl", C.c_int32), ("wave_generic_rows", C.c_int32), ("edge_major_columns", C.c_int32),
+                # vertex sub-problems larger than LDS: 0 refused, 1 split form where needed, 2 split form everywhere
+                ("vertex_workspace", C.c_int32)]
 
 
 class Params(C.Structure):
@@ -127,12 +129,17 @@ class DeviceSolver:
     "edge": tail side of edge e in column e, head side in column E + e -- the edge step becomes a pure stream (the layout for
     large graphs, include/gcsadmm.h ``edge_major_columns``).  Arguments stay in incidence numbering either way; ``col_of``
     maps an incidence column to the state column, and ``copy[:, col_of]`` is the state in incidence order.
+
+    ``vertex_workspace``: vertices whose sub-problem does not fit a CU's LDS.  0 (default): refused.  1: solved with their edge
+    blocks in a device-memory workspace (include/gcsadmm.h ``vertex_workspace``).  2: every workgroup-program vertex that way
+    (tests, tuning).  ``query_workspace()`` reports what was placed there.
     """
 
     def __init__(self, graph: GcsGraph, state_dtype: str = "f64", device: Optional[int] = None,
                  num_incidences: Optional[int] = None, inc_counted=None, edge_counted=None,
                  nx_global: float = 0.0, nmu_global: float = 0.0, program: str = "auto", wave_slots: int = 0,
-                 wave_align: int = 0, wave_store_dl: int = 0, wave_generic_rows: int = 0, columns: str = "incidence"):
+                 wave_align: int = 0, wave_store_dl: int = 0, wave_generic_rows: int = 0, columns: str = "incidence",
+                 vertex_workspace: int = 0):
         import torch
         if not torch.cuda.is_available():
             raise RuntimeError("no HIP device visible: the ADMM loop only runs on the GPU (no CPU fallback)")
@@ -176,7 +183,7 @@ class DeviceSolver:
                          _np_ptr(ic) if ic is not None else None, _np_ptr(ec) if ec is not None else None,
                          float(nx_global), float(nmu_global),
                          {"auto": 0, "wavefront": 1, "workgroup": 2, "workgroup256": 3}[program], int(wave_slots), int(wave_align),
-                         int(wave_store_dl), int(wave_generic_rows), int(self.edge_major))
+                         int(wave_store_dl), int(wave_generic_rows), int(self.edge_major), int(vertex_workspace))
         h = C.c_void_p()
         st = self.lib.gcsadmm_create(C.byref(desc), C.byref(h))
         if st != 0:
@@ -375,6 +382,12 @@ class DeviceSolver:
         self._check(self.lib.gcsadmm_query(self.h, C.byref(a), C.byref(b), C.byref(c), C.byref(d), C.byref(e)), "gcsadmm_query")
         return dict(num_waves=a.value, lds_bytes=b.value, num_special=c.value, num_workgroup_vertices=d.value,
                     workgroup_lds_bytes=e.value)
+
+    def query_workspace(self):
+        """the split form of the workgroup program (``vertex_workspace``): its vertices, LDS per workgroup, device workspace bytes"""
+        a, b, c = C.c_int32(0), C.c_int32(0), C.c_int64(0)
+        self._check(self.lib.gcsadmm_query_workspace(self.h, C.byref(a), C.byref(b), C.byref(c)), "gcsadmm_query_workspace")
+        return dict(num_split_vertices=a.value, split_lds_bytes=b.value, workspace_bytes=c.value)
 
     def unit_iterations(self):
         """Newton iterations of the last vertex step per dispatch unit (empty for handles with fewer than 512 units)."""

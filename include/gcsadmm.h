@@ -42,7 +42,10 @@ extern "C" {
 typedef enum gcsadmm_status {
     GCSADMM_OK = 0,
     GCSADMM_ERR_BAD_ARG = 1,        /* null pointer, negative size, inconsistent CSR, unsupported n */
-    GCSADMM_ERR_UNSUPPORTED = 2,    /* a vertex whose sub-problem does not fit the CU's LDS; 's' / 't' that are not points */
+    GCSADMM_ERR_UNSUPPORTED = 2,    /* n outside 1 .. 8; a vertex whose sub-problem does not fit the CU's LDS (with vertex_workspace 0)
+                                       or whose border system and polytope do not (1, 2); a facet count too large for the wavefront
+                                       program (n = 2, vertex_workspace 0); a point terminal of degree above 256; a terminal that is a
+                                       region without an edge on its live side, or source and target the same region */
     GCSADMM_ERR_HIP = 3,            /* a HIP runtime call failed */
     GCSADMM_ERR_NO_DEVICE = 4
 } gcsadmm_status;
@@ -97,6 +100,13 @@ typedef struct gcsadmm_graph_desc {
      * traffic) and turns the vertex step's column accesses into gathers, which that latency-bound step does not feel:
      * the layout for large graphs.  Same numbers either way. */
     int32_t edge_major_columns;
+    /* Vertex sub-problems larger than LDS.  The workgroup program keeps a vertex's whole sub-problem in the CU's 160 KB of LDS.
+     * 0: a vertex whose sub-problem does not fit is refused (GCSADMM_ERR_UNSUPPORTED).  1: such vertices are solved in SPLIT form:
+     * the part that grows with the degree (one block per incident edge) lives in a device-memory workspace the handle allocates,
+     * LDS keeps the border system and the polytope; every other vertex is placed as with 0.  Also with 1, an n = 2 vertex whose
+     * facet count the wavefront program cannot hold goes to the workgroup program.  2: every workgroup-program vertex is solved in
+     * split form (tuning / tests).  Same numbers in either form.  gcsadmm_query_workspace reports the split. */
+    int32_t vertex_workspace;
 } gcsadmm_graph_desc;
 
 typedef struct gcsadmm_params {
@@ -177,7 +187,11 @@ gcsadmm_status gcsadmm_cost(gcsadmm_handle h, const gcsadmm_state *st, double ep
 gcsadmm_status gcsadmm_query(gcsadmm_handle h, int32_t *num_waves, int32_t *lds_bytes, int32_t *num_special,
                              int32_t *num_workgroup_vertices, int32_t *workgroup_lds_bytes);
 
-/* Diagnostics: Newton iterations of the last vertex step per dispatch unit (wavefronts of the wavefront program: the slowest vertex
+/* The split form of the workgroup program (gcsadmm_graph_desc.vertex_workspace; any pointer may be NULL): vertices solved in it, LDS
+ * bytes of one of its workgroups, bytes of the device-memory workspace that holds their edge blocks. */
+gcsadmm_status gcsadmm_query_workspace(gcsadmm_handle h, int32_t *num_split_vertices, int32_t *split_lds_bytes, int64_t *workspace_bytes);
+
+/* Diagnostics (the split form's vertices are not recorded): Newton iterations of the last vertex step per dispatch unit (wavefronts of the wavefront program: the slowest vertex
  * of each; otherwise workgroups = vertices of the workgroup program), for handles large enough to keep them (>= 512 units: the
  * slowest-first dispatch sorts by them; *count = 0 otherwise).  Synchronises `stream`; copies min(*count, capacity) entries. */
 gcsadmm_status gcsadmm_unit_iterations(gcsadmm_handle h, int32_t *out, int32_t capacity, int32_t *count, void *stream);
