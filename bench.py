@@ -1,12 +1,18 @@
 #!/usr/bin/env python3
 """bench.py -- ADMM iterations/sec of the MI355X loop, one JSON line on stdout.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload benchmark4|s10k|s100k|s6d] [--dump-outputs DIR]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload benchmark4|s10k|s100k|s6d] [--dump-outputs DIR] [--full]
 
 A "step" is one full ADMM iteration (vertex step, edge step, control: admm_solver_v3.py:655-733) on the resident state; K steps are
 enqueued back to back (no host round trip) between two synchronisation points.  The state is already in HBM when the timed region
 starts: the loop is first advanced, untimed, to `config.window.first_iteration` (the vertex solves restart from the previous
 iteration's records -- csrc/warm_start.h -- so the cost of an iteration depends on where in the run it lies).
+
+A plain run does only what the headline needs: it sets up, advances the loop to the window, runs the W warm-up and the K timed steps,
+writes --dump-outputs and prints the line (`value`, `ms_per_step`, `config`).  Everything else described below -- the whole run to the
+stop, the CPU oracle, the rooflines, the other configs, the sharded leg on one rank; at N > 1 the per-stage shares, the one-GPU
+comparison, the strip model and the benchmark4 replicas -- is measured only with --full (--no-cpu, --no-configs and --loop-only trim
+a --full run).
 
 N = 1 (default): the configuration BASELINE.json quotes its metric on, benchmark4 in f64.  The window is CENTRED on the run to the
 reference's own stop (465 iterations: no tuned parameter); `value_to_stop` is the rate over the WHOLE run from the zero state to the
@@ -432,10 +438,12 @@ def dry_launch(args):
     return 0
 
 
-def sharded_leg(args, rank, world, local, steps, warmup, out, with_single, dump=None):
+def sharded_leg(args, rank, world, local, steps, warmup, out, full, dump=None):
     """BASELINE config 4: ONE 316 x 317 lattice in `world` row strips, the loop behind the C ABI (gcsadmm_run_partitioned).  Collective:
     every rank calls it.  Returns (block, rank-0 extras) -- block is {} on ranks > 0.  `dump`: directory the timed loop's outputs
-    of this rank's strip are written to (dump_outputs, names suffixed with the rank, an equal share of the cap per rank)."""
+    of this rank's strip are written to (dump_outputs, names suffixed with the rank, an equal share of the cap per rank).  `full`:
+    also the per-stage shares (a replay of the window), the strip model and, at N > 1, the same lattice on one GPU; without it the
+    rank-0 extras `tm` and `pcb2` are None."""
     import numpy as np
     import torch
     import torch.distributed as dist
@@ -492,11 +500,12 @@ def sharded_leg(args, rank, world, local, steps, warmup, out, with_single, dump=
             arrays = loop_outputs(pdev, pfirst, warmup, steps)
             dump_outputs({f"{k}_rank{rank}": v for k, v in arrays.items()}, dump, cap=DUMP_CAP_BYTES // world)
         halo = float(sum(len(v) for v in part.send_idx.values()))
-        # per-stage device time of THIS rank over a replay of the window (events serialise nothing here: one stream)
-        pdev.reset(max_it=pfirst + warmup + steps + 1, eps_abs=0.0, eps_rel=0.0)
-        pdev.enqueue_partitioned(pfirst + warmup)
-        tm = pdev.enqueue_partitioned_timed(min(steps, 100))
-        pcb2 = pdev.read_control()
+        tm = pcb2 = None
+        if full:      # per-stage device time of THIS rank over a replay of the window (events serialise nothing here: one stream)
+            pdev.reset(max_it=pfirst + warmup + steps + 1, eps_abs=0.0, eps_rel=0.0)
+            pdev.enqueue_partitioned(pfirst + warmup)
+            tm = pdev.enqueue_partitioned_timed(min(steps, 100))
+            pcb2 = pdev.read_control()
         ranks_rccl = pdev.comm_count()
         boundary_waves = pdev.set_overlap(0)      # (reads back the automatic choice: > 0 when this rank has neighbours and runs the wavefront program)
         if world > 1:
@@ -507,7 +516,6 @@ def sharded_leg(args, rank, world, local, steps, warmup, out, with_single, dump=
             dist.all_reduce(cnt, op=dist.ReduceOp.MIN)
             ranks_rccl = int(cnt.item())
         if rank == 0:
-            tot = tm["vertex_ms"] + tm["halo_ms"] + tm["edge_ms"] + tm["reduce_ms"]
             q = pdev.query()
             block = {"workload": "s100k (316 x 317 box lattice, BASELINE config 4)", "V": gl.num_vertices, "E": gl.num_edges,
                      "partition": f"{world} row strip(s), one per GPU", "state_dtype": "f32", "scaling": "strong",
@@ -522,22 +530,24 @@ def sharded_leg(args, rank, world, local, steps, warmup, out, with_single, dump=
                      "path": "gcsadmm_run_partitioned (C ABI, RCCL on the caller's stream, no host synchronisation)",
                      "schedule": (f"overlapped: rank 0's {boundary_waves} boundary wavefronts first, halo exchange on a second stream while the interior is solved"
                                   if boundary_waves > 0 else "serial (no neighbours: nothing to overlap)"),
-                     "serial_schedule_iterations_per_sec": serial_rate,
-                     "rank0_stage_share": {"vertex_step": tm["vertex_ms"] / tot, "halo_exchange": tm["halo_ms"] / tot,
-                                           "edge_step": tm["edge_ms"] / tot, "all_reduce_and_control": tm["reduce_ms"] / tot,
-                                           "source": "HIP events around every stage on the launch stream, replay of the window on rank 0"},
-                     "rank0": {"V": part.graph.num_vertices, "E": part.graph.num_edges, "wavefronts": q["num_waves"],
-                               "newton_iterations_per_vertex": pcb2.inner_iters / max(part.graph.num_vertices - q["num_special"], 1)}}
-            if world > 1 and with_single:      # the same lattice on one GPU, same loop: the strong-scaling reference
-                sdev = DeviceSolver(gl, "f32", device=local, columns="edge")
-                sel = time_window(sdev, pfirst, warmup, steps)
-                block["single_gpu_iterations_per_sec"] = steps / sel
-                block["speedup_vs_1gpu"] = sel / pel
-                sdev.close()
-            try:
-                block["strip_model"] = strip_model(gl, local)
-            except Exception as exc:
-                block["strip_model"] = {"error": f"{type(exc).__name__}: {exc}"}
+                     "serial_schedule_iterations_per_sec": serial_rate}
+            if full:
+                tot = tm["vertex_ms"] + tm["halo_ms"] + tm["edge_ms"] + tm["reduce_ms"]
+                block["rank0_stage_share"] = {"vertex_step": tm["vertex_ms"] / tot, "halo_exchange": tm["halo_ms"] / tot,
+                                              "edge_step": tm["edge_ms"] / tot, "all_reduce_and_control": tm["reduce_ms"] / tot,
+                                              "source": "HIP events around every stage on the launch stream, replay of the window on rank 0"}
+                block["rank0"] = {"V": part.graph.num_vertices, "E": part.graph.num_edges, "wavefronts": q["num_waves"],
+                                  "newton_iterations_per_vertex": pcb2.inner_iters / max(part.graph.num_vertices - q["num_special"], 1)}
+                if world > 1:      # the same lattice on one GPU, same loop: the strong-scaling reference
+                    sdev = DeviceSolver(gl, "f32", device=local, columns="edge")
+                    sel = time_window(sdev, pfirst, warmup, steps)
+                    block["single_gpu_iterations_per_sec"] = steps / sel
+                    block["speedup_vs_1gpu"] = sel / pel
+                    sdev.close()
+                try:
+                    block["strip_model"] = strip_model(gl, local)
+                except Exception as exc:
+                    block["strip_model"] = {"error": f"{type(exc).__name__}: {exc}"}
             block["_rank0_partition"] = (part.graph, q, tm, pcb2)
     if watchdog is not None:
         watchdog.cancel()
@@ -570,8 +580,7 @@ def check_line(d):
     return True
 
 
-def main(argv=None):
-    argv = list(sys.argv[1:] if argv is None else argv)
+def parse_args(argv):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
@@ -583,16 +592,35 @@ def main(argv=None):
     ap.add_argument("--first", type=int, default=-1, help="ADMM iterations run untimed before the warm-up (default: benchmark4: the window is centred on "
                                                           "the run to the reference's stop; synthetic configs: a fixed start in the body of the run)")
     ap.add_argument("--cold-start", action="store_true", help="vertex solves from the fixed interior point every iteration (no warm start)")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-configs", action="store_true", help="default workload only: skip the configs.s10k / configs.s6d blocks")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beyond the headline too: kernel shares and rooflines, the runs to the stop, the CPU oracle on the "
+                         "same window, the configs.s10k / configs.s6d blocks and the sharded leg (at N > 1: the per-stage shares, the one-GPU "
+                         "comparison, the strip model and the benchmark4 replicas)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: no CPU oracle")
+    ap.add_argument("--no-configs", action="store_true", help="with --full, default workload only: skip the configs.s10k / configs.s6d blocks")
     ap.add_argument("--partition-timeout", type=int, default=240, help="seconds the sharded S100k leg may take at N > 1 before the line is printed without it")
     ap.add_argument("--loop-only", action="store_true",
-                    help="only the timed loop and the per-kernel timing (no convergence runs, no CPU baseline): the "
+                    help="with --full: only the timed loop and the per-kernel timing (no convergence runs, no CPU baseline): the "
                          "command to put under rocprofv3, so that its per-kernel averages cover the same launches as roofline.avg_launch_ms")
     ap.add_argument("--dry-launch", action="store_true", help="start the ranks and report what each one sees (RANK / WORLD_SIZE), no GPU work")
     ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the timed loop computed in its last step as "
                                                           "DIR/<name>.npy (at N > 1 every rank its own strip, <name>_rank<r>.npy)")
-    args = ap.parse_args(argv)
+    return ap.parse_args(argv)
+
+
+def print_line(out):
+    """check the contract, print the one JSON line"""
+    try:      # the contract is asserted, but a violation must not cost the measurement: the line is printed with the finding in it
+        check_line(out)
+    except (AssertionError, KeyError) as exc:
+        out["contract_violation"] = f"{type(exc).__name__}: {exc}"
+    print(json.dumps(out), flush=True)
+    return 0
+
+
+def main(argv=None):
+    argv = list(sys.argv[1:] if argv is None else argv)
+    args = parse_args(argv)
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
     if args.steps < 1 or args.warmup < 0:
@@ -650,6 +678,8 @@ def main(argv=None):
                       "seed": None if args.workload == "benchmark4" else 0,
                       "degree_histogram": {int(k): int(v) for k, v in zip(*np.unique(np.diff(g.inc_ptr), return_counts=True))},
                       "facets_histogram": {int(k): int(v) for k, v in zip(*np.unique(np.diff(g.poly_ptr), return_counts=True))}}}
+    if not args.full:      # a plain run: the headline only
+        return print_line(out)
     sv, se, cb_, _ = kernel_shares(dev, first, args.warmup, min(args.steps, 200))
     out.update(rooflines(g, dtype, q, program, args.workload, out["ms_per_step"], sv, se, cb_, columns, with_flops=not args.loop_only))
     # ---- matched convergence: the reference's own stop rule ----
@@ -712,21 +742,16 @@ def main(argv=None):
     # ---- the sharded path on one rank (same code, same RCCL calls as N > 1) ----
     if args.workload == "benchmark4" and not args.loop_only:
         try:
-            blk = sharded_leg(args, 0, 1, local, min(args.steps, 100), min(args.warmup, 10), out, with_single=False)
+            blk = sharded_leg(args, 0, 1, local, min(args.steps, 100), min(args.warmup, 10), out, full=True)
             blk.pop("_rank0_partition", None)
         except Exception as exc:
             blk = {"error": f"{type(exc).__name__}: {exc}"}
         out["partitioned_s100k"] = blk
-    try:      # the contract is asserted, but a violation must not cost the measurement: the line is printed with the finding in it
-        check_line(out)
-    except (AssertionError, KeyError) as exc:
-        out["contract_violation"] = f"{type(exc).__name__}: {exc}"
-    print(json.dumps(out), flush=True)
-    return 0
+    return print_line(out)
 
 
 def main_sharded(args, rank, world, local):
-    """N > 1 ranks: the headline is the sharded path (BASELINE config 4, strong scaling); benchmark4 replicas are a side field"""
+    """N > 1 ranks: the headline is the sharded path (BASELINE config 4, strong scaling); benchmark4 replicas are a side field (--full)"""
     import numpy as np
     import torch
     import torch.distributed as dist
@@ -734,7 +759,7 @@ def main_sharded(args, rank, world, local):
     out = {"metric": "admm_iterations_per_sec", "value": 0.0, "unit": "iterations/s", "n_gpus": world,
            "steps": args.steps, "warmup": args.warmup, "ms_per_step": 0.0, "higher_is_better": True, "scaling": "strong",
            "vs_baseline": None, "dtype": "f64 (interior point) on f32 state", "data": "synthetic"}
-    block = sharded_leg(args, rank, world, local, args.steps, args.warmup, out, with_single=True, dump=args.dump_outputs)
+    block = sharded_leg(args, rank, world, local, args.steps, args.warmup, out, full=args.full, dump=args.dump_outputs)
     rc = 0
     if rank == 0:
         if "error" in block:
@@ -750,34 +775,36 @@ def main_sharded(args, rank, world, local):
                              "inner_arithmetic": "f64", "ipm_tol": IPM_TOL, "vertex_program": "wavefront",
                              "window": block["window"], "parallelism": f"vertex partition: {world} row strips, one per GPU; RCCL halo exchange "
                                                                        "+ all-reduce of 6 f64 per iteration (gcsadmm_run_partitioned)", "seed": 0}
-            out["value_1gpu_same_workload"] = block.get("single_gpu_iterations_per_sec")
-            out["speedup_vs_1gpu"] = block.get("speedup_vs_1gpu")
-            # roofline of the dominant kernel on rank 0: its strip's algorithmic bytes per vertex-step launch over that launch's time
-            tot = tm["vertex_ms"] + tm["halo_ms"] + tm["edge_ms"] + tm["reduce_ms"]
-            v_ms = out["ms_per_step"] * tm["vertex_ms"] / tot
-            alg = pg.algorithmic_bytes_per_iteration(4)
-            ach = alg / (v_ms * 1e-3) / 1e9
-            out["roofline"] = {"bound": "hbm", "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": ach / HBM_PEAK_GBS, "traffic": None,
-                               "kernel": "vertex_kernel<2> (rank 0's strip)", "avg_launch_ms": v_ms,
-                               "avg_launch_ms_source": "ms_per_step x the vertex step's share of rank 0's device time (HIP events around every stage, replay of the window)",
-                               "algorithmic_bytes_per_launch": alg, "waves": q["num_waves"],
-                               "note": "per-rank figure; the vertex step is bound by dependent f64 issue, not by HBM (DESIGN.md section 4)"}
+            if args.full:
+                out["value_1gpu_same_workload"] = block.get("single_gpu_iterations_per_sec")
+                out["speedup_vs_1gpu"] = block.get("speedup_vs_1gpu")
+                # roofline of the dominant kernel on rank 0: its strip's algorithmic bytes per vertex-step launch over that launch's time
+                tot = tm["vertex_ms"] + tm["halo_ms"] + tm["edge_ms"] + tm["reduce_ms"]
+                v_ms = out["ms_per_step"] * tm["vertex_ms"] / tot
+                alg = pg.algorithmic_bytes_per_iteration(4)
+                ach = alg / (v_ms * 1e-3) / 1e9
+                out["roofline"] = {"bound": "hbm", "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": ach / HBM_PEAK_GBS, "traffic": None,
+                                   "kernel": "vertex_kernel<2> (rank 0's strip)", "avg_launch_ms": v_ms,
+                                   "avg_launch_ms_source": "ms_per_step x the vertex step's share of rank 0's device time (HIP events around every stage, replay of the window)",
+                                   "algorithmic_bytes_per_launch": alg, "waves": q["num_waves"],
+                                   "note": "per-rank figure; the vertex step is bound by dependent f64 issue, not by HBM (DESIGN.md section 4)"}
             out["partitioned_s100k"] = block
-    # ---- side field: N independent replicas of benchmark4 (it does not shard) ----
-    try:
-        g, dtype, _ = make_workload("benchmark4")
-        dev = DeviceSolver(g, dtype, device=local)
-        first = window_start("benchmark4", args.warmup, args.steps)
-        el = time_window(dev, first, args.warmup, args.steps, barrier=dist.barrier)
-        t = torch.tensor([el], dtype=torch.float64, device="cuda")
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        if rank == 0:
-            out["replicas_benchmark4"] = {"iterations_per_sec_all_replicas": args.steps / float(t.item()) * world, "replicas": world,
-                                          "note": "throughput of N independent instances of the 42-vertex benchmark4 (no collective): not a scaling result"}
-        dev.close()
-    except Exception as exc:
-        if rank == 0:
-            out["replicas_benchmark4"] = {"error": f"{type(exc).__name__}: {exc}"}
+    # ---- side field (--full): N independent replicas of benchmark4 (it does not shard) ----
+    if args.full:
+        try:
+            g, dtype, _ = make_workload("benchmark4")
+            dev = DeviceSolver(g, dtype, device=local)
+            first = window_start("benchmark4", args.warmup, args.steps)
+            el = time_window(dev, first, args.warmup, args.steps, barrier=dist.barrier)
+            t = torch.tensor([el], dtype=torch.float64, device="cuda")
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            if rank == 0:
+                out["replicas_benchmark4"] = {"iterations_per_sec_all_replicas": args.steps / float(t.item()) * world, "replicas": world,
+                                              "note": "throughput of N independent instances of the 42-vertex benchmark4 (no collective): not a scaling result"}
+            dev.close()
+        except Exception as exc:
+            if rank == 0:
+                out["replicas_benchmark4"] = {"error": f"{type(exc).__name__}: {exc}"}
     if rank == 0:
         if rc == 0:
             try:

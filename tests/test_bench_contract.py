@@ -1,6 +1,6 @@
 """The driver's contract for bench.py, checked on bench.py itself: `--gpus N` really starts N ranks (CPU, gloo), the like-for-like CPU
 column times the window it says it times (tiny fixture, CPU), `check_line` -- the assertions bench.py runs on its own line before
-printing -- holds on the committed lines of the last profile run, and (GPU) on a line produced live."""
+printing -- holds on the committed lines of the last profile run, and (GPU) on lines produced live, plain and with --full."""
 from gcs_admm_amd import IPM_TOL
 import glob
 import json
@@ -110,11 +110,33 @@ def test_check_line_rejects_a_broken_line():
             bench.check_line(bad)
 
 
+def test_full_is_off_by_default():
+    """a plain run measures the headline only; everything else is asked for with --full, which the trimming options refine"""
+    import bench
+    plain = bench.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "5"])
+    assert plain.full is False and not (plain.no_cpu or plain.no_configs or plain.loop_only)
+    assert bench.parse_args(["--full", "--no-configs"]).full is True
+
+
+@pytest.mark.gpu
+def test_plain_bench_line_is_the_headline_only():
+    """the driver's plain command, live: the contract holds and none of what --full measures is in the line"""
+    import bench
+    rc, d, err = _run_bench("--gpus", "1", "--steps", "20", "--warmup", "5", timeout=300)
+    assert rc == 0, err[-3000:]
+    assert bench.check_line(d) and "contract_violation" not in d and d["n_gpus"] == 1 and d["steps"] == 20 and d["warmup"] == 5
+    assert d["config"]["workload"] == "benchmark4" and d["dtype"] == "f64" and d["value"] > 0
+    full_only = {"roofline", "roofline_fp", "roofline_edge", "value_to_stop", "convergence", "iters_to_eps", "reference_published",
+                 "cpu_baseline", "gpu_over_cpu_same_window", "configs", "partitioned_s100k"}
+    assert not full_only & set(d), sorted(full_only & set(d))
+
+
 @pytest.mark.gpu
 def test_live_bench_line_holds_the_contract():
-    """the driver's command, live (headline only): bench.py asserts check_line itself before printing; here once more from outside"""
+    """the driver's command with --full, live (without the configs blocks): bench.py asserts check_line itself before printing; here
+    once more from outside"""
     import bench
-    rc, d, err = _run_bench("--gpus", "1", "--steps", "20", "--warmup", "5", "--no-configs", timeout=900)
+    rc, d, err = _run_bench("--gpus", "1", "--steps", "20", "--warmup", "5", "--full", "--no-configs", timeout=900)
     assert rc == 0, err[-3000:]
     assert bench.check_line(d) and d["n_gpus"] == 1 and d["config"]["workload"] == "benchmark4"
     assert d["cpu_baseline"]["window"] == {k: d["config"]["window"][k] for k in ("first_iteration", "last_iteration")}

@@ -1,5 +1,5 @@
 """Development probe: idle time between consecutive kernels of the loop, from a rocprofv3 --kernel-trace csv
-(rocprofv3 --kernel-trace --output-format csv -d DIR -- python3 bench.py --loop-only ...; python3 tools/kernel_gaps.py DIR)."""
+(rocprofv3 --kernel-trace --output-format csv -d DIR -- python3 bench.py --full --loop-only ...; python3 tools/kernel_gaps.py DIR)."""
 import csv, glob, sys
 import numpy as np
 f = glob.glob(sys.argv[1] + "/**/*kernel_trace.csv", recursive=True)[0]
