@@ -25,7 +25,7 @@ DEPS = [MAIN, HDR] + _c("vertex_program.h", "vertex_program.inc", "vertex_kernel
 UNIT_DEPS = {LP: [LP, HDR] + _c("polytope_lp_core.h"),
              WG: [WG, HDR] + _c("vertex_wg.h", "vertex_wg_kernel.h", "vertex_wg_launch.h", "special_vertex.h", "gcs_math.h", "warm_start.h", "step_args.h")}
 UNIT_DEPS[WGD] = [WGD] + UNIT_DEPS[WG][1:]
-UNIT_DEPS[TERM] = [TERM, HDR] + _c("terminal_region.h", "terminal_launch.h", "gcs_math.h", "step_args.h")
+UNIT_DEPS[TERM] = [TERM, HDR] + _c("terminal_region.h", "terminal_launch.h", "gcs_math.h", "warm_start.h", "step_args.h")
 OUT = os.path.join(HERE, "libgcsadmm.so")
 
 

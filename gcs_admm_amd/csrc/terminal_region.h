@@ -27,6 +27,7 @@
 
 #include "gcs_math.h"
 #include "step_args.h"
+#include "warm_start.h"
 
 namespace gcs_term {
 
@@ -35,12 +36,9 @@ using gcs_math::sqrt_nr;
 // a / b and sqrt in the serial (thread 0) parts: refined hardware estimates on the device (gcs_math.h), IEEE on the host
 GCS_HD double fdiv(double a, double b) { return a * rcp(b); }
 
-constexpr double TERM_REG = 1e-7;         // Tikhonov term on every unknown, as in the vertex programs (REG_DELTA)
-constexpr double TERM_CHOL_SKIP = 1e-12;  // pivot floor relative to the diagonal entry, as in the vertex programs
 // warm start: the rule and the constants of the vertex programs (warm_start.h) with a fixed threshold.  Record of a terminal, in doubles:
 //   [0] valid [1] rho [2] live blocks [3] nu | per live block: p (2n+1) | targets (2n+1) | row duals (2m)
 // (t and the cone's dual are re-centred at the restart: t^2 - mu_ref t - |u|^2 = 0, lambda = (1, -u / t); not kept)
-constexpr double TERM_WS_KAPPA = 3e-3, TERM_WS_MU_MIN = 1e-7, TERM_WS_COLD_DT = 1.0, TERM_WS_SAVE = 10.0, TERM_WS_COLD_REF = 1e-4;
 constexpr int TERM_W_HDR = 4;
 inline long long terminal_record_doubles(int n, int m, int L) { return TERM_W_HDR + (long long)L * (2 * (2 * n + 1) + 2 * m); }
 
@@ -141,8 +139,8 @@ GCS_HD int terminal_region_solve(EX &ex, const TermProblem<T> &P, double *ws, Te
         ex.reduce3(neg, u1, u2);
         const double dT = -neg * P.rho;
         if (tid == 0) {
-            sh.use_warm = comparable && dT <= TERM_WS_COLD_DT;
-            sh.mu_ref = sh.use_warm ? fmax(TERM_WS_MU_MIN, TERM_WS_KAPPA * dT) : TERM_WS_COLD_REF;
+            sh.use_warm = comparable && dT <= gcs_ws::WS_COLD_DT;
+            sh.mu_ref = sh.use_warm ? fmax(gcs_ws::WS_MU_MIN, gcs_ws::WS_KAPPA * dT) : gcs_ws::WS_COLD_REF;
         }
     }
     ex.sync();
@@ -164,11 +162,11 @@ GCS_HD int terminal_region_solve(EX &ex, const TermProblem<T> &P, double *ws, Te
         if (use_warm) {
             double u[N], uu = 0;
             for (int k = 0; k < N; ++k) { double a = 0; for (int e = 0; e < L; ++e) a += pp[e * NW + k] - pp[e * NW + N + k]; u[k] = a; uu += a * a; }
-            sh.t = 0.5 * (sh.mu_ref + sqrt(sh.mu_ref * sh.mu_ref + 4.0 * uu));
+            sh.t = 0.5 * (sh.mu_ref + sqrt(sh.mu_ref * sh.mu_ref + 4.0 * uu));      // (IEEE sqrt: the vertex programs' re-centring uses sqrt_nr)
             sh.lsoc[0] = 1.0;
             for (int k = 0; k < N; ++k) sh.lsoc[1 + k] = -u[k] / sh.t;
             sh.nu = rec[3];
-        } else { sh.t = 1.0; sh.nu = 0.0; sh.mu_ref = TERM_WS_COLD_REF; }
+        } else { sh.t = 1.0; sh.nu = 0.0; sh.mu_ref = gcs_ws::WS_COLD_REF; }
     }
     ex.sync();
     // one Newton solve with the multipliers kap (rows) / sh.ksoc (cone) in place of the duals: leaves dp, ds, sh.dssoc, sh.dt, sh.dnu
@@ -178,7 +176,7 @@ GCS_HD int terminal_region_solve(EX &ex, const TermProblem<T> &P, double *ws, Te
         for (int idx = tid; idx < L * NW; idx += nt) {
             const int e = idx / NW, k = idx - e * NW;
             const double *ke = kap + e * R;
-            double a = -(qd[idx] * (pp[idx] - tg[idx]) + TERM_REG * pp[idx]);
+            double a = -(qd[idx] * (pp[idx] - tg[idx]) + gcs_math::REG_DELTA * pp[idx]);
             if (k < 2 * N) {
                 const int i = k < N ? 0 : 1, kk = k - i * N;
                 for (int j = 0; j < m; ++j) a -= A[j * N + kk] * ke[i * m + j];
@@ -306,8 +304,9 @@ GCS_HD int terminal_region_solve(EX &ex, const TermProblem<T> &P, double *ws, Te
                 for (int k = 0; k < Q; ++k) gap += sh.ssoc[k] * sh.lsoc[k];
                 sh.gap = gap; sh.mu = gap / deg;
                 // the record the next solve restarts from: the first iterate, after at least one Newton step, with mu <= SAVE * mu_ref
-                sh.save_now = rec != nullptr && !sh.saved && it >= 1 && sh.mu <= TERM_WS_SAVE * sh.mu_ref;
+                sh.save_now = rec != nullptr && !sh.saved && it >= 1 && sh.mu <= gcs_ws::WS_SAVE * sh.mu_ref;
                 if (sh.save_now) { sh.saved = 1; rec[0] = 1.0; rec[1] = P.rho; rec[2] = (double)L; rec[3] = sh.nu; }
+                // (gcs_math::mu_converged spelled out: as a call argument sh.stalled would be loaded before the mu test)
                 if (!first_warm && (sh.mu <= P.ipm_tol || (sh.stalled && sh.mu <= 1e3 * P.ipm_tol))) {
                     sh.status = (use_warm && !(sh.mu <= P.ipm_tol)) ? -7 : 0;      // (a warm solve does not leave through the precision-exhausted rule)
                     sh.stop = 1;
@@ -316,8 +315,9 @@ GCS_HD int terminal_region_solve(EX &ex, const TermProblem<T> &P, double *ws, Te
                 else {
                     // Nesterov-Todd scaling of the cone pair, W^{-2}, the scaled point; t eliminated in closed form:
                     // W^{-2} = [c0 cv'; cv Mu],  Su = Mu - cv cv' / c0 = eta^-2 (I - 2 wb1 wb1' / (2 wb0^2 - 1))
+                    // (not gcs_math::soc_scaling_wb: 1 / (2 gamma) and eta are rounded differently here)
                     const double ss = gcs_math::soc_det<Q>(sh.ssoc), zz = gcs_math::soc_det<Q>(sh.lsoc);
-                    if (!(ss > 0.0) || !(zz > 0.0)) { sh.status = (sh.mu <= 1e3 * P.ipm_tol && !use_warm) ? 0 : -4; sh.stop = 1; }
+                    if (!(ss > 0.0) || !(zz > 0.0)) { sh.status = gcs_math::boundary_status(sh.mu, P.ipm_tol, use_warm); sh.stop = 1; }
                     else {
                         const double is = gcs_math::rsqrt_nr(ss), iz = gcs_math::rsqrt_nr(zz);
                         double dot = 0, wb[Q];
@@ -358,7 +358,7 @@ GCS_HD int terminal_region_solve(EX &ex, const TermProblem<T> &P, double *ws, Te
         // ---- block Hessians  H_e = Q_e + REG + sum_rows (lam / s) g g',  g = (a_j on [O]_i, -b_j on y)
         for (int idx = tid; idx < L * NW * NW; idx += nt) {
             const int e = idx / (NW * NW), ac = idx - e * NW * NW, a = ac / NW, c = ac - a * NW;
-            double v = a == c ? qd[e * NW + a] + TERM_REG : 0.0;
+            double v = a == c ? qd[e * NW + a] + gcs_math::REG_DELTA : 0.0;
             const int ia = a < N ? 0 : (a < 2 * N ? 1 : 2), ic = c < N ? 0 : (c < 2 * N ? 1 : 2);
             const double *De = dl + e * R;
             if (ia == 2 && ic == 2) {
@@ -382,8 +382,7 @@ GCS_HD int terminal_region_solve(EX &ex, const TermProblem<T> &P, double *ws, Te
                 const double d0 = Le[j * NW + j];       // (column j is untouched until now: the entry of H itself)
                 double dj = d0;
                 for (int k = 0; k < j; ++k) dj -= Le[j * NW + k] * Le[j * NW + k];
-                if (!(dj > TERM_CHOL_SKIP * d0)) dj = d0 > 0 ? TERM_CHOL_SKIP * d0 : 1.0;
-                const double inv = 1.0 / sqrt(dj);
+                const double inv = 1.0 / sqrt(gcs_math::pivot_floor(dj, d0));
                 Le[j * NW + j] = inv;
                 for (int i = j + 1; i < NW; ++i) {
                     double sv = Le[i * NW + j];
@@ -434,9 +433,7 @@ GCS_HD int terminal_region_solve(EX &ex, const TermProblem<T> &P, double *ws, Te
             amax = fmin(amax, fmin(gcs_math::soc_max_step<Q>(sh.ssoc, sh.dssoc), gcs_math::soc_max_step<Q>(sh.lsoc, sh.dlsoc)));
             for (int k = 0; k < Q; ++k) { c1 += sh.ssoc[k] * sh.dlsoc[k] + sh.lsoc[k] * sh.dssoc[k]; c2 += sh.dssoc[k] * sh.dlsoc[k]; }
             const double al_aff = fmin(1.0, amax);
-            double sig = fdiv(sh.gap + al_aff * c1 + al_aff * al_aff * c2, deg * sh.mu);
-            sig = sig < 0 ? 0 : (sig > 1 ? 1 : sig);
-            sh.sm = sig * sig * sig * sh.mu;
+            sh.sm = gcs_math::centring(fdiv(sh.gap + al_aff * c1 + al_aff * al_aff * c2, deg * sh.mu)) * sh.mu;
             // cone: kappa = sigma mu s^{-1} - W^{-1} (lt \ ((W^{-1} ds_a) o (W dl_a)))
             double a1[Q], a2[Q], pr[Q], qv[Q];
             for (int i = 0; i < Q; ++i) {
@@ -465,14 +462,14 @@ GCS_HD int terminal_region_solve(EX &ex, const TermProblem<T> &P, double *ws, Te
         if (tid == 0) {
             for (int i = 0; i < Q; ++i) { double a = sh.ksoc[i] - sh.lsoc[i]; for (int k = 0; k < Q; ++k) a -= sh.W2[i * Q + k] * sh.dssoc[k]; sh.dlsoc[i] = a; }
             amax = fmin(amax, fmin(gcs_math::soc_max_step<Q>(sh.ssoc, sh.dssoc), gcs_math::soc_max_step<Q>(sh.lsoc, sh.dlsoc)));
-            double al = fmin(1.0, 0.99 * amax);
+            double al = gcs_math::step_length(amax);
             for (int tries = 0; tries < 40; ++tries) {      // keep both cone points strictly inside despite round-off
                 double s2[Q], l2[Q];
                 for (int k = 0; k < Q; ++k) { s2[k] = sh.ssoc[k] + al * sh.dssoc[k]; l2[k] = sh.lsoc[k] + al * sh.dlsoc[k]; }
                 if (gcs_math::soc_interior<Q>(s2) && gcs_math::soc_interior<Q>(l2)) break;
                 al *= 0.7;
             }
-            sh.al = al; sh.stalled = al < 1e-3;
+            sh.al = al; sh.stalled = gcs_math::step_stalled(al);
             sh.t += al * sh.dt; sh.nu += al * sh.dnu;
             for (int k = 0; k < Q; ++k) sh.lsoc[k] += al * sh.dlsoc[k];
             if (sh.status == -5) sh.stop = 1;

@@ -65,62 +65,16 @@ template <int N> GCS_HD double amul2(double x, int j, int k, int l) { const int 
 constexpr int WAVE = 64;
 constexpr int FIXED_FACETS = GCS_MFIX;   // 0: any facet count, facet-row duals in LDS; m: exactly m facets, duals in registers
 constexpr int MAX_SLOTS = 7;     // vertices per wavefront
-constexpr double CHOL_SKIP = 1e-12;
-// Tikhonov term (REG_DELTA/2)|w|^2 on every centred unknown (see oracle/gcs_oracle.c REG_DELTA)
-constexpr double REG_DELTA = 1e-7;
 
-// reciprocal: on the device the hardware estimate refined by two Newton steps (the IEEE division
-// sequence costs ~3x as many instructions and the kernel does ~100 of these per Newton iteration)
-GCS_HD double rcp(double x)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    double r = __builtin_amdgcn_rcp(x);
-    r = fma(fma(-x, r, 1.0), r, r);
-    r = fma(fma(-x, r, 1.0), r, r);
-    return r;
-#else
-    return 1.0 / x;
-#endif
-}
-
-// one Newton step only (relative error ~2e-15; the raw estimate has ~4.6e-8, tools/micro/rcp_accuracy.hip): for
-// the slack reciprocals of the facet-row passes and for step-length ratios
-GCS_HD double rcp1(double x)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    const double r = __builtin_amdgcn_rcp(x);
-    return fma(fma(-x, r, 1.0), r, r);
-#else
-    return 1.0 / x;
-#endif
-}
-
-// reciprocal square root: hardware estimate + two Newton steps on the device (replaces an IEEE sqrt followed
-// by a reciprocal in every Cholesky pivot: ~10 instead of ~35 dependent instructions)
-GCS_HD double rsqrt_nr(double x)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    double r = __builtin_amdgcn_rsq(x);
-    r = fma(0.5 * r, fma(-x * r, r, 1.0), r);
-    r = fma(0.5 * r, fma(-x * r, r, 1.0), r);
-    return r;
-#else
-    return 1.0 / sqrt(x);
-#endif
-}
-
-// square root from the refined reciprocal root plus one Heron correction (an IEEE sqrt is ~140 dependent cycles)
-GCS_HD double sqrt_nr(double x)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    if (!(x > 0.0)) return x < 0.0 ? __builtin_nan("") : x;   // 0 -> 0, NaN -> NaN
-    const double r = rsqrt_nr(x);
-    const double y = x * r;
-    return fma(0.5 * r, fma(-y, y, x), y);
-#else
-    return sqrt(x);
-#endif
-}
+// the numerics shared with the workgroup program and the region terminals
+using gcs_math::REG_DELTA;
+using gcs_math::rcp;
+using gcs_math::rcp1;
+using gcs_math::rsqrt_nr;
+using gcs_math::sqrt_nr;
+using gcs_math::soc_det;
+using gcs_math::soc_interior;
+using gcs_math::soc_max_step;
 
 GCS_HD constexpr int PK(int i, int j) { return i >= j ? i * (i + 1) / 2 + j : j * (j + 1) / 2 + i; }
 
@@ -207,9 +161,7 @@ GCS_HD int lds_doubles(int n, int mm, int slots, int store_dl)
 // ---------------------------------------------------------------------------------------------
 template <int NN> GCS_HD void chol_packed(double (&A)[NN * (NN + 1) / 2])
 {
-    // Pivots that have cancelled below CHOL_SKIP of their own diagonal entry are round-off, not
-    // curvature: they are clamped to that floor (same rule as oracle/gcs_oracle.c chol()).
-    double diag[NN];
+    double diag[NN];   // the pivot floor is relative to the original diagonal entry
 #pragma unroll
     for (int j = 0; j < NN; ++j) diag[j] = A[PK(j, j)];
 #pragma unroll
@@ -217,13 +169,7 @@ template <int NN> GCS_HD void chol_packed(double (&A)[NN * (NN + 1) / 2])
         double d = A[PK(j, j)];
 #pragma unroll
         for (int k = 0; k < j; ++k) d -= A[PK(j, k)] * A[PK(j, k)];
-        if (!(d > CHOL_SKIP * diag[j])) {
-#if !defined(__HIPCC__) && defined(GCS_EMU_TRACE)
-            if (getenv("GCS_EMU_TRACE")) fprintf(stderr, "clamp NN=%d j=%d d=%.3e diag=%.3e\n", NN, j, d, diag[j]);
-#endif
-            d = diag[j] > 0.0 ? CHOL_SKIP * diag[j] : 1.0;
-        }
-        const double inv = rsqrt_nr(d);
+        const double inv = rsqrt_nr(gcs_math::pivot_floor(d, diag[j]));
         A[PK(j, j)] = inv;          // the diagonal holds 1 / L_jj
 #pragma unroll
         for (int i = j + 1; i < NN; ++i) {
@@ -285,58 +231,10 @@ template <int NN> GCS_HD void chol_inverse_packed(const double (&L)[NN * (NN + 1
 // ---------------------------------------------------------------------------------------------
 // second-order cone of dimension Q = N+1
 // ---------------------------------------------------------------------------------------------
-template <int Q> GCS_HD double soc_det(const double *s)
-{
-    double nn = 0;
-#pragma unroll
-    for (int k = 1; k < Q; ++k) nn += s[k] * s[k];
-    nn = sqrt_nr(nn);
-    return (s[0] - nn) * (s[0] + nn);
-}
-template <int Q> GCS_HD bool soc_interior(const double *s)
-{
-    double nn = 0;
-#pragma unroll
-    for (int k = 1; k < Q; ++k) nn += s[k] * s[k];
-    return s[0] > sqrt_nr(nn);
-}
-template <int Q> GCS_HD double soc_max_step(const double *s, const double *ds)
-{
-    double a = ds[0] * ds[0], b = s[0] * ds[0];
-    const double c = soc_det<Q>(s);
-#pragma unroll
-    for (int k = 1; k < Q; ++k) { a -= ds[k] * ds[k]; b -= s[k] * ds[k]; }
-    b *= 2;
-    double al = 1e300;
-    if (ds[0] < 0) al = fmin(al, -s[0] * rcp(ds[0]));
-    if (fabs(a) < 1e-300) {
-        if (b < 0) al = fmin(al, -c * rcp(b));
-    } else {
-        const double disc = b * b - 4 * a * c;
-        if (disc >= 0) {
-            const double sq = sqrt_nr(disc);
-            const double qq = -0.5 * (b + (b >= 0 ? sq : -sq));
-            const double r1 = qq * rcp(a), r2 = (qq != 0.0) ? c * rcp(qq) : 1e300;
-            if (r1 > 0) al = fmin(al, r1);
-            if (r2 > 0) al = fmin(al, r2);
-        }
-    }
-    return al;
-}
 // Nesterov-Todd scaling W (symmetric, full QxQ): W lam = W^{-1} s.  Returns false on a boundary point.
 template <int Q> GCS_HD bool soc_scaling(const double *s, const double *z, double *W, double *Wi, double *wb, double &eta)
 {
-    const double ss = soc_det<Q>(s), zz = soc_det<Q>(z);
-    if (!(ss > 0.0) || !(zz > 0.0)) return false;
-    const double is = rsqrt_nr(ss), iz = rsqrt_nr(zz);
-    double dot = 0;
-#pragma unroll
-    for (int k = 0; k < Q; ++k) dot += (s[k] * is) * (z[k] * iz);
-    const double ig2 = 0.5 * rsqrt_nr(0.5 * (1.0 + dot));   // 1 / (2 gamma)
-    wb[0] = (s[0] * is + z[0] * iz) * ig2;
-#pragma unroll
-    for (int k = 1; k < Q; ++k) wb[k] = (s[k] * is - z[k] * iz) * ig2;
-    eta = sqrt_nr((ss * is) * iz);   // (ss / zz)^(1/4)
+    if (!gcs_math::soc_scaling_wb<Q>(s, z, wb, eta)) return false;
     const double ieta = rcp(eta), i1w0 = rcp(1.0 + wb[0]);
 #pragma unroll
     for (int i = 0; i < Q; ++i)
@@ -365,9 +263,6 @@ template <int N> struct Lane {
     int role, slot, d, d_in, glane, m;
     int out;                       // block lanes: 1 = outgoing.  (Vertex id, incidence slot and edge id are needed
                                    // at load and write-out only: recomputed there by lane_ids, not held in registers.)
-#if !defined(__HIPCC__)
-    int v;                         // host emulation: for the trace output
-#endif
     // unknowns of this lane: p = O_e (block) or z_v (border); yy = y_e or y_v
     double p[D::N2], yy;
     double dpa[D::NW], dp[D::NW];  // affine and final Newton directions of (p, yy)
@@ -592,13 +487,7 @@ template <int N> GCS_HD void block_factor(Lane<N> &L)
     double dy = L.kyy;
 #pragma unroll
     for (int k = 0; k < N; ++k) dy -= l1[k] * l1[k] + l2[k] * l2[k];
-    if (!(dy > CHOL_SKIP * L.kyy)) {
-#if !defined(__HIPCC__) && defined(GCS_EMU_TRACE)
-        if (getenv("GCS_EMU_TRACE")) fprintf(stderr, "clamp ypivot dy=%.3e kyy=%.3e\n", dy, L.kyy);
-#endif
-        dy = L.kyy > 0.0 ? CHOL_SKIP * L.kyy : 1.0;
-    }
-    const double isy = rcp(dy);
+    const double isy = rcp(gcs_math::pivot_floor(dy, L.kyy));
     // u_i = K_i^{-1} k_iy = L_i^{-T} l_i
     double u1[N], u2[N];
 #pragma unroll
@@ -853,9 +742,6 @@ GCS_HD void border_factor_and_affine(Lane<N> &L, const WaveShared &S, const Slot
     for (int k = 0; k < D::Q; ++k) gap += ssoc[k] * (sl + SlotLayout<N>::LSOC)[k];
     const double mu = gap * rcp((double)deg);
     sl[SlotLayout<N>::SC + 5] = mu;
-#if !defined(__HIPCC__) && defined(GCS_EMU_TRACE)
-    if (getenv("GCS_EMU_TRACE")) fprintf(stderr, "v %d it %d mu %.17g\n", L.v, L.iters, mu);
-#endif
     double rp[2][D::NW];
     double rpmax = 0;
 #pragma unroll
@@ -873,6 +759,7 @@ GCS_HD void border_factor_and_affine(Lane<N> &L, const WaveShared &S, const Slot
     // of the group stores its part at the head of pass_B (flag SC + 9)
     sl[SL.SC + 9] = 0.0;
     if (a.warm != nullptr && !(L.fl & F_SAVED) && L.iters >= 1 && mu <= gcs_ws::WS_SAVE * sl[SL.SC + 8]) { L.fl |= F_SAVED; sl[SL.SC + 9] = 1.0; }
+    // (gcs_math::mu_converged spelled out: the call changes the generated code here)
     const bool conv = !first_warm && (mu <= ipm_tol || ((L.fl & F_STALLED) && mu <= 1e3 * ipm_tol));
     bool stop = conv;
     // (a WARM solve does not leave through the precision-exhausted rule: it is repeated cold -- oracle/gcs_oracle.c)
@@ -886,7 +773,7 @@ GCS_HD void border_factor_and_affine(Lane<N> &L, const WaveShared &S, const Slot
     for (int k = 0; k < D::Q; ++k) wb[k] = 0.0;
     GCS_REPEAT(1) if (!stop) {
         GCS_REPEAT_FENCE();
-        if (!soc_scaling<D::Q>(ssoc, (sl + SlotLayout<N>::LSOC), (sl + SlotLayout<N>::W), (sl + SlotLayout<N>::WI), wb, eta)) { stop = true; status = (mu <= 1e3 * ipm_tol && !warm) ? 0 : -4; }
+        if (!soc_scaling<D::Q>(ssoc, (sl + SlotLayout<N>::LSOC), (sl + SlotLayout<N>::W), (sl + SlotLayout<N>::WI), wb, eta)) { stop = true; status = gcs_math::boundary_status(mu, ipm_tol, warm); }
     }
     if (stop) {
         if (status != 0 && a.warm != nullptr) warm_record<N, T>(L, wave, a)[0] = 0.0;      // no restart from a solve that failed
@@ -1193,7 +1080,7 @@ GCS_HD void border_sigma(Lane<N> &L, const WaveShared &S, const SlotLayout<N> &S
     const double gap = sl[SlotLayout<N>::SC + 5] * deg;
     const double mu_aff = (gap + al * c1 + al * al * c2) * rcp((double)deg);
     double sig = mu_aff * rcp(sl[SlotLayout<N>::SC + 5]);
-    sig = sig < 0 ? 0 : (sig > 1 ? 1 : sig);
+    sig = sig < 0 ? 0 : (sig > 1 ? 1 : sig);      // (gcs_math::centring spelled out: the call changes the generated code here)
     sig = sig * sig * sig;
     const double sm = first_warm ? sl[SL.SC + 8] : sig * sl[SlotLayout<N>::SC + 5];      // (warm solve, first step: towards mu_ref e)
     sl[SL.SC + 1] = sm;
@@ -1426,7 +1313,7 @@ GCS_HD void border_alpha(Lane<N> &L, const WaveShared &S, const SlotLayout<N> &S
     if (L.role != BORDER || (L.fl & F_DONE) || (L.fl & F_SKIP)) return;
     double *sl = slot_ptr<N>(S, SL, L.slot);
     const double amax = fmin(L.amax, fmin(sl[SL.SIN + D::R4_BASE], sl[SL.SOUT + D::R4_BASE]));
-    double al = fmin(1.0, 0.99 * amax);
+    double al = gcs_math::step_length(amax);
     double ssoc[D::Q];
     ssoc[0] = sl[SlotLayout<N>::SC + 3];
 #pragma unroll
@@ -1438,10 +1325,7 @@ GCS_HD void border_alpha(Lane<N> &L, const WaveShared &S, const SlotLayout<N> &S
         if (soc_interior<D::Q>(s2) && soc_interior<D::Q>(l2)) break;
         al *= 0.7;
     }
-#if !defined(__HIPCC__) && defined(GCS_EMU_TRACE)
-    if (getenv("GCS_EMU_TRACE")) fprintf(stderr, "v %d it %d alpha %.6g own %.6g in %.6g out %.6g sm %.3g\n", L.v, L.iters, al, L.amax, sl[SL.SIN + D::R4_BASE], sl[SL.SOUT + D::R4_BASE], sl[SL.SC+1]);
-#endif
-    L.fl = (L.fl & ~F_STALLED) | (al < 1e-3 ? F_STALLED : 0);
+    L.fl = (L.fl & ~F_STALLED) | (gcs_math::step_stalled(al) ? F_STALLED : 0);
     sl[SL.SC + 0] = al;
 }
 
@@ -1508,9 +1392,6 @@ GCS_HD void phase_setup(Lane<N> &L, int lane, int wave, const VertexArgs<T> &a, 
         const int lo = a.inc_ptr[v], d = a.inc_ptr[v + 1] - lo;
         const int base = group_base(free_lane, d, a.deg_in[v], a.align_rows);
         if (lane >= base && lane <= base + d) {
-#if !defined(__HIPCC__)
-            L.v = v;
-#endif
             L.slot = s - s0; L.d = d; L.d_in = a.deg_in[v]; L.glane = lane - base;
             L.m = a.poly_ptr[v + 1] - a.poly_ptr[v];
             if (L.glane == 0) L.role = BORDER;

@@ -34,6 +34,7 @@
 
 namespace gcs_wg {
 
+using gcs_math::REG_DELTA;
 using gcs_math::rcp;
 using gcs_math::rcp1;
 using gcs_math::rsqrt_nr;
@@ -45,8 +46,6 @@ using gcs_math::sqrt_nr;
 constexpr int WG_THREADS = GCS_WG_THREADS;        // threads per workgroup (a power of two, whole wavefronts)
 constexpr int WG_WAVES = WG_THREADS / 64;
 constexpr int WG_ITEM_WAVES = WG_WAVES > 1 ? WG_WAVES - 1 : 1;   // wavefronts that share the items of a wave-local pipeline
-constexpr double CHOL_SKIP = 1e-12;
-constexpr double REG_DELTA = 1e-7;   // Tikhonov term on every centred unknown except t (oracle/gcs_oracle.c REG_DELTA)
 
 // WG_VM: the units of the sub-problem are in DEVICE memory (the split form of wg_solve_vertex, which shadows this name with its
 // template flag).  Then a barrier, or a hand-off inside a wavefront, must also wait for the wavefront's global stores and loads:
@@ -391,10 +390,9 @@ template <int DIM> GCS_HD void wave_ldl(double *Mq, double *rd)
     double myr = 0.0;
 #pragma unroll
     for (int k = 0; k < DIM; ++k) {
-        double dk = lane_bcast(a[k], k);
+        const double dk = lane_bcast(a[k], k);
         const double odk = lane_bcast(od, k);     // original diagonal entry (an LDS read here would sit on the pivot-to-pivot chain)
-        if (!(dk > CHOL_SKIP * odk)) dk = odk > 0.0 ? CHOL_SKIP * odk : 1.0;
-        const double rk = rcp(dk), col = a[k], l = col * rk;
+        const double rk = rcp(gcs_math::pivot_floor(dk, odk)), col = a[k], l = col * rk;
         a[k] = l;
         if (lane == k) myr = rk;
 #pragma unroll
@@ -409,9 +407,7 @@ template <int DIM> GCS_HD void wave_ldl(double *Mq, double *rd)
     double od[DIM], col[DIM];
     for (int k = 0; k < DIM; ++k) od[k] = Mq[k * DIM + k];
     for (int k = 0; k < DIM; ++k) {
-        double dk = Mq[k * DIM + k];
-        if (!(dk > CHOL_SKIP * od[k])) dk = od[k] > 0.0 ? CHOL_SKIP * od[k] : 1.0;
-        const double rk = rcp(dk);
+        const double rk = rcp(gcs_math::pivot_floor(Mq[k * DIM + k], od[k]));
         rd[k] = rk;
         for (int i = k + 1; i < DIM; ++i) col[i] = Mq[i * DIM + k];
         for (int i = k + 1; i < DIM; ++i) {
@@ -483,21 +479,6 @@ template <int DIM, bool LOWREG> GCS_HD void ldl_inverse_col(const double *Lm, co
 #pragma unroll
         for (int i = 0; i < DIM; ++i) out[i * ldo + c] = x[i];
     }
-}
-
-// Nesterov-Todd scaling of the cone from (s, z): wb (unit hyperbolic vector), eta; false on a boundary point
-template <int Q> GCS_HD bool soc_scaling_wb(const double *s, const double *z, double *wb, double &eta)
-{
-    const double ss = gcs_math::soc_det<Q>(s), zz = gcs_math::soc_det<Q>(z);
-    if (!(ss > 0.0) || !(zz > 0.0)) return false;
-    const double is = rsqrt_nr(ss), iz = rsqrt_nr(zz);
-    double dot = 0;
-    for (int k = 0; k < Q; ++k) dot += (s[k] * is) * (z[k] * iz);
-    const double ig2 = 0.5 * rsqrt_nr(0.5 * (1.0 + dot));
-    wb[0] = (s[0] * is + z[0] * iz) * ig2;
-    for (int k = 1; k < Q; ++k) wb[k] = (s[k] * is - z[k] * iz) * ig2;
-    eta = sqrt_nr((ss * is) * iz);
-    return true;
 }
 
 // products with the Nesterov-Todd scaling W = eta * [wb0 wb1'; wb1 I + wb1 wb1'/(1+wb0)], its inverse and W^{-2} =
@@ -1064,7 +1045,7 @@ GCS_HD void wg_solve_vertex(const WgArgs<T> &a, int v, double rho, double mu_sca
         }
         WG_FENCE();
         {   // stop on the barrier parameter alone (oracle/gcs_oracle.c); a vanishing step = precision exhausted
-            const bool conv = !first_warm && (mu <= a.ipm_tol || (stalled && mu <= 1e3 * a.ipm_tol));
+            const bool conv = gcs_math::mu_converged(mu, a.ipm_tol, stalled, first_warm);
             bool stop = conv;
             // (a WARM solve does not leave through the precision-exhausted rule: it is repeated cold -- oracle/gcs_oracle.c)
             status = conv ? ((use_warm && !(mu <= a.ipm_tol)) ? -7 : 0) : -1;
@@ -1081,7 +1062,7 @@ GCS_HD void wg_solve_vertex(const WgArgs<T> &a, int v, double rho, double mu_sca
             // cone scaling: W^{-2} = eta^{-2}(2 v v' - J), v = (wb0, -wb1); t is eliminated in closed form (c0, cv, Su):
             // a numerical pivot on t cancels catastrophically once the cone is active
             double wb[Q], eta = 1.0;
-            if (!soc_scaling_wb<Q>(SOC + SO::SS, SOC + SO::LS, wb, eta)) SC[SC_CONEFAIL] = 1.0;
+            if (!gcs_math::soc_scaling_wb<Q>(SOC + SO::SS, SOC + SO::LS, wb, eta)) SC[SC_CONEFAIL] = 1.0;
             else {
                 SC[SC_CONEFAIL] = 0.0; SC[SC_ETA] = eta;
                 const double ieta = rcp(eta), ie2 = ieta * ieta;
@@ -1198,7 +1179,7 @@ GCS_HD void wg_solve_vertex(const WgArgs<T> &a, int v, double rho, double mu_sca
         WG_SYNC();
         WG_STAMP(2);
         if (wg_uniform(SC[SC_CONEFAIL]) != 0.0) {
-            status = (mu <= 1e3 * a.ipm_tol && !use_warm) ? 0 : -4;
+            status = gcs_math::boundary_status(mu, a.ipm_tol, use_warm);
             if (status == 0) break;
             WG_FAIL_OR_RESTART();
         }
@@ -1239,8 +1220,7 @@ GCS_HD void wg_solve_vertex(const WgArgs<T> &a, int v, double rho, double mu_sca
                 double dj = od;
 #pragma unroll
                 for (int k = 0; k < j; ++k) dj -= a[pki(j, k)] * a[pki(j, k)];
-                if (!(dj > CHOL_SKIP * od)) dj = od > 0.0 ? CHOL_SKIP * od : 1.0;
-                const double inv = rsqrt_nr(dj);
+                const double inv = rsqrt_nr(gcs_math::pivot_floor(dj, od));
                 pv[j] = inv;
 #pragma unroll
                 for (int i = j + 1; i < N; ++i) {
@@ -1303,9 +1283,7 @@ GCS_HD void wg_solve_vertex(const WgArgs<T> &a, int v, double rho, double mu_sca
                 if (c < 2 * N) un[W::BQ + c] = un[W::BW + c] * un[W::XD + c] - un[W::XY + c];
                 else {
                     const double kap = un[W::KYY];
-                    double sy = kap - un[W::RV] - un[W::RV + 1];
-                    if (!(sy > CHOL_SKIP * kap)) sy = kap > 0.0 ? CHOL_SKIP * kap : 1.0;
-                    un[W::BRS] = rcp(sy);
+                    un[W::BRS] = rcp(gcs_math::pivot_floor(kap - un[W::RV] - un[W::RV + 1], kap));
                     un[W::BW + 2 * N] = -1.0;
                 }
             }
@@ -1322,9 +1300,7 @@ GCS_HD void wg_solve_vertex(const WgArgs<T> &a, int v, double rho, double mu_sca
             const int u = 1 + t / (NW * NW), ij = t - (u - 1) * (NW * NW), i = ij / NW, j = ij - i * NW;
             double *un = UN(u);
             const double kap = un[W::K + 2 * N * NW + 2 * N];
-            double sy = kap - un[W::RV] - un[W::RV + 1];
-            if (!(sy > CHOL_SKIP * kap)) sy = kap > 0.0 ? CHOL_SKIP * kap : 1.0;
-            const double rs = rcp(sy);
+            const double rs = rcp(gcs_math::pivot_floor(kap - un[W::RV] - un[W::RV + 1], kap));
             const double wi = i < 2 * N ? un[W::PIV + i] : -1.0, wj = j < 2 * N ? un[W::PIV + j] : -1.0;
             const double base = (i < 2 * N && j < 2 * N && i / N == j / N) ? un[W::B + ij] : 0.0;
             un[W::B + ij] = base + wi * wj * rs;
@@ -1571,10 +1547,7 @@ GCS_HD void wg_solve_vertex(const WgArgs<T> &a, int v, double rho, double mu_sca
         {
             const double al = fmin(1.0, rb.mn);
             const double mu_aff = (gap + al * rb.s1 + al * al * rb.s2) * inv_deg;
-            double sig = mu_aff * rcp(mu);
-            sig = sig < 0 ? 0 : (sig > 1 ? 1 : sig);
-            sig = sig * sig * sig;
-            sigmu = wg_uniform(sig * mu);
+            sigmu = wg_uniform(gcs_math::centring(mu_aff * rcp(mu)) * mu);
         }
         }
         // ================= corrector: kappa = (sigma mu - ds_a dl_a) / s per row; cone part by the cone thread =================
@@ -1673,7 +1646,7 @@ GCS_HD void wg_solve_vertex(const WgArgs<T> &a, int v, double rho, double mu_sca
         const Red3 rd = wg_reduce<WG_VM>(Red3{fmin(rmax > 0.0 ? rcp1(rmax) : 1e300, amax_cone), 0.0, 0.0}, sm + W::RED, red_phase);
         WG_STAMP(19);
         WG_CONE() {      // step length with the cone guard (round-off must not push either cone point outside)
-            double al = fmin(1.0, 0.99 * rd.mn);
+            double al = gcs_math::step_length(rd.mn);
             for (int tries = 0; tries < 40; ++tries) {
                 double s2[Q], l2[Q];
 #pragma unroll
@@ -1687,7 +1660,7 @@ GCS_HD void wg_solve_vertex(const WgArgs<T> &a, int v, double rho, double mu_sca
         WG_SYNC();
         WG_STAMP(20);
         const double alpha = wg_uniform(SC[SC_ALPHA]);
-        stalled = alpha < 1e-3;
+        stalled = gcs_math::step_stalled(alpha);
         // ================= update =================
         Place plu;
         WG_ROWS_BEGIN(plu)       // (the slack the macro offers is unused here: the compiler drops it)

@@ -171,7 +171,7 @@ def term_emu():
     here = os.path.dirname(os.path.abspath(__file__))
     csrc = os.path.join(os.path.dirname(here), "gcs_admm_amd", "csrc")
     src, out = os.path.join(here, "hostemu", "term_emu.cpp"), os.path.join(here, "hostemu", "libtermemu.so")
-    deps = [src, os.path.join(csrc, "terminal_region.h"), os.path.join(csrc, "gcs_math.h"), os.path.join(csrc, "step_args.h")]
+    deps = [src] + [os.path.join(csrc, f) for f in ("terminal_region.h", "gcs_math.h", "warm_start.h", "step_args.h")]
     if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(d) for d in deps):
         subprocess.check_call(["g++", "-O1", "-std=c++17", "-fPIC", "-shared", "-I" + csrc, src, "-o", out])
     return C.CDLL(out)
