@@ -4,9 +4,10 @@
 
 template <int N> struct CpuExec {
     Lane<N> Ls[WAVE];
+    std::vector<int> solve_iters;      // count() of this wavefront's vertices, in lane order = slot order
     template <class F> void each(F &&f) { for (int l = 0; l < WAVE; ++l) f(Ls[l], l); }
     template <class P> bool all(P &&p) { for (int l = 0; l < WAVE; ++l) if (!p(Ls[l])) return false; return true; }
-    void count(int *c, int fails, int iters) { c[0] += fails; c[1] += iters; }
+    void count(int *c, int fails, int iters) { c[0] += fails; c[1] += iters; solve_iters.push_back(iters); }
     void note(int *p, int v) { *p = v; }
     template <class F> int wave_max(F &&f) { int m = 0; for (int l = 0; l < WAVE; ++l) m = std::max(m, f(Ls[l])); return m; }
     // lanes run in increasing order inside a phase: the head lane of a segment initialises the sum, the
@@ -31,6 +32,9 @@ static const long long *g_warm_ptr = nullptr;
 #define EMU_CAT_(a, b) a##b
 #define EMU_CAT(a, b) EMU_CAT_(a, b)
 extern "C" void EMU_CAT(EMU_NAME, _set_warm)(double *warm, const long long *warm_ptr) { g_warm = warm; g_warm_ptr = warm_ptr; }
+// Newton iterations of every generic vertex of the following steps ([V]; null = not recorded)
+static int *g_iters = nullptr;
+extern "C" void EMU_CAT(EMU_NAME, _set_iters)(int *iters) { g_iters = iters; }
 
 extern "C" int EMU_NAME(int n, int V, int E, int NI, const int *inc_ptr, const int *inc_edge, const int *inc_out,
                                const int *poly_ptr, const double *poly_A, const double *poly_b, const double *center,
@@ -81,8 +85,13 @@ extern "C" int EMU_NAME(int n, int V, int E, int NI, const int *inc_ptr, const i
             std::fill(smem.begin(), smem.end(), 0.0 / 0.0);   // poison: reads of unwritten LDS show up as NaN
             WaveShared S;
             wave_shared_init(S, smem.data(), n, MM, STORE_DL);
+            ex->solve_iters.clear();
             if (STORE_DL) run_vertex_program<NN, double, 1>(*ex, w, a, S, rho, mu_scale);
             else run_vertex_program<NN, double, 0>(*ex, w, a, S, rho, mu_scale);
+            if (g_iters && (int)ex->solve_iters.size() == wave_slot_ptr[w + 1] - wave_slot_ptr[w])
+                for (int k = 0; k < (int)ex->solve_iters.size(); ++k) g_iters[wave_vtx[wave_slot_ptr[w] + k]] = ex->solve_iters[k];
+            else if (g_iters)
+                for (int k = wave_slot_ptr[w]; k < wave_slot_ptr[w + 1]; ++k) g_iters[wave_vtx[k]] = -1;     // (not one count per vertex)
         }
         delete ex;
     };

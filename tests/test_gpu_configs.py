@@ -16,6 +16,7 @@ import pytest
 
 from gcs_admm_amd.cases import load_fixture
 from gcs_admm_amd.graph import lattice_boxes
+from solve_agreement import Agreement, NewtonParity, device_newton, f32_round, generic_mask, oracle_step
 
 pytestmark = pytest.mark.gpu
 
@@ -249,31 +250,70 @@ def _region_scene(seed, half=0.35):
 def test_region_terminals_vertex_step_against_oracle(torch_gpu, oracle_lib, program, columns, dtype):
     """'s' / 't' that are regions (admm_solver_v3.py:415-464 with delta_sv / delta_tv; the reference's own cases make them points,
     utils.py:12-28): the terminal kernel (csrc/terminal_region.h) against the oracle's solve_terminal_region, vertex step by vertex step
-    along an oracle run and from perturbed states, on the terminals' own columns to 1e-5 (f32 state: 2e-4) and everywhere to the fixture bound"""
+    along an oracle run and from perturbed states, on the terminals' own columns to 1e-5 (f32 state: 2e-4) and everywhere to the fixture bound.
+    Every solve, terminals included, meets the per-solve contract and the run the warm Newton total (tests/solve_agreement.py); with f32
+    state the oracle is given the f32-rounded state the device sees, and a word within one f32 ulp of the oracle's counts as equal."""
     from oracle.oracle import Oracle
     torch = torch_gpu
     rng = np.random.default_rng(3)
+    f32 = dtype == "f32"
+    agree, newton = Agreement(f"region terminals {program} {columns} {dtype}"), NewtonParity(f"region terminals {program} {dtype} warm")
     for g in (_region_row(), _region_scene(1), _region_scene(2, half=0.2)):
         o = Oracle(g, ipm_tol=IPM_TOL)
         d = _solver(g, dtype, program=program, columns=columns)
         d.reset()
         tcols = np.concatenate([np.arange(g.inc_ptr[v], g.inc_ptr[v + 1]) for v in (g.src, g.dst)])
+        solves = generic_mask(g); solves[[g.src, g.dst]] = True
         for it in range(10):
             if it >= 6:
                 o.zedge += 0.03 * rng.normal(size=o.zedge.shape); o.mu += 0.02 * rng.normal(size=o.mu.shape)
+            if f32:           # both sides solve from the state the device stores
+                o.zedge[...] = f32_round(o.zedge); o.mu[...] = f32_round(o.mu)
             perm = torch.from_numpy(d.col_of).cuda()      # incidence column -> state column (edge-major handles)
             d.zedge.copy_(torch.from_numpy(o.zedge)); d.mu[:, perm] = torch.from_numpy(o.mu).to(d.mu.dtype).cuda()
             d.vertex_step()
-            assert o.vertex_step(1.0, 1.0) == 0
+            fails, iters, _ = oracle_step(o)
+            assert fails == 0
             got = d.copy[:, perm].double().cpu().numpy()
+            agree.add(g, solves, got, d.yv.cpu().numpy(), o.copy, o.yv, f32=f32)
             assert np.abs(got[:, tcols] - o.copy[:, tcols]).max() < (1e-5 if dtype == "f64" else 2e-4), (it, np.abs(got[:, tcols] - o.copy[:, tcols]).max())
             assert np.abs(got - o.copy).max() < 2e-3
             xv = d.xv.cpu().numpy(); zv = d.zv.cpu().numpy()
             for v in (g.src, g.dst):
                 assert np.abs(xv[v] - o.xv[v]).max() < (1e-5 if dtype == "f64" else 2e-4) and np.array_equal(xv[v], zv[v]) and d.yv[v].item() == 1.0
             assert d.read_control().inner_failures == 0
+            it_dev, fails_dev = device_newton(d)
+            newton.add(it_dev, iters, fails_dev, fails)
             o.edge_step(1.0)
         d.close()
+    agree.check()
+    newton.check_warm()
+
+
+@pytest.mark.parametrize("cold", [True, False], ids=["cold", "warm"])
+def test_region_terminals_newton_parity_per_step(torch_gpu, oracle_lib, cold):
+    """Newton iterations of every vertex step with region terminals (the terminal kernel beside the vertex programs) against the
+    oracle's for the same step, and the per-solve contract over the generic vertices and the two terminals (tests/solve_agreement.py)"""
+    from oracle.oracle import Oracle
+    torch = torch_gpu
+    g = _region_scene(1)
+    o = Oracle(g, ipm_tol=IPM_TOL, warm_start=not cold)
+    d = _solver(g)
+    d.reset(cold_start=cold)
+    solves = generic_mask(g); solves[[g.src, g.dst]] = True
+    mode = "cold" if cold else "warm"
+    agree, newton = Agreement(f"region terminals {mode}"), NewtonParity(f"region terminals {mode}")
+    for it in range(20):
+        d.zedge.copy_(torch.from_numpy(o.zedge)); d.mu.copy_(torch.from_numpy(o.mu))
+        d.vertex_step()
+        fails, iters, _ = oracle_step(o)
+        agree.add(g, solves, d.copy.cpu().numpy(), d.yv.cpu().numpy(), o.copy, o.yv)
+        it_dev, fails_dev = device_newton(d)
+        newton.add(it_dev, iters, fails_dev, fails)
+        o.edge_step(1.0)
+    d.close()
+    agree.check()
+    newton.check(cold)
 
 
 def _region_star(n, spokes, seed=0):
@@ -315,16 +355,24 @@ def test_region_terminal_other_dimensions_and_degrees(torch_gpu, oracle_lib, n, 
     d = _solver(g)
     d.reset()
     tcols = np.arange(g.inc_ptr[g.src], g.inc_ptr[g.src + 1])
+    solves = generic_mask(g); solves[[g.src, g.dst]] = True
+    agree, newton = Agreement(f"region terminal n={n} spokes {spokes}"), NewtonParity(f"region terminal n={n} spokes {spokes} warm")
     for it in range(8):
         d.zedge.copy_(torch.from_numpy(o.zedge)); d.mu.copy_(torch.from_numpy(o.mu))
         d.vertex_step()
-        assert o.vertex_step(1.0, 1.0) == 0 and d.read_control().inner_failures == 0
+        fails, iters, _ = oracle_step(o)
+        assert fails == 0 and d.read_control().inner_failures == 0
         got = d.copy.cpu().numpy()
+        agree.add(g, solves, got, d.yv.cpu().numpy(), o.copy, o.yv)
+        it_dev, fails_dev = device_newton(d)
+        newton.add(it_dev, iters, fails_dev, fails)
         assert np.abs(got[:, tcols] - o.copy[:, tcols]).max() < 1e-5, (it, np.abs(got[:, tcols] - o.copy[:, tcols]).max())
         assert np.abs(got - o.copy).max() < 2e-3
         assert abs(o.copy[2 * n, tcols[spokes:]].sum() - 1.0) < 1e-9 and d.yv[g.src].item() == 1.0      # the unit of flow leaves the source
         o.edge_step(1.0)
     d.close()
+    agree.check()
+    newton.check_warm()
 
 
 def test_region_terminals_whole_run(torch_gpu, oracle_lib):

@@ -10,6 +10,7 @@ import pytest
 from gcs_admm_amd import IPM_TOL
 from gcs_admm_amd.cases import load_fixture
 from gcs_admm_amd.graph import graph_from_sets, lattice_boxes, sets_of_graph
+from solve_agreement import Agreement, NewtonParity, device_newton, generic_mask, oracle_step
 
 pytestmark = pytest.mark.gpu
 
@@ -164,18 +165,27 @@ def test_oversized_hub_against_oracle(torch_gpu, oracle_lib, name, make, cold):
     d.reset(cold_start=cold)
     torch = torch_gpu
     diffs = []
-    for it in range(12):
+    gen = generic_mask(g)
+    mode = "cold" if cold else "warm"
+    agree, newton = Agreement(f"{name} {mode}"), NewtonParity(f"{name} {mode}")
+    for it in range(24):        # (a hub and its spokes: few generic vertices, so more steps for the per-solve statistic)
         d.zedge.copy_(torch.from_numpy(o.zedge)); d.mu.copy_(torch.from_numpy(o.mu))
         d.vertex_step()
-        assert o.vertex_step(1.0, 1.0) == 0
+        fails, iters, _ = oracle_step(o)
+        assert fails == 0
         copy = d.copy.cpu().numpy()
         assert np.isfinite(copy).all()
         diffs.append(np.abs(copy - o.copy).max())
         assert np.abs(d.yv.cpu().numpy() - o.yv).max() <= 5e-4
+        agree.add(g, gen, copy, d.yv.cpu().numpy(), o.copy, o.yv)
+        it_dev, fails_dev = device_newton(d)
+        newton.add(it_dev, iters, fails_dev, fails)
         d.copy.copy_(torch.from_numpy(o.copy))
         d.edge_step(); o.edge_step(1.0)
     diffs = np.array(diffs)
     assert diffs.max() <= 2e-3 and np.median(diffs) <= 1e-5, (diffs.max(), np.median(diffs))
+    agree.check()
+    newton.check(cold)
     res = d.solve(max_it=400, cold_start=cold)
     ora = oracle_lib.Oracle(g, ipm_tol=IPM_TOL, warm_start=not cold).run(max_it=400)
     assert res["inner_failures"] == 0 and res["iterations"] == ora["iterations"]
@@ -198,6 +208,22 @@ def test_mixed_graph_all_three_launches(torch_gpu, oracle_lib):
     d = _solver(g, vertex_workspace=1)
     q, w = d.query(), d.query_workspace()
     assert q["num_waves"] > 0 and q["num_workgroup_vertices"] == 1 and w["num_split_vertices"] == 1
+    # the three launches of one vertex step, step by step along an oracle run: the per-solve contract and the warm Newton total
+    torch = torch_gpu
+    o = oracle_lib.Oracle(g, ipm_tol=IPM_TOL)
+    d.reset()
+    gen = generic_mask(g)
+    agree, newton = Agreement("mixed"), NewtonParity("mixed warm")
+    for it in range(10):
+        d.zedge.copy_(torch.from_numpy(o.zedge)); d.mu.copy_(torch.from_numpy(o.mu))
+        d.vertex_step()
+        fails, iters, _ = oracle_step(o)
+        agree.add(g, gen, d.copy.cpu().numpy(), d.yv.cpu().numpy(), o.copy, o.yv)
+        it_dev, fails_dev = device_newton(d)
+        newton.add(it_dev, iters, fails_dev, fails)
+        o.edge_step(1.0)
+    agree.check()
+    newton.check_warm()
     kw = dict(max_it=60, eps_abs=0.0, eps_rel=0.0)
     ora = oracle_lib.Oracle(g, ipm_tol=IPM_TOL).run(**kw)
     ref = None

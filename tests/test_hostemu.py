@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 
 from gcs_admm_amd.cases import load_fixture
+from solve_agreement import Agreement, NewtonParity, oracle_step
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
@@ -47,8 +48,10 @@ class WarmRecords:
         self.buf = np.zeros(int(self.ptr[-1]))
 
 
-def emu_step(lib, g, zedge, mu, rho, mu_scale, fn="emu_vertex_step", warm=None):
+def emu_step(lib, g, zedge, mu, rho, mu_scale, fn="emu_vertex_step", warm=None, iters=None):
+    """iters: an int32 [V] array that receives the Newton iterations of every generic vertex"""
     getattr(lib, fn + "_set_warm")(_p(warm.buf) if warm else None, _p(warm.ptr) if warm else None)
+    getattr(lib, fn + "_set_iters")(_p(iters) if iters is not None else None)
     c, NI, V = g.c, 2 * g.num_edges, g.num_vertices
     copy = np.zeros((c, NI)); xv = np.zeros((V, 2 * g.n)); zv = np.zeros_like(xv); yv = np.zeros(V)
     cnt = np.zeros(2, dtype=np.int32); gen = np.zeros(V, dtype=np.int32)
@@ -85,6 +88,30 @@ def test_emulated_wave_program_matches_oracle(emu, oracle_lib, name, steps):
     ho = np.array([[o._warm[o._warm_ptr[v] + k] for k in (2, 3)] for v in gv])
     assert (hd[:, 1] > 0).all() and ((hd[:, 0] == 0) | ((hd[:, 0] >= 0.1) & (hd[:, 0] <= 10.0))).all()
     assert (np.abs(hd - ho).max(axis=1) == 0).mean() >= 0.8
+
+
+@pytest.mark.parametrize("cold", [False, True], ids=["warm", "cold"])
+@pytest.mark.parametrize("name,steps", [("benchmark1", 30), ("benchmark4", 20), ("test_autogen2", 20), ("benchmark3", 20), ("lattice 5x4", 20)])
+def test_emulated_wave_program_meets_the_per_solve_contract(emu, oracle_lib, name, steps, cold):
+    """every solve against the oracle's from identical state, and the Newton iterations per vertex (tests/solve_agreement.py); cold:
+    no records on either side.  benchmark1 has four generic vertices: more steps."""
+    from gcs_admm_amd.graph import lattice_boxes
+    g = lattice_boxes(5, 4, seed=1) if name.startswith("lattice") else load_fixture(name)[1]
+    o = oracle_lib.Oracle(g, ipm_tol=IPM_TOL, warm_start=not cold)
+    w = None if cold else WarmRecords(g)
+    mode = "cold" if cold else "warm"
+    agree, newton = Agreement(f"{name} {mode}"), NewtonParity(f"{name} {mode}")
+    for it in range(steps):
+        pv = np.zeros(g.num_vertices, dtype=np.int32)
+        copy, xv, zv, yv, cnt, gen = emu_step(emu, g, o.zedge.copy(), o.mu.copy(), 1.0, 1.0, warm=w, iters=pv)
+        fails, iters, per_vertex = oracle_step(o)
+        gen = gen == 1
+        assert pv[gen].sum() == cnt[1]             # one count per vertex, in the order of the wavefronts' slots
+        agree.add(g, gen, copy, yv, o.copy, o.yv)
+        newton.add(cnt[1], iters, cnt[0], fails, pv[gen], per_vertex[gen])
+        o.edge_step(1.0)
+    agree.check()
+    newton.check(cold)
 
 
 def test_fixed_facet_variant_equals_generic(emu, oracle_lib):

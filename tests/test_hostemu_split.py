@@ -12,6 +12,7 @@ import pytest
 from gcs_admm_amd import IPM_TOL
 from gcs_admm_amd.cases import load_fixture
 from gcs_admm_amd.graph import lattice_boxes
+from solve_agreement import Agreement, NewtonParity, oracle_step
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
@@ -111,14 +112,18 @@ HUBS = [("n=2 degree 120", lambda: _star(60)), ("n=6 generic degree 30", lambda:
 @pytest.mark.parametrize("cold", [False, True], ids=["warm", "cold"])
 @pytest.mark.parametrize("name,mk", HUBS, ids=[c[0] for c in HUBS])
 def test_oversized_hub_matches_oracle(libs, oracle_lib, name, mk, cold):
-    """the hubs gcsadmm_create refuses with vertex_workspace 0: the split form's vertex steps along an oracle run"""
+    """the hubs gcsadmm_create refuses with vertex_workspace 0: the split form's vertex steps along an oracle run, every solve and its
+    Newton iterations against the oracle's (tests/solve_agreement.py; a hub and its spokes are few generic vertices: 16 steps)"""
     g = mk()
     o = oracle_lib.Oracle(g, ipm_tol=IPM_TOL, warm_start=not cold)
     warm = None if cold else Warm(g)
     diffs = []
-    for it in range(8):
+    mode = "cold" if cold else "warm"
+    agree, newton = Agreement(f"{name} {mode}"), NewtonParity(f"{name} {mode}")
+    for it in range(16):
         a = step(libs[False], g, o.zedge.copy(), o.mu.copy(), 1, False, warm)
-        assert o.vertex_step(1.0, 1.0) == 0
+        fails, iters, per_vertex = oracle_step(o)
+        assert fails == 0
         assert a[4][0] == 0
         gen = a[6] > 0
         mask = np.zeros(2 * g.num_edges, bool)
@@ -126,6 +131,10 @@ def test_oversized_hub_matches_oracle(libs, oracle_lib, name, mk, cold):
             mask[g.inc_ptr[v]:g.inc_ptr[v + 1]] = True
         diffs.append(np.abs(a[0][:, mask] - o.copy[:, mask]).max())
         assert np.abs(a[3][gen] - o.yv[gen]).max() <= 5e-4
+        agree.add(g, gen, a[0], a[3], o.copy, o.yv)
+        newton.add(a[4][1], iters, a[4][0], fails, a[6][gen], per_vertex[gen])
         o.edge_step(1.0)
     diffs = np.array(diffs)
     assert diffs.max() <= 2e-3 and np.median(diffs) <= 1e-5, diffs
+    agree.check()
+    newton.check(cold)

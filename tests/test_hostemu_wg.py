@@ -14,6 +14,7 @@ import pytest
 
 from gcs_admm_amd.cases import load_fixture
 from gcs_admm_amd.graph import lattice_boxes
+from solve_agreement import Agreement, NewtonParity, oracle_step
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
@@ -108,6 +109,31 @@ def test_workgroup_program_matches_oracle_and_is_order_independent(libs, oracle_
     ho = np.array([[o._warm[o._warm_ptr[v] + k] for k in (2, 3)] for v in gv])
     assert (hd[:, 1] > 0).all() and ((hd[:, 0] == 0) | ((hd[:, 0] >= 0.1) & (hd[:, 0] <= 10.0))).all()
     assert (np.abs(hd - ho).max(axis=1) == 0).mean() >= 0.8
+
+
+CONTRACT_CASES = [("benchmark1", 30), ("benchmark4", 20), ("test_autogen2", 20), ("benchmark3", 20), ("lattice 5x4", 20)]
+
+
+@pytest.mark.parametrize("cold", [False, True], ids=["warm", "cold"])
+@pytest.mark.parametrize("name,steps", CONTRACT_CASES)
+def test_workgroup_program_meets_the_per_solve_contract(libs, oracle_lib, name, steps, cold):
+    """every solve against the oracle's from identical state, and the Newton iterations per vertex (tests/solve_agreement.py); cold:
+    no records on either side.  benchmark1 has four generic vertices: more steps."""
+    fwd, _ = libs
+    g = lattice_boxes(5, 4, seed=1) if name.startswith("lattice") else load_fixture(name)[1]
+    o = oracle_lib.Oracle(g, ipm_tol=IPM_TOL, warm_start=not cold)
+    w = None if cold else WarmRecords(fwd, g)
+    mode = "cold" if cold else "warm"
+    agree, newton = Agreement(f"{name} {mode}"), NewtonParity(f"{name} {mode}")
+    for it in range(steps):
+        a = wg_step(fwd, "wg_emu_vertex_step", g, o.zedge.copy(), o.mu.copy(), warm=w)
+        fails, iters, per_vertex = oracle_step(o)
+        gen = a[5]
+        agree.add(g, gen, a[0], a[3], o.copy, o.yv)
+        newton.add(a[4][1], iters, a[4][0], fails, a[7][gen], per_vertex[gen])
+        o.edge_step(1.0)
+    agree.check()
+    newton.check(cold)
 
 
 @pytest.mark.parametrize("lat", [(5, 4, 2), (4, 3, 3), (4, 3, 6)])
