@@ -3,7 +3,9 @@ libgcsadmm.so), against the CPU oracle on the same inputs, against the reference
 records, and -- at the benchmark's full size -- through size-independent properties.
 
 Stated tolerances (f64):
-  * edge step / control: same arithmetic on both sides -> 1e-12 relative.
+  * edge step / control / cost: the contract of tests/loop_reference.py, held on the device by tests/test_gpu_edge_control.py in
+    every launch mode (zedge and mu bitwise, the five sums within (N + 8) 2^-53 relative, control decisions exact).  The edge-step
+    assertions below (sums 1e-12 relative, zedge bitwise, mu 1e-15 on the fixtures at mu_scale = 1) stay as a first alarm.
   * one vertex step from identical state: coupled words within 2e-3 absolute (observed worst ~6e-4), median over steps
     below 1e-5.  Both sides run the same interior-point iteration to barrier parameter 1e-9, which
     resolves the sub-problem's minimiser to ~1e-4 in its weakly determined components (the
