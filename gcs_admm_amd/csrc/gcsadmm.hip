@@ -2,7 +2,7 @@
 //
 // Kernels (one HIP stream, launched back to back, no host round trip inside the loop):
 //   vertex_kernel<2,T>   x-update, wavefront program (n = 2, degree <= 63): one wavefront per workgroup, several vertices
-//                        per wavefront, program in vertex_program.h     (admm_solver_v3.py:352-540)
+//                        per wavefront, program in vertex_program.inc   (admm_solver_v3.py:352-540)
 //   vertex_wg_kernel<N,T> (vertex_wg.hip) x-update, workgroup program: one 256-thread workgroup per vertex, any n / degree
 //                        trailing workgroups of either launch: x-update of s, t (closed form) and of vertices no flow can cross
 //   vertex_wg_split_kernel<N,T> (vertex_wg.hip) the same program for vertices too large for LDS, edge blocks in a device workspace
@@ -21,6 +21,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <new>
 #include <string>
 #include <type_traits>
@@ -344,74 +345,120 @@ __global__ __launch_bounds__(256) void cost_kernel(int V, int E, int n, const do
 // =================================================================================================
 // host side
 // =================================================================================================
+// ---- owners of the device resources: the only places that allocate and release them.  They release in their destructors, so
+// whoever destroys one has the handle's device current (gcsadmm_destroy and the failure path of gcsadmm_create hold the guard) ----
+struct HipRelease {
+    void operator()(void *p) const { (void)hipFree(p); }
+    void operator()(hipStream_t s) const { (void)hipStreamDestroy(s); }
+    void operator()(hipEvent_t e) const { (void)hipEventDestroy(e); }
+};
+using Stream = std::unique_ptr<std::remove_pointer_t<hipStream_t>, HipRelease>;
+using Event = std::unique_ptr<std::remove_pointer_t<hipEvent_t>, HipRelease>;
+template <class T> class DevBuf {
+    std::unique_ptr<T, HipRelease> p_;
+    size_t count_ = 0;
+public:
+    T *get() const { return p_.get(); }
+    size_t size() const { return p_ ? count_ : 0; }      // elements asked for (a count of 0 still allocates one)
+    explicit operator bool() const { return (bool)p_; }
+    void reset() { p_.reset(); }
+    hipError_t alloc(size_t count)              // uninitialised
+    {
+        T *p = nullptr;
+        const hipError_t e = hipMalloc((void **)&p, std::max<size_t>(count, 1) * sizeof(T));
+        p_.reset(e == hipSuccess ? p : nullptr);
+        count_ = count;
+        return e;
+    }
+    hipError_t upload(const T *src, size_t count)      // src == nullptr: zero-filled
+    {
+        const size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
+        const hipError_t e = alloc(count);
+        if (e != hipSuccess) return e;
+        return src ? hipMemcpy(get(), src, bytes, hipMemcpyHostToDevice) : hipMemset(get(), 0, bytes);
+    }
+    hipError_t zero(hipStream_t s) const { return size() ? hipMemsetAsync(get(), 0, size() * sizeof(T), s) : hipSuccess; }
+};
+// fills an empty Stream / Event through the HIP call that creates one with flags
+template <class O> static hipError_t create_owned(O &owner, hipError_t (*create)(typename O::pointer *, unsigned), unsigned flags)
+{
+    typename O::pointer x = nullptr;
+    const hipError_t e = create(&x, flags);
+    owner.reset(x);
+    return e;
+}
+
+// vertex partition across GPUs (gcsadmm_attach_comm): halo index lists and message buffers
+struct Halo {
+    std::vector<int> peers, peer_cnt, peer_off;   // neighbour ranks; columns per peer; first column of each peer's block
+    std::vector<int> send_cols;       // host copy of the send list as validated at attach (the overlap split is derived from it)
+    int n_send = 0, n_recv = 0;       // halo columns sent / received per iteration
+    DevBuf<int> d_send_cols, d_send_base, d_send_stride, d_recv_cols, d_recv_base, d_recv_stride;
+    DevBuf<char> d_sendbuf, d_recvbuf;
+    DevBuf<double> d_sums6;           // the five norms + the inner-failure count, all-reduced together
+    bool attached() const { return (bool)d_sums6; }
+};
+// overlapped partitioned loop (boundary vertices first, the halo exchange behind them while the interior is solved): the
+// split of the wavefronts into boundary (holding a vertex with a cut edge) and interior, a second stream for the exchange and two events
+struct Overlap {
+    int n_wave_b = 0;         // boundary wavefronts (0: no split)
+    DevBuf<int> d_split_ids, d_split_order;    // [n_waves] static ids / launch order: boundary wavefronts first, then interior
+    Stream comm_stream;
+    Event ev_boundary, ev_halo;
+};
+// terminals that are regions (terminal_region.h): at most two, one workgroup each, on an auxiliary stream beside the vertex-step launch
+struct Terminals {
+    DevBuf<double> d_term_ws, d_term_rec;      // work arrays (when they do not fit LDS); warm-start records
+    Stream term_stream;
+    Event ev_term_fork, ev_term_join;
+};
+
+// The decisions of create are the plan's (create_plan.h), kept as made; the handle adds the descriptor's scalars, the run state and
+// the owners of what lives on the device, grouped by lifetime.
 struct gcsadmm_handle_s {
-    int n = 0, V = 0, E = 0, NI = 0, NI_owned = 0, c = 0, MM = 0, dtype = 0, device = 0;
-    int n_waves = 0, n_special = 0, slots_cap = 0, lds_bytes = 0, edge_blocks = 0;
-    int n_wg = 0, wg_lds_bytes = 0;   // vertices solved by the workgroup program (vertex_wg.hip), LDS per workgroup
-    int wg_box = 0;           // every workgroup-program vertex is a canonical box: BOX instantiation of that program
-    int wg_t512 = 0;          // the launch uses the 512-thread build of the workgroup program (at most one workgroup per CU)
-    // split form of the workgroup program (gcsadmm_graph_desc.vertex_workspace): vertices, LDS per workgroup, their units' slabs
-    int n_split = 0, split_lds_bytes = 0;
-    int *d_split_vtx = nullptr;
-    long long *d_split_off = nullptr;
-    double *d_split_ws = nullptr;
-    size_t split_doubles = 0;
-    int edge_unroll = 1;      // edges in flight per thread of the edge kernel
+    int n = 0, V = 0, E = 0, NI = 0, c = 0, dtype = 0, device = 0, src = -1, dst = -1;
     int edge_major = 0;       // state columns numbered by edge (gcsadmm_graph_desc.edge_major_columns)
-    std::vector<char> col_owned;   // [NI] 1: the column of an incidence of this handle's vertices, 0: a ghost column
-    int all_m4 = 0;           // 2: every wavefront-program vertex is a canonical box (4 facets) -> the box instantiation; 0: the generic one
-    int align_rows = 0;       // group placement rule (group_base)
-    int store_dl = 0;         // LDS holds the final dual directions of the facet rows (kernel template SDL)
-    double nx = 0, nmu = 0;
+    CreatePlan plan;          // (its arrays that only fed an upload are released after it: the buffers below know their lengths)
     gcsadmm_params params{};
     bool params_set = false;
-    // device buffers
-    int *d_inc_ptr = nullptr, *d_deg_in = nullptr, *d_inc_edge = nullptr, *d_poly_ptr = nullptr;
-    int *d_edge_inc_tail = nullptr, *d_edge_inc_head = nullptr;
-    int *d_wave_slot_ptr = nullptr, *d_wave_vtx = nullptr, *d_special_vtx = nullptr, *d_special_kind = nullptr, *d_wg_vtx = nullptr;
-    double *d_poly_A = nullptr, *d_poly_bc = nullptr, *d_center = nullptr;
-    uint8_t *d_inc_counted = nullptr, *d_edge_counted = nullptr;
-    gcsadmm_control_block *d_cb = nullptr;
-    int *d_counters = nullptr;
-    double *d_partials = nullptr, *d_sums = nullptr;
-    unsigned *d_ticket = nullptr;
-    // prox configuration (gcsadmm_vertex_prox): every non-terminal vertex, LDS of the border-only problem, own counters
-    int *d_prox_vtx = nullptr, *d_prox_counters = nullptr, n_prox = 0, prox_lds_bytes = 0, src = -1, dst = -1;     // arrival counter of the single-launch edge step (edge_kernel MODE 2)
-    std::vector<hipEvent_t> events;
-    std::string err;
-    // vertex partition across GPUs (gcsadmm_attach_comm): RCCL communicator, halo index lists and message buffers
-    void *comm = nullptr;             // ncclComm_t
-    int rank = 0, world = 1;
-    std::vector<int> peers, peer_cnt, peer_off;   // neighbour ranks; columns per peer; first column of each peer's block
-    int n_send = 0, n_recv = 0;       // halo columns sent / received per iteration
-    int *d_send_cols = nullptr, *d_send_base = nullptr, *d_send_stride = nullptr;
-    int *d_recv_cols = nullptr, *d_recv_base = nullptr, *d_recv_stride = nullptr;
-    void *d_sendbuf = nullptr, *d_recvbuf = nullptr;
-    double *d_sums6 = nullptr;        // the five norms + the inner-failure count, all-reduced together
-    // warm start of the vertex solves (warm_start.h): one record per generic vertex, d_warm + d_warm_ptr[v]
-    double *d_warm = nullptr;
-    long long *d_warm_ptr = nullptr;
-    size_t warm_doubles = 0;
-    // slowest-first dispatch (reorder_kernel): per wavefront / per workgroup-program vertex, last Newton iteration count and launch order
-    int *d_wave_iters = nullptr, *d_wave_order = nullptr, *d_wg_iters = nullptr, *d_wg_order = nullptr;
     int vertex_steps = 0;     // vertex steps enqueued since the last reset
-    // overlapped partitioned loop (boundary vertices first, the halo exchange behind them while the interior is solved):
-    // host copies of the wavefront packing (which wavefront holds which vertex) and of the column -> vertex map, the split of the
-    // wavefronts into boundary (holding a vertex with a cut edge) and interior, a second stream for the exchange and two events
-    std::vector<int> h_wave_slot_ptr, h_wave_vtx, col_vertex;
     int overlap_mode = 0;     // gcsadmm_set_overlap: 0 automatic, 1 forced (tests: works without peers), 2 off
-    int n_wave_b = 0;         // boundary wavefronts (0: no split)
-    int *d_split_ids = nullptr, *d_split_order = nullptr;    // [n_waves] static ids / launch order: boundary wavefronts first, then interior
-    hipStream_t comm_stream = nullptr;
-    hipEvent_t ev_boundary = nullptr, ev_halo = nullptr;
-    // terminals that are regions (terminal_region.h): at most two, one workgroup each, on an auxiliary stream beside the vertex-step launch
-    int n_term = 0, term_vtx[2] = {-1, -1}, term_is_src[2] = {0, 0};
-    long long term_ws_off[2] = {0, 0}, term_rec_off[2] = {0, 0};
-    double *d_term_ws = nullptr, *d_term_rec = nullptr;      // work arrays (when they do not fit LDS); warm-start records
-    size_t term_rec_doubles = 0;
-    int term_threads = 256, term_lds_doubles = 0;     // launch shape: one wavefront and LDS work arrays for small terminals
-    hipStream_t term_stream = nullptr;
-    hipEvent_t ev_term_fork = nullptr, ev_term_join = nullptr;
+    std::string err;
+    void *comm = nullptr;     // ncclComm_t (gcsadmm_attach_comm)
+    int rank = 0, world = 1;
+    std::vector<int> iota;    // 0, 1, ..: the initial launch order of the slowest-first dispatch (create and every reset upload it)
+    // the graph and what the plan made of it: from create to destroy
+    struct Graph {
+        DevBuf<int> d_inc_ptr, d_deg_in, d_inc_edge, d_poly_ptr, d_edge_inc_tail, d_edge_inc_head;
+        DevBuf<int> d_wave_slot_ptr, d_wave_vtx, d_special_vtx, d_special_kind, d_wg_vtx;
+        DevBuf<double> d_poly_A, d_poly_bc, d_center;
+        DevBuf<uint8_t> d_inc_counted, d_edge_counted;      // may stay empty
+        // split form of the workgroup program (gcsadmm_graph_desc.vertex_workspace): vertices, their units' slabs
+        DevBuf<int> d_split_vtx;
+        DevBuf<long long> d_split_off;
+        DevBuf<double> d_split_ws;
+        // warm start of the vertex solves (warm_start.h): one record per generic vertex, d_warm + d_warm_ptr[v]
+        DevBuf<double> d_warm;
+        DevBuf<long long> d_warm_ptr;
+        // slowest-first dispatch (reorder_kernel): per wavefront / per workgroup-program vertex, last Newton iteration count and launch order
+        DevBuf<int> d_wave_iters, d_wave_order, d_wg_iters, d_wg_order;
+    } g;
+    // scratch of the iteration loop
+    struct Loop {
+        DevBuf<gcsadmm_control_block> d_cb;
+        DevBuf<int> d_counters;
+        DevBuf<double> d_partials, d_sums;
+        DevBuf<unsigned> d_ticket;      // arrival counter of the single-launch edge step (edge_kernel MODE 2)
+    } loop;
+    struct Prox { DevBuf<int> d_prox_vtx, d_prox_counters; } prox;      // gcsadmm_vertex_prox: every non-terminal vertex, own counters
+    Halo halo;
+    Overlap overlap;
+    Terminals term;
+    std::vector<Event> events;      // pool of timing events (gcsadmm_run_timed, gcsadmm_run_partitioned_timed)
+
+    int n_special() const { return (int)g.d_special_vtx.size(); }
+    int n_wg() const { return (int)g.d_wg_vtx.size(); }       // vertices solved by the workgroup program (vertex_wg.hip)
+    int n_split() const { return (int)g.d_split_vtx.size(); }
 };
 
 // ---- RCCL, bound at run time ----
@@ -502,30 +549,27 @@ struct DeviceGuard {
         }                                                                                            \
     } while (0)
 
-template <class U> static hipError_t upload(U **dst, const U *src, size_t count)
-{
-    *dst = nullptr;
-    if (count == 0) count = 1;
-    hipError_t e = hipMalloc((void **)dst, count * sizeof(U));
-    if (e != hipSuccess) return e;
-    if (src) return hipMemcpy(*dst, src, count * sizeof(U), hipMemcpyHostToDevice);
-    return hipMemset(*dst, 0, count * sizeof(U));
-}
+// f(double()) or f(float()): the one switch on the handle's state type
+template <class F> static auto with_state(const gcsadmm_handle_s *h, F &&f) { return with_state_type(h->dtype == GCSADMM_F64, f); }
+static size_t state_bytes(const gcsadmm_handle_s *h) { return h->dtype == GCSADMM_F64 ? 8 : 4; }
 
-static VertexLaunchDesc make_launch_desc(gcsadmm_handle h, const gcsadmm_state *st);
-static void halo_free(gcsadmm_handle h);
+static ControlParams control_params(const gcsadmm_handle_s *h)
+{
+    const gcsadmm_params &p = h->params;
+    return ControlParams{p.tau_incr, p.tau_decr, p.nu, p.eps_abs, p.eps_rel, h->plan.nx, h->plan.nmu, p.it_rho_limit, p.max_it};
+}
 
 // the inputs every vertex-step launch shares (step_args.h)
 static StepDesc make_step(gcsadmm_handle h, const gcsadmm_state *st)
 {
     StepDesc a;
-    a.inc_ptr = h->d_inc_ptr; a.deg_in = h->d_deg_in; a.inc_edge = h->d_inc_edge; a.poly_ptr = h->d_poly_ptr;
-    a.poly_A = h->d_poly_A; a.poly_bc = h->d_poly_bc; a.center = h->d_center;
+    a.inc_ptr = h->g.d_inc_ptr.get(); a.deg_in = h->g.d_deg_in.get(); a.inc_edge = h->g.d_inc_edge.get(); a.poly_ptr = h->g.d_poly_ptr.get();
+    a.poly_A = h->g.d_poly_A.get(); a.poly_bc = h->g.d_poly_bc.get(); a.center = h->g.d_center.get();
     a.E = h->E; a.NI = h->NI; a.edge_major = h->edge_major;
     a.zedge = st->zedge; a.mu = st->mu; a.copy = st->copy; a.xv = st->xv; a.zv = st->zv; a.yv = st->yv;
-    a.counters = h->d_counters; a.cb = h->d_cb;
+    a.counters = h->loop.d_counters.get(); a.cb = h->loop.d_cb.get();
     a.eps_edge = h->params.eps_edge; a.ipm_tol = h->params.ipm_tol; a.ipm_max_iter = h->params.ipm_max_iter;
-    a.warm = h->params.cold_start ? nullptr : h->d_warm; a.warm_ptr = h->d_warm_ptr;
+    a.warm = h->params.cold_start ? nullptr : h->g.d_warm.get(); a.warm_ptr = h->g.d_warm_ptr.get();
     return a;
 }
 
@@ -536,112 +580,130 @@ static WgLaunchDesc make_wg_desc(gcsadmm_handle h, const gcsadmm_state *st, bool
 {
     WgLaunchDesc d;
     d.step = make_step(h, st);
-    d.n = h->n; d.dtype = h->dtype; d.n_vtx = h->n_wg; d.n_special = with_special ? h->n_special : 0; d.lds_bytes = h->wg_lds_bytes;
-    d.vtx = h->d_wg_vtx; d.special_vtx = h->d_special_vtx; d.special_kind = h->d_special_kind; d.box = h->wg_box;
-    d.order = h->d_wg_order; d.unit_iters = h->d_wg_iters;
+    d.n = h->n; d.dtype = h->dtype; d.n_vtx = h->n_wg(); d.n_special = with_special ? h->n_special() : 0; d.lds_bytes = h->plan.wg_lds_bytes;
+    d.vtx = h->g.d_wg_vtx.get(); d.special_vtx = h->g.d_special_vtx.get(); d.special_kind = h->g.d_special_kind.get(); d.box = h->plan.wg_box;
+    d.order = h->g.d_wg_order.get(); d.unit_iters = h->g.d_wg_iters.get();
+    return d;
+}
+
+static gcsadmm_k::TermLaunchDesc make_term_desc(gcsadmm_handle h, const gcsadmm_state *st)
+{
+    gcsadmm_k::TermLaunchDesc d;
+    const CreatePlan &p = h->plan;
+    d.step = make_step(h, st);
+    d.n = h->n; d.dtype = h->dtype; d.count = p.n_term; d.threads = p.term_threads; d.lds_doubles = p.term_lds_doubles;
+    for (int i = 0; i < 2; ++i) {
+        d.t.vtx[i] = p.term_vtx[i]; d.t.is_src[i] = p.term_is_src[i]; d.t.ws_off[i] = p.term_ws_off[i]; d.t.rec_off[i] = p.term_rec_off[i];
+    }
+    d.t.ws = h->term.d_term_ws.get();
+    d.t.rec = h->params.cold_start ? nullptr : h->term.d_term_rec.get();
+    return d;
+}
+
+static VertexLaunchDesc make_launch_desc(gcsadmm_handle h, const gcsadmm_state *st)
+{
+    VertexLaunchDesc d;
+    const CreatePlan &p = h->plan;
+    d.step = make_step(h, st);
+    d.n_waves = p.n_waves(); d.n_special = h->n_special(); d.all_m4 = p.all_m4; d.lds_bytes = p.lds_bytes; d.align_rows = p.align_rows;
+    d.store_dl = p.store_dl; d.MM = p.wave_mm;
+    d.wave_slot_ptr = h->g.d_wave_slot_ptr.get(); d.wave_vtx = h->g.d_wave_vtx.get(); d.special_vtx = h->g.d_special_vtx.get(); d.special_kind = h->g.d_special_kind.get();
+    d.wave_order = h->g.d_wave_order.get(); d.wave_iters = h->g.d_wave_iters.get();
     return d;
 }
 
 // part: -1 the whole vertex step; 0 / 1 the boundary / interior wavefronts of the overlapped partitioned loop (handles whose generic
 // vertices are all on the wavefront program; the closed-form vertices ride with the boundary part)
-static gcsadmm_k::TermLaunchDesc make_term_desc(gcsadmm_handle h, const gcsadmm_state *st)
+static gcsadmm_status launch_vertex(gcsadmm_handle h, const gcsadmm_state *st, hipStream_t s, int part = -1, bool reorder = false)
 {
-    gcsadmm_k::TermLaunchDesc d;
-    d.step = make_step(h, st);
-    d.n = h->n; d.dtype = h->dtype; d.count = h->n_term; d.threads = h->term_threads; d.lds_doubles = h->term_lds_doubles;
-    for (int i = 0; i < 2; ++i) {
-        d.t.vtx[i] = h->term_vtx[i]; d.t.is_src[i] = h->term_is_src[i]; d.t.ws_off[i] = h->term_ws_off[i]; d.t.rec_off[i] = h->term_rec_off[i];
-    }
-    d.t.ws = h->d_term_ws;
-    d.t.rec = h->params.cold_start ? nullptr : h->d_term_rec;
-    return d;
-}
-
-template <class T> static gcsadmm_status launch_vertex(gcsadmm_handle h, const gcsadmm_state *st, hipStream_t s, int part = -1, bool reorder = false)
-{
+    const auto &g = h->g;
+    const int n_waves = h->plan.n_waves();
+    const gcsadmm_control_block *cb = h->loop.d_cb.get();
+    auto launch_waves = [&](const VertexLaunchDesc &d) { with_state(h, [&](auto t) { launch_vertex_dim<2, decltype(t)>(d, s); }); };
     // terminals that are regions: their kernel runs on the auxiliary stream beside the launches below (it is a latency-bound solve in
     // one or two workgroups; the vertex launches do not wait for it, the caller's stream does at the end)
-    const bool with_term = h->n_term > 0 && part <= 0;
+    const bool with_term = h->plan.n_term > 0 && part <= 0;
     if (with_term) {
-        HIPCHK(h, hipEventRecord(h->ev_term_fork, s));
-        HIPCHK(h, hipStreamWaitEvent(h->term_stream, h->ev_term_fork, 0));
-        gcsadmm_terminal_launch(make_term_desc(h, st), h->term_stream);
-        HIPCHK(h, hipEventRecord(h->ev_term_join, h->term_stream));
+        HIPCHK(h, hipEventRecord(h->term.ev_term_fork.get(), s));
+        HIPCHK(h, hipStreamWaitEvent(h->term.term_stream.get(), h->term.ev_term_fork.get(), 0));
+        gcsadmm_terminal_launch(make_term_desc(h, st), h->term.term_stream.get());
+        HIPCHK(h, hipEventRecord(h->term.ev_term_join.get(), h->term.term_stream.get()));
     }
     struct Join {       // (every return path below joins)
         gcsadmm_handle h; hipStream_t s; bool on;
-        ~Join() { if (on) (void)hipStreamWaitEvent(s, h->ev_term_join, 0); }
+        ~Join() { if (on) (void)hipStreamWaitEvent(s, h->term.ev_term_join.get(), 0); }
     } join_{h, s, with_term};
     if (part >= 0) {
+        const Overlap &o = h->overlap;
         VertexLaunchDesc d = make_launch_desc(h, st);
-        const int off = part ? h->n_wave_b : 0, cnt = part ? h->n_waves - h->n_wave_b : h->n_wave_b;
-        d.wave_order = h->d_split_order + off;
+        const int off = part ? o.n_wave_b : 0, cnt = part ? n_waves - o.n_wave_b : o.n_wave_b;
+        d.wave_order = o.d_split_order.get() + off;
         d.n_waves = cnt;
         if (part) d.n_special = 0;
-        launch_vertex_dim<2, T>(d, s);
-        if (reorder && h->d_wave_iters)      // slowest first inside the part, on the part's own stream (its next launch reads the order)
-            hipLaunchKernelGGL(reorder_kernel, dim3(1), dim3(REORDER_THREADS), 0, s, cnt, h->d_wave_iters, h->d_split_order + off, h->d_cb, h->d_split_ids + off);
+        launch_waves(d);
+        if (reorder && g.d_wave_iters)      // slowest first inside the part, on the part's own stream (its next launch reads the order)
+            hipLaunchKernelGGL(reorder_kernel, dim3(1), dim3(REORDER_THREADS), 0, s, cnt, g.d_wave_iters.get(), o.d_split_order.get() + off, cb, o.d_split_ids.get() + off);
         HIPCHK(h, hipGetLastError());
         return GCSADMM_OK;
     }
-    const bool special_on_wave = h->n_waves > 0;
-    if (h->n_waves > 0) {
-        VertexLaunchDesc d = make_launch_desc(h, st);
-        launch_vertex_dim<2, T>(d, s);
-    }
-    if (h->n_wg > 0 || (!special_on_wave && h->n_special > 0)) {
-        if (h->wg_t512) gcsadmm_wg_launch_t512(make_wg_desc(h, st, !special_on_wave), s);
+    const bool special_on_wave = n_waves > 0;
+    if (n_waves > 0) launch_waves(make_launch_desc(h, st));
+    if (h->n_wg() > 0 || (!special_on_wave && h->n_special() > 0)) {
+        if (h->plan.wg_t512) gcsadmm_wg_launch_t512(make_wg_desc(h, st, !special_on_wave), s);
         else gcsadmm_wg_launch(make_wg_desc(h, st, !special_on_wave), s);
     }
-    if (h->n_split > 0) {      // the vertices too large for LDS: the split form, units in the handle's workspace
+    if (h->n_split() > 0) {      // the vertices too large for LDS: the split form, units in the handle's workspace
         WgLaunchDesc d = make_wg_desc(h, st, false);
-        d.n_vtx = h->n_split; d.vtx = h->d_split_vtx; d.lds_bytes = h->split_lds_bytes; d.order = nullptr; d.unit_iters = nullptr;
-        gcsadmm_wg_launch_split(d, WgSplitArgs{h->d_split_ws, h->d_split_off}, s);
+        d.n_vtx = h->n_split(); d.vtx = g.d_split_vtx.get(); d.lds_bytes = h->plan.split_lds_bytes; d.order = nullptr; d.unit_iters = nullptr;
+        gcsadmm_wg_launch_split(d, WgSplitArgs{g.d_split_ws.get(), g.d_split_off.get()}, s);
     }
     if (++h->vertex_steps % REORDER_EVERY == 0) {      // slowest-first dispatch of the following launches (graphs that need more than one round)
-        if (h->d_wave_order) hipLaunchKernelGGL(reorder_kernel, dim3(1), dim3(REORDER_THREADS), 0, s, h->n_waves, h->d_wave_iters, h->d_wave_order, h->d_cb);
-        if (h->d_wg_order) hipLaunchKernelGGL(reorder_kernel, dim3(1), dim3(REORDER_THREADS), 0, s, h->n_wg, h->d_wg_iters, h->d_wg_order, h->d_cb);
+        if (g.d_wave_order) hipLaunchKernelGGL(reorder_kernel, dim3(1), dim3(REORDER_THREADS), 0, s, n_waves, g.d_wave_iters.get(), g.d_wave_order.get(), cb);
+        if (g.d_wg_order) hipLaunchKernelGGL(reorder_kernel, dim3(1), dim3(REORDER_THREADS), 0, s, h->n_wg(), g.d_wg_iters.get(), g.d_wg_order.get(), cb);
     }
     HIPCHK(h, hipGetLastError());
     return GCSADMM_OK;
 }
 
 // with_control: the control step rides in the same launches (gcsadmm_run); trace may be null
-template <class T> static gcsadmm_status launch_edge(gcsadmm_handle h, const gcsadmm_state *st, double *sums, hipStream_t s,
-                                                     bool with_control = false, double *trace = nullptr, bool sums6 = false)
+static gcsadmm_status launch_edge(gcsadmm_handle h, const gcsadmm_state *st, double *sums, hipStream_t s, bool with_control = false,
+                                  double *trace = nullptr, bool sums6 = false)
 {
-    const gcsadmm_params &pp = h->params;
-    const ControlParams cp{pp.tau_incr, pp.tau_decr, pp.nu, pp.eps_abs, pp.eps_rel, h->nx, h->nmu, pp.it_rho_limit, pp.max_it};
-    EdgeArgs<T> a;
-    a.E = h->E; a.NI = h->NI; a.c = h->c;
-    a.edge_inc_tail = h->edge_major ? nullptr : h->d_edge_inc_tail; a.edge_inc_head = h->edge_major ? nullptr : h->d_edge_inc_head;
-    a.inc_counted = h->d_inc_counted; a.edge_counted = h->d_edge_counted;
-    a.copy = (const T *)st->copy; a.zedge = (T *)st->zedge; a.mu = (T *)st->mu; a.partials = h->d_partials;
-    // one kernel instantiation per (state type, mode, words per copy)
-    auto go = [&](auto mode, int blocks) {
-        constexpr int M = decltype(mode)::value;
-#define GCS_EDGE_U(CC, UU) hipLaunchKernelGGL((edge_kernel<T, M, CC, UU>), dim3(blocks), dim3(EDGE_BLOCK), 0, s, a, h->d_cb, sums, cp, h->d_counters, trace, h->d_ticket)
-#define GCS_EDGE(CC) do { if (h->edge_unroll > 1) GCS_EDGE_U(CC, (edge_unroll<T, CC>())); else GCS_EDGE_U(CC, 1); } while (0)
-        switch (h->c) {      // c = 2n + 1
-        case 3: GCS_EDGE(3); break;
-        case 5: GCS_EDGE(5); break;
-        case 7: GCS_EDGE(7); break;
-        case 9: GCS_EDGE(9); break;
-        case 11: GCS_EDGE(11); break;
-        case 13: GCS_EDGE(13); break;
-        case 15: GCS_EDGE(15); break;
-        default: GCS_EDGE(17);          // n = 8 (gcsadmm_create admits n = 1 .. 8)
-        }
+    const ControlParams cp = control_params(h);
+    const int edge_blocks = h->plan.edge_blocks;
+    with_state(h, [&](auto t) {
+        using T = decltype(t);
+        EdgeArgs<T> a;
+        a.E = h->E; a.NI = h->NI; a.c = h->c;
+        a.edge_inc_tail = h->edge_major ? nullptr : h->g.d_edge_inc_tail.get(); a.edge_inc_head = h->edge_major ? nullptr : h->g.d_edge_inc_head.get();
+        a.inc_counted = h->g.d_inc_counted.get(); a.edge_counted = h->g.d_edge_counted.get();
+        a.copy = (const T *)st->copy; a.zedge = (T *)st->zedge; a.mu = (T *)st->mu; a.partials = h->loop.d_partials.get();
+        // one kernel instantiation per (state type, mode, words per copy)
+        auto go = [&](auto mode, int blocks) {
+            constexpr int M = decltype(mode)::value;
+#define GCS_EDGE_U(CC, UU) hipLaunchKernelGGL((edge_kernel<T, M, CC, UU>), dim3(blocks), dim3(EDGE_BLOCK), 0, s, a, h->loop.d_cb.get(), sums, cp, h->loop.d_counters.get(), trace, h->loop.d_ticket.get())
+#define GCS_EDGE(CC) do { if (h->plan.edge_unroll > 1) GCS_EDGE_U(CC, (edge_unroll<T, CC>())); else GCS_EDGE_U(CC, 1); } while (0)
+            switch (h->c) {      // c = 2n + 1
+            case 3: GCS_EDGE(3); break;
+            case 5: GCS_EDGE(5); break;
+            case 7: GCS_EDGE(7); break;
+            case 9: GCS_EDGE(9); break;
+            case 11: GCS_EDGE(11); break;
+            case 13: GCS_EDGE(13); break;
+            case 15: GCS_EDGE(15); break;
+            default: GCS_EDGE(17);          // n = 8 (gcsadmm_create admits n = 1 .. 8)
+            }
 #undef GCS_EDGE_U
 #undef GCS_EDGE
-    };
-    if (sums6) go(std::integral_constant<int, 3>(), h->edge_blocks);
-    else if (with_control && h->edge_blocks == 1) go(std::integral_constant<int, 1>(), 1);
-    else if (with_control) go(std::integral_constant<int, 2>(), h->edge_blocks);
-    else {
-        go(std::integral_constant<int, 0>(), h->edge_blocks);
-        hipLaunchKernelGGL(finalize_kernel, dim3(1), dim3(256), 0, s, h->d_partials, h->edge_blocks, sums, h->d_cb);
-    }
+        };
+        if (sums6) go(std::integral_constant<int, 3>(), edge_blocks);
+        else if (with_control && edge_blocks == 1) go(std::integral_constant<int, 1>(), 1);
+        else if (with_control) go(std::integral_constant<int, 2>(), edge_blocks);
+        else {
+            go(std::integral_constant<int, 0>(), edge_blocks);
+            hipLaunchKernelGGL(finalize_kernel, dim3(1), dim3(256), 0, s, a.partials, edge_blocks, sums, h->loop.d_cb.get());
+        }
+    });
     HIPCHK(h, hipGetLastError());
     return GCSADMM_OK;
 }
@@ -651,17 +713,6 @@ static bool state_ok(gcsadmm_handle h, const gcsadmm_state *st)
     if (!h || !st || !st->copy || !st->mu || !st->zedge || !st->xv || !st->zv || !st->yv) { if (h) h->err = "null state pointer"; return false; }
     if (!h->params_set) { h->err = "gcsadmm_reset has not been called"; return false; }
     return true;
-}
-
-static VertexLaunchDesc make_launch_desc(gcsadmm_handle h, const gcsadmm_state *st)
-{
-    VertexLaunchDesc d;
-    d.step = make_step(h, st);
-    d.n_waves = h->n_waves; d.n_special = h->n_special; d.all_m4 = h->all_m4; d.lds_bytes = h->lds_bytes; d.align_rows = h->align_rows;
-    d.store_dl = h->store_dl; d.MM = h->MM;
-    d.wave_slot_ptr = h->d_wave_slot_ptr; d.wave_vtx = h->d_wave_vtx; d.special_vtx = h->d_special_vtx; d.special_kind = h->d_special_kind;
-    d.wave_order = h->d_wave_order; d.wave_iters = h->d_wave_iters;
-    return d;
 }
 
 // ---- halo of a vertex partition: host-side helpers (C++ linkage) ----
@@ -678,108 +729,97 @@ static gcsadmm_status halo_validate(gcsadmm_handle h, int rank, int world, const
         if (cnt < 0 || hd->recv_ptr[p + 1] - hd->recv_ptr[p] != cnt || hd->recv_ptr[p] != lo) { h->err = "halo lists: send and receive counts per peer must agree"; return GCSADMM_ERR_BAD_ARG; }
         if (hd->peer_rank[p] < 0 || hd->peer_rank[p] >= world || hd->peer_rank[p] == rank) { h->err = "halo lists: bad peer rank"; return GCSADMM_ERR_BAD_ARG; }
     }
+    const std::vector<char> &col_owned = h->plan.col_owned;
     for (int j = 0; j < n_send; ++j) {
         if (hd->send_cols[j] < 0 || hd->send_cols[j] >= h->NI || hd->recv_cols[j] < 0 || hd->recv_cols[j] >= h->NI) { h->err = "halo lists: column out of range"; return GCSADMM_ERR_BAD_ARG; }
-        if (!h->col_owned[hd->send_cols[j]]) { h->err = "halo lists: send column is not an owned incidence"; return GCSADMM_ERR_BAD_ARG; }
-        if (h->col_owned[hd->recv_cols[j]]) { h->err = "halo lists: receive column is not a ghost column"; return GCSADMM_ERR_BAD_ARG; }
+        if (!col_owned[hd->send_cols[j]]) { h->err = "halo lists: send column is not an owned incidence"; return GCSADMM_ERR_BAD_ARG; }
+        if (col_owned[hd->recv_cols[j]]) { h->err = "halo lists: receive column is not a ghost column"; return GCSADMM_ERR_BAD_ARG; }
     }
     return GCSADMM_OK;
 }
 
-static void overlap_free(gcsadmm_handle h)
+// The split of the wavefronts for the overlapped loop: boundary = holds a vertex one of whose columns (send_cols) is sent to a neighbour.
+// Only for handles whose generic vertices all run the wavefront program (config 4's strips); mode 1 (tests) splits even without
+// neighbours -- the first quarter of the wavefronts plays the boundary -- so that the two launches, the second stream and the events can
+// be exercised on one GPU.  Leaves n_wave_b = 0 when there is nothing to split.
+static gcsadmm_status overlap_setup(gcsadmm_handle h, const std::vector<int> &send_cols)
 {
-    for (void **p : {(void **)&h->d_split_ids, (void **)&h->d_split_order})
-        if (*p) { (void)hipFree(*p); *p = nullptr; }
-    if (h->ev_boundary) { (void)hipEventDestroy(h->ev_boundary); h->ev_boundary = nullptr; }
-    if (h->ev_halo) { (void)hipEventDestroy(h->ev_halo); h->ev_halo = nullptr; }
-    if (h->comm_stream) { (void)hipStreamDestroy(h->comm_stream); h->comm_stream = nullptr; }
-    h->n_wave_b = 0;
-}
-
-// The split of the wavefronts for the overlapped loop: boundary = holds a vertex one of whose columns is sent to a neighbour.  Only for
-// handles whose generic vertices all run the wavefront program (config 4's strips); mode 1 (tests) splits even without neighbours --
-// the first quarter of the wavefronts plays the boundary -- so that the two launches, the second stream and the events can be
-// exercised on one GPU.  Leaves n_wave_b = 0 when there is nothing to split.
-static gcsadmm_status overlap_setup(gcsadmm_handle h, const gcsadmm_halo_desc *hd)
-{
-    overlap_free(h);
-    if (h->overlap_mode == 2 || h->n_waves < 2 || h->n_wg > 0 || h->n_split > 0) return GCSADMM_OK;
-    const int n_send = (hd && hd->num_peers > 0) ? hd->send_ptr[hd->num_peers] : 0;
+    const CreatePlan &p = h->plan;
+    const int n_waves = p.n_waves(), n_send = (int)send_cols.size();
+    Overlap &o = h->overlap;
+    o = {};
+    if (h->overlap_mode == 2 || n_waves < 2 || h->n_wg() > 0 || h->n_split() > 0) return GCSADMM_OK;
     if (n_send == 0 && h->overlap_mode != 1) return GCSADMM_OK;
     std::vector<char> vb((size_t)std::max(h->V, 1), 0);
     for (int j = 0; j < n_send; ++j) {
-        const int v = h->col_vertex[hd->send_cols[j]];
+        const int v = p.col_vertex[send_cols[j]];
         if (v >= 0) vb[v] = 1;
     }
     std::vector<int> ids_b, ids_i;
-    for (int w = 0; w < h->n_waves; ++w) {
-        bool b = (n_send == 0) && w < std::max(1, h->n_waves / 4);
-        for (int q = h->h_wave_slot_ptr[w]; q < h->h_wave_slot_ptr[w + 1] && !b; ++q) b = vb[h->h_wave_vtx[q]] != 0;
+    for (int w = 0; w < n_waves; ++w) {
+        bool b = (n_send == 0) && w < std::max(1, n_waves / 4);
+        for (int q = p.wave_slot_ptr[w]; q < p.wave_slot_ptr[w + 1] && !b; ++q) b = vb[p.wave_vtx[q]] != 0;
         (b ? ids_b : ids_i).push_back(w);
     }
     if (ids_b.empty() || ids_i.empty()) return GCSADMM_OK;      // nothing to overlap with
-    h->n_wave_b = (int)ids_b.size();
+    o.n_wave_b = (int)ids_b.size();
     ids_b.insert(ids_b.end(), ids_i.begin(), ids_i.end());
-    HIPCHK(h, upload(&h->d_split_ids, ids_b.data(), ids_b.size()));
-    HIPCHK(h, upload(&h->d_split_order, ids_b.data(), ids_b.size()));
-    if (!h->d_wave_iters) HIPCHK(h, upload(&h->d_wave_iters, (const int *)nullptr, (size_t)h->n_waves));
-    HIPCHK(h, hipStreamCreateWithFlags(&h->comm_stream, hipStreamNonBlocking));
-    HIPCHK(h, hipEventCreateWithFlags(&h->ev_boundary, hipEventDisableTiming));
-    HIPCHK(h, hipEventCreateWithFlags(&h->ev_halo, hipEventDisableTiming));
+    HIPCHK(h, o.d_split_ids.upload(ids_b.data(), ids_b.size()));
+    HIPCHK(h, o.d_split_order.upload(ids_b.data(), ids_b.size()));
+    if (!h->g.d_wave_iters) HIPCHK(h, h->g.d_wave_iters.upload(nullptr, (size_t)n_waves));
+    HIPCHK(h, create_owned(o.comm_stream, hipStreamCreateWithFlags, hipStreamNonBlocking));
+    HIPCHK(h, create_owned(o.ev_boundary, hipEventCreateWithFlags, hipEventDisableTiming));
+    HIPCHK(h, create_owned(o.ev_halo, hipEventCreateWithFlags, hipEventDisableTiming));
     return GCSADMM_OK;
-}
-
-static void halo_free(gcsadmm_handle h)
-{
-    for (void **p : {(void **)&h->d_send_cols, (void **)&h->d_send_base, (void **)&h->d_send_stride, (void **)&h->d_recv_cols, (void **)&h->d_recv_base,
-                     (void **)&h->d_recv_stride, &h->d_sendbuf, &h->d_recvbuf, (void **)&h->d_sums6})
-        if (*p) { (void)hipFree(*p); *p = nullptr; }
-    h->peers.clear(); h->peer_cnt.clear(); h->peer_off.clear(); h->n_send = h->n_recv = 0;
 }
 
 static gcsadmm_status halo_upload(gcsadmm_handle h, const gcsadmm_halo_desc *hd)
 {
     const int P = hd->num_peers, c = h->c;
-    h->peers.assign(hd->peer_rank, hd->peer_rank + P);
-    h->peer_cnt.resize(P); h->peer_off.resize(P);
-    h->n_send = P ? hd->send_ptr[P] : 0; h->n_recv = P ? hd->recv_ptr[P] : 0;
-    std::vector<int> sbase(std::max(h->n_send, 1)), sstride(std::max(h->n_send, 1));
+    Halo &H = h->halo;
+    H.peers.assign(hd->peer_rank, hd->peer_rank + P);
+    H.peer_cnt.resize(P); H.peer_off.resize(P);
+    H.n_send = P ? hd->send_ptr[P] : 0; H.n_recv = P ? hd->recv_ptr[P] : 0;
+    H.send_cols.assign(hd->send_cols, hd->send_cols + H.n_send);
+    std::vector<int> sbase(std::max(H.n_send, 1)), sstride(std::max(H.n_send, 1));
     for (int p = 0; p < P; ++p) {
         const int lo = hd->send_ptr[p], cnt = hd->send_ptr[p + 1] - lo;
-        h->peer_cnt[p] = cnt; h->peer_off[p] = lo;
+        H.peer_cnt[p] = cnt; H.peer_off[p] = lo;
         for (int j = 0; j < cnt; ++j) { sbase[lo + j] = lo * c + j; sstride[lo + j] = cnt; }     // block of peer p: [c][cnt] at lo * c
     }
-    const size_t esz = h->dtype == GCSADMM_F64 ? 8 : 4;
-    HIPCHK(h, upload(&h->d_send_cols, hd->send_cols, (size_t)h->n_send));
-    HIPCHK(h, upload(&h->d_recv_cols, hd->recv_cols, (size_t)h->n_recv));
-    HIPCHK(h, upload(&h->d_send_base, sbase.data(), (size_t)h->n_send));
-    HIPCHK(h, upload(&h->d_send_stride, sstride.data(), (size_t)h->n_send));
-    HIPCHK(h, upload(&h->d_recv_base, sbase.data(), (size_t)h->n_recv));        // same block layout on the receiving side
-    HIPCHK(h, upload(&h->d_recv_stride, sstride.data(), (size_t)h->n_recv));
-    HIPCHK(h, hipMalloc(&h->d_sendbuf, std::max<size_t>((size_t)h->n_send * c * esz, 16)));
-    HIPCHK(h, hipMalloc(&h->d_recvbuf, std::max<size_t>((size_t)h->n_recv * c * esz, 16)));
+    const size_t esz = state_bytes(h);
+    HIPCHK(h, H.d_send_cols.upload(hd->send_cols, (size_t)H.n_send));
+    HIPCHK(h, H.d_recv_cols.upload(hd->recv_cols, (size_t)H.n_recv));
+    HIPCHK(h, H.d_send_base.upload(sbase.data(), (size_t)H.n_send));
+    HIPCHK(h, H.d_send_stride.upload(sstride.data(), (size_t)H.n_send));
+    HIPCHK(h, H.d_recv_base.upload(sbase.data(), (size_t)H.n_recv));        // same block layout on the receiving side
+    HIPCHK(h, H.d_recv_stride.upload(sstride.data(), (size_t)H.n_recv));
+    HIPCHK(h, H.d_sendbuf.alloc(std::max<size_t>((size_t)H.n_send * c * esz, 16)));
+    HIPCHK(h, H.d_recvbuf.alloc(std::max<size_t>((size_t)H.n_recv * c * esz, 16)));
     // [0..6): this partition's five norms + inner failures, written by the edge step; [6..12): their sum over the ranks.  (Out of
     // place: after the stop test has fired the edge step no longer writes, and an in-place all-reduce would multiply the stale
     // values by `world` with every further iteration that was enqueued.)
-    HIPCHK(h, upload(&h->d_sums6, (const double *)nullptr, 12));
+    HIPCHK(h, H.d_sums6.upload(nullptr, 12));
     return GCSADMM_OK;
 }
 
 template <class T> static gcsadmm_status halo_pack(gcsadmm_handle h, const gcsadmm_state *st, hipStream_t s)
 {
-    if (h->n_send == 0) return GCSADMM_OK;
-    const int tot = h->c * h->n_send;
-    hipLaunchKernelGGL((halo_pack_kernel<T>), dim3((tot + 255) / 256), dim3(256), 0, s, h->c, h->n_send, h->NI, h->d_send_cols,
-                       h->d_send_base, h->d_send_stride, (const T *)st->copy, (T *)h->d_sendbuf, h->d_cb);
+    const Halo &H = h->halo;
+    if (H.n_send == 0) return GCSADMM_OK;
+    const int tot = h->c * H.n_send;
+    hipLaunchKernelGGL((halo_pack_kernel<T>), dim3((tot + 255) / 256), dim3(256), 0, s, h->c, H.n_send, h->NI, H.d_send_cols.get(),
+                       H.d_send_base.get(), H.d_send_stride.get(), (const T *)st->copy, (T *)H.d_sendbuf.get(), h->loop.d_cb.get());
     HIPCHK(h, hipGetLastError());
     return GCSADMM_OK;
 }
 template <class T> static gcsadmm_status halo_unpack(gcsadmm_handle h, const gcsadmm_state *st, hipStream_t s)
 {
-    if (h->n_recv == 0) return GCSADMM_OK;
-    const int tot = h->c * h->n_recv;
-    hipLaunchKernelGGL((halo_unpack_kernel<T>), dim3((tot + 255) / 256), dim3(256), 0, s, h->c, h->n_recv, h->NI, h->d_recv_cols,
-                       h->d_recv_base, h->d_recv_stride, (const T *)h->d_recvbuf, (T *)st->copy, h->d_cb);
+    const Halo &H = h->halo;
+    if (H.n_recv == 0) return GCSADMM_OK;
+    const int tot = h->c * H.n_recv;
+    hipLaunchKernelGGL((halo_unpack_kernel<T>), dim3((tot + 255) / 256), dim3(256), 0, s, h->c, H.n_recv, h->NI, H.d_recv_cols.get(),
+                       H.d_recv_base.get(), H.d_recv_stride.get(), (const T *)H.d_recvbuf.get(), (T *)st->copy, h->loop.d_cb.get());
     HIPCHK(h, hipGetLastError());
     return GCSADMM_OK;
 }
@@ -787,17 +827,29 @@ template <class T> static gcsadmm_status halo_unpack(gcsadmm_handle h, const gcs
 // the grouped point-to-point exchange of the packed halo (one message per neighbour and direction)
 static gcsadmm_status halo_transfer(gcsadmm_handle h, hipStream_t s)
 {
-    if (h->peers.empty()) return GCSADMM_OK;
+    const Halo &H = h->halo;
+    if (H.peers.empty()) return GCSADMM_OK;
     if (!h->comm) { h->err = "halo exchange needs a communicator (gcsadmm_attach_comm with an id)"; return GCSADMM_ERR_BAD_ARG; }
     const ncclDataType_t dt = h->dtype == GCSADMM_F64 ? ncclFloat64 : ncclFloat32;
-    const size_t esz = h->dtype == GCSADMM_F64 ? 8 : 4;
+    const size_t esz = state_bytes(h);
     NCCLCHK(h, rccl().GroupStart());
-    for (size_t p = 0; p < h->peers.size(); ++p) {
-        const size_t off = (size_t)h->peer_off[p] * h->c * esz, cnt = (size_t)h->peer_cnt[p] * h->c;
-        NCCLCHK(h, rccl().Send((const char *)h->d_sendbuf + off, cnt, dt, h->peers[p], (ncclComm_t)h->comm, s));
-        NCCLCHK(h, rccl().Recv((char *)h->d_recvbuf + off, cnt, dt, h->peers[p], (ncclComm_t)h->comm, s));
+    for (size_t p = 0; p < H.peers.size(); ++p) {
+        const size_t off = (size_t)H.peer_off[p] * h->c * esz, cnt = (size_t)H.peer_cnt[p] * h->c;
+        NCCLCHK(h, rccl().Send(H.d_sendbuf.get() + off, cnt, dt, H.peers[p], (ncclComm_t)h->comm, s));
+        NCCLCHK(h, rccl().Recv(H.d_recvbuf.get() + off, cnt, dt, H.peers[p], (ncclComm_t)h->comm, s));
     }
     NCCLCHK(h, rccl().GroupEnd());
+    return GCSADMM_OK;
+}
+
+// the timing entry points bracket their stages with events of the handle's pool: at least `count` of them
+static gcsadmm_status ensure_events(gcsadmm_handle h, size_t count)
+{
+    while (h->events.size() < count) {
+        Event e;
+        HIPCHK(h, create_owned(e, hipEventCreateWithFlags, hipEventDefault));
+        h->events.push_back(std::move(e));
+    }
     return GCSADMM_OK;
 }
 
@@ -808,23 +860,8 @@ const char *gcsadmm_last_error(gcsadmm_handle h) { return h ? h->err.c_str() : g
 void gcsadmm_destroy(gcsadmm_handle h)
 {
     if (!h) return;
-    DeviceGuard device_guard_(h->device);
-    void *ptrs[] = {h->d_inc_ptr, h->d_deg_in, h->d_inc_edge, h->d_poly_ptr, h->d_edge_inc_tail, h->d_edge_inc_head,
-                    h->d_wave_slot_ptr, h->d_wave_vtx, h->d_special_vtx, h->d_special_kind, h->d_wg_vtx, h->d_poly_A, h->d_poly_bc,
-                    h->d_center, h->d_inc_counted, h->d_edge_counted, h->d_cb, h->d_counters, h->d_partials, h->d_sums, h->d_ticket, h->d_prox_vtx, h->d_prox_counters,
-                    h->d_warm, h->d_warm_ptr, h->d_wave_iters, h->d_wave_order, h->d_wg_iters, h->d_wg_order, h->d_split_vtx,
-                    h->d_split_off, h->d_split_ws};
-    for (void *p : ptrs)
-        if (p) (void)hipFree(p);
-    halo_free(h);
-    overlap_free(h);
-    if (h->d_term_ws) (void)hipFree(h->d_term_ws);
-    if (h->d_term_rec) (void)hipFree(h->d_term_rec);
-    if (h->ev_term_fork) (void)hipEventDestroy(h->ev_term_fork);
-    if (h->ev_term_join) (void)hipEventDestroy(h->ev_term_join);
-    if (h->term_stream) (void)hipStreamDestroy(h->term_stream);
+    DeviceGuard device_guard_(h->device);      // the owners release on the handle's device
     if (h->comm && rccl().ok()) (void)rccl().CommDestroy((ncclComm_t)h->comm);
-    for (auto ev : h->events) (void)hipEventDestroy(ev);
     delete h;
 }
 
@@ -839,93 +876,83 @@ gcsadmm_status gcsadmm_create(const gcsadmm_graph_desc *g, gcsadmm_handle *out)
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(GCSADMM_ERR_NO_DEVICE, "no HIP device");
     if (g->device < 0 || g->device >= ndev) return fail(GCSADMM_ERR_BAD_ARG, "device ordinal out of range");
-    CreatePlan p;
-    if ((st = make_create_plan(*g, p, msg)) != GCSADMM_OK) return fail(st, msg);
+    CreatePlan plan;
+    if ((st = make_create_plan(*g, plan, msg)) != GCSADMM_OK) return fail(st, msg);
 
     const int V = g->num_vertices, E = g->num_edges, n = g->n, NIo = g->inc_ptr[V], MT = g->poly_ptr[V];
     auto *h = new (std::nothrow) gcsadmm_handle_s;
     if (!h) return fail(GCSADMM_ERR_HIP, "out of host memory");
-    h->n = n; h->V = V; h->E = E; h->NI = g->num_incidences; h->NI_owned = NIo; h->c = 2 * n + 1; h->MM = p.wave_mm;
-    h->edge_major = g->edge_major_columns;
-    h->col_owned = std::move(p.col_owned); h->col_vertex = std::move(p.col_vertex);
-    h->h_wave_slot_ptr = p.wave_slot_ptr; h->h_wave_vtx = p.wave_vtx;
+    h->n = n; h->V = V; h->E = E; h->NI = g->num_incidences; h->c = 2 * n + 1;
+    h->edge_major = g->edge_major_columns; h->src = g->src; h->dst = g->dst;
     h->dtype = g->state_dtype; h->device = g->device;
-    h->n_waves = p.n_waves(); h->n_special = (int)p.special_vtx.size();
-    h->slots_cap = p.slots_cap; h->all_m4 = p.all_m4; h->align_rows = p.align_rows; h->store_dl = p.store_dl; h->lds_bytes = p.lds_bytes;
-    h->n_wg = (int)p.wg_vtx.size(); h->wg_lds_bytes = p.wg_lds_bytes; h->wg_box = p.wg_box; h->wg_t512 = p.wg_t512;
-    h->n_split = (int)p.split_vtx.size(); h->split_lds_bytes = p.split_lds_bytes; h->split_doubles = (size_t)p.split_doubles;
-    h->nx = p.nx; h->nmu = p.nmu;
-    h->edge_unroll = p.edge_unroll; h->edge_blocks = p.edge_blocks;
-    auto bail = [&](hipError_t e, const char *what) {
+    h->plan = std::move(plan);
+    CreatePlan &p = h->plan;
+    DeviceGuard device_guard_(g->device);
+    auto bail = [&](hipError_t e, const char *what) {      // (under the guard: whatever has been filled is released with the handle)
         g_create_error = std::string(what) + ": " + hipGetErrorString(e);
-        gcsadmm_destroy(h);
+        delete h;
         return GCSADMM_ERR_HIP;
     };
     hipError_t e;
-    DeviceGuard device_guard_(g->device);
     if ((e = device_guard_.err) != hipSuccess) return bail(e, "hipSetDevice");
-#define UP(dst, src, cnt) if ((e = upload(&h->dst, src, (size_t)(cnt))) != hipSuccess) return bail(e, "upload " #dst)
-    UP(d_inc_ptr, g->inc_ptr, V + 1);
-    UP(d_deg_in, p.deg_in.data(), V);
-    UP(d_inc_edge, g->inc_edge, NIo);
-    UP(d_poly_ptr, g->poly_ptr, V + 1);
-    UP(d_edge_inc_tail, g->edge_inc_tail, E);
-    UP(d_edge_inc_head, g->edge_inc_head, E);
-    UP(d_wave_slot_ptr, p.wave_slot_ptr.data(), p.wave_slot_ptr.size());
-    UP(d_wave_vtx, p.wave_vtx.data(), p.wave_vtx.size());
-    UP(d_special_vtx, p.special_vtx.data(), p.special_vtx.size());
-    UP(d_special_kind, p.special_kind.data(), p.special_kind.size());
-    UP(d_wg_vtx, p.wg_vtx.data(), p.wg_vtx.size());
-    if (h->n_split > 0) {
-        UP(d_split_vtx, p.split_vtx.data(), p.split_vtx.size());
-        UP(d_split_off, p.split_off.data(), p.split_off.size());
-        UP(d_split_ws, (const double *)nullptr, h->split_doubles);
+#define UP(group, dst, src, cnt) if ((e = h->group.dst.upload(src, (size_t)(cnt))) != hipSuccess) return bail(e, "upload " #dst)
+    UP(g, d_inc_ptr, g->inc_ptr, V + 1);
+    UP(g, d_deg_in, p.deg_in.data(), V);
+    UP(g, d_inc_edge, g->inc_edge, NIo);
+    UP(g, d_poly_ptr, g->poly_ptr, V + 1);
+    UP(g, d_edge_inc_tail, g->edge_inc_tail, E);
+    UP(g, d_edge_inc_head, g->edge_inc_head, E);
+    UP(g, d_wave_slot_ptr, p.wave_slot_ptr.data(), p.wave_slot_ptr.size());
+    UP(g, d_wave_vtx, p.wave_vtx.data(), p.wave_vtx.size());
+    UP(g, d_special_vtx, p.special_vtx.data(), p.special_vtx.size());
+    UP(g, d_special_kind, p.special_kind.data(), p.special_kind.size());
+    UP(g, d_wg_vtx, p.wg_vtx.data(), p.wg_vtx.size());
+    if (!p.split_vtx.empty()) {
+        UP(g, d_split_vtx, p.split_vtx.data(), p.split_vtx.size());
+        UP(g, d_split_off, p.split_off.data(), p.split_off.size());
+        UP(g, d_split_ws, nullptr, p.split_doubles);
     }
-    UP(d_poly_A, g->poly_A, (size_t)MT * n);
-    UP(d_poly_bc, p.bc.data(), MT);
-    UP(d_center, g->center, (size_t)V * n);
-    if (g->inc_counted) UP(d_inc_counted, g->inc_counted, g->num_incidences);
-    if (g->edge_counted) UP(d_edge_counted, g->edge_counted, E);
-    UP(d_cb, (const gcsadmm_control_block *)nullptr, 1);
-    UP(d_counters, (const int *)nullptr, 2);
-    UP(d_partials, (const double *)nullptr, (size_t)h->edge_blocks * 5);
-    UP(d_sums, (const double *)nullptr, 5);
-    UP(d_ticket, (const unsigned *)nullptr, 1);
+    UP(g, d_poly_A, g->poly_A, (size_t)MT * n);
+    UP(g, d_poly_bc, p.bc.data(), MT);
+    UP(g, d_center, g->center, (size_t)V * n);
+    if (g->inc_counted) UP(g, d_inc_counted, g->inc_counted, g->num_incidences);
+    if (g->edge_counted) UP(g, d_edge_counted, g->edge_counted, E);
+    UP(loop, d_cb, nullptr, 1);
+    UP(loop, d_counters, nullptr, 2);
+    UP(loop, d_partials, nullptr, (size_t)p.edge_blocks * 5);
+    UP(loop, d_sums, nullptr, 5);
+    UP(loop, d_ticket, nullptr, 1);
     if (p.n_term > 0) {       // region terminals: workspace, an auxiliary stream and the fork / join events
-        h->n_term = p.n_term;
-        for (int i = 0; i < p.n_term; ++i) {
-            h->term_vtx[i] = p.term_vtx[i]; h->term_is_src[i] = p.term_is_src[i];
-            h->term_ws_off[i] = p.term_ws_off[i]; h->term_rec_off[i] = p.term_rec_off[i];
-        }
-        h->term_lds_doubles = p.term_lds_doubles; h->term_threads = p.term_threads;
-        UP(d_term_ws, (const double *)nullptr, (size_t)p.term_ws_doubles);
-        h->term_rec_doubles = (size_t)p.term_rec_doubles;
-        UP(d_term_rec, (const double *)nullptr, h->term_rec_doubles);
-        if ((e = hipStreamCreateWithFlags(&h->term_stream, hipStreamNonBlocking)) != hipSuccess) return bail(e, "hipStreamCreate");
-        if ((e = hipEventCreateWithFlags(&h->ev_term_fork, hipEventDisableTiming)) != hipSuccess) return bail(e, "hipEventCreate");
-        if ((e = hipEventCreateWithFlags(&h->ev_term_join, hipEventDisableTiming)) != hipSuccess) return bail(e, "hipEventCreate");
+        UP(term, d_term_ws, nullptr, p.term_ws_doubles);
+        UP(term, d_term_rec, nullptr, p.term_rec_doubles);
+        if ((e = create_owned(h->term.term_stream, hipStreamCreateWithFlags, hipStreamNonBlocking)) != hipSuccess) return bail(e, "hipStreamCreate");
+        if ((e = create_owned(h->term.ev_term_fork, hipEventCreateWithFlags, hipEventDisableTiming)) != hipSuccess) return bail(e, "hipEventCreate");
+        if ((e = create_owned(h->term.ev_term_join, hipEventCreateWithFlags, hipEventDisableTiming)) != hipSuccess) return bail(e, "hipEventCreate");
     }
-    h->warm_doubles = (size_t)p.warm_ptr[V];
-    UP(d_warm_ptr, p.warm_ptr.data(), V + 1);
-    UP(d_warm, (const double *)nullptr, h->warm_doubles);
-    {   // slowest-first dispatch: only where a launch needs more than one round of the chip (small graphs run all at once)
-        std::vector<int> iota(std::max(std::max(h->n_waves, h->n_wg), 1));
-        for (size_t i = 0; i < iota.size(); ++i) iota[i] = (int)i;
-        if (p.wave_reorder) { UP(d_wave_iters, (const int *)nullptr, h->n_waves); UP(d_wave_order, iota.data(), h->n_waves); }
-        if (p.wg_reorder) { UP(d_wg_iters, (const int *)nullptr, h->n_wg); UP(d_wg_order, iota.data(), h->n_wg); }
-    }
-    h->n_prox = (int)p.prox_vtx.size(); h->src = g->src; h->dst = g->dst; h->prox_lds_bytes = p.prox_lds_bytes;
-    UP(d_prox_vtx, p.prox_vtx.data(), p.prox_vtx.size());
-    UP(d_prox_counters, (const int *)nullptr, 2);
+    UP(g, d_warm_ptr, p.warm_ptr.data(), V + 1);
+    UP(g, d_warm, nullptr, p.warm_ptr[V]);
+    // slowest-first dispatch: only where a launch needs more than one round of the chip (small graphs run all at once)
+    const int n_waves = p.n_waves(), n_wg = h->n_wg();
+    h->iota.resize(std::max(std::max(n_waves, n_wg), 1));
+    for (size_t i = 0; i < h->iota.size(); ++i) h->iota[i] = (int)i;
+    if (p.wave_reorder) { UP(g, d_wave_iters, nullptr, n_waves); UP(g, d_wave_order, h->iota.data(), n_waves); }
+    if (p.wg_reorder) { UP(g, d_wg_iters, nullptr, n_wg); UP(g, d_wg_order, h->iota.data(), n_wg); }
+    UP(prox, d_prox_vtx, p.prox_vtx.data(), p.prox_vtx.size());
+    UP(prox, d_prox_counters, nullptr, 2);
 #undef UP
-    if (h->lds_bytes > 48 * 1024) {
-        e = h->dtype == GCSADMM_F64 ? set_lds_attr<2, double>(h->all_m4, h->lds_bytes) : set_lds_attr<2, float>(h->all_m4, h->lds_bytes);
+    // the plan's arrays that only fed an upload (the three the halo checks and the overlap split read stay: wave_slot_ptr, wave_vtx,
+    // col_owned / col_vertex)
+    auto release = [](auto &v) { v.clear(); v.shrink_to_fit(); };
+    release(p.bc); release(p.deg_in); release(p.warm_ptr); release(p.prox_vtx); release(p.special_vtx); release(p.special_kind);
+    release(p.wg_vtx); release(p.split_vtx); release(p.split_off);
+    if (p.lds_bytes > 48 * 1024) {
+        e = with_state(h, [&](auto t) { return set_lds_attr<2, decltype(t)>(p.all_m4, p.lds_bytes); });
         if (e != hipSuccess) return bail(e, "hipFuncSetAttribute(MaxDynamicSharedMemorySize)");
     }
-    if (h->wg_lds_bytes > 48 * 1024 && (e = h->wg_t512 ? gcsadmm_wg_set_lds_t512(h->n, h->dtype, h->wg_lds_bytes)
-                                                        : gcsadmm_wg_set_lds(h->n, h->dtype, h->wg_lds_bytes)) != hipSuccess)
+    if (p.wg_lds_bytes > 48 * 1024 && (e = p.wg_t512 ? gcsadmm_wg_set_lds_t512(h->n, h->dtype, p.wg_lds_bytes)
+                                                      : gcsadmm_wg_set_lds(h->n, h->dtype, p.wg_lds_bytes)) != hipSuccess)
         return bail(e, "hipFuncSetAttribute(MaxDynamicSharedMemorySize, workgroup program)");
-    if (h->split_lds_bytes > 48 * 1024 && (e = gcsadmm_wg_set_split_lds(h->n, h->dtype, h->split_lds_bytes)) != hipSuccess)
+    if (p.split_lds_bytes > 48 * 1024 && (e = gcsadmm_wg_set_split_lds(h->n, h->dtype, p.split_lds_bytes)) != hipSuccess)
         return bail(e, "hipFuncSetAttribute(MaxDynamicSharedMemorySize, split workgroup program)");
     *out = h;
     return GCSADMM_OK;
@@ -939,21 +966,18 @@ gcsadmm_status gcsadmm_reset(gcsadmm_handle h, const gcsadmm_params *p, void *st
     gcsadmm_control_block cb{};
     cb.rho = p->rho; cb.mu_scale = 1.0; cb.it = 1; cb.status = GCSADMM_RUNNING;
     USE_DEVICE(h);
-    HIPCHK(h, hipMemcpyAsync(h->d_cb, &cb, sizeof(cb), hipMemcpyHostToDevice, (hipStream_t)stream));
-    HIPCHK(h, hipMemsetAsync(h->d_counters, 0, 2 * sizeof(int), (hipStream_t)stream));
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(h, hipMemcpyAsync(h->loop.d_cb.get(), &cb, sizeof(cb), hipMemcpyHostToDevice, s));
+    HIPCHK(h, h->loop.d_counters.zero(s));
     // a new run starts without warm-start records (runs from the same state are then identical, whatever ran before)
-    if (h->warm_doubles > 0) HIPCHK(h, hipMemsetAsync(h->d_warm, 0, h->warm_doubles * sizeof(double), (hipStream_t)stream));
-    if (h->term_rec_doubles > 0) HIPCHK(h, hipMemsetAsync(h->d_term_rec, 0, h->term_rec_doubles * sizeof(double), (hipStream_t)stream));
+    HIPCHK(h, h->g.d_warm.zero(s));
+    HIPCHK(h, h->term.d_term_rec.zero(s));
     h->vertex_steps = 0;
-    if (h->d_split_order) HIPCHK(h, hipMemcpyAsync(h->d_split_order, h->d_split_ids, sizeof(int) * (size_t)h->n_waves, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    for (auto po : {std::make_pair(h->d_wave_order, h->n_waves), std::make_pair(h->d_wg_order, h->n_wg)})
-        if (po.first) {
-            std::vector<int> iota(po.second);
-            for (int i = 0; i < po.second; ++i) iota[i] = i;
-            HIPCHK(h, hipMemcpyAsync(po.first, iota.data(), sizeof(int) * po.second, hipMemcpyHostToDevice, (hipStream_t)stream));
-            HIPCHK(h, hipStreamSynchronize((hipStream_t)stream));      // iota is a stack object
-        }
-    HIPCHK(h, hipStreamSynchronize((hipStream_t)stream));   // cb is a stack object
+    const Overlap &o = h->overlap;
+    if (o.d_split_order) HIPCHK(h, hipMemcpyAsync(o.d_split_order.get(), o.d_split_ids.get(), sizeof(int) * o.d_split_order.size(), hipMemcpyDeviceToDevice, s));
+    for (const DevBuf<int> *order : {&h->g.d_wave_order, &h->g.d_wg_order})      // (h->iota outlives the copies)
+        if (*order) HIPCHK(h, hipMemcpyAsync(order->get(), h->iota.data(), sizeof(int) * order->size(), hipMemcpyHostToDevice, s));
+    HIPCHK(h, hipStreamSynchronize(s));   // cb is a stack object
     return GCSADMM_OK;
 }
 
@@ -961,23 +985,21 @@ gcsadmm_status gcsadmm_vertex_step(gcsadmm_handle h, const gcsadmm_state *st, vo
 {
     if (!state_ok(h, st)) return GCSADMM_ERR_BAD_ARG;
     USE_DEVICE(h);
-    return h->dtype == GCSADMM_F64 ? launch_vertex<double>(h, st, (hipStream_t)stream) : launch_vertex<float>(h, st, (hipStream_t)stream);
+    return launch_vertex(h, st, (hipStream_t)stream);
 }
 
 gcsadmm_status gcsadmm_edge_step(gcsadmm_handle h, const gcsadmm_state *st, double *sums_dev, void *stream)
 {
     if (!state_ok(h, st) || !sums_dev) return GCSADMM_ERR_BAD_ARG;
     USE_DEVICE(h);
-    return h->dtype == GCSADMM_F64 ? launch_edge<double>(h, st, sums_dev, (hipStream_t)stream) : launch_edge<float>(h, st, sums_dev, (hipStream_t)stream);
+    return launch_edge(h, st, sums_dev, (hipStream_t)stream);
 }
 
 gcsadmm_status gcsadmm_control(gcsadmm_handle h, const double *sums_dev, double *trace_dev, void *stream)
 {
     if (!h || !sums_dev || !h->params_set) return GCSADMM_ERR_BAD_ARG;
     USE_DEVICE(h);
-    const gcsadmm_params &p = h->params;
-    ControlParams cp{p.tau_incr, p.tau_decr, p.nu, p.eps_abs, p.eps_rel, h->nx, h->nmu, p.it_rho_limit, p.max_it};
-    hipLaunchKernelGGL(control_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, h->d_cb, sums_dev, cp, h->d_counters, trace_dev, false);
+    hipLaunchKernelGGL(control_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, h->loop.d_cb.get(), sums_dev, control_params(h), h->loop.d_counters.get(), trace_dev, false);
     HIPCHK(h, hipGetLastError());
     return GCSADMM_OK;
 }
@@ -990,9 +1012,7 @@ gcsadmm_status gcsadmm_run(gcsadmm_handle h, const gcsadmm_state *st, int32_t k,
         gcsadmm_status s;
         if ((s = gcsadmm_vertex_step(h, st, stream)) != GCSADMM_OK) return s;
         // edge step and control step in two launches (one when all edges fit a single workgroup)
-        s = h->dtype == GCSADMM_F64 ? launch_edge<double>(h, st, h->d_sums, (hipStream_t)stream, true, trace_dev)
-                                    : launch_edge<float>(h, st, h->d_sums, (hipStream_t)stream, true, trace_dev);
-        if (s != GCSADMM_OK) return s;
+        if ((s = launch_edge(h, st, h->loop.d_sums.get(), (hipStream_t)stream, true, trace_dev)) != GCSADMM_OK) return s;
     }
     return GCSADMM_OK;
 }
@@ -1020,7 +1040,7 @@ gcsadmm_status gcsadmm_comm_unique_id(void *id128)
 gcsadmm_status gcsadmm_check_halo(gcsadmm_handle h, int32_t rank, int32_t world, const gcsadmm_halo_desc *halo)
 {
     if (!h) return GCSADMM_ERR_BAD_ARG;
-    if (h->d_sums6) { h->err = "a communicator is already attached"; return GCSADMM_ERR_BAD_ARG; }
+    if (h->halo.attached()) { h->err = "a communicator is already attached"; return GCSADMM_ERR_BAD_ARG; }
     return halo_validate(h, rank, world, halo);
 }
 
@@ -1032,7 +1052,7 @@ gcsadmm_status gcsadmm_attach_comm(gcsadmm_handle h, int32_t rank, int32_t world
     if (id128 && !rccl().ok()) { h->err = rccl().err; return GCSADMM_ERR_HIP; }
     USE_DEVICE(h);
     h->rank = rank; h->world = world;
-    if ((st = halo_upload(h, halo)) != GCSADMM_OK) { halo_free(h); return st; }
+    if ((st = halo_upload(h, halo)) != GCSADMM_OK) { h->halo = {}; return st; }
     if (id128) {      // id128 == NULL: no communicator (the host moves the packed buffers itself; gcsadmm_run_partitioned needs one)
         ncclUniqueId id;
         std::memcpy(&id, id128, sizeof(id));
@@ -1040,53 +1060,76 @@ gcsadmm_status gcsadmm_attach_comm(gcsadmm_handle h, int32_t rank, int32_t world
         const ncclResult_t r = rccl().CommInitRank(&comm, world, id, rank);
         if (r != ncclSuccess) {      // not attached: the handle can be attached again
             h->err = std::string("ncclCommInitRank: ") + (rccl().GetErrorString ? rccl().GetErrorString(r) : "RCCL error");
-            halo_free(h);
+            h->halo = {};
             return GCSADMM_ERR_HIP;
         }
         h->comm = comm;
     }
-    return overlap_setup(h, halo);
+    return overlap_setup(h, h->halo.send_cols);
 }
 
 gcsadmm_status gcsadmm_halo_pack(gcsadmm_handle h, const gcsadmm_state *st, void *stream)
 {
-    if (!state_ok(h, st) || !h->d_sums6) { if (h) h->err = "no halo attached"; return GCSADMM_ERR_BAD_ARG; }
+    if (!state_ok(h, st) || !h->halo.attached()) { if (h) h->err = "no halo attached"; return GCSADMM_ERR_BAD_ARG; }
     USE_DEVICE(h);
-    return h->dtype == GCSADMM_F64 ? halo_pack<double>(h, st, (hipStream_t)stream) : halo_pack<float>(h, st, (hipStream_t)stream);
+    return with_state(h, [&](auto t) { return halo_pack<decltype(t)>(h, st, (hipStream_t)stream); });
 }
 gcsadmm_status gcsadmm_halo_unpack(gcsadmm_handle h, const gcsadmm_state *st, void *stream)
 {
-    if (!state_ok(h, st) || !h->d_sums6) { if (h) h->err = "no halo attached"; return GCSADMM_ERR_BAD_ARG; }
+    if (!state_ok(h, st) || !h->halo.attached()) { if (h) h->err = "no halo attached"; return GCSADMM_ERR_BAD_ARG; }
     USE_DEVICE(h);
-    return h->dtype == GCSADMM_F64 ? halo_unpack<double>(h, st, (hipStream_t)stream) : halo_unpack<float>(h, st, (hipStream_t)stream);
+    return with_state(h, [&](auto t) { return halo_unpack<decltype(t)>(h, st, (hipStream_t)stream); });
 }
 gcsadmm_status gcsadmm_halo_buffers(gcsadmm_handle h, void **send_buf, void **recv_buf, int64_t *num_elements)
 {
-    if (!h || !h->d_sums6) { if (h) h->err = "no halo attached"; return GCSADMM_ERR_BAD_ARG; }
-    if (send_buf) *send_buf = h->d_sendbuf;
-    if (recv_buf) *recv_buf = h->d_recvbuf;
-    if (num_elements) *num_elements = (int64_t)h->c * h->n_send;
+    if (!h || !h->halo.attached()) { if (h) h->err = "no halo attached"; return GCSADMM_ERR_BAD_ARG; }
+    if (send_buf) *send_buf = h->halo.d_sendbuf.get();
+    if (recv_buf) *recv_buf = h->halo.d_recvbuf.get();
+    if (num_elements) *num_elements = (int64_t)h->c * h->halo.n_send;
     return GCSADMM_OK;
 }
 
 gcsadmm_status gcsadmm_halo_exchange(gcsadmm_handle h, const gcsadmm_state *st, void *stream)
 {
-    if (!state_ok(h, st) || !h->d_sums6) { if (h) h->err = "no halo attached"; return GCSADMM_ERR_BAD_ARG; }
+    if (!state_ok(h, st) || !h->halo.attached()) { if (h) h->err = "no halo attached"; return GCSADMM_ERR_BAD_ARG; }
     USE_DEVICE(h);
     hipStream_t s = (hipStream_t)stream;
-    gcsadmm_status r;
-    if ((r = h->dtype == GCSADMM_F64 ? halo_pack<double>(h, st, s) : halo_pack<float>(h, st, s)) != GCSADMM_OK) return r;
-    if ((r = halo_transfer(h, s)) != GCSADMM_OK) return r;
-    return h->dtype == GCSADMM_F64 ? halo_unpack<double>(h, st, s) : halo_unpack<float>(h, st, s);
+    return with_state(h, [&](auto t) {
+        using T = decltype(t);
+        gcsadmm_status r;
+        if ((r = halo_pack<T>(h, st, s)) != GCSADMM_OK) return r;
+        if ((r = halo_transfer(h, s)) != GCSADMM_OK) return r;
+        return halo_unpack<T>(h, st, s);
+    });
+}
+
+// The end of an iteration of the partitioned loop, on the caller's stream: the edge step (sums + failure count, one launch), the
+// all-reduce of the six doubles where a communicator is attached, the control step fed from the reduced sums.  ev != nullptr (the
+// stage-timed serial schedule): three events, recorded after the edge step, after the all-reduce and after the control step.
+static gcsadmm_status partitioned_tail(gcsadmm_handle h, const gcsadmm_state *st, double *trace_dev, hipStream_t s, const Event *ev)
+{
+    double *sums6 = h->halo.d_sums6.get();
+    gcsadmm_status r = launch_edge(h, st, sums6, s, false, nullptr, true);
+    if (r != GCSADMM_OK) return r;
+    if (ev) HIPCHK(h, hipEventRecord(ev[0].get(), s));
+    const double *reduced = sums6;
+    if (h->comm) {
+        NCCLCHK(h, rccl().AllReduce(sums6, sums6 + 6, 6, ncclFloat64, ncclSum, (ncclComm_t)h->comm, s));
+        reduced = sums6 + 6;
+    }
+    if (ev) HIPCHK(h, hipEventRecord(ev[1].get(), s));
+    hipLaunchKernelGGL(control_kernel, dim3(1), dim3(1), 0, s, h->loop.d_cb.get(), reduced, control_params(h), h->loop.d_counters.get(), trace_dev, true);
+    HIPCHK(h, hipGetLastError());
+    if (ev) HIPCHK(h, hipEventRecord(ev[2].get(), s));
+    return GCSADMM_OK;
 }
 
 // one loop for gcsadmm_run_partitioned and its event-bracketed twin: ev != nullptr records 6 events per iteration on the stream
 // (before / after the vertex step, after the halo exchange, after the edge step, after the all-reduce, after the control step)
-static gcsadmm_status run_partitioned_loop(gcsadmm_handle h, const gcsadmm_state *st, int k, double *trace_dev, hipStream_t s, hipEvent_t *ev)
+static gcsadmm_status run_partitioned_loop(gcsadmm_handle h, const gcsadmm_state *st, int k, double *trace_dev, hipStream_t s, const Event *ev)
 {
-    const gcsadmm_params &pp = h->params;
-    const ControlParams cp{pp.tau_incr, pp.tau_decr, pp.nu, pp.eps_abs, pp.eps_rel, h->nx, h->nmu, pp.it_rho_limit, pp.max_it};
     if (!h->comm && h->world > 1) { h->err = "gcsadmm_run_partitioned needs a communicator (gcsadmm_attach_comm with an id)"; return GCSADMM_ERR_BAD_ARG; }
+    gcsadmm_status r;
     // OVERLAPPED form (not for the stage-timed twin, whose events want one stream): the wavefronts that hold a vertex with a
     // cut edge are launched FIRST and on a second stream, with pack, grouped send / recv and unpack of the halo behind them; the interior
     // wavefronts are launched on the caller's stream at the same time, and the edge step waits for both.  Same kernels, same numbers: the
@@ -1096,53 +1139,32 @@ static gcsadmm_status run_partitioned_loop(gcsadmm_handle h, const gcsadmm_state
     // (The two launches must be CONCURRENT: one after the other on one stream each waits for its own slowest wavefront -- measured on a
     // strip of 12.6 k vertices, 348 -> 509 us per iteration.  RCCL orders the operations of one communicator across streams itself;
     // every rank issues them in the same order.)
-    const bool overlap = !ev && h->n_wave_b > 0 && h->overlap_mode != 2;
-    for (int i = 0; i < k && overlap; ++i) {
-        gcsadmm_status r;
-        const bool f64 = h->dtype == GCSADMM_F64;
-        const bool reorder = ++h->vertex_steps % REORDER_EVERY == 0;
-        HIPCHK(h, hipEventRecord(h->ev_boundary, s));
-        HIPCHK(h, hipStreamWaitEvent(h->comm_stream, h->ev_boundary, 0));
-        if ((r = f64 ? launch_vertex<double>(h, st, h->comm_stream, 0, reorder) : launch_vertex<float>(h, st, h->comm_stream, 0, reorder)) != GCSADMM_OK) return r;
-        if ((r = gcsadmm_halo_exchange(h, st, (void *)h->comm_stream)) != GCSADMM_OK) return r;
-        HIPCHK(h, hipEventRecord(h->ev_halo, h->comm_stream));
-        if ((r = f64 ? launch_vertex<double>(h, st, s, 1, reorder) : launch_vertex<float>(h, st, s, 1, reorder)) != GCSADMM_OK) return r;
-        HIPCHK(h, hipStreamWaitEvent(s, h->ev_halo, 0));
-        r = f64 ? launch_edge<double>(h, st, h->d_sums6, s, false, nullptr, true) : launch_edge<float>(h, st, h->d_sums6, s, false, nullptr, true);
-        if (r != GCSADMM_OK) return r;
-        const double *reduced = h->d_sums6;
-        if (h->comm) {
-            NCCLCHK(h, rccl().AllReduce(h->d_sums6, h->d_sums6 + 6, 6, ncclFloat64, ncclSum, (ncclComm_t)h->comm, s));
-            reduced = h->d_sums6 + 6;
+    const Overlap &o = h->overlap;
+    if (!ev && o.n_wave_b > 0 && h->overlap_mode != 2) {
+        hipStream_t sc = o.comm_stream.get();
+        for (int i = 0; i < k; ++i) {
+            const bool reorder = ++h->vertex_steps % REORDER_EVERY == 0;
+            HIPCHK(h, hipEventRecord(o.ev_boundary.get(), s));
+            HIPCHK(h, hipStreamWaitEvent(sc, o.ev_boundary.get(), 0));
+            if ((r = launch_vertex(h, st, sc, 0, reorder)) != GCSADMM_OK) return r;
+            if ((r = gcsadmm_halo_exchange(h, st, (void *)sc)) != GCSADMM_OK) return r;
+            HIPCHK(h, hipEventRecord(o.ev_halo.get(), sc));
+            if ((r = launch_vertex(h, st, s, 1, reorder)) != GCSADMM_OK) return r;
+            HIPCHK(h, hipStreamWaitEvent(s, o.ev_halo.get(), 0));
+            if ((r = partitioned_tail(h, st, trace_dev, s, nullptr)) != GCSADMM_OK) return r;
         }
-        hipLaunchKernelGGL(control_kernel, dim3(1), dim3(1), 0, s, h->d_cb, reduced, cp, h->d_counters, trace_dev, true);
-        HIPCHK(h, hipGetLastError());
-    }
-    if (overlap) {      // the caller's stream is the one the caller synchronises: nothing of this call may still run on the other
-        HIPCHK(h, hipEventRecord(h->ev_halo, h->comm_stream));
-        HIPCHK(h, hipStreamWaitEvent(s, h->ev_halo, 0));
+        // the caller's stream is the one the caller synchronises: nothing of this call may still run on the other
+        HIPCHK(h, hipEventRecord(o.ev_halo.get(), sc));
+        HIPCHK(h, hipStreamWaitEvent(s, o.ev_halo.get(), 0));
         return GCSADMM_OK;
     }
     for (int i = 0; i < k; ++i) {
-        gcsadmm_status r;
-        if (ev) HIPCHK(h, hipEventRecord(ev[6 * i + 0], s));
+        if (ev) HIPCHK(h, hipEventRecord(ev[6 * i + 0].get(), s));
         if ((r = gcsadmm_vertex_step(h, st, (void *)s)) != GCSADMM_OK) return r;
-        if (ev) HIPCHK(h, hipEventRecord(ev[6 * i + 1], s));
+        if (ev) HIPCHK(h, hipEventRecord(ev[6 * i + 1].get(), s));
         if ((r = gcsadmm_halo_exchange(h, st, (void *)s)) != GCSADMM_OK) return r;
-        if (ev) HIPCHK(h, hipEventRecord(ev[6 * i + 2], s));
-        r = h->dtype == GCSADMM_F64 ? launch_edge<double>(h, st, h->d_sums6, s, false, nullptr, true)
-                                    : launch_edge<float>(h, st, h->d_sums6, s, false, nullptr, true);      // sums + failure count, one launch
-        if (r != GCSADMM_OK) return r;
-        if (ev) HIPCHK(h, hipEventRecord(ev[6 * i + 3], s));
-        const double *reduced = h->d_sums6;
-        if (h->comm) {
-            NCCLCHK(h, rccl().AllReduce(h->d_sums6, h->d_sums6 + 6, 6, ncclFloat64, ncclSum, (ncclComm_t)h->comm, s));
-            reduced = h->d_sums6 + 6;
-        }
-        if (ev) HIPCHK(h, hipEventRecord(ev[6 * i + 4], s));
-        hipLaunchKernelGGL(control_kernel, dim3(1), dim3(1), 0, s, h->d_cb, reduced, cp, h->d_counters, trace_dev, true);
-        HIPCHK(h, hipGetLastError());
-        if (ev) HIPCHK(h, hipEventRecord(ev[6 * i + 5], s));
+        if (ev) HIPCHK(h, hipEventRecord(ev[6 * i + 2].get(), s));
+        if ((r = partitioned_tail(h, st, trace_dev, s, ev ? ev + 6 * i + 3 : nullptr)) != GCSADMM_OK) return r;
     }
     return GCSADMM_OK;
 }
@@ -1150,7 +1172,7 @@ static gcsadmm_status run_partitioned_loop(gcsadmm_handle h, const gcsadmm_state
 gcsadmm_status gcsadmm_run_partitioned(gcsadmm_handle h, const gcsadmm_state *st, int32_t k, double *trace_dev, void *stream)
 {
     if (!state_ok(h, st) || k < 0) return GCSADMM_ERR_BAD_ARG;
-    if (!h->d_sums6) { h->err = "gcsadmm_attach_comm has not been called"; return GCSADMM_ERR_BAD_ARG; }
+    if (!h->halo.attached()) { h->err = "gcsadmm_attach_comm has not been called"; return GCSADMM_ERR_BAD_ARG; }
     USE_DEVICE(h);
     return run_partitioned_loop(h, st, k, trace_dev, (hipStream_t)stream, nullptr);
 }
@@ -1159,24 +1181,21 @@ gcsadmm_status gcsadmm_run_partitioned_timed(gcsadmm_handle h, const gcsadmm_sta
                                              float *vertex_ms, float *halo_ms, float *edge_ms, float *reduce_ms)
 {
     if (!state_ok(h, st) || k < 0 || !vertex_ms || !halo_ms || !edge_ms || !reduce_ms) return GCSADMM_ERR_BAD_ARG;
-    if (!h->d_sums6) { h->err = "gcsadmm_attach_comm has not been called"; return GCSADMM_ERR_BAD_ARG; }
+    if (!h->halo.attached()) { h->err = "gcsadmm_attach_comm has not been called"; return GCSADMM_ERR_BAD_ARG; }
     USE_DEVICE(h);
     hipStream_t s = (hipStream_t)stream;
-    while (h->events.size() < (size_t)6 * k) {
-        hipEvent_t e;
-        HIPCHK(h, hipEventCreate(&e));
-        h->events.push_back(e);
-    }
-    gcsadmm_status r = run_partitioned_loop(h, st, k, trace_dev, s, h->events.data());
+    gcsadmm_status r = ensure_events(h, (size_t)6 * k);
     if (r != GCSADMM_OK) return r;
+    const std::vector<Event> &ev = h->events;
+    if ((r = run_partitioned_loop(h, st, k, trace_dev, s, ev.data())) != GCSADMM_OK) return r;
     HIPCHK(h, hipStreamSynchronize(s));
     double acc[4] = {0, 0, 0, 0};
     for (int i = 0; i < k; ++i) {
         float t = 0;
-        HIPCHK(h, hipEventElapsedTime(&t, h->events[6 * i + 0], h->events[6 * i + 1])); acc[0] += t;
-        HIPCHK(h, hipEventElapsedTime(&t, h->events[6 * i + 1], h->events[6 * i + 2])); acc[1] += t;
-        HIPCHK(h, hipEventElapsedTime(&t, h->events[6 * i + 2], h->events[6 * i + 3])); acc[2] += t;
-        HIPCHK(h, hipEventElapsedTime(&t, h->events[6 * i + 3], h->events[6 * i + 5])); acc[3] += t;
+        HIPCHK(h, hipEventElapsedTime(&t, ev[6 * i + 0].get(), ev[6 * i + 1].get())); acc[0] += t;
+        HIPCHK(h, hipEventElapsedTime(&t, ev[6 * i + 1].get(), ev[6 * i + 2].get())); acc[1] += t;
+        HIPCHK(h, hipEventElapsedTime(&t, ev[6 * i + 2].get(), ev[6 * i + 3].get())); acc[2] += t;
+        HIPCHK(h, hipEventElapsedTime(&t, ev[6 * i + 3].get(), ev[6 * i + 5].get())); acc[3] += t;
     }
     *vertex_ms = (float)acc[0]; *halo_ms = (float)acc[1]; *edge_ms = (float)acc[2]; *reduce_ms = (float)acc[3];
     return GCSADMM_OK;
@@ -1186,18 +1205,11 @@ gcsadmm_status gcsadmm_set_overlap(gcsadmm_handle h, int32_t mode, int32_t *boun
 {
     if (!h || mode < 0 || mode > 2) return GCSADMM_ERR_BAD_ARG;
     if (boundary_units) *boundary_units = 0;
-    if (!h->d_sums6) { h->err = "gcsadmm_attach_comm has not been called"; return GCSADMM_ERR_BAD_ARG; }
+    if (!h->halo.attached()) { h->err = "gcsadmm_attach_comm has not been called"; return GCSADMM_ERR_BAD_ARG; }
     USE_DEVICE(h);
     h->overlap_mode = mode;
-    // the split is derived from the halo lists uploaded at attach: rebuild them as a descriptor of host arrays
-    std::vector<int> send_cols((size_t)std::max(h->n_send, 1)), ptr(h->peers.size() + 1, 0);
-    if (h->n_send > 0) HIPCHK(h, hipMemcpy(send_cols.data(), h->d_send_cols, sizeof(int) * (size_t)h->n_send, hipMemcpyDeviceToHost));
-    for (size_t p = 0; p < h->peers.size(); ++p) ptr[p + 1] = ptr[p] + h->peer_cnt[p];
-    gcsadmm_halo_desc hd{};
-    hd.num_peers = (int)h->peers.size(); hd.peer_rank = h->peers.data(); hd.send_ptr = ptr.data(); hd.send_cols = send_cols.data();
-    hd.recv_ptr = ptr.data(); hd.recv_cols = send_cols.data();
-    const gcsadmm_status r = overlap_setup(h, &hd);
-    if (boundary_units) *boundary_units = h->n_wave_b;
+    const gcsadmm_status r = overlap_setup(h, h->halo.send_cols);      // the split is derived from the send list validated at attach
+    if (boundary_units) *boundary_units = h->overlap.n_wave_b;
     return r;
 }
 
@@ -1218,22 +1230,23 @@ gcsadmm_status gcsadmm_vertex_prox(gcsadmm_handle h, const double *q_dev, const 
                                    double *yv_dev, double ipm_tol, int32_t ipm_max_iter, int32_t *failures_host, void *stream)
 {
     if (!h || !q_dev || !c_dev || !xv_dev || !zv_dev || !yv_dev || !(ipm_tol > 0) || ipm_max_iter < 1) { if (h) h->err = "bad prox argument"; return GCSADMM_ERR_BAD_ARG; }
-    if (h->prox_lds_bytes > 160 * 1024) { h->err = "facet count too large for LDS"; return GCSADMM_ERR_UNSUPPORTED; }
-    if (h->n_term > 0) { h->err = "the prox kernel (v1 x-update) takes its terminals as points; this graph has a terminal that is a region"; return GCSADMM_ERR_UNSUPPORTED; }
+    if (h->plan.prox_lds_bytes > 160 * 1024) { h->err = "facet count too large for LDS"; return GCSADMM_ERR_UNSUPPORTED; }
+    if (h->plan.n_term > 0) { h->err = "the prox kernel (v1 x-update) takes its terminals as points; this graph has a terminal that is a region"; return GCSADMM_ERR_UNSUPPORTED; }
     USE_DEVICE(h);
     hipStream_t s = (hipStream_t)stream;
-    HIPCHK(h, hipMemsetAsync(h->d_prox_counters, 0, 2 * sizeof(int), s));
+    const auto &g = h->g;
+    HIPCHK(h, h->prox.d_prox_counters.zero(s));
     WgLaunchDesc d{};
-    d.n = h->n; d.dtype = GCSADMM_F64; d.n_vtx = h->n_prox; d.lds_bytes = h->prox_lds_bytes; d.vtx = h->d_prox_vtx;
+    d.n = h->n; d.dtype = GCSADMM_F64; d.n_vtx = (int)h->prox.d_prox_vtx.size(); d.lds_bytes = h->plan.prox_lds_bytes; d.vtx = h->prox.d_prox_vtx.get();
     StepDesc &p = d.step;     // the ADMM state, the edge tolerance and the warm start stay unset: the PROX solve reads none of them
-    p.inc_ptr = h->d_inc_ptr; p.deg_in = h->d_deg_in; p.inc_edge = h->d_inc_edge; p.poly_ptr = h->d_poly_ptr;
-    p.poly_A = h->d_poly_A; p.poly_bc = h->d_poly_bc; p.center = h->d_center;
-    p.xv = xv_dev; p.zv = zv_dev; p.yv = yv_dev; p.counters = h->d_prox_counters; p.ipm_tol = ipm_tol; p.ipm_max_iter = ipm_max_iter;
+    p.inc_ptr = g.d_inc_ptr.get(); p.deg_in = g.d_deg_in.get(); p.inc_edge = g.d_inc_edge.get(); p.poly_ptr = g.d_poly_ptr.get();
+    p.poly_A = g.d_poly_A.get(); p.poly_bc = g.d_poly_bc.get(); p.center = g.d_center.get();
+    p.xv = xv_dev; p.zv = zv_dev; p.yv = yv_dev; p.counters = h->prox.d_prox_counters.get(); p.ipm_tol = ipm_tol; p.ipm_max_iter = ipm_max_iter;
     gcsadmm_wg_launch_prox(d, q_dev, c_dev, h->src, h->dst, s);
     HIPCHK(h, hipGetLastError());
     if (failures_host) {      // optional: synchronises the stream
         int cnt[2] = {0, 0};
-        HIPCHK(h, hipMemcpyAsync(cnt, h->d_prox_counters, sizeof(cnt), hipMemcpyDeviceToHost, s));
+        HIPCHK(h, hipMemcpyAsync(cnt, h->prox.d_prox_counters.get(), sizeof(cnt), hipMemcpyDeviceToHost, s));
         HIPCHK(h, hipStreamSynchronize(s));
         *failures_host = cnt[0];
     }
@@ -1246,28 +1259,23 @@ gcsadmm_status gcsadmm_run_timed(gcsadmm_handle h, const gcsadmm_state *st, int3
     if (!state_ok(h, st) || k < 0 || !vertex_ms || !edge_ms || !vertex_launches || !edge_launches) return GCSADMM_ERR_BAD_ARG;
     USE_DEVICE(h);
     hipStream_t s = (hipStream_t)stream;
-    const size_t need = (size_t)4 * k;
-    while (h->events.size() < need) {
-        hipEvent_t ev;
-        HIPCHK(h, hipEventCreate(&ev));
-        h->events.push_back(ev);
-    }
+    gcsadmm_status r = ensure_events(h, (size_t)4 * k);
+    if (r != GCSADMM_OK) return r;
+    const std::vector<Event> &ev = h->events;
     for (int i = 0; i < k; ++i) {
-        gcsadmm_status r;
-        HIPCHK(h, hipEventRecord(h->events[4 * i + 0], s));
+        HIPCHK(h, hipEventRecord(ev[4 * i + 0].get(), s));
         if ((r = gcsadmm_vertex_step(h, st, stream)) != GCSADMM_OK) return r;
-        HIPCHK(h, hipEventRecord(h->events[4 * i + 1], s));
-        HIPCHK(h, hipEventRecord(h->events[4 * i + 2], s));
-        r = h->dtype == GCSADMM_F64 ? launch_edge<double>(h, st, h->d_sums, s, true, trace_dev) : launch_edge<float>(h, st, h->d_sums, s, true, trace_dev);
-        if (r != GCSADMM_OK) return r;
-        HIPCHK(h, hipEventRecord(h->events[4 * i + 3], s));
+        HIPCHK(h, hipEventRecord(ev[4 * i + 1].get(), s));
+        HIPCHK(h, hipEventRecord(ev[4 * i + 2].get(), s));
+        if ((r = launch_edge(h, st, h->loop.d_sums.get(), s, true, trace_dev)) != GCSADMM_OK) return r;
+        HIPCHK(h, hipEventRecord(ev[4 * i + 3].get(), s));
     }
     HIPCHK(h, hipStreamSynchronize(s));
     double vm = 0, em = 0;
     for (int i = 0; i < k; ++i) {
         float t = 0;
-        HIPCHK(h, hipEventElapsedTime(&t, h->events[4 * i + 0], h->events[4 * i + 1])); vm += t;
-        HIPCHK(h, hipEventElapsedTime(&t, h->events[4 * i + 2], h->events[4 * i + 3])); em += t;
+        HIPCHK(h, hipEventElapsedTime(&t, ev[4 * i + 0].get(), ev[4 * i + 1].get())); vm += t;
+        HIPCHK(h, hipEventElapsedTime(&t, ev[4 * i + 2].get(), ev[4 * i + 3].get())); em += t;
     }
     *vertex_ms = (float)vm; *edge_ms = (float)em; *vertex_launches = k; *edge_launches = k;
     return GCSADMM_OK;
@@ -1277,7 +1285,7 @@ gcsadmm_status gcsadmm_read_control(gcsadmm_handle h, gcsadmm_control_block *out
 {
     if (!h || !out) return GCSADMM_ERR_BAD_ARG;
     USE_DEVICE(h);
-    HIPCHK(h, hipMemcpyAsync(out, h->d_cb, sizeof(*out), hipMemcpyDeviceToHost, (hipStream_t)stream));
+    HIPCHK(h, hipMemcpyAsync(out, h->loop.d_cb.get(), sizeof(*out), hipMemcpyDeviceToHost, (hipStream_t)stream));
     HIPCHK(h, hipStreamSynchronize((hipStream_t)stream));
     return GCSADMM_OK;
 }
@@ -1286,12 +1294,11 @@ gcsadmm_status gcsadmm_cost(gcsadmm_handle h, const gcsadmm_state *st, double ep
 {
     if (!h || !st || !st->zv || !st->zedge || !cost_dev) return GCSADMM_ERR_BAD_ARG;
     USE_DEVICE(h);
-    if (h->dtype == GCSADMM_F64)
-        hipLaunchKernelGGL((cost_kernel<double>), dim3(1), dim3(256), 0, (hipStream_t)stream, h->V, h->E, h->n, st->zv,
-                           (const double *)st->zedge, h->d_edge_counted, eps_edge, cost_dev);
-    else
-        hipLaunchKernelGGL((cost_kernel<float>), dim3(1), dim3(256), 0, (hipStream_t)stream, h->V, h->E, h->n, st->zv,
-                           (const float *)st->zedge, h->d_edge_counted, eps_edge, cost_dev);
+    with_state(h, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((cost_kernel<T>), dim3(1), dim3(256), 0, (hipStream_t)stream, h->V, h->E, h->n, st->zv,
+                           (const T *)st->zedge, h->g.d_edge_counted.get(), eps_edge, cost_dev);
+    });
     HIPCHK(h, hipGetLastError());
     return GCSADMM_OK;
 }
@@ -1312,20 +1319,20 @@ gcsadmm_status gcsadmm_query(gcsadmm_handle h, int32_t *num_waves, int32_t *lds_
                              int32_t *num_workgroup_vertices, int32_t *workgroup_lds_bytes)
 {
     if (!h) return GCSADMM_ERR_BAD_ARG;
-    if (num_waves) *num_waves = h->n_waves;
-    if (lds_bytes) *lds_bytes = h->lds_bytes;
-    if (num_special) *num_special = h->n_special;
-    if (num_workgroup_vertices) *num_workgroup_vertices = h->n_wg;
-    if (workgroup_lds_bytes) *workgroup_lds_bytes = h->wg_lds_bytes;
+    if (num_waves) *num_waves = h->plan.n_waves();
+    if (lds_bytes) *lds_bytes = h->plan.lds_bytes;
+    if (num_special) *num_special = h->n_special();
+    if (num_workgroup_vertices) *num_workgroup_vertices = h->n_wg();
+    if (workgroup_lds_bytes) *workgroup_lds_bytes = h->plan.wg_lds_bytes;
     return GCSADMM_OK;
 }
 
 gcsadmm_status gcsadmm_query_workspace(gcsadmm_handle h, int32_t *num_split_vertices, int32_t *split_lds_bytes, int64_t *workspace_bytes)
 {
     if (!h) return GCSADMM_ERR_BAD_ARG;
-    if (num_split_vertices) *num_split_vertices = h->n_split;
-    if (split_lds_bytes) *split_lds_bytes = h->split_lds_bytes;
-    if (workspace_bytes) *workspace_bytes = (int64_t)(h->split_doubles * sizeof(double));
+    if (num_split_vertices) *num_split_vertices = h->n_split();
+    if (split_lds_bytes) *split_lds_bytes = h->plan.split_lds_bytes;
+    if (workspace_bytes) *workspace_bytes = (int64_t)((size_t)h->plan.split_doubles * sizeof(double));
     return GCSADMM_OK;
 }
 
@@ -1333,8 +1340,9 @@ gcsadmm_status gcsadmm_unit_iterations(gcsadmm_handle h, int32_t *out, int32_t c
 {
     if (!h || !count) return GCSADMM_ERR_BAD_ARG;
     USE_DEVICE(h);
-    const int *src = h->d_wave_iters ? h->d_wave_iters : h->d_wg_iters;
-    const int n = h->d_wave_iters ? h->n_waves : (h->d_wg_iters ? h->n_wg : 0);
+    const auto &g = h->g;
+    const int *src = g.d_wave_iters ? g.d_wave_iters.get() : g.d_wg_iters.get();
+    const int n = g.d_wave_iters ? h->plan.n_waves() : (g.d_wg_iters ? h->n_wg() : 0);
     *count = n;
     if (n == 0 || !out) return GCSADMM_OK;
     HIPCHK(h, hipStreamSynchronize((hipStream_t)stream));

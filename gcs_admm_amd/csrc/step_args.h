@@ -74,4 +74,7 @@ template <int... Ns, class F> bool dispatch_dim(int n, F &&f)
     return ((n == Ns ? (f(std::integral_constant<int, Ns>()), true) : false) || ...);
 }
 
+// f(double()) or f(float()): the state type T of StepArgs<T>, chosen at run time (f64: the handle's dtype is GCSADMM_F64)
+template <class F> auto with_state_type(bool f64, F &&f) { return f64 ? f(double()) : f(float()); }
+
 }  // namespace gcsadmm_k

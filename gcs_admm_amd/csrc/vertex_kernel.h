@@ -185,53 +185,49 @@ __global__ __launch_bounds__(WAVE) void vertex_kernel(typename PROG::template Ar
 #endif
 }
 
-template <class PROG, int N, class T> static void launch_vertex_prog(const VertexLaunchDesc &d, hipStream_t s)
+// The instantiations of the kernel, listed once: N = 2 (the tuned dimension) has PROG x RMODE x SDL -- dense packing + wave shifts, and
+// the stored dual directions, exist for it only -- every other N the generic <0, 0> alone.  align_rows / store_dl: the plan's choices.
+template <class PROG, int N, class T> using VertexKernelFn = void (*)(typename PROG::template Args<T>, SpecialArgs, const gcsadmm_control_block *);
+template <class PROG, int N, class T> static VertexKernelFn<PROG, N, T> vertex_kernel_for(int align_rows, int store_dl)
 {
-    typename PROG::template Args<T> a;
-    static_cast<StepArgs<T> &>(a) = d.step.typed<T>();
-    a.n_waves = d.n_waves; a.align_rows = d.align_rows; a.wave_slot_ptr = d.wave_slot_ptr; a.wave_vtx = d.wave_vtx; a.MM = d.MM;
-    a.wave_order = d.wave_order; a.wave_iters = d.wave_iters;
-    const SpecialArgs sp{d.n_special, d.special_vtx, d.special_kind};
-    const unsigned grid = (unsigned)(d.n_waves + (d.n_special + WAVE - 1) / WAVE);
-    const int lds = std::max(d.lds_bytes, (int)(4 * MAX_SPECIAL_DEG * sizeof(double)));   // room for the special work arrays
-#define GCS_LAUNCH(RM, DL) hipLaunchKernelGGL((vertex_kernel<PROG, N, T, RM, DL>), dim3(grid), dim3(WAVE), lds, s, a, sp, d.step.cb)
-    if constexpr (N == 2) {   // dense packing + wave shifts, and the stored dual directions, exist for the tuned dimension only
-        if (!d.align_rows) { if (d.store_dl) GCS_LAUNCH(1, 1); else GCS_LAUNCH(1, 0); }
-        else { if (d.store_dl) GCS_LAUNCH(0, 1); else GCS_LAUNCH(0, 0); }
+    if constexpr (N == 2) {
+        static const VertexKernelFn<PROG, N, T> by_rmode_sdl[2][2] = {{vertex_kernel<PROG, N, T, 0, 0>, vertex_kernel<PROG, N, T, 0, 1>},
+                                                                      {vertex_kernel<PROG, N, T, 1, 0>, vertex_kernel<PROG, N, T, 1, 1>}};
+        return by_rmode_sdl[align_rows ? 0 : 1][store_dl ? 1 : 0];
     } else {
-        GCS_LAUNCH(0, 0);
+        return vertex_kernel<PROG, N, T, 0, 0>;
     }
-#undef GCS_LAUNCH
 }
-
 // vertex step for space dimension N: generic vertices (wavefront program) + special vertices (closed form)
 template <int N, class T> static void launch_vertex_dim(const VertexLaunchDesc &d, hipStream_t s)
 {
-    if (d.n_waves + d.n_special > 0) {
-        if constexpr (N == 2) {     // the m = 4 program exists for n = 2 only
-            if (d.all_m4 == 2) launch_vertex_prog<ProgBox, N, T>(d, s);
-            else launch_vertex_prog<ProgGeneric, N, T>(d, s);
-        } else {
-            launch_vertex_prog<ProgGeneric, N, T>(d, s);
-        }
-    }
+    if (d.n_waves + d.n_special <= 0) return;
+    auto go = [&](auto prog) {
+        using PROG = decltype(prog);
+        typename PROG::template Args<T> a;
+        static_cast<StepArgs<T> &>(a) = d.step.typed<T>();
+        a.n_waves = d.n_waves; a.align_rows = d.align_rows; a.wave_slot_ptr = d.wave_slot_ptr; a.wave_vtx = d.wave_vtx; a.MM = d.MM;
+        a.wave_order = d.wave_order; a.wave_iters = d.wave_iters;
+        const SpecialArgs sp{d.n_special, d.special_vtx, d.special_kind};
+        const unsigned grid = (unsigned)(d.n_waves + (d.n_special + WAVE - 1) / WAVE);
+        const int lds = std::max(d.lds_bytes, (int)(4 * MAX_SPECIAL_DEG * sizeof(double)));   // room for the special work arrays
+        hipLaunchKernelGGL((vertex_kernel_for<PROG, N, T>(d.align_rows, d.store_dl)), dim3(grid), dim3(WAVE), lds, s, a, sp, d.step.cb);
+    };
+    if (N != 2 || d.all_m4 != 2) go(ProgGeneric());
+    else if constexpr (N == 2) go(ProgBox());     // the m = 4 program exists for n = 2 only
 }
 
+// raise the dynamic-LDS limit (needed above 48 KB) of every instantiation a handle with this all_m4 may launch
 template <int N, class T> static hipError_t set_lds_attr(int all_m4, int lds_bytes)
 {
     hipError_t e = hipSuccess;
-    auto set = [&](const void *fn) { if (e == hipSuccess) e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes); };
-    set((const void *)vertex_kernel<ProgGeneric, N, T, 0, 0>);
+    auto set_all = [&](auto prog) {
+        for (int k = 0; k < (N == 2 ? 4 : 1) && e == hipSuccess; ++k)       // (RMODE, SDL) = (0, 0), (0, 1), (1, 0), (1, 1)
+            e = hipFuncSetAttribute((const void *)vertex_kernel_for<decltype(prog), N, T>(k < 2, k & 1), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
+    };
+    set_all(ProgGeneric());
     if constexpr (N == 2) {
-        set((const void *)vertex_kernel<ProgGeneric, N, T, 0, 1>);
-        set((const void *)vertex_kernel<ProgGeneric, N, T, 1, 0>);
-        set((const void *)vertex_kernel<ProgGeneric, N, T, 1, 1>);
-        if (all_m4 == 2) {
-            set((const void *)vertex_kernel<ProgBox, N, T, 0, 0>);
-            set((const void *)vertex_kernel<ProgBox, N, T, 0, 1>);
-            set((const void *)vertex_kernel<ProgBox, N, T, 1, 0>);
-            set((const void *)vertex_kernel<ProgBox, N, T, 1, 1>);
-        }
+        if (all_m4 == 2) set_all(ProgBox());
     }
     return e;
 }

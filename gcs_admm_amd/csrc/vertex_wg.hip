@@ -27,13 +27,13 @@ bool GCS_WG_SYM(gcsadmm_wg_has_box)(int n) { return gcs_wg::wg_has_box(n); }
 hipError_t GCS_WG_SYM(gcsadmm_wg_set_lds)(int n, int dtype, int lds_bytes)
 {
     hipError_t e = hipSuccess;
-    if (dispatch_dim<2, 3, 6>(n, [&](auto nn) { e = set_lds_n<decltype(nn)::value>(dtype, lds_bytes); })) return e;
+    if (dispatch_dim<2, 3, 6>(n, [&](auto nn) { e = set_lds<InLdsKernels, decltype(nn)::value>(dtype, lds_bytes); })) return e;
     return GCS_WG_SYM(gcsadmm_wg_set_lds_dims)(n, dtype, lds_bytes);
 }
 
 void GCS_WG_SYM(gcsadmm_wg_launch)(const WgLaunchDesc &d, hipStream_t s)
 {
-    if (!dispatch_dim<2, 3, 6>(d.n, [&](auto nn) { launch_n<decltype(nn)::value>(d, s); })) GCS_WG_SYM(gcsadmm_wg_launch_dims)(d, s);
+    if (!dispatch_dim<2, 3, 6>(d.n, [&](auto nn) { launch<decltype(nn)::value>(d, s); })) GCS_WG_SYM(gcsadmm_wg_launch_dims)(d, s);
 }
 
 void GCS_WG_SYM(gcsadmm_wg_launch_prox)(const WgLaunchDesc &d, const double *q, const double *c, int src, int dst, hipStream_t s)
@@ -50,13 +50,13 @@ void gcsadmm_wg_launch_split_dims(const WgLaunchDesc &d, const WgSplitArgs &w, h
 hipError_t gcsadmm_wg_set_split_lds(int n, int dtype, int lds_bytes)
 {
     hipError_t e = hipSuccess;
-    if (dispatch_dim<2, 3, 6>(n, [&](auto nn) { e = set_split_lds_n<decltype(nn)::value>(dtype, lds_bytes); })) return e;
+    if (dispatch_dim<2, 3, 6>(n, [&](auto nn) { e = set_lds<SplitKernels, decltype(nn)::value>(dtype, lds_bytes); })) return e;
     return gcsadmm_wg_set_split_lds_dims(n, dtype, lds_bytes);
 }
 
 void gcsadmm_wg_launch_split(const WgLaunchDesc &d, const WgSplitArgs &w, hipStream_t s)
 {
-    if (!dispatch_dim<2, 3, 6>(d.n, [&](auto nn) { launch_split_n<decltype(nn)::value>(d, w, s); })) gcsadmm_wg_launch_split_dims(d, w, s);
+    if (!dispatch_dim<2, 3, 6>(d.n, [&](auto nn) { launch_split<decltype(nn)::value>(d, w, s); })) gcsadmm_wg_launch_split_dims(d, w, s);
 }
 #endif
 

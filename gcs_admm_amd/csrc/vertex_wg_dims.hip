@@ -13,13 +13,13 @@ using namespace gcsadmm_k;
 hipError_t GCS_WG_SYM(gcsadmm_wg_set_lds_dims)(int n, int dtype, int lds_bytes)
 {
     hipError_t e = hipErrorInvalidValue;
-    dispatch_dim<1, 4, 5, 7, 8>(n, [&](auto nn) { e = set_lds_n<decltype(nn)::value>(dtype, lds_bytes); });
+    dispatch_dim<1, 4, 5, 7, 8>(n, [&](auto nn) { e = set_lds<InLdsKernels, decltype(nn)::value>(dtype, lds_bytes); });
     return e;
 }
 
 void GCS_WG_SYM(gcsadmm_wg_launch_dims)(const WgLaunchDesc &d, hipStream_t s)
 {
-    dispatch_dim<1, 4, 5, 7, 8>(d.n, [&](auto nn) { launch_n<decltype(nn)::value>(d, s); });
+    dispatch_dim<1, 4, 5, 7, 8>(d.n, [&](auto nn) { launch<decltype(nn)::value>(d, s); });
 }
 
 void GCS_WG_SYM(gcsadmm_wg_launch_prox_dims)(const WgLaunchDesc &d, const double *q, const double *c, int src, int dst, hipStream_t s)
@@ -31,12 +31,12 @@ void GCS_WG_SYM(gcsadmm_wg_launch_prox_dims)(const WgLaunchDesc &d, const double
 hipError_t gcsadmm_wg_set_split_lds_dims(int n, int dtype, int lds_bytes)
 {
     hipError_t e = hipErrorInvalidValue;
-    dispatch_dim<1, 4, 5, 7, 8>(n, [&](auto nn) { e = set_split_lds_n<decltype(nn)::value>(dtype, lds_bytes); });
+    dispatch_dim<1, 4, 5, 7, 8>(n, [&](auto nn) { e = set_lds<SplitKernels, decltype(nn)::value>(dtype, lds_bytes); });
     return e;
 }
 
 void gcsadmm_wg_launch_split_dims(const WgLaunchDesc &d, const WgSplitArgs &w, hipStream_t s)
 {
-    dispatch_dim<1, 4, 5, 7, 8>(d.n, [&](auto nn) { launch_split_n<decltype(nn)::value>(d, w, s); });
+    dispatch_dim<1, 4, 5, 7, 8>(d.n, [&](auto nn) { launch_split<decltype(nn)::value>(d, w, s); });
 }
 #endif

@@ -91,59 +91,61 @@ __global__ __launch_bounds__(WG_THREADS, (wg_split_min_blocks<N, BOX>())) void v
     }
 }
 
-template <int N, class T> void launch(const WgLaunchDesc &d, hipStream_t s)
+// The two kernel families of the program, by name.  Each has a BOX instantiation at n = 3 and 6: it pays from n = 3 (n = 6: -9 % per
+// Newton iteration); at n = 2 the loops it shortens are two terms long and it measured 1 % slower, so n = 2 has none.
+struct InLdsKernels { template <int N, class T, bool BOX> static constexpr auto kernel() { return vertex_wg_kernel<N, T, BOX>; } };
+struct SplitKernels { template <int N, class T, bool BOX> static constexpr auto kernel() { return vertex_wg_split_kernel<N, T, BOX>; } };
+template <int N> constexpr bool WG_HAS_BOX = N == 3 || N == 6;
+// the state type of a launch (WgLaunchDesc::dtype)
+template <class F> auto with_state(int dtype, F &&f) { return with_state_type(dtype == GCSADMM_F64, f); }
+
+// one launch of family K: `extra` is the kernel's second argument (the closed-form vertices / the split form's workspace)
+template <class K, int N, class T, class X>
+void launch_kernels(const WgLaunchDesc &d, const gcs_wg::WgArgs<T> &a, unsigned grid, int lds, const X &extra, hipStream_t s)
 {
-    gcs_wg::WgArgs<T> a;
-    static_cast<StepArgs<T> &>(a) = d.step.typed<T>();
-    a.n_vtx = d.n_vtx; a.vtx = d.vtx; a.order = d.order; a.unit_iters = d.unit_iters;
-    const SpecialArgs sp{d.n_special, d.special_vtx, d.special_kind};
-    const unsigned grid = (unsigned)(d.n_vtx + (d.n_special + WG_THREADS - 1) / WG_THREADS);
-    if (grid == 0) return;
-    const int lds = std::max(d.lds_bytes, (int)(4 * MAX_SPECIAL_DEG * sizeof(double)));
-    // the BOX instantiation pays from n = 3 (n = 6: -9 % per Newton iteration); at n = 2 the loops it shortens are two terms long and
-    // it measured 1 % slower, so n = 2 has none
-    if constexpr (N == 3 || N == 6) {
-        if (d.box) { hipLaunchKernelGGL((vertex_wg_kernel<N, T, true>), dim3(grid), dim3(WG_THREADS), lds, s, a, sp, d.step.cb); return; }
+    if constexpr (WG_HAS_BOX<N>) {
+        if (d.box) { hipLaunchKernelGGL((K::template kernel<N, T, true>()), dim3(grid), dim3(WG_THREADS), lds, s, a, extra, d.step.cb); return; }
     }
-    hipLaunchKernelGGL((vertex_wg_kernel<N, T, false>), dim3(grid), dim3(WG_THREADS), lds, s, a, sp, d.step.cb);
+    hipLaunchKernelGGL((K::template kernel<N, T, false>()), dim3(grid), dim3(WG_THREADS), lds, s, a, extra, d.step.cb);
 }
 
-// the state type of the launch (d.dtype)
-template <int N> void launch_n(const WgLaunchDesc &d, hipStream_t s)
+// raise the dynamic-LDS limit of family K's instantiations (needed above 48 KB)
+template <class K, int N> hipError_t set_lds(int dtype, int lds_bytes)
 {
-    if (d.dtype == GCSADMM_F64) launch<N, double>(d, s);
-    else launch<N, float>(d, s);
+    return with_state(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipError_t e = hipFuncSetAttribute((const void *)K::template kernel<N, T, false>(), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
+        if constexpr (WG_HAS_BOX<N>)
+            if (e == hipSuccess) e = hipFuncSetAttribute((const void *)K::template kernel<N, T, true>(), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
+        return e;
+    });
 }
 
-template <int N, class T> void launch_split(const WgLaunchDesc &d, const WgSplitArgs &w, hipStream_t s)
+template <int N> void launch(const WgLaunchDesc &d, hipStream_t s)
+{
+    with_state(d.dtype, [&](auto t) {
+        using T = decltype(t);
+        gcs_wg::WgArgs<T> a;
+        static_cast<StepArgs<T> &>(a) = d.step.typed<T>();
+        a.n_vtx = d.n_vtx; a.vtx = d.vtx; a.order = d.order; a.unit_iters = d.unit_iters;
+        const SpecialArgs sp{d.n_special, d.special_vtx, d.special_kind};
+        const unsigned grid = (unsigned)(d.n_vtx + (d.n_special + WG_THREADS - 1) / WG_THREADS);
+        if (grid == 0) return;
+        const int lds = std::max(d.lds_bytes, (int)(4 * MAX_SPECIAL_DEG * sizeof(double)));
+        launch_kernels<InLdsKernels, N, T>(d, a, grid, lds, sp, s);
+    });
+}
+
+template <int N> void launch_split(const WgLaunchDesc &d, const WgSplitArgs &w, hipStream_t s)
 {
     if (d.n_vtx <= 0) return;
-    gcs_wg::WgArgs<T> a;
-    static_cast<StepArgs<T> &>(a) = d.step.typed<T>();
-    a.n_vtx = d.n_vtx; a.vtx = d.vtx;
-    if constexpr (N == 3 || N == 6) {
-        if (d.box) { hipLaunchKernelGGL((vertex_wg_split_kernel<N, T, true>), dim3(d.n_vtx), dim3(WG_THREADS), d.lds_bytes, s, a, w, d.step.cb); return; }
-    }
-    hipLaunchKernelGGL((vertex_wg_split_kernel<N, T, false>), dim3(d.n_vtx), dim3(WG_THREADS), d.lds_bytes, s, a, w, d.step.cb);
-}
-
-template <int N> void launch_split_n(const WgLaunchDesc &d, const WgSplitArgs &w, hipStream_t s)
-{
-    if (d.dtype == GCSADMM_F64) launch_split<N, double>(d, w, s);
-    else launch_split<N, float>(d, w, s);
-}
-
-template <int N, class T> hipError_t set_split_lds(int lds_bytes)
-{
-    hipError_t e = hipFuncSetAttribute((const void *)vertex_wg_split_kernel<N, T, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-    if constexpr (N == 3 || N == 6)
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void *)vertex_wg_split_kernel<N, T, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-    return e;
-}
-
-template <int N> hipError_t set_split_lds_n(int dtype, int lds_bytes)
-{
-    return dtype == GCSADMM_F64 ? set_split_lds<N, double>(lds_bytes) : set_split_lds<N, float>(lds_bytes);
+    with_state(d.dtype, [&](auto t) {
+        using T = decltype(t);
+        gcs_wg::WgArgs<T> a;
+        static_cast<StepArgs<T> &>(a) = d.step.typed<T>();
+        a.n_vtx = d.n_vtx; a.vtx = d.vtx;
+        launch_kernels<SplitKernels, N, T>(d, a, (unsigned)d.n_vtx, d.lds_bytes, w, s);
+    });
 }
 
 // PROX configuration (admm_solver_v1.py:334-383): one workgroup per vertex, no edge blocks; the two trailing
@@ -191,19 +193,6 @@ template <int N> void launch_prox(const WgLaunchDesc &d, const double *q, const 
     if (d.lds_bytes > 48 * 1024)
         (void)hipFuncSetAttribute((const void *)vertex_prox_kernel<N>, hipFuncAttributeMaxDynamicSharedMemorySize, d.lds_bytes);
     hipLaunchKernelGGL((vertex_prox_kernel<N>), dim3(d.n_vtx + 1), dim3(WG_THREADS), d.lds_bytes, s, a, src, dst);
-}
-
-template <int N, class T> hipError_t set_lds(int lds_bytes)
-{
-    hipError_t e = hipFuncSetAttribute((const void *)vertex_wg_kernel<N, T, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-    if constexpr (N == 3 || N == 6)
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void *)vertex_wg_kernel<N, T, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-    return e;
-}
-
-template <int N> hipError_t set_lds_n(int dtype, int lds_bytes)
-{
-    return dtype == GCSADMM_F64 ? set_lds<N, double>(lds_bytes) : set_lds<N, float>(lds_bytes);
 }
 
 }  // namespace

@@ -101,9 +101,21 @@ def test_every_launching_entry_point_selects_the_handles_device():
             i += 1
         bodies[m.group(1)] = ext[start:i]
     assert len(bodies) >= 20, sorted(bodies)
-    touches = re.compile(r"\bhip[A-Z]\w+\(|hipLaunchKernelGGL|launch_vertex<|launch_edge<|halo_pack<|halo_unpack<|halo_transfer\(|halo_upload\(|rccl\(\)\.(?!ok\b|err\b|GetErrorString\b)\w+\(|run_partitioned_loop\(|gcsadmm_wg_launch")
+    # device work as this file spells it: the HIP runtime and kernel launches, the helpers that enqueue (launch_vertex, launch_edge, the
+    # halo helpers, the partitioned loop), the owners that allocate (DevBuf upload / alloc / zero, create_owned, ensure_events,
+    # overlap_setup) or release (delete h, a sub-struct of owners reset with `= {}`), RCCL, and the other objects' launch / attribute entries
+    touches = re.compile(r"\bhip[A-Z]\w+\(|hipLaunchKernelGGL|\blaunch_vertex\(|\blaunch_edge\(|\bhalo_pack<|\bhalo_unpack<|\bhalo_transfer\(|\bhalo_upload\("
+                         r"|\.(?:upload|alloc|zero)\(|\bcreate_owned\(|\bensure_events\(|\boverlap_setup\(|\bdelete h\b|h->(?:halo|overlap) = \{\}"
+                         r"|\bset_lds_attr<|rccl\(\)\.(?!ok\b|err\b|GetErrorString\b)\w+\(|\brun_partitioned_loop\(|\bpartitioned_tail\(|gcsadmm_wg_launch|gcsadmm_wg_set")
     guarded = re.compile(r"USE_DEVICE\(h\)|DeviceGuard device_guard_")
     exempt = {"gcsadmm_comm_unique_id", "gcsadmm_debug_sub_cycles", "gcsadmm_debug_phase_cycles"}        # no handle: ncclGetUniqueId; symbols of the diagnostic build
+    # the pattern must not go blind: these entry points do device work, whatever helper spells it
+    must_touch = {"gcsadmm_" + n for n in ("create", "destroy", "reset", "vertex_step", "edge_step", "control", "run", "run_timed", "attach_comm",
+                                           "halo_pack", "halo_unpack", "halo_exchange", "run_partitioned", "run_partitioned_timed", "set_overlap",
+                                           "vertex_prox", "read_control", "cost", "unit_iterations")}
+    assert must_touch <= set(bodies), sorted(must_touch - set(bodies))
+    for name in must_touch:
+        assert touches.search(bodies[name]), f"{name}: no device work found -- the pattern no longer matches how this file spells it"
     for name, body in bodies.items():
         if name in exempt or not touches.search(body):
             continue
@@ -114,3 +126,23 @@ def test_every_launching_entry_point_selects_the_handles_device():
         pre = body[:g.start()]
         early = [t.group(0) for t in touches.finditer(pre) if t.group(0) not in ("hipGetDeviceCount(", "hipGetErrorString(")]
         assert not early, (name, early)
+
+
+def test_device_resources_are_released_by_their_owners_alone():
+    """Ownership rule of csrc/gcsadmm.hip: a device allocation, a stream and an event each belong to an owning type (DevBuf, Stream,
+    Event) whose destructor releases it, so hipFree, hipStreamDestroy and hipEventDestroy are each written exactly once -- in the
+    owners' releasing functor -- and hipMalloc only inside DevBuf.  A buffer added to the handle as a raw pointer and freed by hand fails here."""
+    import os
+    import re
+    from gcs_admm_amd import build
+    src = open(os.path.join(build.CSRC, "gcsadmm.hip")).read()
+    for call in ("hipFree(", "hipStreamDestroy(", "hipEventDestroy("):
+        assert src.count(call) == 1, (call, src.count(call))
+    m = re.search(r"\nstruct HipRelease \{\n.*?\n\};\n", src, re.S)
+    assert m, "the one releasing functor of the owners (struct HipRelease) was not found"
+    assert all(call in m.group(0) for call in ("hipFree(", "hipStreamDestroy(", "hipEventDestroy("))
+    m = re.search(r"\bclass DevBuf \{\n.*?\n\};\n", src, re.S)
+    assert m, "the owner of device allocations (class DevBuf) was not found"
+    owner = m.group(0)
+    assert owner.count("hipMalloc(") >= 1
+    assert len(re.findall(r"\bhip\w*Malloc\w*\(", src)) == owner.count("hipMalloc("), "an allocation outside DevBuf"

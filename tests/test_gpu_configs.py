@@ -461,7 +461,8 @@ def test_region_terminal_refusals(torch_gpu):
 def test_partitioned_loop_behind_the_abi_single_rank(torch_gpu):
     """gcsadmm_run_partitioned with a REAL RCCL communicator of one rank (what a one-GPU box can exercise: run-time binding
     of librccl, communicator creation, the 6-double all-reduce on the caller's stream, the control step fed from it):
-    the trace equals the single-handle loop's bit for bit."""
+    the trace equals the single-handle loop's bit for bit.  So does that of the loop's stage-timed twin (the same enqueues with six
+    events per iteration between them), whose four stage times are finite and not negative."""
     from gcs_admm_amd.solver import DeviceSolver
     g = lattice_boxes(20, 18, seed=2)
     a = DeviceSolver(g, "f64", device=0)
@@ -471,10 +472,18 @@ def test_partitioned_loop_behind_the_abi_single_rank(torch_gpu):
     b.attach_comm(0, 1, b.unique_id(), {}, {})
     b.reset(max_it=40)
     b.enqueue_partitioned(30)
-    ca, cb = a.read_control(), b.read_control()
-    assert ca.it == cb.it == 31 and ca.status == cb.status and cb.inner_failures == 0
+    t = DeviceSolver(g, "f64", device=0)
+    t.attach_comm(0, 1, t.unique_id(), {}, {})
+    t.reset(max_it=40)
+    ms = t.enqueue_partitioned_timed(30)
+    ca, cb, ct = a.read_control(), b.read_control(), t.read_control()
+    assert ca.it == cb.it == ct.it == 31 and ca.status == cb.status == ct.status and cb.inner_failures == 0 and ct.inner_failures == 0
     assert np.array_equal(a.trace[:30].cpu().numpy(), b.trace[:30].cpu().numpy())
     assert np.array_equal(a.zedge.cpu().numpy(), b.zedge.cpu().numpy())
+    assert np.array_equal(b.trace[:30].cpu().numpy(), t.trace[:30].cpu().numpy())
+    assert np.array_equal(b.zedge.cpu().numpy(), t.zedge.cpu().numpy())
+    assert sorted(ms) == ["edge_ms", "halo_ms", "reduce_ms", "vertex_ms"]
+    assert all(np.isfinite(v) and v >= 0.0 for v in ms.values()), ms
 
 
 @pytest.mark.parametrize("columns,terminals", [("incidence", "points"), ("edge", "points"), ("edge", "boxes")])
@@ -484,7 +493,8 @@ def test_overlapped_partitioned_loop_equals_serial(torch_gpu, columns, terminals
     loop: the same bits.  One rank (a real one-rank RCCL communicator), so the split is forced: the first quarter of the wavefronts
     plays the boundary -- the two launches, their slowest-first re-ordering inside each part (every eighth step), the second stream
     and the two events are what is exercised; the exchange itself moves nothing here.  "boxes": the terminals are regions, their kernel
-    forks from and joins whichever stream carries the boundary part."""
+    forks from and joins whichever stream carries the boundary part; that case also sets the schedule as 1 -> 2 -> 1 before its
+    overlapped run (the split is dropped and derived again from the send list kept at attach)."""
     from gcs_admm_amd.solver import DeviceSolver
     g = lattice_boxes(40, 40, seed=3)
     if terminals == "boxes":
@@ -498,6 +508,10 @@ def test_overlapped_partitioned_loop_equals_serial(torch_gpu, columns, terminals
             d.attach_comm(0, 1, d.unique_id(), {}, {})
             nb = d.set_overlap(mode)
             assert (nb > 0) == (mode == 1) and nb < d.query()["num_waves"]
+            if mode == 1 and (columns, terminals) == ("edge", "boxes"):
+                # the split, its stream and its events torn down and made again (beside the terminals' own stream): the same split
+                assert d.set_overlap(2) == 0
+                assert d.set_overlap(1) == nb
         d.reset(max_it=steps + 10)
         (d.enqueue if mode == "plain" else d.enqueue_partitioned)(steps)
         cb = d.read_control()
