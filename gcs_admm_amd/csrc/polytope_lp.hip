@@ -64,13 +64,9 @@ __global__ __launch_bounds__(WAVE) void bounds_kernel(Polys S, const double *cen
     const int t = blockIdx.x * WAVE + threadIdx.x, lane = threadIdx.x;
     if (t >= S.P * 2 * N) return;
     const int p = t / (2 * N), j = t % (2 * N), k = j >> 1, upper = j & 1;
-    Rows<N, false> R(S, p, -1);
-    double w[N], c[N];
-#pragma unroll
-    for (int kk = 0; kk < N; ++kk) { w[kk] = centers[(size_t)p * N + kk]; c[kk] = 0.0; }
-    c[k] = upper ? -1.0 : 1.0;
-    const int st = lp_ipm<N, false>(R, c, w, lam, dlam, lane, false, 0.0, nullptr);
-    (upper ? hi : lo)[(size_t)p * N + k] = w[k];
+    double xk;
+    const int st = bound_lp<N>(S, p, centers + (size_t)p * N, k, upper, lam, dlam, lane, xk, nullptr);
+    (upper ? hi : lo)[(size_t)p * N + k] = xk;
     if (out_status) out_status[t] = st;
 }
 
@@ -138,8 +134,8 @@ template <int N>
 static int launch_ball(const Scene &sc, long count, const int *d_pa, const int *d_pb, const double *d_x0, int rows_max,
                        double tol, int early, double *d_w, unsigned char *d_flag, int *d_status)
 {
-    const size_t lds = (size_t)2 * rows_max * WAVE * sizeof(double);
-    if (lds > 160 * 1024) { g_err = "too many facet rows per LP for LDS"; return GCSADMM_ERR_UNSUPPORTED; }
+    const size_t lds = lds_bytes(rows_max);
+    if (lds > LDS_MAX_BYTES) { g_err = "too many facet rows per LP for LDS"; return GCSADMM_ERR_UNSUPPORTED; }
     hipError_t e;
     CK(hipFuncSetAttribute((const void *)ball_kernel<N>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     if (count > 0)
@@ -151,9 +147,9 @@ static int launch_ball(const Scene &sc, long count, const int *d_pa, const int *
 template <int N>
 static int launch_bounds(const Scene &sc, const double *d_centers, double *d_lo, double *d_hi, int *d_status)
 {
-    const int rows_max = sc.maxm + 2 * N;
-    const size_t lds = (size_t)2 * rows_max * WAVE * sizeof(double);
-    if (lds > 160 * 1024) { g_err = "too many facet rows per LP for LDS"; return GCSADMM_ERR_UNSUPPORTED; }
+    const int rows_max = bounds_rows(sc.maxm, N);
+    const size_t lds = lds_bytes(rows_max);
+    if (lds > LDS_MAX_BYTES) { g_err = "too many facet rows per LP for LDS"; return GCSADMM_ERR_UNSUPPORTED; }
     hipError_t e;
     CK(hipFuncSetAttribute((const void *)bounds_kernel<N>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     const long count = (long)sc.S.P * 2 * N;
@@ -195,7 +191,7 @@ int gcsadmm_polytope_centers(int n, int num_polytopes, const int *poly_ptr, cons
     DevBuf w, st;
     hipError_t e;
     CK(w.alloc(sizeof(double) * (size_t)P * (n + 1))); CK(st.alloc(sizeof(int) * (size_t)P));
-    DISPATCH_N(n, (launch_ball<NN>(sc, P, nullptr, nullptr, nullptr, sc.maxm + 1, 0.0, 0, w.as<double>(), nullptr, st.as<int>())));
+    DISPATCH_N(n, (launch_ball<NN>(sc, P, nullptr, nullptr, nullptr, centre_rows(sc.maxm), 0.0, 0, w.as<double>(), nullptr, st.as<int>())));
     if (rc != GCSADMM_OK) return rc;
     std::vector<double> hw((size_t)P * (n + 1));
     std::vector<int> hs((size_t)P);
@@ -254,7 +250,7 @@ int gcsadmm_polytope_overlaps(int n, int num_polytopes, const int *poly_ptr, con
         CK(dc.alloc(sizeof(double) * P * n));
         CK(hipMemcpy(dc.p, centers, sizeof(double) * P * n, hipMemcpyHostToDevice));
     }
-    DISPATCH_N(n, (launch_ball<NN>(sc, num_pairs, da.as<int>(), db.as<int>(), centers ? dc.as<double>() : nullptr, 2 * sc.maxm + 1, tol, 1,
+    DISPATCH_N(n, (launch_ball<NN>(sc, num_pairs, da.as<int>(), db.as<int>(), centers ? dc.as<double>() : nullptr, overlap_rows(sc.maxm), tol, 1,
                                    nullptr, df.as<unsigned char>(), st.as<int>())));
     if (rc != GCSADMM_OK) return rc;
     CK(hipMemcpy(overlap, df.p, T, hipMemcpyDeviceToHost));

@@ -63,7 +63,8 @@ class PolytopeScene:
         return cen, rad, st
 
     def bounds(self, centers=None):
-        """(lo [P, n], hi [P, n], LP status [P, 2n])."""
+        """(lo [P, n], hi [P, n], LP status [P, 2n]).  ``centers`` must be strictly inside their regions (the LPs start there):
+        a side started from a point that is outside, or not finite, reports status -1."""
         cen = np.ascontiguousarray(centers if centers is not None else (self._centers if self._centers is not None else self.centers()[0]))
         lo = np.empty((self.P, self.n)); hi = np.empty((self.P, self.n)); st = np.empty((self.P, 2 * self.n), np.int32)
         rc = self.lib.gcsadmm_polytope_bounds(C.c_int(self.n), C.c_int(self.P), _ptr(self.ptr, C.c_int), _ptr(self.A, C.c_double),
@@ -73,7 +74,13 @@ class PolytopeScene:
         return lo, hi, st
 
     def overlaps(self, pair_a, pair_b, tol: float = 1e-9, centers=None):
-        """uint8 flags [num_pairs] and LP status: do regions pair_a[t], pair_b[t] intersect?"""
+        """uint8 flags [num_pairs] and LP status: do regions pair_a[t], pair_b[t] intersect?
+
+        ``centers`` [P, n] are start points only (the LP of pair t starts at ``centers[pair_a[t]]``) and need not be centres; a
+        row with a NaN or an inf in it is not used: that LP starts from the least-squares point of its rows, as all do with
+        ``centers=None``.  Status 0: converged, decided on ``r* >= -tol``; 1 / 2: decided early (a point with a ball around it /
+        a dual bound below ``-tol``); -1: iteration limit or a non-finite iterate -- the flag of such a pair is not a decision
+        (``build_graph_device`` decides it again on the host).  A non-finite result is never reported with a status >= 0."""
         pa = np.ascontiguousarray(pair_a, np.int32); pb = np.ascontiguousarray(pair_b, np.int32)
         out = np.zeros(len(pa), np.uint8); st = np.zeros(len(pa), np.int32)
         cen = centers if centers is not None else self._centers
@@ -86,7 +93,12 @@ class PolytopeScene:
         return out, st
 
 
-def candidate_pairs(lo: np.ndarray, hi: np.ndarray, pad: float = 1e-7):
+# A bounds LP returns an interior iterate, so a box is always slightly too small: the sweep pads every box by this much.  The boxes
+# must therefore be short by (much) less than the pad -- tests/lp_cases.py holds them to a tenth of it.
+SWEEP_PAD = 1e-7
+
+
+def candidate_pairs(lo: np.ndarray, hi: np.ndarray, pad: float = SWEEP_PAD):
     """Unordered pairs (i < j) whose padded boxes intersect: sort on the first coordinate, sweep with a
     vectorised window per box (numpy searchsorted), test the remaining coordinates on the candidates."""
     P = lo.shape[0]

@@ -34,3 +34,38 @@ extern "C" int lp_emu_ball(int n, int P, const int *ptr, const double *A, const 
     }
     return -99;
 }
+
+template <int N> static int bound(const Polys &S, int p, const double *centre, int k, int upper, double *out, int *iters)
+{
+    const int m = S.ptr[p + 1] - S.ptr[p] + 2 * N;
+    std::vector<double> lam((size_t)m * WAVE), dlam((size_t)m * WAVE);
+    return bound_lp<N>(S, p, centre, k, upper, lam.data(), dlam.data(), 0, *out, iters);
+}
+
+// bounds LP of polytope p from its interior point `centre` (n doubles): min (upper = 0) or max of x_k -> *out; the body of
+// bounds_kernel on one lane; returns the LP status
+extern "C" int lp_emu_bound(int n, int P, const int *ptr, const double *A, const double *b, const double *nrm, int p,
+                            const double *centre, int k, int upper, double *out, int *iters)
+{
+    Polys S{n, P, ptr, A, b, nrm};
+    if (k < 0 || k >= n) return -99;
+    switch (n) {
+    case 1: return bound<1>(S, p, centre, k, upper, out, iters);
+    case 2: return bound<2>(S, p, centre, k, upper, out, iters);
+    case 3: return bound<3>(S, p, centre, k, upper, out, iters);
+    case 4: return bound<4>(S, p, centre, k, upper, out, iters);
+    case 5: return bound<5>(S, p, centre, k, upper, out, iters);
+    case 6: return bound<6>(S, p, centre, k, upper, out, iters);
+    case 7: return bound<7>(S, p, centre, k, upper, out, iters);
+    case 8: return bound<8>(S, p, centre, k, upper, out, iters);
+    }
+    return -99;
+}
+
+// the most rows a polytope may have for the device to take the scene: kind 0 centres, 1 overlaps, 2 bounds (the launchers' own test)
+extern "C" int lp_emu_rows_admitted(int kind, int n)
+{
+    int maxm = 0;
+    while (lds_bytes(kind == 0 ? centre_rows(maxm + 1) : kind == 1 ? overlap_rows(maxm + 1) : bounds_rows(maxm + 1, n)) <= LDS_MAX_BYTES) ++maxm;
+    return maxm;
+}

@@ -1,0 +1,68 @@
+"""The contract of tests/lp_cases.py has teeth: the host build of the per-lane LP solver (tests/hostemu/lp_emu.cpp) compiled from a
+copy of csrc/polytope_lp_core.h with one seeded error each must fail it, and the clean copy must pass.
+  * the stop on the complementarity loosened from 1e-11 to 1e-6: boxes too small, radii off;
+  * 0.99 -> 0.5 in the step rule: still converges to the same answers, in more Newton steps than the bound allows;
+  * the margin of the early dual bound dropped: touching regions 300 from the origin are decided "apart" on a dual bound that is
+    only valid up to the dual residual times |x|."""
+import ctypes as C
+import os
+import shutil
+import subprocess
+
+import pytest
+
+import lp_cases as L
+
+# (anchor in polytope_lp_core.h, replacement): each anchor must occur exactly once
+MUTANTS = {
+    "clean": [],
+    "loose_stop": [("const double mu_stop = 1e-11 * fmax(", "const double mu_stop = 1e-6 * fmax(")],
+    "short_steps": [("const double al = fmin(1.0, 0.99 * amax);", "const double al = fmin(1.0, 0.5 * amax);")],
+    "no_margin": [("hl < -tol - 1e-6)", "hl < -tol)")],
+}
+CASES = [(name, n) for n in (1, 2, 3) for name in ("touching", "scales", "mixed_rows")]
+
+
+@pytest.fixture(scope="module")
+def builds(tmp_path_factory):
+    base = tmp_path_factory.mktemp("lp_mutants")
+    procs = {}
+    for name, subs in MUTANTS.items():
+        csrc = base / name
+        csrc.mkdir()
+        text = open(os.path.join(L.CSRC, "polytope_lp_core.h")).read()
+        for old, new in subs:
+            assert text.count(old) == 1, f"mutant {name}: anchor {old!r} does not occur exactly once in polytope_lp_core.h -- update MUTANTS"
+            text = text.replace(old, new)
+        (csrc / "polytope_lp_core.h").write_text(text)
+        so = csrc / "liblpemu.so"
+        procs[name] = (subprocess.Popen(["g++", "-O1", "-std=c++17", "-fPIC", "-shared", "-I" + str(csrc), L.EMU_SRC, "-o", str(so)]), so)
+    libs = {}
+    for name, (p, so) in procs.items():
+        assert p.wait() == 0, f"build of mutant {name} failed"
+        libs[name] = C.CDLL(str(so))
+    return libs
+
+
+def _violations(lib):
+    out = {}
+    for name, n in CASES:
+        fam = L.family(name, n)
+        try:
+            L.check_contract(fam, L.produce(L.HostLP(lib, fam.polys), fam), L.reference(name, n), newton=True)
+        except AssertionError as e:
+            out[name, n] = str(e)
+    return out
+
+
+def test_clean_copy_meets_the_contract(builds):
+    assert _violations(builds["clean"]) == {}
+
+
+@pytest.mark.parametrize("mutant,what", [("loose_stop", "radius|too small|against"), ("short_steps", "Newton steps"), ("no_margin", "wrong decisions")])
+def test_contract_rejects_the_seeded_error(builds, mutant, what):
+    import re
+    found = _violations(builds[mutant])
+    print(found)
+    assert found, f"the contract let the seeded error {mutant} through"
+    assert any(re.search(what, msg) for msg in found.values()), found

@@ -16,13 +16,7 @@ sys.path.insert(0, ROOT)
 from oracle import polytope_oracle as PO   # noqa: E402
 
 
-def random_polytope(rng, n, m, centre, scale):
-    """m random half-spaces at distance ~scale around `centre` plus a bounding box (always bounded)."""
-    A = rng.normal(size=(m, n)); A /= np.linalg.norm(A, axis=1)[:, None]
-    b = A @ centre + scale * rng.uniform(0.3, 1.0, size=m)
-    A = np.vstack([A, np.eye(n), -np.eye(n)])
-    b = np.hstack([b, centre + 2 * scale, -(centre - 2 * scale)])
-    return A, b
+from lp_cases import BOX_SHORTFALL, load_lp_emu, random_polytope   # noqa: E402
 
 
 # ------------------------------------------------------------------------------------------- CPU
@@ -70,7 +64,10 @@ def test_device_graph_matches_fixture(name):
         slack = (bs[k] - As[k] @ cen[i]) / np.linalg.norm(As[k], axis=1)
         assert slack.min() >= rad[i] - 1e-7                      # the returned point has that ball around it
         lo_o, hi_o = PO.bounding_box(As[k], bs[k])
-        assert np.allclose(lo[i], lo_o, atol=1e-6) and np.allclose(hi[i], hi_o, atol=1e-6)
+        # a box is an interior iterate's, always slightly too small: by less than a tenth of the sweep's pad (tests/lp_cases.py)
+        assert max((lo[i] - lo_o).max(), (hi_o - hi[i]).max()) <= BOX_SHORTFALL, (k, lo[i] - lo_o, hi_o - hi[i])
+        assert np.all(np.abs(lo[i] - lo_o) <= 1e-8 * np.maximum(1.0, np.abs(lo_o))), (k, lo[i], lo_o)
+        assert np.all(np.abs(hi[i] - hi_o) <= 1e-8 * np.maximum(1.0, np.abs(hi_o))), (k, hi[i], hi_o)
 
 
 @pytest.mark.gpu
@@ -154,14 +151,7 @@ def test_device_lp_errors():
 # ------------------------------------------------------------------------------------------- CPU: the LP core
 @pytest.fixture(scope="module")
 def lp_emu():
-    import ctypes as C
-    import subprocess
-    src = os.path.join(ROOT, "tests", "hostemu", "lp_emu.cpp")
-    out = os.path.join(ROOT, "tests", "hostemu", "liblpemu.so")
-    hdr = os.path.join(ROOT, "gcs_admm_amd", "csrc", "polytope_lp_core.h")
-    if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(src), os.path.getmtime(hdr)):
-        subprocess.check_call(["g++", "-O1", "-std=c++17", "-fPIC", "-shared", "-I" + os.path.dirname(hdr), src, "-o", out])
-    return C.CDLL(out)
+    return load_lp_emu()
 
 
 def _emu_ball(lib, polys, p, q, x0=None, early=0, tol=1e-9):
