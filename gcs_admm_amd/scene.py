@@ -12,6 +12,11 @@ few hundred regions.  Here:
      decision as the reference's feasibility solve (closed sets, touching counts);
   4. edges in the reference's double-loop order, both directions of every intersecting pair.
 
+``DeviceScene`` is the same pipeline on a scene that stays on the device (``gcsadmm_scene_*``): the polytopes are uploaded once,
+centres, boxes and pairs never come back to the host between the steps, and step 2 is a kernel (``sweep_kernel``) that returns
+the pair list of ``candidate_pairs`` element for element.  ``build_graph_arrays_device`` drives it and returns edge arrays;
+``build_graph_device(..., broad_phase="device")`` and ``graph_from_sets_device(..., broad_phase="device")`` go through it.
+
 It raises if the HIP library or a device is missing.  LP statuses are checked (build_graph_device): the only host LPs this
 module ever runs are re-decisions of overlap LPs that hit their iteration limit.  The host functions of
 ``gcs_admm_amd.graph`` (scipy LPs) remain what the small reference cases are built with.
@@ -26,7 +31,7 @@ import numpy as np
 from .graph import GcsGraph, _finish_graph
 from .solver import GcsAdmmError, load_library
 
-__all__ = ["PolytopeScene", "build_graph_device", "graph_from_sets_device"]
+__all__ = ["PolytopeScene", "DeviceScene", "build_graph_device", "build_graph_arrays_device", "edge_arrays", "graph_from_sets_device"]
 
 
 def _ptr(a, t):
@@ -120,8 +125,150 @@ def candidate_pairs(lo: np.ndarray, hi: np.ndarray, pad: float = SWEEP_PAD):
     return a, b
 
 
+class DeviceScene:
+    """The regions of a ``PolytopeScene`` resident on the device (``gcsadmm_scene``): uploaded once; the centres, the boxes and the
+    pair list stay there between the calls, and the broad phase runs there.  Call order: ``centers``, ``bounds`` (or ``set_boxes``),
+    ``candidate_pairs``, ``overlaps``, ``pairs``.  There is no CPU fallback.  Release with ``close()`` or use as a context manager."""
+
+    def __init__(self, polys: Sequence[Tuple[np.ndarray, np.ndarray]], device: int = 0):
+        host = PolytopeScene(polys, device)
+        self.n, self.P, self.device, self.lib = host.n, host.P, host.device, host.lib
+        self.num_pairs = 0
+        self._decided = False
+        lib = self.lib
+        for name, args in (("create", [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+                           ("centers", [C.c_void_p] * 4), ("bounds", [C.c_void_p] * 4), ("set_boxes", [C.c_void_p] * 3),
+                           ("candidate_pairs", [C.c_void_p, C.c_double, C.c_void_p]), ("overlaps", [C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]),
+                           ("read_pairs", [C.c_void_p] * 5), ("destroy", [C.c_void_p])):
+            f = getattr(lib, "gcsadmm_scene_" + name)
+            f.argtypes, f.restype = args, (None if name == "destroy" else C.c_int)
+        self._h = C.c_void_p()
+        rc = lib.gcsadmm_scene_create(self.n, self.P, host.ptr.ctypes.data, host.A.ctypes.data, host.b.ctypes.data, self.device, C.byref(self._h))
+        self._check(rc, "gcsadmm_scene_create")
+
+    def _check(self, rc, what):
+        if rc != 0:
+            raise GcsAdmmError(f"{what}: {self.lib.gcsadmm_polytope_last_error().decode()} (status {rc})")
+
+    def _handle(self):
+        if not self._h:
+            raise GcsAdmmError("the scene is closed")
+        return self._h
+
+    def close(self):
+        if self._h:
+            self.lib.gcsadmm_scene_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def centers(self):
+        """(centres [P, n], radii [P], LP status [P]); the centres stay on the device for ``bounds`` and ``overlaps``."""
+        cen = np.empty((self.P, self.n)); rad = np.empty(self.P); st = np.empty(self.P, np.int32)
+        self._check(self.lib.gcsadmm_scene_centers(self._handle(), cen.ctypes.data, rad.ctypes.data, st.ctypes.data), "gcsadmm_scene_centers")
+        return cen, rad, st
+
+    def bounds(self):
+        """(lo [P, n], hi [P, n], LP status [P, 2n]) from the resident centres.  A side whose LP reports status < 0 comes back, and
+        stays on the device, opened to -inf / +inf (the rule of ``build_graph_device``)."""
+        lo = np.empty((self.P, self.n)); hi = np.empty((self.P, self.n)); st = np.empty((self.P, 2 * self.n), np.int32)
+        self._check(self.lib.gcsadmm_scene_bounds(self._handle(), lo.ctypes.data, hi.ctypes.data, st.ctypes.data), "gcsadmm_scene_bounds")
+        self._decided = False
+        return lo, hi, st
+
+    def set_boxes(self, lo, hi):
+        """Replace the resident boxes; a NaN or ``lo > hi`` is refused."""
+        lo = np.ascontiguousarray(lo, float); hi = np.ascontiguousarray(hi, float)
+        if lo.shape != (self.P, self.n) or hi.shape != (self.P, self.n):
+            raise ValueError(f"boxes must be [{self.P}, {self.n}]")
+        self._check(self.lib.gcsadmm_scene_set_boxes(self._handle(), lo.ctypes.data, hi.ctypes.data), "gcsadmm_scene_set_boxes")
+        self._decided = False
+
+    def candidate_pairs(self, pad: float = SWEEP_PAD) -> int:
+        """Broad phase on the device; returns the number of pairs.  The list (``pairs``) is that of ``candidate_pairs(lo, hi, pad)``
+        on the resident boxes, element for element.  Returns after the device has finished."""
+        num = C.c_int64(0)
+        self._decided = False
+        self._check(self.lib.gcsadmm_scene_candidate_pairs(self._handle(), float(pad), C.addressof(num)), "gcsadmm_scene_candidate_pairs")
+        self.num_pairs = int(num.value)
+        return self.num_pairs
+
+    def overlaps(self, tol: float = 1e-9):
+        """Narrow phase on the resident pairs, each LP started at the resident centre of its first region: (pairs that overlap, pairs
+        whose LP reports status < 0 -- their flag is not a decision)."""
+        over = C.c_int64(0); und = C.c_int64(0)
+        self._check(self.lib.gcsadmm_scene_overlaps(self._handle(), float(tol), C.addressof(over), C.addressof(und)), "gcsadmm_scene_overlaps")
+        self._decided = True
+        return int(over.value), int(und.value)
+
+    def pairs(self):
+        """(pair_a, pair_b, flags, status) of the resident pair list, a < b; flags and status are None before ``overlaps``."""
+        T = self.num_pairs
+        pa = np.empty(T, np.int32); pb = np.empty(T, np.int32)
+        flags = np.empty(T, np.uint8) if self._decided else None
+        st = np.empty(T, np.int32) if self._decided else None
+        self._check(self.lib.gcsadmm_scene_read_pairs(self._handle(), pa.ctypes.data, pb.ctypes.data, flags.ctypes.data if self._decided else None,
+                                                      st.ctypes.data if self._decided else None), "gcsadmm_scene_read_pairs")
+        return pa, pb, flags, st
+
+
+def edge_arrays(pa, pb, flags):
+    """both directions of every intersecting pair in the reference's double-loop order (by tail, then head), int32"""
+    keep = np.asarray(flags) != 0
+    a = pa[keep]; b = pb[keep]
+    tail = np.concatenate([a, b]); head = np.concatenate([b, a])
+    o = np.lexsort((head, tail))
+    return tail[o].astype(np.int32), head[o].astype(np.int32)
+
+
+def build_graph_arrays_device(polys: Sequence[Tuple[np.ndarray, np.ndarray]], device: int = 0, tol: float = 1e-9, scene=None,
+                              stats: dict | None = None, names: Sequence[Hashable] | None = None):
+    """``build_graph_device`` on a resident scene, with arrays in and out: ``polys[p] = (A_p, b_p)``; returns
+    ``(edge_tail, edge_head, centres)``, int32 region indices in the reference's double-loop order.  The LP statuses are acted on as
+    there (centre failure raises with the indices of the regions; failed box sides are opened, on the device; undecided pairs are
+    decided again on the host), and ``stats`` receives the same three counts.  ``scene``: a prepared DeviceScene (it is left open).
+    ``names``: what to call the regions in an error message (default: their indices)."""
+    name = (lambda idx: [names[i] for i in idx]) if names is not None else (lambda idx: idx.tolist())
+    own = scene is None
+    if own:
+        scene = DeviceScene(polys, device)
+    try:
+        cen, rad, st_c = scene.centers()
+        if np.any(st_c < 0):
+            raise GcsAdmmError(f"centre LP did not converge for regions {name(np.nonzero(st_c < 0)[0][:8])} (of {int((st_c < 0).sum())})")
+        if np.any(rad <= 0):
+            raise ValueError(f"regions without interior: {name(np.nonzero(rad <= 0)[0][:5])}")
+        _, _, st_b = scene.bounds()
+        num_pairs = scene.candidate_pairs()
+        _, undecided = scene.overlaps(tol)
+        pa, pb, flags, st_o = scene.pairs()
+    finally:
+        if own:
+            scene.close()
+    if undecided:
+        from .graph import polytopes_overlap
+        flags = np.array(flags, copy=True)
+        for t in np.nonzero(np.asarray(st_o) < 0)[0]:
+            (A1, b1), (A2, b2) = polys[pa[t]], polys[pb[t]]
+            flags[t] = 1 if polytopes_overlap(np.asarray(A1, float), np.asarray(b1, float), np.asarray(A2, float), np.asarray(b2, float)) else 0
+    if stats is not None:
+        stats.update(bounds_opened=int((np.asarray(st_b) < 0).sum()), overlaps_redone_on_host=int(undecided), candidate_pairs=int(num_pairs))
+    tail, head = edge_arrays(pa, pb, flags)
+    return tail, head, cen
+
+
 def build_graph_device(As: Dict[Hashable, np.ndarray], bs: Dict[Hashable, np.ndarray], device: int = 0, tol: float = 1e-9,
-                       scene=None, stats: dict | None = None):
+                       scene=None, stats: dict | None = None, broad_phase: str = "host"):
     """``utils.build_graph`` (reference utils.py:31-82) with the LPs on the device.  Returns
     ``(vertices, edges, I_v_in, I_v_out, centres)``; ``edges`` in the reference's double-loop order.
 
@@ -131,8 +278,16 @@ def build_graph_device(As: Dict[Hashable, np.ndarray], bs: Dict[Hashable, np.nda
         would silently drop real neighbours: that side of the box is opened up (+-inf), which only adds candidates;
       * an overlap LP that did not converge is decided again by the host LP of ``graph.polytopes_overlap`` (one HiGHS
         solve per pair, the reference's own method) instead of from its unfinished iterate.
-    ``stats`` (optional dict) receives the counts.  ``scene``: a prepared PolytopeScene (tests inject one)."""
+    ``stats`` (optional dict) receives the counts.  ``scene``: a prepared PolytopeScene (tests inject one).
+    ``broad_phase="device"``: the whole pipeline on a resident scene (``build_graph_arrays_device``; ``scene``, if given, is a
+    DeviceScene) -- the same edges, without the host sweep and the copies between the steps."""
     vertices = list(As.keys())
+    if broad_phase not in ("host", "device"):
+        raise ValueError(f"broad_phase must be 'host' or 'device', not {broad_phase!r}")
+    if broad_phase == "device":
+        tail, head, cen = build_graph_arrays_device([(As[v], bs[v]) for v in vertices], device, tol, scene, stats, names=vertices)
+        edges = [(vertices[t], vertices[h]) for t, h in zip(tail.tolist(), head.tolist())]
+        return (vertices, edges) + _incidence_lists(vertices, edges) + (cen,)
     if scene is None:
         scene = PolytopeScene([(As[v], bs[v]) for v in vertices], device)
     cen, rad, st_c = scene.centers()
@@ -161,25 +316,34 @@ def build_graph_device(As: Dict[Hashable, np.ndarray], bs: Dict[Hashable, np.nda
     if stats is not None:
         stats.update(bounds_opened=int(fail_lo.sum() + fail_hi.sum()), overlaps_redone_on_host=int(len(redo)),
                      candidate_pairs=int(len(pa)))
-    a = pa[flags != 0]; b = pb[flags != 0]
-    tail = np.concatenate([a, b]); head = np.concatenate([b, a])
-    o = np.lexsort((head, tail))                      # double-loop order: by tail, then head
-    edges = [(vertices[t], vertices[h]) for t, h in zip(tail[o], head[o])]
+    tail, head = edge_arrays(pa, pb, flags)
+    edges = [(vertices[t], vertices[h]) for t, h in zip(tail, head)]
+    return (vertices, edges) + _incidence_lists(vertices, edges) + (cen,)
+
+
+def _incidence_lists(vertices, edges):
     I_v_in = {v: [] for v in vertices}
     I_v_out = {v: [] for v in vertices}
     for e in edges:
         I_v_out[e[0]].append(e)
         I_v_in[e[1]].append(e)
-    return vertices, edges, I_v_in, I_v_out, cen
+    return I_v_in, I_v_out
 
 
-def graph_from_sets_device(As, bs, n, device: int = 0) -> GcsGraph:
-    """``graph_from_sets`` with edges and interior points from the device LPs."""
+def graph_from_sets_device(As, bs, n, device: int = 0, broad_phase: str = "host") -> GcsGraph:
+    """``graph_from_sets`` with edges and interior points from the device LPs.  ``broad_phase="device"``: on a resident scene, the
+    edge arrays go straight into the CSR (no edge list of key pairs in between)."""
     keys = list(As.keys())
     if 's' not in As or 't' not in As:
         raise KeyError("case must define vertices 's' and 't'")
-    _, edges, _, _, cen = build_graph_device(As, bs, device)
     index = {k: i for i, k in enumerate(keys)}
+    if broad_phase == "device":
+        polys = [(np.asarray(As[k], float), np.asarray(bs[k], float)) for k in keys]
+        tail, head, cen = build_graph_arrays_device(polys, device)
+        return _finish_graph(int(n), keys, tail, head, polys, cen, index['s'], index['t'])
+    if broad_phase != "host":
+        raise ValueError(f"broad_phase must be 'host' or 'device', not {broad_phase!r}")
+    _, edges, _, _, cen = build_graph_device(As, bs, device)
     tail = [index[u] for u, _ in edges]
     head = [index[w] for _, w in edges]
     polys = [(np.asarray(As[k], float), np.asarray(bs[k], float)) for k in keys]

@@ -30,7 +30,10 @@ EXPORTS = ["gcsadmm_create", "gcsadmm_destroy", "gcsadmm_last_error", "gcsadmm_r
            "gcsadmm_comm_unique_id", "gcsadmm_check_halo", "gcsadmm_attach_comm", "gcsadmm_run_partitioned", "gcsadmm_halo_pack", "gcsadmm_halo_unpack",
            "gcsadmm_halo_exchange", "gcsadmm_halo_buffers", "gcsadmm_run_partitioned_timed", "gcsadmm_comm_count", "gcsadmm_set_overlap",
            # graph construction at scale (gcs_admm_amd/scene.py)
-           "gcsadmm_polytope_last_error", "gcsadmm_polytope_centers", "gcsadmm_polytope_bounds", "gcsadmm_polytope_overlaps"]
+           "gcsadmm_polytope_last_error", "gcsadmm_polytope_centers", "gcsadmm_polytope_bounds", "gcsadmm_polytope_overlaps",
+           # the same pipeline on a resident scene with a device broad phase (scene.DeviceScene)
+           "gcsadmm_scene_create", "gcsadmm_scene_destroy", "gcsadmm_scene_centers", "gcsadmm_scene_bounds", "gcsadmm_scene_set_boxes",
+           "gcsadmm_scene_candidate_pairs", "gcsadmm_scene_overlaps", "gcsadmm_scene_read_pairs"]
 
 
 class GraphDesc(C.Structure):

@@ -47,7 +47,8 @@ typedef enum gcsadmm_status {
                                        program (n = 2, vertex_workspace 0); a point terminal of degree above 256; a terminal that is a
                                        region without an edge on its live side, or source and target the same region */
     GCSADMM_ERR_HIP = 3,            /* a HIP runtime call failed */
-    GCSADMM_ERR_NO_DEVICE = 4
+    GCSADMM_ERR_NO_DEVICE = 4,
+    GCSADMM_ERR_NO_MEMORY = 5       /* a host allocation failed (gcsadmm_scene_*) */
 } gcsadmm_status;
 
 enum { GCSADMM_F64 = 0, GCSADMM_F32 = 1 };
@@ -282,7 +283,7 @@ gcsadmm_status gcsadmm_halo_buffers(gcsadmm_handle h, void **send_buf, void **re
  * check_overlap); these entry points run the same decisions as batches of tiny LPs on the device, one LP
  * per lane (polytope_lp.hip).  All pointers are HOST pointers (set-up code, called once per scene); the
  * polytope CSR is the one of gcsadmm_graph_desc (rows of region p: poly_ptr[p] .. poly_ptr[p+1]).
- * n = 1..6.  Return value: gcsadmm_status; text of the last failure: gcsadmm_polytope_last_error().
+ * n = 1..8.  Return value: gcsadmm_status; text of the last failure: gcsadmm_polytope_last_error().
  * Optional `status` arrays receive the LP status per problem: 0 converged, 1 / 2 decided early
  * (overlap / separation proven), -1 iteration limit.
  */
@@ -304,6 +305,44 @@ int gcsadmm_polytope_bounds(int n, int num_polytopes, const int *poly_ptr, const
 int gcsadmm_polytope_overlaps(int n, int num_polytopes, const int *poly_ptr, const double *poly_A, const double *poly_b,
                               const double *centers, long num_pairs, const int *pair_a, const int *pair_b, double tol,
                               int device, unsigned char *overlap, int *status);
+
+/* ---------------------------------------------------------------------------------------------
+ * The same pipeline on a RESIDENT scene: the polytope CSR is checked and uploaded once, and the centres, the boxes and the pair
+ * list stay on the device from the first LP to the last.  The broad phase -- sort-and-sweep over the first coordinate of the
+ * boxes -- runs on the device too (sweep_kernel; csrc/box_sweep_core.h has its contract: the pair list of
+ * gcs_admm_amd.scene.candidate_pairs, element for element).  The call order is centers, bounds (or set_boxes), candidate_pairs,
+ * overlaps, read_pairs; a call whose input is not resident yet returns GCSADMM_ERR_BAD_ARG.  All pointers are HOST pointers; every
+ * output pointer may be NULL.  Every call works on the scene's device and hands the caller's current device back; calls on one
+ * scene are not re-entrant.  Text of the last failure: gcsadmm_polytope_last_error().
+ */
+typedef struct gcsadmm_scene_s *gcsadmm_scene;
+
+/* The checks and the upload of the three entry points above, once. */
+int gcsadmm_scene_create(int n, int num_polytopes, const int *poly_ptr, const double *poly_A, const double *poly_b, int device,
+                         gcsadmm_scene *out);
+void gcsadmm_scene_destroy(gcsadmm_scene s);
+
+/* The centre LPs of gcsadmm_polytope_centers; the centres stay resident.  centers[P][n], radii[P], status[P]. */
+int gcsadmm_scene_centers(gcsadmm_scene s, double *centers, double *radii, int *status);
+
+/* The bounds LPs of gcsadmm_polytope_bounds from the resident centres.  A side whose LP reports status < 0 is an interior iterate,
+ * a box that is too small: it is opened to -inf / +inf in the resident boxes, and in lo / hi if given.  lo[P][n], hi[P][n],
+ * status[P][n][2] = (min, max) per axis. */
+int gcsadmm_scene_bounds(gcsadmm_scene s, double *lo, double *hi, int *status);
+
+/* Replace the resident boxes (hosts that have their own; tests).  A NaN, or lo > hi in any coordinate: GCSADMM_ERR_BAD_ARG. */
+int gcsadmm_scene_set_boxes(gcsadmm_scene s, const double *lo, const double *hi);
+
+/* Broad phase: the unordered pairs a < b of regions whose boxes, each side moved out by pad, meet; they stay resident.  More than
+ * 2^31 - 1 pairs: GCSADMM_ERR_UNSUPPORTED. */
+int gcsadmm_scene_candidate_pairs(gcsadmm_scene s, double pad, int64_t *num_pairs);
+
+/* Narrow phase: the decision of gcsadmm_polytope_overlaps for every resident pair, each LP started at the resident centre of the
+ * pair's first region.  num_undecided counts the pairs with status < 0, whose flag is not a decision. */
+int gcsadmm_scene_overlaps(gcsadmm_scene s, double tol, int64_t *num_overlapping, int64_t *num_undecided);
+
+/* The resident pair list, num_pairs entries each; overlap and status need gcsadmm_scene_overlaps to have run. */
+int gcsadmm_scene_read_pairs(gcsadmm_scene s, int *pair_a, int *pair_b, unsigned char *overlap, int *status);
 
 #ifdef __cplusplus
 }

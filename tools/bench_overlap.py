@@ -1,7 +1,10 @@
 """Measurement for graph construction at scale: LPs per second of the device path
 (gcs_admm_amd/scene.py -> csrc/polytope_lp.hip) on a scene of random 2-D / 3-D / 6-D polytopes, next to the CPU
 restatement (oracle/polytope_oracle.py: one HiGHS LP per pair, as the reference does with MOSEK) on a bounded
-sample.  One JSON line per dimension.
+sample.  One JSON line per dimension.  Beside the host sweep (``host_sweep_s``) it times the device broad phase of the resident
+scene (``device_sweep_s``) and the whole pipeline both ways on the same scene (``resident_pipeline_s`` against ``host_pipeline_s``:
+scene.build_graph_arrays_device against the four steps through the host, alternated, median of five), and says whether the two pair
+lists are equal (``pairs_equal_host``).
 
   python tools/bench_overlap.py [--regions 20000] [--cpu-pairs 300]
 """
@@ -9,7 +12,7 @@ import argparse, json, os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: F401  (HIP runtime first, see solver.load_library)
-from gcs_admm_amd.scene import PolytopeScene, candidate_pairs
+from gcs_admm_amd.scene import DeviceScene, PolytopeScene, edge_arrays, build_graph_arrays_device, candidate_pairs
 from oracle import polytope_oracle as PO
 
 
@@ -23,6 +26,29 @@ def scene_polys(rng, n, P, m_extra):
         A = np.vstack([A, np.eye(n), -np.eye(n)]); b = np.hstack([b, c + 1.5, -(c - 1.5)])
         polys.append((A, b))
     return polys
+
+
+def host_pipeline(polys, tol=1e-9):
+    """the four steps of build_graph_device (upload and LPs, boxes back, numpy sweep, pairs up, flags back) to the same edge arrays"""
+    scene = PolytopeScene(polys)
+    cen, _, _ = scene.centers()
+    lo, hi, st_b = scene.bounds(cen)
+    st_b = np.asarray(st_b).reshape(len(polys), -1, 2)
+    lo = np.where(st_b[:, :, 0] < 0, -np.inf, lo); hi = np.where(st_b[:, :, 1] < 0, np.inf, hi)
+    pa, pb = candidate_pairs(lo, hi)
+    flags, _ = scene.overlaps(pa, pb, tol, cen)
+    return edge_arrays(pa, pb, flags)
+
+
+def pipelines(polys, repeats=5):
+    """median wall time of the two pipelines, alternated (both end in a copy from the device, which synchronises)"""
+    t_host, t_res = [], []
+    for _ in range(repeats):
+        t0 = time.perf_counter(); th, hh = host_pipeline(polys); t_host.append(time.perf_counter() - t0)
+        t0 = time.perf_counter(); tr, hr, _ = build_graph_arrays_device(polys); t_res.append(time.perf_counter() - t0)
+        if not (np.array_equal(th, tr) and np.array_equal(hh, hr)):
+            raise SystemExit("the resident pipeline and the host pipeline disagree on the edges")
+    return float(np.median(t_host)), float(np.median(t_res))
 
 
 def main():
@@ -39,6 +65,13 @@ def main():
         t0 = time.perf_counter(); lo, hi, _ = scene.bounds(cen); t_b = time.perf_counter() - t0
         t0 = time.perf_counter(); pa, pb = candidate_pairs(lo, hi); t_s = time.perf_counter() - t0
         t0 = time.perf_counter(); flags, st = scene.overlaps(pa, pb, 1e-9, cen); t_o = time.perf_counter() - t0
+        with DeviceScene(polys) as resident:
+            resident.centers(); resident.bounds()
+            resident.candidate_pairs()                        # warm-up (code objects, pair buffers)
+            t0 = time.perf_counter(); resident.candidate_pairs(); t_ds = time.perf_counter() - t0    # returns after a device synchronise
+            da, db, _, _ = resident.pairs()
+        pairs_equal = bool(np.array_equal(da, pa) and np.array_equal(db, pb))
+        t_hp, t_rp = pipelines(polys)
         k = min(args.cpu_pairs, len(pa))
         sel = rng.choice(len(pa), k, replace=False)
         t0 = time.perf_counter()
@@ -50,6 +83,7 @@ def main():
             "candidate_pairs": int(len(pa)), "overlapping": int(flags.sum()),
             "device_overlap_LPs_per_sec": len(pa) / t_o, "device_centre_LPs_per_sec": args.regions / t_c,
             "device_bound_LPs_per_sec": args.regions * 2 * n / t_b, "host_sweep_s": t_s,
+            "device_sweep_s": t_ds, "host_pipeline_s": t_hp, "resident_pipeline_s": t_rp, "pairs_equal_host": pairs_equal,
             "early_exit_share": float(np.mean(st > 0)),
             "note": "device times include the host<->device copies of the scene (set-up API with host pointers)",
             "cpu_baseline": {"value": k / t_cpu, "unit": "LPs/s", "cores": 1, "kind": "port",
