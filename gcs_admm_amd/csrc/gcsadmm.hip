@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "gcsadmm.h"
+#include "hip_owners.h"
 #include "terminal_launch.h"
 #ifdef GCS_PHASE_TIMING
 // diagnostic build: sub-phase stamps inside the border factorisation (lane 0 of each wavefront)
@@ -345,49 +346,7 @@ __global__ __launch_bounds__(256) void cost_kernel(int V, int E, int n, const do
 // =================================================================================================
 // host side
 // =================================================================================================
-// ---- owners of the device resources: the only places that allocate and release them.  They release in their destructors, so
-// whoever destroys one has the handle's device current (gcsadmm_destroy and the failure path of gcsadmm_create hold the guard) ----
-struct HipRelease {
-    void operator()(void *p) const { (void)hipFree(p); }
-    void operator()(hipStream_t s) const { (void)hipStreamDestroy(s); }
-    void operator()(hipEvent_t e) const { (void)hipEventDestroy(e); }
-};
-using Stream = std::unique_ptr<std::remove_pointer_t<hipStream_t>, HipRelease>;
-using Event = std::unique_ptr<std::remove_pointer_t<hipEvent_t>, HipRelease>;
-template <class T> class DevBuf {
-    std::unique_ptr<T, HipRelease> p_;
-    size_t count_ = 0;
-public:
-    T *get() const { return p_.get(); }
-    size_t size() const { return p_ ? count_ : 0; }      // elements asked for (a count of 0 still allocates one)
-    explicit operator bool() const { return (bool)p_; }
-    void reset() { p_.reset(); }
-    hipError_t alloc(size_t count)              // uninitialised
-    {
-        T *p = nullptr;
-        const hipError_t e = hipMalloc((void **)&p, std::max<size_t>(count, 1) * sizeof(T));
-        p_.reset(e == hipSuccess ? p : nullptr);
-        count_ = count;
-        return e;
-    }
-    hipError_t upload(const T *src, size_t count)      // src == nullptr: zero-filled
-    {
-        const size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
-        const hipError_t e = alloc(count);
-        if (e != hipSuccess) return e;
-        return src ? hipMemcpy(get(), src, bytes, hipMemcpyHostToDevice) : hipMemset(get(), 0, bytes);
-    }
-    hipError_t zero(hipStream_t s) const { return size() ? hipMemsetAsync(get(), 0, size() * sizeof(T), s) : hipSuccess; }
-};
-// fills an empty Stream / Event through the HIP call that creates one with flags
-template <class O> static hipError_t create_owned(O &owner, hipError_t (*create)(typename O::pointer *, unsigned), unsigned flags)
-{
-    typename O::pointer x = nullptr;
-    const hipError_t e = create(&x, flags);
-    owner.reset(x);
-    return e;
-}
-
+// (the owners of the device resources -- DevBuf<T>, Stream, Event -- and the DeviceGuard: hip_owners.h)
 // vertex partition across GPUs (gcsadmm_attach_comm): halo index lists and message buffers
 struct Halo {
     std::vector<int> peers, peer_cnt, peer_off;   // neighbour ranks; columns per peer; first column of each peer's block
@@ -514,24 +473,10 @@ RcclApi &rccl()
     } while (0)
 
 
-static std::string g_create_error;
+static thread_local std::string g_create_error;      // gcsadmm_last_error(NULL): the calling thread's last failed create
 
-// Entry points work on the handle's device and leave the caller's current device as they found it (a process may hold
-// handles on several devices, and PyTorch tracks "its" current device on its own).
-struct DeviceGuard {
-    int prev = -1;
-    hipError_t err = hipSuccess;
-    explicit DeviceGuard(int dev)
-    {
-        int cur = -1;
-        err = hipGetDevice(&cur);
-        if (err == hipSuccess && cur != dev) { err = hipSetDevice(dev); if (err == hipSuccess) prev = cur; }
-    }
-    ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-    DeviceGuard(const DeviceGuard &) = delete;
-    DeviceGuard &operator=(const DeviceGuard &) = delete;
-};
-#define USE_DEVICE(h)                                                                                \
+// every entry point holds the handle's device for the call (DeviceGuard, hip_owners.h)
+#define USE_DEVICE(h)                                                                               \
     DeviceGuard device_guard_((h)->device);                                                          \
     do {                                                                                             \
         if (device_guard_.err != hipSuccess) {                                                       \

@@ -23,16 +23,31 @@
 // broad phase is sweep_kernel (box_sweep_core.h has the contract), so that only counts and the final pair list cross to the host.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <new>
+#include <optional>
 #include <string>
 #include <vector>
 
 #include "gcsadmm.h"
+#include "hip_owners.h"
+#include "step_args.h"      // dispatch_dim
 
 #include "polytope_lp_core.h"
 #include "box_sweep_core.h"
+
+// the calling thread's last failure (gcsadmm_polytope_last_error)
+static thread_local std::string g_err;
+#define LPCHK(call)                                                                                  \
+    do {                                                                                             \
+        hipError_t e_ = (call);                                                                      \
+        if (e_ != hipSuccess) {                                                                      \
+            g_err = std::string(#call) + ": " + hipGetErrorString(e_);                               \
+            return GCSADMM_ERR_HIP;                                                                  \
+        }                                                                                            \
+    } while (0)
 
 namespace gcsadmm_lp {
 
@@ -145,37 +160,61 @@ __global__ __launch_bounds__(SWEEP_WAVE) void sweep_kernel(SortedBoxes B, double
     if (!FILL && lane == 0) count[k] = total;
 }
 
-static std::string g_err;
+} // namespace gcsadmm_lp
 
-// the entry points switch to the requested device (upload_scene) and hand the caller's current device back on return
-struct RestoreDevice {
-    int prev = -1;
-    RestoreDevice() { if (hipGetDevice(&prev) != hipSuccess) prev = -1; }
-    ~RestoreDevice()
-    {
-        int cur = -1;
-        if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
-    }
+using namespace gcsadmm_lp;
+
+// The scene: everything graph construction computes stays in these buffers until it is read.  A gcsadmm_scene holds one from create
+// to destroy (read: gcsadmm_scene_read_pairs); a batch call (gcsadmm_polytope_*) holds one on its stack, with the buffers of its stage.
+struct gcsadmm_scene_s {
+    int n = 0, P = 0, device = 0;
+    int maxm = 0;                                      // most rows of one polytope
+    DevBuf<int> ptr;                                   // the polytopes: CSR, rows, right-hand sides, norms of the rows (S points at them)
+    DevBuf<double> A, b, nrm;
+    Polys S{};
+    DevBuf<double> w, cen, rad;                        // centre LPs: (x, r) records, centres [P][n], radii,
+    DevBuf<int> st_c;                                  //   statuses
+    DevBuf<double> lo, hi;                             // boxes [P][n]
+    DevBuf<int> st_b;                                  //   and the statuses of their LPs [P][n][2]
+    DevBuf<double> lo0, slo, shi;                      // sweep: first lower bounds, sorted boxes [n][P],
+    DevBuf<int> order, count;                          //   sort order, counts,
+    DevBuf<long long> offset;                          //   offsets
+    DevBuf<int> pa, pb, st_o;                          // pair list with the narrow phase's statuses,
+    DevBuf<unsigned char> flag;                        //   flags
+    DevBuf<unsigned long long> counts;                 //   and the two counts of them
+    long long T = 0;
+    bool have_centers = false, have_boxes = false, have_pairs = false, have_overlaps = false;
 };
 
-struct DevBuf {
-    void *p = nullptr;
-    DevBuf() = default;
-    DevBuf(const DevBuf &) = delete;
-    DevBuf &operator=(const DevBuf &) = delete;
-    ~DevBuf() { release(); }
-    hipError_t alloc(size_t bytes) { release(); return hipMalloc(&p, bytes ? bytes : 8); }
-    void release() { if (p) (void)hipFree(p); p = nullptr; }
-    template <class T> T *as() { return (T *)p; }
-};
+namespace {
 
-struct Scene {
-    DevBuf ptr, A, b, nrm;
-    Polys S;
-    int maxm = 0;
-};
+constexpr int TB = 256;      // threads per block of the element-wise helpers
+inline unsigned blocks_of(long count) { return (unsigned)((count + TB - 1) / TB); }
 
-static int upload_scene(Scene &sc, int n, int P, const int *poly_ptr, const double *A, const double *b, int device)
+// f(std::integral_constant<int, N>) for the scene's n (upload_scene admits 1..8 only)
+template <class F> int for_dim(int n, F &&f)
+{
+    int rc = GCSADMM_ERR_UNSUPPORTED;
+    gcsadmm_k::dispatch_dim<1, 2, 3, 4, 5, 6, 7, 8>(n, [&](auto N) { rc = f(N); });
+    return rc;
+}
+
+int guard_status(const DeviceGuard &guard)
+{
+    if (guard.err == hipSuccess) return GCSADMM_OK;
+    g_err = std::string("hipSetDevice: ") + hipGetErrorString(guard.err);
+    return GCSADMM_ERR_HIP;
+}
+// entry of every call on a resident scene: the scene's device for the call, the caller's back on return
+#define USE_SCENE(s)                                                                                 \
+    if (!(s)) { g_err = "null scene"; return GCSADMM_ERR_BAD_ARG; }                                  \
+    DeviceGuard device_guard_((s)->device);                                                          \
+    if (int rc_ = guard_status(device_guard_)) return rc_
+
+// Checks the polytopes on the host; only then takes the device (the guard lives in the caller's frame, declared before the scene,
+// and hands the caller's device back on return) and uploads them.
+int upload_scene(gcsadmm_scene_s &s, std::optional<DeviceGuard> &guard, int n, int P, const int *poly_ptr, const double *A, const double *b,
+                 int device)
 {
     if (n < 1 || n > 8) { g_err = "polytope LPs are instantiated for n = 1..8"; return GCSADMM_ERR_UNSUPPORTED; }
     if (P < 0 || !poly_ptr || (P > 0 && (!A || !b))) { g_err = "null polytope array"; return GCSADMM_ERR_BAD_ARG; }
@@ -186,114 +225,145 @@ static int upload_scene(Scene &sc, int n, int P, const int *poly_ptr, const doub
     for (int p = 0; p < P; ++p) {
         const int m = poly_ptr[p + 1] - poly_ptr[p];
         if (m < 1) { g_err = "polytope without rows"; return GCSADMM_ERR_BAD_ARG; }
-        sc.maxm = std::max(sc.maxm, m);
+        s.maxm = std::max(s.maxm, m);
     }
-    const int rows = poly_ptr[P];
-    std::vector<double> nrm((size_t)rows);
-    for (int r = 0; r < rows; ++r) {
-        double s = 0;
-        for (int k = 0; k < n; ++k) s += A[(size_t)r * n + k] * A[(size_t)r * n + k];
-        if (!(s > 0.0)) { g_err = "zero facet normal"; return GCSADMM_ERR_BAD_ARG; }
-        nrm[r] = std::sqrt(s);
+    const size_t rows = (size_t)poly_ptr[P];
+    std::vector<double> nrm(rows);
+    for (size_t r = 0; r < rows; ++r) {
+        double sq = 0;
+        for (int k = 0; k < n; ++k) sq += A[r * n + k] * A[r * n + k];
+        if (!(sq > 0.0)) { g_err = "zero facet normal"; return GCSADMM_ERR_BAD_ARG; }
+        nrm[r] = std::sqrt(sq);
     }
-    hipError_t e;
-#define CK(x) if ((e = (x)) != hipSuccess) { g_err = std::string(#x) + ": " + hipGetErrorString(e); return GCSADMM_ERR_HIP; }
-    CK(hipSetDevice(device));
-    CK(sc.ptr.alloc(sizeof(int) * (P + 1))); CK(sc.A.alloc(sizeof(double) * rows * n));
-    CK(sc.b.alloc(sizeof(double) * rows)); CK(sc.nrm.alloc(sizeof(double) * rows));
-    CK(hipMemcpy(sc.ptr.p, poly_ptr, sizeof(int) * (P + 1), hipMemcpyHostToDevice));
-    CK(hipMemcpy(sc.A.p, A, sizeof(double) * rows * n, hipMemcpyHostToDevice));
-    CK(hipMemcpy(sc.b.p, b, sizeof(double) * rows, hipMemcpyHostToDevice));
-    CK(hipMemcpy(sc.nrm.p, nrm.data(), sizeof(double) * rows, hipMemcpyHostToDevice));
-    sc.S = Polys{n, P, sc.ptr.as<int>(), sc.A.as<double>(), sc.b.as<double>(), sc.nrm.as<double>()};
+    guard.emplace(device);
+    if (int rc = guard_status(*guard)) return rc;
+    LPCHK(s.ptr.upload(poly_ptr, (size_t)P + 1));
+    if (rows > 0) {      // (upload copies one element even for a count of 0)
+        LPCHK(s.A.upload(A, rows * n)); LPCHK(s.b.upload(b, rows)); LPCHK(s.nrm.upload(nrm.data(), rows));
+    }
+    s.n = n; s.P = P; s.device = device;
+    s.S = Polys{n, P, s.ptr.get(), s.A.get(), s.b.get(), s.nrm.get()};
     return GCSADMM_OK;
 }
 
-template <int N>
-static int launch_ball(const Scene &sc, long count, const int *d_pa, const int *d_pb, const double *d_x0, int rows_max,
-                       double tol, int early, double *d_w, unsigned char *d_flag, int *d_status)
-{
-    const size_t lds = lds_bytes(rows_max);
-    if (lds > LDS_MAX_BYTES) { g_err = "too many facet rows per LP for LDS"; return GCSADMM_ERR_UNSUPPORTED; }
-    hipError_t e;
-    CK(hipFuncSetAttribute((const void *)ball_kernel<N>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    if (count > 0)
-        hipLaunchKernelGGL(ball_kernel<N>, dim3((unsigned)((count + WAVE - 1) / WAVE)), dim3(WAVE), lds, 0, sc.S, (int)count, d_pa, d_pb,
-                           d_x0, rows_max, tol, early, d_w, d_flag, d_status);
-    CK(hipGetLastError());
-    return GCSADMM_OK;
-}
-template <int N>
-static int launch_bounds(const Scene &sc, const double *d_centers, double *d_lo, double *d_hi, int *d_status)
-{
-    const int rows_max = bounds_rows(sc.maxm, N);
-    const size_t lds = lds_bytes(rows_max);
-    if (lds > LDS_MAX_BYTES) { g_err = "too many facet rows per LP for LDS"; return GCSADMM_ERR_UNSUPPORTED; }
-    hipError_t e;
-    CK(hipFuncSetAttribute((const void *)bounds_kernel<N>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    const long count = (long)sc.S.P * 2 * N;
-    if (count > 0)
-        hipLaunchKernelGGL(bounds_kernel<N>, dim3((unsigned)((count + WAVE - 1) / WAVE)), dim3(WAVE), lds, 0, sc.S, d_centers, rows_max, d_lo, d_hi, d_status);
-    CK(hipGetLastError());
-    return GCSADMM_OK;
-}
-
-#define DISPATCH_N(n, CALL)                                                                          \
-    switch (n) {                                                                                       \
-    case 1: { constexpr int NN = 1; rc = CALL; } break;                                                \
-    case 2: { constexpr int NN = 2; rc = CALL; } break;                                                \
-    case 3: { constexpr int NN = 3; rc = CALL; } break;                                                \
-    case 4: { constexpr int NN = 4; rc = CALL; } break;                                                \
-    case 5: { constexpr int NN = 5; rc = CALL; } break;                                                \
-    case 6: { constexpr int NN = 6; rc = CALL; } break;                                                \
-    case 7: { constexpr int NN = 7; rc = CALL; } break;                                                \
-    default: { constexpr int NN = 8; rc = CALL; } break;                                               \
-    }
-
-} // namespace gcsadmm_lp
-
-using namespace gcsadmm_lp;
-
-// The resident scene: everything graph construction computes stays in these buffers until gcsadmm_scene_read_pairs.
-struct gcsadmm_scene_s {
-    Scene sc;
-    int n = 0, P = 0, device = 0;
-    DevBuf w, cen, rad, st_c;                          // centre LPs: (x, r) records, centres [P][n], radii, statuses
-    DevBuf lo, hi, st_b;                               // boxes [P][n] and the statuses of their LPs [P][n][2]
-    DevBuf lo0, order, slo, shi, count, offset;        // sweep: first lower bounds, sort order, sorted boxes [n][P], counts, offsets
-    DevBuf pa, pb, flag, st_o, counts;                 // pair list with the narrow phase's flags and statuses, and the two counts of them
-    long long T = 0;
-    bool have_centers = false, have_boxes = false, have_pairs = false, have_overlaps = false;
+// The buffers of the stages are allocated here and nowhere else: gcsadmm_scene_create takes a resident scene's, and
+// gcsadmm_scene_candidate_pairs the pair list's once it knows T; a batch call takes those of its one stage.
+enum : unsigned {
+    BUF_CEN = 1,            // the centres: written by the centre stage, read by the other two
+    BUF_CENTRE_LP = 2, BUF_BOXES = 4, BUF_PAIRS = 8,
+    BUF_RESIDENT = 16       // the sweep's arrays and the counts of decisions: what only a resident scene has
 };
+int alloc_buffers(gcsadmm_scene_s *s, unsigned which, size_t T = 0)
+{
+    const size_t P = (size_t)s->P, n = (size_t)s->n;
+    hipError_t e = hipSuccess;
+    auto take = [&](unsigned group, auto &buf, size_t count) {
+        if (!(which & group) || e != hipSuccess) return;
+        buf.reset();      // (before the new one is taken: a pair list is replaced, not held twice)
+        e = buf.alloc(count);
+    };
+    take(BUF_CEN, s->cen, P * n);
+    take(BUF_CENTRE_LP, s->w, P * (n + 1)); take(BUF_CENTRE_LP, s->rad, P); take(BUF_CENTRE_LP, s->st_c, P);
+    take(BUF_BOXES, s->lo, P * n); take(BUF_BOXES, s->hi, P * n); take(BUF_BOXES, s->st_b, P * 2 * n);
+    take(BUF_RESIDENT, s->lo0, P); take(BUF_RESIDENT, s->order, P); take(BUF_RESIDENT, s->slo, P * n); take(BUF_RESIDENT, s->shi, P * n);
+    take(BUF_RESIDENT, s->count, P); take(BUF_RESIDENT, s->offset, P); take(BUF_RESIDENT, s->counts, 2);
+    take(BUF_PAIRS, s->pa, T); take(BUF_PAIRS, s->pb, T); take(BUF_PAIRS, s->flag, T); take(BUF_PAIRS, s->st_o, T);
+    if (e != hipSuccess) { g_err = std::string("hipMalloc: ") + hipGetErrorString(e); return GCSADMM_ERR_HIP; }
+    return GCSADMM_OK;
+}
 
-namespace {
+// all of a buffer to the host; dst == nullptr: the caller does not want it
+template <class T> hipError_t download(T *dst, const DevBuf<T> &src)
+{
+    return dst ? hipMemcpy(dst, src.get(), sizeof(T) * src.size(), hipMemcpyDeviceToHost) : hipSuccess;
+}
 
-constexpr int TB = 256;      // threads per block of the element-wise helpers
-inline unsigned blocks_of(long count) { return (unsigned)((count + TB - 1) / TB); }
+// ---- the launches ----
+template <int N>
+int launch_ball(const gcsadmm_scene_s &s, long count, const int *d_pa, const int *d_pb, const double *d_x0, int rows_max, double tol, int early,
+                double *d_w, unsigned char *d_flag, int *d_status)
+{
+    const size_t lds = lds_bytes(rows_max);
+    if (lds > LDS_MAX_BYTES) { g_err = "too many facet rows per LP for LDS"; return GCSADMM_ERR_UNSUPPORTED; }
+    LPCHK(hipFuncSetAttribute((const void *)ball_kernel<N>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    if (count > 0)
+        hipLaunchKernelGGL(ball_kernel<N>, dim3((unsigned)((count + WAVE - 1) / WAVE)), dim3(WAVE), lds, 0, s.S, (int)count, d_pa, d_pb,
+                           d_x0, rows_max, tol, early, d_w, d_flag, d_status);
+    LPCHK(hipGetLastError());
+    return GCSADMM_OK;
+}
+
+template <int N>
+int launch_bounds(const gcsadmm_scene_s &s, const double *d_centers, double *d_lo, double *d_hi, int *d_status)
+{
+    const int rows_max = bounds_rows(s.maxm, N);
+    const size_t lds = lds_bytes(rows_max);
+    if (lds > LDS_MAX_BYTES) { g_err = "too many facet rows per LP for LDS"; return GCSADMM_ERR_UNSUPPORTED; }
+    LPCHK(hipFuncSetAttribute((const void *)bounds_kernel<N>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    const long count = (long)s.S.P * 2 * N;
+    if (count > 0)
+        hipLaunchKernelGGL(bounds_kernel<N>, dim3((unsigned)((count + WAVE - 1) / WAVE)), dim3(WAVE), lds, 0, s.S, d_centers, rows_max, d_lo, d_hi, d_status);
+    LPCHK(hipGetLastError());
+    return GCSADMM_OK;
+}
 
 template <int N>
 int launch_sweep(gcsadmm_scene_s *s, bool fill, double pad)
 {
-    const SortedBoxes B{s->P, s->slo.as<double>(), s->shi.as<double>(), s->order.as<int>()};
-    hipError_t e;
+    const SortedBoxes B{s->P, s->slo.get(), s->shi.get(), s->order.get()};
     if (s->P > 0) {
         if (fill)
-            hipLaunchKernelGGL((sweep_kernel<N, true>), dim3((unsigned)s->P), dim3(SWEEP_WAVE), 0, 0, B, pad, nullptr,
-                               s->offset.as<long long>(), s->pa.as<int>(), s->pb.as<int>());
+            hipLaunchKernelGGL((sweep_kernel<N, true>), dim3((unsigned)s->P), dim3(SWEEP_WAVE), 0, 0, B, pad, nullptr, s->offset.get(), s->pa.get(),
+                               s->pb.get());
         else
-            hipLaunchKernelGGL((sweep_kernel<N, false>), dim3((unsigned)s->P), dim3(SWEEP_WAVE), 0, 0, B, pad, s->count.as<int>(), nullptr,
-                               nullptr, nullptr);
+            hipLaunchKernelGGL((sweep_kernel<N, false>), dim3((unsigned)s->P), dim3(SWEEP_WAVE), 0, 0, B, pad, s->count.get(), nullptr, nullptr, nullptr);
     }
-    CK(hipGetLastError());
+    LPCHK(hipGetLastError());
     return GCSADMM_OK;
 }
 
-// entry of every scene call: the handle's device for the call, the caller's back on return (RestoreDevice in the caller's frame)
-int enter_scene(gcsadmm_scene_s *s)
+// ---- the three LP stages, on the scene's buffers: what both families of entry points run ----
+// centre LPs of all polytopes into w and st_c, then the centres and radii out of the records
+int run_centers(gcsadmm_scene_s *s)
 {
-    if (!s) { g_err = "null scene"; return GCSADMM_ERR_BAD_ARG; }
-    hipError_t e;
-    CK(hipSetDevice(s->device));
+    const int rc = for_dim(s->n, [&](auto N) {
+        return launch_ball<decltype(N)::value>(*s, s->P, nullptr, nullptr, nullptr, centre_rows(s->maxm), 0.0, 0, s->w.get(), nullptr, s->st_c.get());
+    });
+    if (rc != GCSADMM_OK) return rc;
+    if (s->P > 0) hipLaunchKernelGGL(split_centres_kernel, dim3(blocks_of(s->P)), dim3(TB), 0, 0, s->w.get(), s->n, s->P, s->cen.get(), s->rad.get());
+    LPCHK(hipGetLastError());
+    return GCSADMM_OK;
+}
+
+// the 2n bound LPs of every polytope, started at cen, into lo, hi and st_b: what the LPs left (a failed side is not opened here)
+int run_bounds(gcsadmm_scene_s *s)
+{
+    return for_dim(s->n, [&](auto N) { return launch_bounds<decltype(N)::value>(*s, s->cen.get(), s->lo.get(), s->hi.get(), s->st_b.get()); });
+}
+
+// one LP per pair of pa, pb into flag and st_o; x0: the scene's centres (LP t starts at x0[pa[t]]), or nullptr (least-squares points)
+int run_overlaps(gcsadmm_scene_s *s, const double *x0, double tol)
+{
+    return for_dim(s->n, [&](auto N) {
+        return launch_ball<decltype(N)::value>(*s, (long)s->T, s->pa.get(), s->pb.get(), x0, overlap_rows(s->maxm), tol, 1, nullptr, s->flag.get(),
+                                               s->st_o.get());
+    });
+}
+
+// ---- their results to the host (a null pointer: not wanted) ----
+int read_centers(gcsadmm_scene_s *s, double *centers, double *radii, int *status)
+{
+    LPCHK(download(centers, s->cen)); LPCHK(download(radii, s->rad)); LPCHK(download(status, s->st_c));
+    return GCSADMM_OK;
+}
+int read_boxes(gcsadmm_scene_s *s, double *lo, double *hi, int *status)
+{
+    LPCHK(download(lo, s->lo)); LPCHK(download(hi, s->hi)); LPCHK(download(status, s->st_b));
+    return GCSADMM_OK;
+}
+int read_decisions(gcsadmm_scene_s *s, unsigned char *overlap, int *status)
+{
+    LPCHK(download(overlap, s->flag)); LPCHK(download(status, s->st_o));
     return GCSADMM_OK;
 }
 
@@ -303,111 +373,74 @@ extern "C" {
 
 const char *gcsadmm_polytope_last_error(void) { return g_err.c_str(); }
 
+// ---- batch calls: a scene for the length of the call, with the buffers of one stage; host arrays in, host arrays out ----
 int gcsadmm_polytope_centers(int n, int num_polytopes, const int *poly_ptr, const double *poly_A, const double *poly_b,
                              int device, double *centers, double *radii, int *status)
 {
-    RestoreDevice restore_device_;
     if (!centers) { g_err = "null output"; return GCSADMM_ERR_BAD_ARG; }
-    Scene sc;
-    int rc = upload_scene(sc, n, num_polytopes, poly_ptr, poly_A, poly_b, device);
-    if (rc != GCSADMM_OK) return rc;
-    const int P = num_polytopes;
-    DevBuf w, st;
-    hipError_t e;
-    CK(w.alloc(sizeof(double) * (size_t)P * (n + 1))); CK(st.alloc(sizeof(int) * (size_t)P));
-    DISPATCH_N(n, (launch_ball<NN>(sc, P, nullptr, nullptr, nullptr, centre_rows(sc.maxm), 0.0, 0, w.as<double>(), nullptr, st.as<int>())));
-    if (rc != GCSADMM_OK) return rc;
-    std::vector<double> hw((size_t)P * (n + 1));
-    std::vector<int> hs((size_t)P);
-    CK(hipMemcpy(hw.data(), w.p, sizeof(double) * hw.size(), hipMemcpyDeviceToHost));
-    CK(hipMemcpy(hs.data(), st.p, sizeof(int) * hs.size(), hipMemcpyDeviceToHost));
-    for (int p = 0; p < P; ++p) {
-        for (int k = 0; k < n; ++k) centers[(size_t)p * n + k] = hw[(size_t)p * (n + 1) + k];
-        if (radii) radii[p] = hw[(size_t)p * (n + 1) + n];
-        if (status) status[p] = hs[p];
-    }
-    return GCSADMM_OK;
+    std::optional<DeviceGuard> guard;
+    gcsadmm_scene_s s;
+    int rc = upload_scene(s, guard, n, num_polytopes, poly_ptr, poly_A, poly_b, device);
+    if (rc == GCSADMM_OK) rc = alloc_buffers(&s, BUF_CEN | BUF_CENTRE_LP);
+    if (rc == GCSADMM_OK) rc = run_centers(&s);
+    if (rc == GCSADMM_OK) rc = read_centers(&s, centers, radii, status);
+    return rc;
 }
 
 int gcsadmm_polytope_bounds(int n, int num_polytopes, const int *poly_ptr, const double *poly_A, const double *poly_b,
                             const double *centers, int device, double *lo, double *hi, int *status)
 {
-    RestoreDevice restore_device_;
     if (!centers || !lo || !hi) { g_err = "null centres or output"; return GCSADMM_ERR_BAD_ARG; }
-    Scene sc;
-    int rc = upload_scene(sc, n, num_polytopes, poly_ptr, poly_A, poly_b, device);
+    std::optional<DeviceGuard> guard;
+    gcsadmm_scene_s s;
+    int rc = upload_scene(s, guard, n, num_polytopes, poly_ptr, poly_A, poly_b, device);
+    if (rc == GCSADMM_OK) rc = alloc_buffers(&s, BUF_CEN | BUF_BOXES);
     if (rc != GCSADMM_OK) return rc;
-    const size_t P = (size_t)num_polytopes;
-    DevBuf dc, dlo, dhi, st;
-    hipError_t e;
-    CK(dc.alloc(sizeof(double) * P * n)); CK(dlo.alloc(sizeof(double) * P * n)); CK(dhi.alloc(sizeof(double) * P * n));
-    CK(st.alloc(sizeof(int) * P * 2 * n));
-    CK(hipMemcpy(dc.p, centers, sizeof(double) * P * n, hipMemcpyHostToDevice));
-    DISPATCH_N(n, (launch_bounds<NN>(sc, dc.as<double>(), dlo.as<double>(), dhi.as<double>(), st.as<int>())));
-    if (rc != GCSADMM_OK) return rc;
-    CK(hipMemcpy(lo, dlo.p, sizeof(double) * P * n, hipMemcpyDeviceToHost));
-    CK(hipMemcpy(hi, dhi.p, sizeof(double) * P * n, hipMemcpyDeviceToHost));
-    if (status) CK(hipMemcpy(status, st.p, sizeof(int) * P * 2 * n, hipMemcpyDeviceToHost));
-    return GCSADMM_OK;
+    LPCHK(hipMemcpy(s.cen.get(), centers, sizeof(double) * s.cen.size(), hipMemcpyHostToDevice));
+    rc = run_bounds(&s);
+    if (rc == GCSADMM_OK) rc = read_boxes(&s, lo, hi, status);      // as the LPs left them: opening a failed side is the caller's
+    return rc;
 }
 
 int gcsadmm_polytope_overlaps(int n, int num_polytopes, const int *poly_ptr, const double *poly_A, const double *poly_b,
                               const double *centers, long num_pairs, const int *pair_a, const int *pair_b, double tol,
                               int device, unsigned char *overlap, int *status)
 {
-    RestoreDevice restore_device_;
     if (num_pairs < 0 || (num_pairs > 0 && (!pair_a || !pair_b || !overlap))) { g_err = "null pair list or output"; return GCSADMM_ERR_BAD_ARG; }
     for (long t = 0; t < num_pairs; ++t)
         if (pair_a[t] < 0 || pair_a[t] >= num_polytopes || pair_b[t] < 0 || pair_b[t] >= num_polytopes) {
             g_err = "pair index out of range"; return GCSADMM_ERR_BAD_ARG;
         }
-    Scene sc;
-    int rc = upload_scene(sc, n, num_polytopes, poly_ptr, poly_A, poly_b, device);
+    std::optional<DeviceGuard> guard;
+    gcsadmm_scene_s s;
+    int rc = upload_scene(s, guard, n, num_polytopes, poly_ptr, poly_A, poly_b, device);
+    if (rc == GCSADMM_OK) rc = alloc_buffers(&s, (centers ? BUF_CEN : 0u) | BUF_PAIRS, (size_t)num_pairs);
     if (rc != GCSADMM_OK) return rc;
-    const size_t P = (size_t)num_polytopes, T = (size_t)num_pairs;
-    DevBuf da, db, dc, df, st;
-    hipError_t e;
-    CK(da.alloc(sizeof(int) * T)); CK(db.alloc(sizeof(int) * T)); CK(df.alloc(T)); CK(st.alloc(sizeof(int) * T));
-    CK(hipMemcpy(da.p, pair_a, sizeof(int) * T, hipMemcpyHostToDevice));
-    CK(hipMemcpy(db.p, pair_b, sizeof(int) * T, hipMemcpyHostToDevice));
-    if (centers) {
-        CK(dc.alloc(sizeof(double) * P * n));
-        CK(hipMemcpy(dc.p, centers, sizeof(double) * P * n, hipMemcpyHostToDevice));
-    }
-    DISPATCH_N(n, (launch_ball<NN>(sc, num_pairs, da.as<int>(), db.as<int>(), centers ? dc.as<double>() : nullptr, overlap_rows(sc.maxm), tol, 1,
-                                   nullptr, df.as<unsigned char>(), st.as<int>())));
-    if (rc != GCSADMM_OK) return rc;
-    CK(hipMemcpy(overlap, df.p, T, hipMemcpyDeviceToHost));
-    if (status) CK(hipMemcpy(status, st.p, sizeof(int) * T, hipMemcpyDeviceToHost));
-    return GCSADMM_OK;
+    s.T = num_pairs;
+    LPCHK(hipMemcpy(s.pa.get(), pair_a, sizeof(int) * s.pa.size(), hipMemcpyHostToDevice));
+    LPCHK(hipMemcpy(s.pb.get(), pair_b, sizeof(int) * s.pb.size(), hipMemcpyHostToDevice));
+    if (centers) LPCHK(hipMemcpy(s.cen.get(), centers, sizeof(double) * s.cen.size(), hipMemcpyHostToDevice));
+    rc = run_overlaps(&s, s.cen.get(), tol);      // (no centres: no buffer, every LP starts from its least-squares point)
+    if (rc == GCSADMM_OK) rc = read_decisions(&s, overlap, status);
+    return rc;
 }
 
+// ---- the resident scene: precondition, stage, what only it does, results, synchronise, flag ----
 int gcsadmm_scene_create(int n, int num_polytopes, const int *poly_ptr, const double *poly_A, const double *poly_b, int device,
                          gcsadmm_scene *out)
 {
-    RestoreDevice restore_device_;
     if (!out) { g_err = "null output"; return GCSADMM_ERR_BAD_ARG; }
     *out = nullptr;
+    std::optional<DeviceGuard> guard;
     gcsadmm_scene_s *s = new (std::nothrow) gcsadmm_scene_s;
     if (!s) { g_err = "out of host memory"; return GCSADMM_ERR_NO_MEMORY; }
     int rc;
     try {
-        rc = upload_scene(s->sc, n, num_polytopes, poly_ptr, poly_A, poly_b, device);
+        rc = upload_scene(*s, guard, n, num_polytopes, poly_ptr, poly_A, poly_b, device);
     } catch (const std::bad_alloc &) {
         g_err = "out of host memory"; rc = GCSADMM_ERR_NO_MEMORY;
     }
-    if (rc == GCSADMM_OK) {
-        s->n = n; s->P = num_polytopes; s->device = device;
-        const size_t P = (size_t)num_polytopes, d = sizeof(double);
-        hipError_t e = hipSuccess;
-        const struct { DevBuf *buf; size_t bytes; } bufs[] = {
-            {&s->w, d * P * (n + 1)}, {&s->cen, d * P * n}, {&s->rad, d * P}, {&s->st_c, sizeof(int) * P}, {&s->lo, d * P * n}, {&s->hi, d * P * n},
-            {&s->st_b, sizeof(int) * P * 2 * n}, {&s->lo0, d * P}, {&s->order, sizeof(int) * P}, {&s->slo, d * P * n}, {&s->shi, d * P * n},
-            {&s->count, sizeof(int) * P}, {&s->offset, sizeof(long long) * P}, {&s->counts, 2 * sizeof(unsigned long long)}};
-        for (const auto &b : bufs)
-            if (e == hipSuccess) e = b.buf->alloc(b.bytes);
-        if (e != hipSuccess) { g_err = std::string("hipMalloc: ") + hipGetErrorString(e); rc = GCSADMM_ERR_HIP; }
-    }
+    if (rc == GCSADMM_OK) rc = alloc_buffers(s, BUF_CEN | BUF_CENTRE_LP | BUF_BOXES | BUF_RESIDENT);
     if (rc != GCSADMM_OK) { delete s; return rc; }
     *out = s;
     return GCSADMM_OK;
@@ -415,113 +448,89 @@ int gcsadmm_scene_create(int n, int num_polytopes, const int *poly_ptr, const do
 
 void gcsadmm_scene_destroy(gcsadmm_scene s)
 {
-    RestoreDevice restore_device_;
     if (!s) return;
-    (void)hipSetDevice(s->device);
+    DeviceGuard device_guard_(s->device);
     delete s;
 }
 
 int gcsadmm_scene_centers(gcsadmm_scene s, double *centers, double *radii, int *status)
 {
-    RestoreDevice restore_device_;
-    int rc = enter_scene(s);
-    if (rc != GCSADMM_OK) return rc;
-    const int n = s->n, P = s->P;
-    hipError_t e;
+    USE_SCENE(s);
     s->have_centers = false;
-    DISPATCH_N(n, (launch_ball<NN>(s->sc, P, nullptr, nullptr, nullptr, centre_rows(s->sc.maxm), 0.0, 0, s->w.as<double>(), nullptr, s->st_c.as<int>())));
+    int rc = run_centers(s);
+    if (rc == GCSADMM_OK) rc = read_centers(s, centers, radii, status);
     if (rc != GCSADMM_OK) return rc;
-    if (P > 0) hipLaunchKernelGGL(split_centres_kernel, dim3(blocks_of(P)), dim3(TB), 0, 0, s->w.as<double>(), n, P, s->cen.as<double>(), s->rad.as<double>());
-    CK(hipGetLastError());
-    if (centers) CK(hipMemcpy(centers, s->cen.p, sizeof(double) * (size_t)P * n, hipMemcpyDeviceToHost));
-    if (radii) CK(hipMemcpy(radii, s->rad.p, sizeof(double) * (size_t)P, hipMemcpyDeviceToHost));
-    if (status) CK(hipMemcpy(status, s->st_c.p, sizeof(int) * (size_t)P, hipMemcpyDeviceToHost));
-    CK(hipStreamSynchronize(nullptr));
+    LPCHK(hipStreamSynchronize(nullptr));
     s->have_centers = true;
     return GCSADMM_OK;
 }
 
 int gcsadmm_scene_bounds(gcsadmm_scene s, double *lo, double *hi, int *status)
 {
-    RestoreDevice restore_device_;
-    int rc = enter_scene(s);
-    if (rc != GCSADMM_OK) return rc;
+    USE_SCENE(s);
     if (!s->have_centers) { g_err = "no resident centres: call gcsadmm_scene_centers first"; return GCSADMM_ERR_BAD_ARG; }
-    const int n = s->n, P = s->P;
-    const size_t cells = (size_t)P * n;
-    hipError_t e;
     s->have_boxes = s->have_pairs = s->have_overlaps = false;
-    DISPATCH_N(n, (launch_bounds<NN>(s->sc, s->cen.as<double>(), s->lo.as<double>(), s->hi.as<double>(), s->st_b.as<int>())));
+    int rc = run_bounds(s);
     if (rc != GCSADMM_OK) return rc;
-    if (cells > 0)
-        hipLaunchKernelGGL(open_failed_sides_kernel, dim3(blocks_of((long)cells * 2)), dim3(TB), 0, 0, s->st_b.as<int>(), n, P, s->lo.as<double>(),
-                           s->hi.as<double>());
-    CK(hipGetLastError());
-    if (lo) CK(hipMemcpy(lo, s->lo.p, sizeof(double) * cells, hipMemcpyDeviceToHost));
-    if (hi) CK(hipMemcpy(hi, s->hi.p, sizeof(double) * cells, hipMemcpyDeviceToHost));
-    if (status) CK(hipMemcpy(status, s->st_b.p, sizeof(int) * cells * 2, hipMemcpyDeviceToHost));
-    CK(hipStreamSynchronize(nullptr));
+    const long sides = (long)s->P * s->n * 2;
+    if (sides > 0) hipLaunchKernelGGL(open_failed_sides_kernel, dim3(blocks_of(sides)), dim3(TB), 0, 0, s->st_b.get(), s->n, s->P, s->lo.get(), s->hi.get());
+    LPCHK(hipGetLastError());
+    if ((rc = read_boxes(s, lo, hi, status)) != GCSADMM_OK) return rc;
+    LPCHK(hipStreamSynchronize(nullptr));
     s->have_boxes = true;
     return GCSADMM_OK;
 }
 
 int gcsadmm_scene_set_boxes(gcsadmm_scene s, const double *lo, const double *hi)
 {
-    RestoreDevice restore_device_;
-    int rc = enter_scene(s);
-    if (rc != GCSADMM_OK) return rc;
+    USE_SCENE(s);
     const size_t cells = (size_t)s->P * s->n;
     if (cells > 0 && (!lo || !hi)) { g_err = "null boxes"; return GCSADMM_ERR_BAD_ARG; }
     for (size_t i = 0; i < cells; ++i)
         if (!(lo[i] <= hi[i])) { g_err = "box with a NaN or with lo > hi"; return GCSADMM_ERR_BAD_ARG; }
-    hipError_t e;
     s->have_boxes = s->have_pairs = s->have_overlaps = false;
-    CK(hipMemcpy(s->lo.p, lo, sizeof(double) * cells, hipMemcpyHostToDevice));
-    CK(hipMemcpy(s->hi.p, hi, sizeof(double) * cells, hipMemcpyHostToDevice));
+    LPCHK(hipMemcpy(s->lo.get(), lo, sizeof(double) * cells, hipMemcpyHostToDevice));
+    LPCHK(hipMemcpy(s->hi.get(), hi, sizeof(double) * cells, hipMemcpyHostToDevice));
     s->have_boxes = true;
     return GCSADMM_OK;
 }
 
 static int candidate_pairs(gcsadmm_scene s, double pad, int64_t *num_pairs)
 {
-    int rc = enter_scene(s);
-    if (rc != GCSADMM_OK) return rc;
+    USE_SCENE(s);
     if (!s->have_boxes) { g_err = "no resident boxes: call gcsadmm_scene_bounds or gcsadmm_scene_set_boxes first"; return GCSADMM_ERR_BAD_ARG; }
     if (!(pad == pad)) { g_err = "pad is NaN"; return GCSADMM_ERR_BAD_ARG; }
     const int n = s->n, P = s->P;
-    hipError_t e;
     s->have_pairs = s->have_overlaps = false;
     s->T = 0;
     // sort on the host (P log P on P doubles; a device radix sort would order -0.0 before +0.0 and change the order of ties)
     std::vector<double> lo0((size_t)P);
     std::vector<int> order((size_t)P), count((size_t)P);
     std::vector<long long> offset((size_t)P);
-    if (P > 0) hipLaunchKernelGGL(first_lower_bounds_kernel, dim3(blocks_of(P)), dim3(TB), 0, 0, s->lo.as<double>(), n, P, s->lo0.as<double>());
-    CK(hipGetLastError());
-    CK(hipMemcpy(lo0.data(), s->lo0.p, sizeof(double) * (size_t)P, hipMemcpyDeviceToHost));
+    if (P > 0) hipLaunchKernelGGL(first_lower_bounds_kernel, dim3(blocks_of(P)), dim3(TB), 0, 0, s->lo.get(), n, P, s->lo0.get());
+    LPCHK(hipGetLastError());
+    LPCHK(download(lo0.data(), s->lo0));
     for (int p = 0; p < P; ++p)      // a NaN has no place in the order (set_boxes refuses one; a bounds LP reports none with a status >= 0)
         if (!(lo0[p] == lo0[p])) { g_err = "resident box with a NaN lower bound"; return GCSADMM_ERR_BAD_ARG; }
     sweep_order(lo0.data(), P, order.data());
-    CK(hipMemcpy(s->order.p, order.data(), sizeof(int) * (size_t)P, hipMemcpyHostToDevice));
+    LPCHK(hipMemcpy(s->order.get(), order.data(), sizeof(int) * (size_t)P, hipMemcpyHostToDevice));
     if (P > 0)
-        hipLaunchKernelGGL(sweep_gather_kernel, dim3(blocks_of(P)), dim3(TB), 0, 0, s->lo.as<double>(), s->hi.as<double>(), s->order.as<int>(), n, P,
-                           s->slo.as<double>(), s->shi.as<double>());
-    CK(hipGetLastError());
-    DISPATCH_N(n, (launch_sweep<NN>(s, false, pad)));
+        hipLaunchKernelGGL(sweep_gather_kernel, dim3(blocks_of(P)), dim3(TB), 0, 0, s->lo.get(), s->hi.get(), s->order.get(), n, P, s->slo.get(), s->shi.get());
+    LPCHK(hipGetLastError());
+    int rc = for_dim(n, [&](auto N) { return launch_sweep<decltype(N)::value>(s, false, pad); });
     if (rc != GCSADMM_OK) return rc;
-    CK(hipMemcpy(count.data(), s->count.p, sizeof(int) * (size_t)P, hipMemcpyDeviceToHost));
+    LPCHK(download(count.data(), s->count));
     long long total = 0;
     if (!sweep_scan(count.data(), P, offset.data(), &total)) {      // before anything is allocated
         g_err = "more than 2^31 - 1 candidate pairs"; return GCSADMM_ERR_UNSUPPORTED;
     }
-    CK(s->pa.alloc(sizeof(int) * (size_t)total)); CK(s->pb.alloc(sizeof(int) * (size_t)total));
-    CK(s->flag.alloc((size_t)total)); CK(s->st_o.alloc(sizeof(int) * (size_t)total));
-    CK(hipMemcpy(s->offset.p, offset.data(), sizeof(long long) * (size_t)P, hipMemcpyHostToDevice));
+    if ((rc = alloc_buffers(s, BUF_PAIRS, (size_t)total)) != GCSADMM_OK) return rc;
+    LPCHK(hipMemcpy(s->offset.get(), offset.data(), sizeof(long long) * (size_t)P, hipMemcpyHostToDevice));
     if (total > 0) {
-        DISPATCH_N(n, (launch_sweep<NN>(s, true, pad)));
+        rc = for_dim(n, [&](auto N) { return launch_sweep<decltype(N)::value>(s, true, pad); });
         if (rc != GCSADMM_OK) return rc;
     }
-    CK(hipStreamSynchronize(nullptr));
+    LPCHK(hipStreamSynchronize(nullptr));
     s->T = total;
     s->have_pairs = true;
     if (num_pairs) *num_pairs = total;
@@ -530,7 +539,6 @@ static int candidate_pairs(gcsadmm_scene s, double pad, int64_t *num_pairs)
 
 int gcsadmm_scene_candidate_pairs(gcsadmm_scene s, double pad, int64_t *num_pairs)
 {
-    RestoreDevice restore_device_;
     try {
         return candidate_pairs(s, pad, num_pairs);
     } catch (const std::bad_alloc &) {      // the host arrays of the sort and the scan
@@ -540,47 +548,34 @@ int gcsadmm_scene_candidate_pairs(gcsadmm_scene s, double pad, int64_t *num_pair
 
 int gcsadmm_scene_overlaps(gcsadmm_scene s, double tol, int64_t *num_overlapping, int64_t *num_undecided)
 {
-    RestoreDevice restore_device_;
-    int rc = enter_scene(s);
-    if (rc != GCSADMM_OK) return rc;
+    USE_SCENE(s);
     if (!s->have_pairs) { g_err = "no resident pairs: call gcsadmm_scene_candidate_pairs first"; return GCSADMM_ERR_BAD_ARG; }
     if (!s->have_centers) { g_err = "no resident centres: call gcsadmm_scene_centers first"; return GCSADMM_ERR_BAD_ARG; }
-    const size_t T = (size_t)s->T;
-    hipError_t e;
     s->have_overlaps = false;
-    DISPATCH_N(s->n, (launch_ball<NN>(s->sc, (long)s->T, s->pa.as<int>(), s->pb.as<int>(), s->cen.as<double>(), overlap_rows(s->sc.maxm), tol, 1,
-                                      nullptr, s->flag.as<unsigned char>(), s->st_o.as<int>())));
+    const int rc = run_overlaps(s, s->cen.get(), tol);
     if (rc != GCSADMM_OK) return rc;
     if (num_overlapping || num_undecided) {      // counted where the flags are: two numbers come back, the arrays stay for read_pairs
         unsigned long long counts[2] = {0, 0};
-        CK(hipMemcpy(s->counts.p, counts, sizeof(counts), hipMemcpyHostToDevice));
-        if (T > 0)
-            hipLaunchKernelGGL(count_decisions_kernel, dim3(blocks_of((long)T)), dim3(TB), 0, 0, s->flag.as<unsigned char>(), s->st_o.as<int>(), (long)T,
-                               s->counts.as<unsigned long long>());
-        CK(hipGetLastError());
-        CK(hipMemcpy(counts, s->counts.p, sizeof(counts), hipMemcpyDeviceToHost));
+        LPCHK(hipMemcpy(s->counts.get(), counts, sizeof(counts), hipMemcpyHostToDevice));
+        if (s->T > 0)
+            hipLaunchKernelGGL(count_decisions_kernel, dim3(blocks_of((long)s->T)), dim3(TB), 0, 0, s->flag.get(), s->st_o.get(), (long)s->T, s->counts.get());
+        LPCHK(hipGetLastError());
+        LPCHK(download(counts, s->counts));
         if (num_overlapping) *num_overlapping = (int64_t)counts[0];
         if (num_undecided) *num_undecided = (int64_t)counts[1];
     }
-    CK(hipStreamSynchronize(nullptr));
+    LPCHK(hipStreamSynchronize(nullptr));
     s->have_overlaps = true;
     return GCSADMM_OK;
 }
 
 int gcsadmm_scene_read_pairs(gcsadmm_scene s, int *pair_a, int *pair_b, unsigned char *overlap, int *status)
 {
-    RestoreDevice restore_device_;
-    int rc = enter_scene(s);
-    if (rc != GCSADMM_OK) return rc;
+    USE_SCENE(s);
     if (!s->have_pairs) { g_err = "no resident pairs: call gcsadmm_scene_candidate_pairs first"; return GCSADMM_ERR_BAD_ARG; }
     if ((overlap || status) && !s->have_overlaps) { g_err = "the resident pairs are not decided: call gcsadmm_scene_overlaps first"; return GCSADMM_ERR_BAD_ARG; }
-    const size_t T = (size_t)s->T;
-    hipError_t e;
-    if (pair_a) CK(hipMemcpy(pair_a, s->pa.p, sizeof(int) * T, hipMemcpyDeviceToHost));
-    if (pair_b) CK(hipMemcpy(pair_b, s->pb.p, sizeof(int) * T, hipMemcpyDeviceToHost));
-    if (overlap) CK(hipMemcpy(overlap, s->flag.p, T, hipMemcpyDeviceToHost));
-    if (status) CK(hipMemcpy(status, s->st_o.p, sizeof(int) * T, hipMemcpyDeviceToHost));
-    return GCSADMM_OK;
+    LPCHK(download(pair_a, s->pa)); LPCHK(download(pair_b, s->pb));
+    return read_decisions(s, overlap, status);
 }
 
 } // extern "C"

@@ -1,30 +1,34 @@
 """Graph construction at scale on the device.
 
-The reference's ``build_graph`` (utils.py:31-82) decides every ordered pair of regions with one LP
-feasibility solve through Drake/MOSEK (``check_overlap``, :49-65) -- |V|^2 host solves, which caps it at a
-few hundred regions.  Here:
+The reference's ``build_graph`` (utils.py:31-82) decides every ordered pair of regions with one LP feasibility solve through
+Drake/MOSEK (``check_overlap``, :49-65) -- |V|^2 host solves, which caps it at a few hundred regions.  Here:
 
-  1. Chebyshev centres and axis-aligned bounding boxes of all regions: batched tiny LPs on the MI355X
-     (``gcsadmm_polytope_centers`` / ``gcsadmm_polytope_bounds``, csrc/polytope_lp.hip);
-  2. broad phase on the host: sort-and-sweep over the first coordinate of the boxes (numpy), which leaves
-     only pairs whose boxes touch;
-  3. narrow phase on the device: one LP per candidate pair (``gcsadmm_polytope_overlaps``), the same
-     decision as the reference's feasibility solve (closed sets, touching counts);
+  1. Chebyshev centres and axis-aligned bounding boxes of all regions: batched tiny LPs on the MI355X (csrc/polytope_lp.hip);
+  2. broad phase: sort-and-sweep over the first coordinate of the boxes, which leaves only pairs whose boxes touch;
+  3. narrow phase on the device: one LP per candidate pair, the same decision as the reference's feasibility solve (closed sets,
+     touching counts);
   4. edges in the reference's double-loop order, both directions of every intersecting pair.
 
-``DeviceScene`` is the same pipeline on a scene that stays on the device (``gcsadmm_scene_*``): the polytopes are uploaded once,
-centres, boxes and pairs never come back to the host between the steps, and step 2 is a kernel (``sweep_kernel``) that returns
-the pair list of ``candidate_pairs`` element for element.  ``build_graph_arrays_device`` drives it and returns edge arrays;
-``build_graph_device(..., broad_phase="device")`` and ``graph_from_sets_device(..., broad_phase="device")`` go through it.
+``build_graph_arrays_device`` is the one pipeline: it acts on the LP statuses and makes the edge arrays.  Its two broad phases differ
+only in the calls that produce centres, box statuses and the decided pair list:
 
-It raises if the HIP library or a device is missing.  LP statuses are checked (build_graph_device): the only host LPs this
-module ever runs are re-decisions of overlap LPs that hit their iteration limit.  The host functions of
-``gcs_admm_amd.graph`` (scipy LPs) remain what the small reference cases are built with.
+  * ``"host"``: a ``PolytopeScene`` -- the batch calls ``gcsadmm_polytope_*``, arrays up and down around every step, and the sweep in
+    numpy (``candidate_pairs``);
+  * ``"device"``: a ``DeviceScene`` -- the regions uploaded once (``gcsadmm_scene_*``); centres, boxes and pairs never come back to
+    the host between the steps, and the sweep is a kernel (``sweep_kernel``) that returns the pair list of ``candidate_pairs``
+    element for element.
+
+Both run the same three LP stages of polytope_lp.hip.  ``build_graph_device`` and ``graph_from_sets_device`` are front ends that turn
+region keys into indices and back.
+
+It raises if the HIP library or a device is missing.  The only host LPs this module ever runs are re-decisions of overlap LPs that
+hit their iteration limit.  The host functions of ``gcs_admm_amd.graph`` (scipy LPs) remain what the small reference cases are built
+with.
 """
 from __future__ import annotations
 
 import ctypes as C
-from typing import Dict, Hashable, List, Sequence, Tuple
+from typing import Dict, Hashable, Sequence, Tuple
 
 import numpy as np
 
@@ -33,9 +37,40 @@ from .solver import GcsAdmmError, load_library
 
 __all__ = ["PolytopeScene", "DeviceScene", "build_graph_device", "build_graph_arrays_device", "edge_arrays", "graph_from_sets_device"]
 
+_i, _d, _p = C.c_int, C.c_double, C.c_void_p
+# the graph-construction entry points of include/gcsadmm.h: (argument types, result type); arrays go in as addresses
+_PROTOTYPES = {
+    "gcsadmm_polytope_last_error": ([], C.c_char_p),
+    "gcsadmm_polytope_centers": ([_i, _i, _p, _p, _p, _i, _p, _p, _p], _i),
+    "gcsadmm_polytope_bounds": ([_i, _i, _p, _p, _p, _p, _i, _p, _p, _p], _i),
+    "gcsadmm_polytope_overlaps": ([_i, _i, _p, _p, _p, _p, C.c_long, _p, _p, _d, _i, _p, _p], _i),
+    "gcsadmm_scene_create": ([_i, _i, _p, _p, _p, _i, _p], _i),
+    "gcsadmm_scene_destroy": ([_p], None),
+    "gcsadmm_scene_centers": ([_p] * 4, _i),
+    "gcsadmm_scene_bounds": ([_p] * 4, _i),
+    "gcsadmm_scene_set_boxes": ([_p] * 3, _i),
+    "gcsadmm_scene_candidate_pairs": ([_p, _d, _p], _i),
+    "gcsadmm_scene_overlaps": ([_p, _d, _p, _p], _i),
+    "gcsadmm_scene_read_pairs": ([_p] * 5, _i),
+}
+_lib = None
 
-def _ptr(a, t):
-    return a.ctypes.data_as(C.POINTER(t))
+
+def _library():
+    """the HIP library, with the prototypes above declared when it is first loaded"""
+    global _lib
+    if _lib is None:
+        lib = load_library()
+        for name, (argtypes, restype) in _PROTOTYPES.items():
+            f = getattr(lib, name)
+            f.argtypes, f.restype = argtypes, restype
+        _lib = lib
+    return _lib
+
+
+def _check(lib, rc, what):
+    if rc != 0:
+        raise GcsAdmmError(f"{what}: {lib.gcsadmm_polytope_last_error().decode()} (status {rc})")
 
 
 class PolytopeScene:
@@ -49,33 +84,27 @@ class PolytopeScene:
         self.A = np.ascontiguousarray(np.vstack([np.asarray(A, float).reshape(-1, self.n) for A, _ in polys]))
         self.b = np.ascontiguousarray(np.hstack([np.asarray(b, float).ravel() for _, b in polys]))
         self.device = int(device)
-        self.lib = load_library()
-        self.lib.gcsadmm_polytope_last_error.restype = C.c_char_p
+        self.lib = _library()
         self._centers = None
 
-    def _check(self, rc, what):
-        if rc != 0:
-            raise GcsAdmmError(f"{what}: {self.lib.gcsadmm_polytope_last_error().decode()} (status {rc})")
+    def _csr(self):
+        return self.n, self.P, self.ptr.ctypes.data, self.A.ctypes.data, self.b.ctypes.data
 
     def centers(self):
         """(centres [P, n], radii [P], LP status [P])."""
         cen = np.empty((self.P, self.n)); rad = np.empty(self.P); st = np.empty(self.P, np.int32)
-        rc = self.lib.gcsadmm_polytope_centers(C.c_int(self.n), C.c_int(self.P), _ptr(self.ptr, C.c_int), _ptr(self.A, C.c_double),
-                                               _ptr(self.b, C.c_double), C.c_int(self.device), _ptr(cen, C.c_double),
-                                               _ptr(rad, C.c_double), _ptr(st, C.c_int))
-        self._check(rc, "gcsadmm_polytope_centers")
+        rc = self.lib.gcsadmm_polytope_centers(*self._csr(), self.device, cen.ctypes.data, rad.ctypes.data, st.ctypes.data)
+        _check(self.lib, rc, "gcsadmm_polytope_centers")
         self._centers = cen
         return cen, rad, st
 
     def bounds(self, centers=None):
-        """(lo [P, n], hi [P, n], LP status [P, 2n]).  ``centers`` must be strictly inside their regions (the LPs start there):
-        a side started from a point that is outside, or not finite, reports status -1."""
+        """(lo [P, n], hi [P, n], LP status [P, 2n]), as the LPs left them.  ``centers`` must be strictly inside their regions (the
+        LPs start there): a side started from a point that is outside, or not finite, reports status -1."""
         cen = np.ascontiguousarray(centers if centers is not None else (self._centers if self._centers is not None else self.centers()[0]))
         lo = np.empty((self.P, self.n)); hi = np.empty((self.P, self.n)); st = np.empty((self.P, 2 * self.n), np.int32)
-        rc = self.lib.gcsadmm_polytope_bounds(C.c_int(self.n), C.c_int(self.P), _ptr(self.ptr, C.c_int), _ptr(self.A, C.c_double),
-                                              _ptr(self.b, C.c_double), _ptr(cen, C.c_double), C.c_int(self.device),
-                                              _ptr(lo, C.c_double), _ptr(hi, C.c_double), _ptr(st, C.c_int))
-        self._check(rc, "gcsadmm_polytope_bounds")
+        rc = self.lib.gcsadmm_polytope_bounds(*self._csr(), cen.ctypes.data, self.device, lo.ctypes.data, hi.ctypes.data, st.ctypes.data)
+        _check(self.lib, rc, "gcsadmm_polytope_bounds")
         return lo, hi, st
 
     def overlaps(self, pair_a, pair_b, tol: float = 1e-9, centers=None):
@@ -90,11 +119,9 @@ class PolytopeScene:
         out = np.zeros(len(pa), np.uint8); st = np.zeros(len(pa), np.int32)
         cen = centers if centers is not None else self._centers
         cen = np.ascontiguousarray(cen) if cen is not None else None
-        rc = self.lib.gcsadmm_polytope_overlaps(C.c_int(self.n), C.c_int(self.P), _ptr(self.ptr, C.c_int), _ptr(self.A, C.c_double),
-                                                _ptr(self.b, C.c_double), _ptr(cen, C.c_double) if cen is not None else None,
-                                                C.c_long(len(pa)), _ptr(pa, C.c_int), _ptr(pb, C.c_int), C.c_double(tol),
-                                                C.c_int(self.device), _ptr(out, C.c_ubyte), _ptr(st, C.c_int))
-        self._check(rc, "gcsadmm_polytope_overlaps")
+        rc = self.lib.gcsadmm_polytope_overlaps(*self._csr(), cen.ctypes.data if cen is not None else None, len(pa), pa.ctypes.data,
+                                                pb.ctypes.data, tol, self.device, out.ctypes.data, st.ctypes.data)
+        _check(self.lib, rc, "gcsadmm_polytope_overlaps")
         return out, st
 
 
@@ -135,20 +162,11 @@ class DeviceScene:
         self.n, self.P, self.device, self.lib = host.n, host.P, host.device, host.lib
         self.num_pairs = 0
         self._decided = False
-        lib = self.lib
-        for name, args in (("create", [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
-                           ("centers", [C.c_void_p] * 4), ("bounds", [C.c_void_p] * 4), ("set_boxes", [C.c_void_p] * 3),
-                           ("candidate_pairs", [C.c_void_p, C.c_double, C.c_void_p]), ("overlaps", [C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]),
-                           ("read_pairs", [C.c_void_p] * 5), ("destroy", [C.c_void_p])):
-            f = getattr(lib, "gcsadmm_scene_" + name)
-            f.argtypes, f.restype = args, (None if name == "destroy" else C.c_int)
         self._h = C.c_void_p()
-        rc = lib.gcsadmm_scene_create(self.n, self.P, host.ptr.ctypes.data, host.A.ctypes.data, host.b.ctypes.data, self.device, C.byref(self._h))
-        self._check(rc, "gcsadmm_scene_create")
+        self._check(self.lib.gcsadmm_scene_create(*host._csr(), self.device, C.byref(self._h)), "gcsadmm_scene_create")
 
     def _check(self, rc, what):
-        if rc != 0:
-            raise GcsAdmmError(f"{what}: {self.lib.gcsadmm_polytope_last_error().decode()} (status {rc})")
+        _check(self.lib, rc, what)
 
     def _handle(self):
         if not self._h:
@@ -180,7 +198,7 @@ class DeviceScene:
 
     def bounds(self):
         """(lo [P, n], hi [P, n], LP status [P, 2n]) from the resident centres.  A side whose LP reports status < 0 comes back, and
-        stays on the device, opened to -inf / +inf (the rule of ``build_graph_device``)."""
+        stays on the device, opened to -inf / +inf (the rule of ``build_graph_arrays_device``)."""
         lo = np.empty((self.P, self.n)); hi = np.empty((self.P, self.n)); st = np.empty((self.P, 2 * self.n), np.int32)
         self._check(self.lib.gcsadmm_scene_bounds(self._handle(), lo.ctypes.data, hi.ctypes.data, st.ctypes.data), "gcsadmm_scene_bounds")
         self._decided = False
@@ -232,45 +250,9 @@ def edge_arrays(pa, pb, flags):
 
 
 def build_graph_arrays_device(polys: Sequence[Tuple[np.ndarray, np.ndarray]], device: int = 0, tol: float = 1e-9, scene=None,
-                              stats: dict | None = None, names: Sequence[Hashable] | None = None):
-    """``build_graph_device`` on a resident scene, with arrays in and out: ``polys[p] = (A_p, b_p)``; returns
-    ``(edge_tail, edge_head, centres)``, int32 region indices in the reference's double-loop order.  The LP statuses are acted on as
-    there (centre failure raises with the indices of the regions; failed box sides are opened, on the device; undecided pairs are
-    decided again on the host), and ``stats`` receives the same three counts.  ``scene``: a prepared DeviceScene (it is left open).
-    ``names``: what to call the regions in an error message (default: their indices)."""
-    name = (lambda idx: [names[i] for i in idx]) if names is not None else (lambda idx: idx.tolist())
-    own = scene is None
-    if own:
-        scene = DeviceScene(polys, device)
-    try:
-        cen, rad, st_c = scene.centers()
-        if np.any(st_c < 0):
-            raise GcsAdmmError(f"centre LP did not converge for regions {name(np.nonzero(st_c < 0)[0][:8])} (of {int((st_c < 0).sum())})")
-        if np.any(rad <= 0):
-            raise ValueError(f"regions without interior: {name(np.nonzero(rad <= 0)[0][:5])}")
-        _, _, st_b = scene.bounds()
-        num_pairs = scene.candidate_pairs()
-        _, undecided = scene.overlaps(tol)
-        pa, pb, flags, st_o = scene.pairs()
-    finally:
-        if own:
-            scene.close()
-    if undecided:
-        from .graph import polytopes_overlap
-        flags = np.array(flags, copy=True)
-        for t in np.nonzero(np.asarray(st_o) < 0)[0]:
-            (A1, b1), (A2, b2) = polys[pa[t]], polys[pb[t]]
-            flags[t] = 1 if polytopes_overlap(np.asarray(A1, float), np.asarray(b1, float), np.asarray(A2, float), np.asarray(b2, float)) else 0
-    if stats is not None:
-        stats.update(bounds_opened=int((np.asarray(st_b) < 0).sum()), overlaps_redone_on_host=int(undecided), candidate_pairs=int(num_pairs))
-    tail, head = edge_arrays(pa, pb, flags)
-    return tail, head, cen
-
-
-def build_graph_device(As: Dict[Hashable, np.ndarray], bs: Dict[Hashable, np.ndarray], device: int = 0, tol: float = 1e-9,
-                       scene=None, stats: dict | None = None, broad_phase: str = "host"):
-    """``utils.build_graph`` (reference utils.py:31-82) with the LPs on the device.  Returns
-    ``(vertices, edges, I_v_in, I_v_out, centres)``; ``edges`` in the reference's double-loop order.
+                              stats: dict | None = None, names: Sequence[Hashable] | None = None, broad_phase: str = "device"):
+    """``utils.build_graph`` (reference utils.py:31-82) with the LPs on the device, arrays in and out: ``polys[p] = (A_p, b_p)``;
+    returns ``(edge_tail, edge_head, centres)``, int32 region indices in the reference's double-loop order.
 
     Every LP reports a status (0 converged, 1 / 2 decided early, -1 iteration limit) and none is ignored:
       * a centre LP that did not converge has no trustworthy interior point -> GcsAdmmError naming the regions;
@@ -278,73 +260,79 @@ def build_graph_device(As: Dict[Hashable, np.ndarray], bs: Dict[Hashable, np.nda
         would silently drop real neighbours: that side of the box is opened up (+-inf), which only adds candidates;
       * an overlap LP that did not converge is decided again by the host LP of ``graph.polytopes_overlap`` (one HiGHS
         solve per pair, the reference's own method) instead of from its unfinished iterate.
-    ``stats`` (optional dict) receives the counts.  ``scene``: a prepared PolytopeScene (tests inject one).
-    ``broad_phase="device"``: the whole pipeline on a resident scene (``build_graph_arrays_device``; ``scene``, if given, is a
-    DeviceScene) -- the same edges, without the host sweep and the copies between the steps."""
-    vertices = list(As.keys())
+    ``stats`` (optional dict) receives the counts.  ``broad_phase``: ``"host"`` (the batch LP calls of a PolytopeScene around the numpy
+    sweep) or ``"device"`` (a resident DeviceScene: no host sweep, no copies between the steps) -- the same edges.  ``scene``: a
+    prepared scene of that kind (tests inject one; a DeviceScene is left open).  ``names``: what to call the regions in an error
+    message (default: their indices)."""
     if broad_phase not in ("host", "device"):
         raise ValueError(f"broad_phase must be 'host' or 'device', not {broad_phase!r}")
-    if broad_phase == "device":
-        tail, head, cen = build_graph_arrays_device([(As[v], bs[v]) for v in vertices], device, tol, scene, stats, names=vertices)
-        edges = [(vertices[t], vertices[h]) for t, h in zip(tail.tolist(), head.tolist())]
-        return (vertices, edges) + _incidence_lists(vertices, edges) + (cen,)
-    if scene is None:
-        scene = PolytopeScene([(As[v], bs[v]) for v in vertices], device)
-    cen, rad, st_c = scene.centers()
-    if np.any(st_c < 0):
-        bad = [vertices[i] for i in np.nonzero(st_c < 0)[0][:8]]
-        raise GcsAdmmError(f"centre LP did not converge for regions {bad} (of {int((st_c < 0).sum())})")
-    if np.any(rad <= 0):
-        bad = [vertices[i] for i in np.nonzero(rad <= 0)[0][:5]]
-        raise ValueError(f"regions without interior: {bad}")
-    lo, hi, st_b = scene.bounds(cen)
-    n = lo.shape[1]
-    # status layout of gcsadmm_polytope_bounds (polytope_lp.hip bounds_kernel): [P][n][2] = (min, max) per axis
-    st_b = np.asarray(st_b).reshape(len(vertices), n, 2)
-    fail_lo, fail_hi = st_b[:, :, 0] < 0, st_b[:, :, 1] < 0
-    lo = np.where(fail_lo, -np.inf, lo); hi = np.where(fail_hi, np.inf, hi)
-    pa, pb = candidate_pairs(lo, hi)
-    flags, st_o = scene.overlaps(pa, pb, tol, cen)
+    name = (lambda idx: [names[i] for i in idx]) if names is not None else (lambda idx: idx.tolist())
+
+    def check_centres(rad, st_c):
+        if np.any(st_c < 0):
+            raise GcsAdmmError(f"centre LP did not converge for regions {name(np.nonzero(st_c < 0)[0][:8])} (of {int((st_c < 0).sum())})")
+        if np.any(rad <= 0):
+            raise ValueError(f"regions without interior: {name(np.nonzero(rad <= 0)[0][:5])}")
+
+    # the two call sequences to (cen, st_b, pa, pb, flags, st_o); everything after them is common
+    if broad_phase == "host":
+        if scene is None:
+            scene = PolytopeScene(polys, device)
+        cen, rad, st_c = scene.centers()
+        check_centres(rad, st_c)
+        lo, hi, st_b = scene.bounds(cen)
+        # the batch call opens nothing; status layout of bounds_kernel (polytope_lp.hip): [P][n][2] = (min, max) per axis
+        st_b = np.asarray(st_b).reshape(lo.shape + (2,))
+        pa, pb = candidate_pairs(np.where(st_b[..., 0] < 0, -np.inf, lo), np.where(st_b[..., 1] < 0, np.inf, hi))
+        flags, st_o = scene.overlaps(pa, pb, tol, cen)
+    else:
+        own = scene is None
+        if own:
+            scene = DeviceScene(polys, device)
+        try:
+            cen, rad, st_c = scene.centers()
+            check_centres(rad, st_c)
+            _, _, st_b = scene.bounds()          # failed sides are opened on the device
+            scene.candidate_pairs()
+            scene.overlaps(tol)
+            pa, pb, flags, st_o = scene.pairs()
+        finally:
+            if own:
+                scene.close()
     redo = np.nonzero(np.asarray(st_o) < 0)[0]
     if len(redo):
         from .graph import polytopes_overlap
         flags = np.array(flags, copy=True)
         for t in redo:
-            u, w = vertices[pa[t]], vertices[pb[t]]
-            flags[t] = 1 if polytopes_overlap(np.asarray(As[u], float), np.asarray(bs[u], float),
-                                              np.asarray(As[w], float), np.asarray(bs[w], float)) else 0
+            (A1, b1), (A2, b2) = polys[pa[t]], polys[pb[t]]
+            flags[t] = 1 if polytopes_overlap(np.asarray(A1, float), np.asarray(b1, float), np.asarray(A2, float), np.asarray(b2, float)) else 0
     if stats is not None:
-        stats.update(bounds_opened=int(fail_lo.sum() + fail_hi.sum()), overlaps_redone_on_host=int(len(redo)),
-                     candidate_pairs=int(len(pa)))
+        stats.update(bounds_opened=int((np.asarray(st_b) < 0).sum()), overlaps_redone_on_host=int(len(redo)), candidate_pairs=int(len(pa)))
     tail, head = edge_arrays(pa, pb, flags)
-    edges = [(vertices[t], vertices[h]) for t, h in zip(tail, head)]
-    return (vertices, edges) + _incidence_lists(vertices, edges) + (cen,)
+    return tail, head, cen
 
 
-def _incidence_lists(vertices, edges):
+def build_graph_device(As: Dict[Hashable, np.ndarray], bs: Dict[Hashable, np.ndarray], device: int = 0, tol: float = 1e-9,
+                       scene=None, stats: dict | None = None, broad_phase: str = "host"):
+    """``build_graph_arrays_device`` by region key.  Returns ``(vertices, edges, I_v_in, I_v_out, centres)``; ``edges`` are key pairs in
+    the reference's double-loop order.  ``scene``, ``stats``, ``broad_phase``: as there (``scene`` is a PolytopeScene for ``"host"``, a
+    DeviceScene for ``"device"``); an error message names the regions by key."""
+    vertices = list(As.keys())
+    tail, head, cen = build_graph_arrays_device([(As[v], bs[v]) for v in vertices], device, tol, scene, stats, names=vertices, broad_phase=broad_phase)
+    edges = [(vertices[t], vertices[h]) for t, h in zip(tail.tolist(), head.tolist())]
     I_v_in = {v: [] for v in vertices}
     I_v_out = {v: [] for v in vertices}
     for e in edges:
         I_v_out[e[0]].append(e)
         I_v_in[e[1]].append(e)
-    return I_v_in, I_v_out
+    return vertices, edges, I_v_in, I_v_out, cen
 
 
 def graph_from_sets_device(As, bs, n, device: int = 0, broad_phase: str = "host") -> GcsGraph:
-    """``graph_from_sets`` with edges and interior points from the device LPs.  ``broad_phase="device"``: on a resident scene, the
-    edge arrays go straight into the CSR (no edge list of key pairs in between)."""
+    """``graph_from_sets`` with edges and interior points from the device LPs: the edge arrays go straight into the CSR."""
     keys = list(As.keys())
     if 's' not in As or 't' not in As:
         raise KeyError("case must define vertices 's' and 't'")
-    index = {k: i for i, k in enumerate(keys)}
-    if broad_phase == "device":
-        polys = [(np.asarray(As[k], float), np.asarray(bs[k], float)) for k in keys]
-        tail, head, cen = build_graph_arrays_device(polys, device)
-        return _finish_graph(int(n), keys, tail, head, polys, cen, index['s'], index['t'])
-    if broad_phase != "host":
-        raise ValueError(f"broad_phase must be 'host' or 'device', not {broad_phase!r}")
-    _, edges, _, _, cen = build_graph_device(As, bs, device)
-    tail = [index[u] for u, _ in edges]
-    head = [index[w] for _, w in edges]
     polys = [(np.asarray(As[k], float), np.asarray(bs[k], float)) for k in keys]
-    return _finish_graph(int(n), keys, tail, head, polys, cen, index['s'], index['t'])
+    tail, head, cen = build_graph_arrays_device(polys, device, names=keys, broad_phase=broad_phase)
+    return _finish_graph(int(n), keys, tail, head, polys, cen, keys.index('s'), keys.index('t'))

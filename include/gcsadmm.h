@@ -154,7 +154,7 @@ typedef struct gcsadmm_handle_s *gcsadmm_handle;
 
 gcsadmm_status gcsadmm_create(const gcsadmm_graph_desc *desc, gcsadmm_handle *out);
 void gcsadmm_destroy(gcsadmm_handle h);
-const char *gcsadmm_last_error(gcsadmm_handle h);   /* h may be NULL: error of the last failed create */
+const char *gcsadmm_last_error(gcsadmm_handle h);   /* h may be NULL: error of the calling thread's last failed create */
 
 /* (Re)start the loop: control block := {rho, mu_scale 1, it 1, RUNNING}.  Does not touch the state. */
 gcsadmm_status gcsadmm_reset(gcsadmm_handle h, const gcsadmm_params *p, void *stream);
@@ -283,7 +283,7 @@ gcsadmm_status gcsadmm_halo_buffers(gcsadmm_handle h, void **send_buf, void **re
  * check_overlap); these entry points run the same decisions as batches of tiny LPs on the device, one LP
  * per lane (polytope_lp.hip).  All pointers are HOST pointers (set-up code, called once per scene); the
  * polytope CSR is the one of gcsadmm_graph_desc (rows of region p: poly_ptr[p] .. poly_ptr[p+1]).
- * n = 1..8.  Return value: gcsadmm_status; text of the last failure: gcsadmm_polytope_last_error().
+ * n = 1..8.  Return value: gcsadmm_status; text of the calling thread's last failure: gcsadmm_polytope_last_error().
  * Optional `status` arrays receive the LP status per problem: 0 converged, 1 / 2 decided early
  * (overlap / separation proven), -1 iteration limit.
  */
@@ -313,7 +313,7 @@ int gcsadmm_polytope_overlaps(int n, int num_polytopes, const int *poly_ptr, con
  * gcs_admm_amd.scene.candidate_pairs, element for element).  The call order is centers, bounds (or set_boxes), candidate_pairs,
  * overlaps, read_pairs; a call whose input is not resident yet returns GCSADMM_ERR_BAD_ARG.  All pointers are HOST pointers; every
  * output pointer may be NULL.  Every call works on the scene's device and hands the caller's current device back; calls on one
- * scene are not re-entrant.  Text of the last failure: gcsadmm_polytope_last_error().
+ * scene are not re-entrant.  Text of the calling thread's last failure: gcsadmm_polytope_last_error().
  */
 typedef struct gcsadmm_scene_s *gcsadmm_scene;
 

@@ -164,6 +164,27 @@ def test_device_non_finite_start_is_not_an_overlap(lp_emu, host, n):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("n", [1, 2, 3, 8])
+def test_device_batch_bounds_report_a_failed_side_and_open_nothing(n):
+    """gcsadmm_polytope_bounds reports what the LPs left: started from a finite point outside polytope 3, every side of that polytope
+    comes back with status -1 and lo == hi == the start coordinate (opening such a side is build_graph_arrays_device's job; the
+    resident scene's bounds call opens it on the device), and every other side is bit for bit that of a call with the good centres"""
+    fam = L.touching(n)
+    sc = _scene(fam.polys)
+    cen = sc.centers()[0]
+    lo0, hi0, st0 = sc.bounds(cen)
+    bad = np.array(cen, copy=True)
+    bad[3] += 5.0
+    lo, hi, st = sc.bounds(bad)
+    print(n, st[3].tolist(), lo[3].tolist(), hi[3].tolist(), bad[3].tolist())
+    assert st.shape == (len(fam.polys), 2 * n) and np.all(st[3] == -1)
+    assert np.array_equal(lo[3], bad[3]) and np.array_equal(hi[3], bad[3])
+    rest = np.arange(len(fam.polys)) != 3
+    assert np.all(st[rest] == 0) and np.all(st0 == 0)
+    assert np.array_equal(lo[rest], lo0[rest]) and np.array_equal(hi[rest], hi0[rest])
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("n", [1, 3, 5, 8])
 def test_device_pipeline_on_mixed_rows(n):
     """centres -> boxes -> sweep -> pair LPs on 40 regions of the mixed_rows family: the edge list is the brute-force ordered double

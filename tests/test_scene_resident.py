@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import sweep_cases as S
+from scene_fakes import FakeScene, four_boxes as _four_boxes
 from gcs_admm_amd import scene as sc
 
 
@@ -84,16 +85,8 @@ def test_scan_reports_a_total_beyond_int32_without_overflow(emu):
 
 
 # ------------------------------------------------------------------------------------------- the array pipeline on a stand-in scene
-def _four_boxes():
-    A = np.vstack([np.eye(2), -np.eye(2)])
-    As = {k: A for k in range(4)}
-    bs = {0: np.array([1.0, 1.0, 0.0, 0.0]), 1: np.array([2.0, 1.0, -0.9, 0.0]),      # 0-1 overlap, 1-2 overlap, 3 apart
-          2: np.array([3.0, 1.0, -1.9, 0.0]), 3: np.array([9.0, 9.0, -8.0, -8.0])}
-    return As, bs
-
-
 class FakeDeviceScene:
-    """the interface of scene.DeviceScene with the failures of tests/test_graph.py's FakeScene: a centre LP, one side of a box, every
+    """the interface of scene.DeviceScene with the failures of scene_fakes.FakeScene: a centre LP, one side of a box, every
     overlap LP (with the wrong flag)"""
 
     def __init__(self, mode):
@@ -149,6 +142,12 @@ def test_array_pipeline_acts_on_lp_status(mode):
     assert stats["bounds_opened"] == (1 if mode == "bounds" else 0)
     assert stats["overlaps_redone_on_host"] == (stats["candidate_pairs"] if mode == "overlap" else 0)
     assert stats["candidate_pairs"] == 2                      # 0-1 and 1-2; the opened side of region 1 reaches region 3 in x only
+    # the same entry point in host mode, on the stand-in for a PolytopeScene: the same edges and the same three counts
+    host_stats = {}
+    tail_h, head_h, cen_h = sc.build_graph_arrays_device(polys, scene=FakeScene(mode), stats=host_stats, broad_phase="host")
+    assert tail_h.dtype == head_h.dtype == np.int32
+    assert np.array_equal(tail_h, tail) and np.array_equal(head_h, head) and np.array_equal(cen_h, cen)
+    assert host_stats == stats
     # the keyed front end on the same scene: the reference's lists
     _, E, I_in, I_out, _ = sc.build_graph_device(As, bs, scene=FakeDeviceScene(mode), broad_phase="device")
     assert E == E_ref and I_in == I_in_ref and I_out == I_out_ref
@@ -161,6 +160,11 @@ def test_array_pipeline_refuses_a_failed_centre():
         sc.build_graph_device(As, bs, scene=FakeDeviceScene("center"), broad_phase="device")
     with pytest.raises(sc.GcsAdmmError, match=r"centre LP did not converge for regions \[2\]"):
         sc.build_graph_arrays_device([(As[v], bs[v]) for v in As], scene=FakeDeviceScene("center"))
+    # host mode says the same, by key and by index
+    with pytest.raises(sc.GcsAdmmError, match=r"centre LP did not converge for regions \['r2'\] \(of 1\)"):
+        sc.build_graph_arrays_device([(As[v], bs[v]) for v in As], scene=FakeScene("center"), names=list(As), broad_phase="host")
+    with pytest.raises(sc.GcsAdmmError, match=r"centre LP did not converge for regions \[2\] \(of 1\)"):
+        sc.build_graph_arrays_device([(As[v], bs[v]) for v in As], scene=FakeScene("center"), broad_phase="host")
 
 
 def test_broad_phase_default_is_the_host_sweep():

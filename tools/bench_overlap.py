@@ -3,7 +3,7 @@
 restatement (oracle/polytope_oracle.py: one HiGHS LP per pair, as the reference does with MOSEK) on a bounded
 sample.  One JSON line per dimension.  Beside the host sweep (``host_sweep_s``) it times the device broad phase of the resident
 scene (``device_sweep_s``) and the whole pipeline both ways on the same scene (``resident_pipeline_s`` against ``host_pipeline_s``:
-scene.build_graph_arrays_device against the four steps through the host, alternated, median of five), and says whether the two pair
+scene.build_graph_arrays_device with broad_phase="device" against broad_phase="host", alternated, median of five), and says whether the two pair
 lists are equal (``pairs_equal_host``).
 
   python tools/bench_overlap.py [--regions 20000] [--cpu-pairs 300]
@@ -12,7 +12,7 @@ import argparse, json, os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: F401  (HIP runtime first, see solver.load_library)
-from gcs_admm_amd.scene import DeviceScene, PolytopeScene, edge_arrays, build_graph_arrays_device, candidate_pairs
+from gcs_admm_amd.scene import DeviceScene, PolytopeScene, build_graph_arrays_device, candidate_pairs
 from oracle import polytope_oracle as PO
 
 
@@ -28,23 +28,11 @@ def scene_polys(rng, n, P, m_extra):
     return polys
 
 
-def host_pipeline(polys, tol=1e-9):
-    """the four steps of build_graph_device (upload and LPs, boxes back, numpy sweep, pairs up, flags back) to the same edge arrays"""
-    scene = PolytopeScene(polys)
-    cen, _, _ = scene.centers()
-    lo, hi, st_b = scene.bounds(cen)
-    st_b = np.asarray(st_b).reshape(len(polys), -1, 2)
-    lo = np.where(st_b[:, :, 0] < 0, -np.inf, lo); hi = np.where(st_b[:, :, 1] < 0, np.inf, hi)
-    pa, pb = candidate_pairs(lo, hi)
-    flags, _ = scene.overlaps(pa, pb, tol, cen)
-    return edge_arrays(pa, pb, flags)
-
-
 def pipelines(polys, repeats=5):
     """median wall time of the two pipelines, alternated (both end in a copy from the device, which synchronises)"""
     t_host, t_res = [], []
     for _ in range(repeats):
-        t0 = time.perf_counter(); th, hh = host_pipeline(polys); t_host.append(time.perf_counter() - t0)
+        t0 = time.perf_counter(); th, hh, _ = build_graph_arrays_device(polys, broad_phase="host"); t_host.append(time.perf_counter() - t0)
         t0 = time.perf_counter(); tr, hr, _ = build_graph_arrays_device(polys); t_res.append(time.perf_counter() - t0)
         if not (np.array_equal(th, tr) and np.array_equal(hh, hr)):
             raise SystemExit("the resident pipeline and the host pipeline disagree on the edges")
