@@ -32,45 +32,17 @@ from typing import Dict, Hashable, Sequence, Tuple
 
 import numpy as np
 
+from . import abi
+from .abi import GcsAdmmError
 from .graph import GcsGraph, _finish_graph
-from .solver import GcsAdmmError, load_library
 
 __all__ = ["PolytopeScene", "DeviceScene", "build_graph_device", "build_graph_arrays_device", "edge_arrays", "graph_from_sets_device"]
 
-_i, _d, _p = C.c_int, C.c_double, C.c_void_p
-# the graph-construction entry points of include/gcsadmm.h: (argument types, result type); arrays go in as addresses
-_PROTOTYPES = {
-    "gcsadmm_polytope_last_error": ([], C.c_char_p),
-    "gcsadmm_polytope_centers": ([_i, _i, _p, _p, _p, _i, _p, _p, _p], _i),
-    "gcsadmm_polytope_bounds": ([_i, _i, _p, _p, _p, _p, _i, _p, _p, _p], _i),
-    "gcsadmm_polytope_overlaps": ([_i, _i, _p, _p, _p, _p, C.c_long, _p, _p, _d, _i, _p, _p], _i),
-    "gcsadmm_scene_create": ([_i, _i, _p, _p, _p, _i, _p], _i),
-    "gcsadmm_scene_destroy": ([_p], None),
-    "gcsadmm_scene_centers": ([_p] * 4, _i),
-    "gcsadmm_scene_bounds": ([_p] * 4, _i),
-    "gcsadmm_scene_set_boxes": ([_p] * 3, _i),
-    "gcsadmm_scene_candidate_pairs": ([_p, _d, _p], _i),
-    "gcsadmm_scene_overlaps": ([_p, _d, _p, _p], _i),
-    "gcsadmm_scene_read_pairs": ([_p] * 5, _i),
-}
-_lib = None
 
-
-def _library():
-    """the HIP library, with the prototypes above declared when it is first loaded"""
-    global _lib
-    if _lib is None:
-        lib = load_library()
-        for name, (argtypes, restype) in _PROTOTYPES.items():
-            f = getattr(lib, name)
-            f.argtypes, f.restype = argtypes, restype
-        _lib = lib
-    return _lib
-
-
-def _check(lib, rc, what):
-    if rc != 0:
-        raise GcsAdmmError(f"{what}: {lib.gcsadmm_polytope_last_error().decode()} (status {rc})")
+def _call(lib, name, *args):
+    """the one call into the library (prototypes: abi.PROTOTYPES; arrays go in as addresses); a status other than 0 raises GcsAdmmError"""
+    rc = getattr(lib, name)(*args)
+    abi.check(rc, lambda: f"{name}: {lib.gcsadmm_polytope_last_error().decode()} (status {rc})")
 
 
 class PolytopeScene:
@@ -84,7 +56,7 @@ class PolytopeScene:
         self.A = np.ascontiguousarray(np.vstack([np.asarray(A, float).reshape(-1, self.n) for A, _ in polys]))
         self.b = np.ascontiguousarray(np.hstack([np.asarray(b, float).ravel() for _, b in polys]))
         self.device = int(device)
-        self.lib = _library()
+        self.lib = abi.load_library()
         self._centers = None
 
     def _csr(self):
@@ -93,8 +65,7 @@ class PolytopeScene:
     def centers(self):
         """(centres [P, n], radii [P], LP status [P])."""
         cen = np.empty((self.P, self.n)); rad = np.empty(self.P); st = np.empty(self.P, np.int32)
-        rc = self.lib.gcsadmm_polytope_centers(*self._csr(), self.device, cen.ctypes.data, rad.ctypes.data, st.ctypes.data)
-        _check(self.lib, rc, "gcsadmm_polytope_centers")
+        _call(self.lib, "gcsadmm_polytope_centers", *self._csr(), self.device, cen.ctypes.data, rad.ctypes.data, st.ctypes.data)
         self._centers = cen
         return cen, rad, st
 
@@ -103,8 +74,7 @@ class PolytopeScene:
         LPs start there): a side started from a point that is outside, or not finite, reports status -1."""
         cen = np.ascontiguousarray(centers if centers is not None else (self._centers if self._centers is not None else self.centers()[0]))
         lo = np.empty((self.P, self.n)); hi = np.empty((self.P, self.n)); st = np.empty((self.P, 2 * self.n), np.int32)
-        rc = self.lib.gcsadmm_polytope_bounds(*self._csr(), cen.ctypes.data, self.device, lo.ctypes.data, hi.ctypes.data, st.ctypes.data)
-        _check(self.lib, rc, "gcsadmm_polytope_bounds")
+        _call(self.lib, "gcsadmm_polytope_bounds", *self._csr(), cen.ctypes.data, self.device, lo.ctypes.data, hi.ctypes.data, st.ctypes.data)
         return lo, hi, st
 
     def overlaps(self, pair_a, pair_b, tol: float = 1e-9, centers=None):
@@ -119,9 +89,8 @@ class PolytopeScene:
         out = np.zeros(len(pa), np.uint8); st = np.zeros(len(pa), np.int32)
         cen = centers if centers is not None else self._centers
         cen = np.ascontiguousarray(cen) if cen is not None else None
-        rc = self.lib.gcsadmm_polytope_overlaps(*self._csr(), cen.ctypes.data if cen is not None else None, len(pa), pa.ctypes.data,
-                                                pb.ctypes.data, tol, self.device, out.ctypes.data, st.ctypes.data)
-        _check(self.lib, rc, "gcsadmm_polytope_overlaps")
+        _call(self.lib, "gcsadmm_polytope_overlaps", *self._csr(), cen.ctypes.data if cen is not None else None, len(pa), pa.ctypes.data,
+              pb.ctypes.data, tol, self.device, out.ctypes.data, st.ctypes.data)
         return out, st
 
 
@@ -163,19 +132,16 @@ class DeviceScene:
         self.num_pairs = 0
         self._decided = False
         self._h = C.c_void_p()
-        self._check(self.lib.gcsadmm_scene_create(*host._csr(), self.device, C.byref(self._h)), "gcsadmm_scene_create")
+        _call(self.lib, "gcsadmm_scene_create", *host._csr(), self.device, C.byref(self._h))
 
-    def _check(self, rc, what):
-        _check(self.lib, rc, what)
-
-    def _handle(self):
+    def _call(self, name, *args):
         if not self._h:
             raise GcsAdmmError("the scene is closed")
-        return self._h
+        _call(self.lib, name, self._h, *args)
 
     def close(self):
         if self._h:
-            self.lib.gcsadmm_scene_destroy(self._h)
+            self._call("gcsadmm_scene_destroy")
             self._h = C.c_void_p()
 
     def __enter__(self):
@@ -193,14 +159,14 @@ class DeviceScene:
     def centers(self):
         """(centres [P, n], radii [P], LP status [P]); the centres stay on the device for ``bounds`` and ``overlaps``."""
         cen = np.empty((self.P, self.n)); rad = np.empty(self.P); st = np.empty(self.P, np.int32)
-        self._check(self.lib.gcsadmm_scene_centers(self._handle(), cen.ctypes.data, rad.ctypes.data, st.ctypes.data), "gcsadmm_scene_centers")
+        self._call("gcsadmm_scene_centers", cen.ctypes.data, rad.ctypes.data, st.ctypes.data)
         return cen, rad, st
 
     def bounds(self):
         """(lo [P, n], hi [P, n], LP status [P, 2n]) from the resident centres.  A side whose LP reports status < 0 comes back, and
         stays on the device, opened to -inf / +inf (the rule of ``build_graph_arrays_device``)."""
         lo = np.empty((self.P, self.n)); hi = np.empty((self.P, self.n)); st = np.empty((self.P, 2 * self.n), np.int32)
-        self._check(self.lib.gcsadmm_scene_bounds(self._handle(), lo.ctypes.data, hi.ctypes.data, st.ctypes.data), "gcsadmm_scene_bounds")
+        self._call("gcsadmm_scene_bounds", lo.ctypes.data, hi.ctypes.data, st.ctypes.data)
         self._decided = False
         return lo, hi, st
 
@@ -209,7 +175,7 @@ class DeviceScene:
         lo = np.ascontiguousarray(lo, float); hi = np.ascontiguousarray(hi, float)
         if lo.shape != (self.P, self.n) or hi.shape != (self.P, self.n):
             raise ValueError(f"boxes must be [{self.P}, {self.n}]")
-        self._check(self.lib.gcsadmm_scene_set_boxes(self._handle(), lo.ctypes.data, hi.ctypes.data), "gcsadmm_scene_set_boxes")
+        self._call("gcsadmm_scene_set_boxes", lo.ctypes.data, hi.ctypes.data)
         self._decided = False
 
     def candidate_pairs(self, pad: float = SWEEP_PAD) -> int:
@@ -217,7 +183,7 @@ class DeviceScene:
         on the resident boxes, element for element.  Returns after the device has finished."""
         num = C.c_int64(0)
         self._decided = False
-        self._check(self.lib.gcsadmm_scene_candidate_pairs(self._handle(), float(pad), C.addressof(num)), "gcsadmm_scene_candidate_pairs")
+        self._call("gcsadmm_scene_candidate_pairs", float(pad), C.addressof(num))
         self.num_pairs = int(num.value)
         return self.num_pairs
 
@@ -225,7 +191,7 @@ class DeviceScene:
         """Narrow phase on the resident pairs, each LP started at the resident centre of its first region: (pairs that overlap, pairs
         whose LP reports status < 0 -- their flag is not a decision)."""
         over = C.c_int64(0); und = C.c_int64(0)
-        self._check(self.lib.gcsadmm_scene_overlaps(self._handle(), float(tol), C.addressof(over), C.addressof(und)), "gcsadmm_scene_overlaps")
+        self._call("gcsadmm_scene_overlaps", float(tol), C.addressof(over), C.addressof(und))
         self._decided = True
         return int(over.value), int(und.value)
 
@@ -235,8 +201,8 @@ class DeviceScene:
         pa = np.empty(T, np.int32); pb = np.empty(T, np.int32)
         flags = np.empty(T, np.uint8) if self._decided else None
         st = np.empty(T, np.int32) if self._decided else None
-        self._check(self.lib.gcsadmm_scene_read_pairs(self._handle(), pa.ctypes.data, pb.ctypes.data, flags.ctypes.data if self._decided else None,
-                                                      st.ctypes.data if self._decided else None), "gcsadmm_scene_read_pairs")
+        self._call("gcsadmm_scene_read_pairs", pa.ctypes.data, pb.ctypes.data, flags.ctypes.data if self._decided else None,
+                   st.ctypes.data if self._decided else None)
         return pa, pb, flags, st
 
 

@@ -1,6 +1,5 @@
-"""Host side of the MI355X ADMM loop: thin ctypes binding of the C ABI
-(include/gcsadmm.h, built from gcs_admm_amd/csrc by ``build.py``) plus the
-driver that mirrors the reference's main loop (admm_solver_v3.py:621-733).
+"""Host side of the MI355X ADMM loop: the driver that mirrors the reference's main loop (admm_solver_v3.py:621-733) over the C ABI
+(include/gcsadmm.h, built from gcs_admm_amd/csrc by ``build.py``; its Python binding is gcs_admm_amd/abi.py).
 
 Device buffers are PyTorch-ROCm tensors; the library only ever sees their
 ``data_ptr()`` and the current HIP stream.  There is NO fallback: if the HIP
@@ -8,63 +7,22 @@ library is missing or no GPU is visible this module raises.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
-import os
+import time
 from typing import Optional
 
 import numpy as np
 
+from . import abi
+from .abi import (CONVERGED, DIVERGED, EXPORTS, F32, F64, LIB_PATH, MAX_IT, RUNNING, STATUS_NAME,  # noqa: F401  (re-exported)
+                  ControlBlock, GcsAdmmError, GraphDesc, HaloDesc, Params, State)
 from .graph import GcsGraph
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(_HERE, "libgcsadmm.so")
 
-F64, F32 = 0, 1
-RUNNING, CONVERGED, MAX_IT, DIVERGED = -1, 0, 1, 2
-STATUS_NAME = {RUNNING: "running", CONVERGED: "converged", MAX_IT: "max_it", DIVERGED: "diverged"}
-
-EXPORTS = ["gcsadmm_create", "gcsadmm_destroy", "gcsadmm_last_error", "gcsadmm_reset", "gcsadmm_vertex_step",
-           "gcsadmm_edge_step", "gcsadmm_control", "gcsadmm_run", "gcsadmm_run_timed", "gcsadmm_read_control",
-           "gcsadmm_cost", "gcsadmm_query", "gcsadmm_query_workspace", "gcsadmm_unit_iterations", "gcsadmm_vertex_prox",
-           # vertex partitions across GPUs (RCCL)
-           "gcsadmm_comm_unique_id", "gcsadmm_check_halo", "gcsadmm_attach_comm", "gcsadmm_run_partitioned", "gcsadmm_halo_pack", "gcsadmm_halo_unpack",
-           "gcsadmm_halo_exchange", "gcsadmm_halo_buffers", "gcsadmm_run_partitioned_timed", "gcsadmm_comm_count", "gcsadmm_set_overlap",
-           # graph construction at scale (gcs_admm_amd/scene.py)
-           "gcsadmm_polytope_last_error", "gcsadmm_polytope_centers", "gcsadmm_polytope_bounds", "gcsadmm_polytope_overlaps",
-           # the same pipeline on a resident scene with a device broad phase (scene.DeviceScene)
-           "gcsadmm_scene_create", "gcsadmm_scene_destroy", "gcsadmm_scene_centers", "gcsadmm_scene_bounds", "gcsadmm_scene_set_boxes",
-           "gcsadmm_scene_candidate_pairs", "gcsadmm_scene_overlaps", "gcsadmm_scene_read_pairs"]
-
-
-class GraphDesc(C.Structure):
-    _fields_ = [("n", C.c_int32), ("num_vertices", C.c_int32), ("num_edges", C.c_int32), ("num_incidences", C.c_int32),
-                ("inc_ptr", C.c_void_p), ("inc_edge", C.c_void_p), ("inc_out", C.c_void_p),
-                ("edge_inc_tail", C.c_void_p), ("edge_inc_head", C.c_void_p),
-                ("poly_ptr", C.c_void_p), ("poly_A", C.c_void_p), ("poly_b", C.c_void_p), ("center", C.c_void_p),
-                ("src", C.c_int32), ("dst", C.c_int32), ("state_dtype", C.c_int32), ("device", C.c_int32),
-                ("inc_counted", C.c_void_p), ("edge_counted", C.c_void_p),
-                ("nx_global", C.c_double), ("nmu_global", C.c_double),
-                # schedule of the vertex step (0 = automatic): see include/gcsadmm.h
-                ("vertex_program", C.c_int32), ("wave_slots", C.c_int32), ("wave_align", C.c_int32),
-                ("wave_store_dl", C.c_int32), ("wave_generic_rows", C.c_int32), ("edge_major_columns", C.c_int32),
-                # vertex sub-problems larger than LDS: 0 refused, 1 split form where needed, 2 split form everywhere
-                ("vertex_workspace", C.c_int32)]
-
-
-class Params(C.Structure):
-    _fields_ = [("rho", C.c_double), ("tau_incr", C.c_double), ("tau_decr", C.c_double), ("nu", C.c_double),
-                ("it_rho_limit", C.c_int32), ("max_it", C.c_int32), ("eps_abs", C.c_double), ("eps_rel", C.c_double),
-                ("eps_edge", C.c_double), ("ipm_tol", C.c_double), ("ipm_max_iter", C.c_int32), ("cold_start", C.c_int32)]
-
-
-class State(C.Structure):
-    _fields_ = [("copy", C.c_void_p), ("mu", C.c_void_p), ("zedge", C.c_void_p),
-                ("xv", C.c_void_p), ("zv", C.c_void_p), ("yv", C.c_void_p)]
-
-
-class HaloDesc(C.Structure):
-    _fields_ = [("num_peers", C.c_int32), ("peer_rank", C.c_void_p), ("send_ptr", C.c_void_p), ("send_cols", C.c_void_p),
-                ("recv_ptr", C.c_void_p), ("recv_cols", C.c_void_p)]
+def load_library() -> C.CDLL:
+    """abi.load_library at this module's LIB_PATH (diagnostic tools point it at a variant build before they make a solver)"""
+    return abi.load_library(LIB_PATH)
 
 
 def halo_arrays(send_idx, recv_idx):
@@ -80,43 +38,6 @@ def halo_arrays(send_idx, recv_idx):
     ptr = np.zeros(len(peers) + 1, np.int32); ptr[1:] = np.cumsum(cnt)
     cat = lambda d: (np.concatenate([np.asarray(d[r], np.int32) for r in peers]) if peers else np.zeros(0, np.int32))
     return np.asarray(peers, np.int32), ptr, np.ascontiguousarray(cat(send_idx)), np.ascontiguousarray(cat(recv_idx))
-
-
-class ControlBlock(C.Structure):
-    _fields_ = [("rho", C.c_double), ("mu_scale", C.c_double), ("sums", C.c_double * 5),
-                ("pri", C.c_double), ("dual", C.c_double), ("eps_pri", C.c_double), ("eps_dual", C.c_double),
-                ("it", C.c_int32), ("status", C.c_int32), ("inner_failures", C.c_int32), ("inner_iters", C.c_int32)]
-
-
-_lib = None
-
-
-def load_library() -> C.CDLL:
-    """dlopen the in-tree HIP library; fail loudly if it has not been built."""
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise RuntimeError(f"{LIB_PATH} is missing: run `python -m gcs_admm_amd.build` (hipcc, gfx950). "
-                               "There is no CPU fallback.")
-        # PyTorch-ROCm ships its own HIP runtime (same SONAME as /opt/rocm's): it must be the one already
-        # loaded when libgcsadmm.so resolves libamdhip64, or the process ends up with two runtimes and
-        # the tensors' device pointers mean nothing to the library.
-        import torch  # noqa: F401
-        lib = C.CDLL(LIB_PATH)
-        lib.gcsadmm_last_error.restype = C.c_char_p
-        lib.gcsadmm_last_error.argtypes = [C.c_void_p]
-        lib.gcsadmm_destroy.restype = None
-        lib.gcsadmm_destroy.argtypes = [C.c_void_p]
-        _lib = lib
-    return _lib
-
-
-class GcsAdmmError(RuntimeError):
-    pass
-
-
-def _np_ptr(a):
-    return a.ctypes.data_as(C.c_void_p)
 
 
 class DeviceSolver:
@@ -148,49 +69,19 @@ class DeviceSolver:
             raise RuntimeError("no HIP device visible: the ADMM loop only runs on the GPU (no CPU fallback)")
         self.torch = torch
         self.lib = load_library()
-        self.g = graph
+        self.g = g = graph
         self.device_index = torch.cuda.current_device() if device is None else int(device)
         self.device = torch.device("cuda", self.device_index)
         self.dtype_code = {"f64": F64, "f32": F32}[state_dtype]
         self.tdtype = torch.float64 if state_dtype == "f64" else torch.float32
-        g = graph
-        ni_owned = int(g.inc_ptr[-1])
-        self.NI = int(num_incidences) if num_incidences is not None else ni_owned
-        if columns not in ("incidence", "edge"):
-            raise ValueError("columns must be 'incidence' or 'edge'")
-        self.edge_major = columns == "edge"
-        tail, head = g.edge_inc_tail.astype(np.int32), g.edge_inc_head.astype(np.int32)
-        self.col_of = np.arange(self.NI, dtype=np.int64)          # incidence column -> state column
-        if self.edge_major:
-            E_ = g.num_edges
-            if self.NI != 2 * E_:
-                raise ValueError("edge-major columns need exactly two columns per edge")
-            self.col_of = np.empty(self.NI, dtype=np.int64)
-            self.col_of[tail] = np.arange(E_); self.col_of[head] = E_ + np.arange(E_)
-            tail, head = np.arange(E_, dtype=np.int32), (E_ + np.arange(E_)).astype(np.int32)
-            if inc_counted is not None:
-                ic_new = np.empty(self.NI, dtype=np.uint8)
-                ic_new[self.col_of] = np.asarray(inc_counted, dtype=np.uint8)
-                inc_counted = ic_new
-        self._keep = [np.ascontiguousarray(a) for a in (
-            g.inc_ptr.astype(np.int32), g.inc_edge.astype(np.int32), g.inc_out.astype(np.int32),
-            tail, head, g.poly_ptr.astype(np.int32),
-            g.poly_A.astype(np.float64), g.poly_b.astype(np.float64), g.interior.astype(np.float64))]
-        k = self._keep
-        ic = np.ascontiguousarray(inc_counted, dtype=np.uint8) if inc_counted is not None else None
-        ec = np.ascontiguousarray(edge_counted, dtype=np.uint8) if edge_counted is not None else None
-        self._keep += [ic, ec]
-        desc = GraphDesc(g.n, g.num_vertices, g.num_edges, self.NI, _np_ptr(k[0]), _np_ptr(k[1]), _np_ptr(k[2]),
-                         _np_ptr(k[3]), _np_ptr(k[4]), _np_ptr(k[5]), _np_ptr(k[6]), _np_ptr(k[7]), _np_ptr(k[8]),
-                         g.src, g.dst, self.dtype_code, self.device_index,
-                         _np_ptr(ic) if ic is not None else None, _np_ptr(ec) if ec is not None else None,
-                         float(nx_global), float(nmu_global),
-                         {"auto": 0, "wavefront": 1, "workgroup": 2, "workgroup256": 3}[program], int(wave_slots), int(wave_align),
-                         int(wave_store_dl), int(wave_generic_rows), int(self.edge_major), int(vertex_workspace))
+        desc, self._keep, self.col_of = abi.graph_desc(
+            g, state_dtype=self.dtype_code, device=self.device_index, num_incidences=num_incidences, inc_counted=inc_counted,
+            edge_counted=edge_counted, nx_global=nx_global, nmu_global=nmu_global, columns=columns,
+            vertex_program={"auto": 0, "wavefront": 1, "workgroup": 2, "workgroup256": 3}[program], wave_slots=wave_slots,
+            wave_align=wave_align, wave_store_dl=wave_store_dl, wave_generic_rows=wave_generic_rows, vertex_workspace=vertex_workspace)
+        self.NI, self.edge_major = desc.num_incidences, columns == "edge"
         h = C.c_void_p()
-        st = self.lib.gcsadmm_create(C.byref(desc), C.byref(h))
-        if st != 0:
-            raise GcsAdmmError(f"gcsadmm_create failed ({st}): {self.lib.gcsadmm_last_error(None).decode()}")
+        self._call("gcsadmm_create", C.byref(desc), C.byref(h), handle=False, select=False)
         self.h = h
         c, E, V, n = g.c, g.num_edges, g.num_vertices, g.n
         z = lambda *s, dt=self.tdtype: torch.zeros(*s, dtype=dt, device=self.device)
@@ -205,16 +96,22 @@ class DeviceSolver:
         self.trace = None
 
     # ------------------------------------------------------------------
-    def _check(self, st, what):
-        if st != 0:
-            raise GcsAdmmError(f"{what} failed ({st}): {self.lib.gcsadmm_last_error(self.h).decode()}")
+    def _call(self, name, *args, handle=True, select=True):
+        """The one call into the library: ``name(self.h, *args)`` (``handle=False``: ``name(*args)``, and the error text is the calling
+        thread's); a status other than 0 raises GcsAdmmError.  ``select``: with the handle's device current -- the stream handed over is
+        torch's current stream OF THAT DEVICE, and a null stream handle is bound by HIP to whatever device is current.  The calls made
+        without it rely on the library working on the handle's device; a poll of the loop is 2 us shorter (profiles/abi_binding)."""
+        h = self.h if handle else None
+        with self.torch.cuda.device(self.device) if select else contextlib.nullcontext():
+            st = getattr(self.lib, name)(*((h,) if handle else ()), *args)
+        abi.check(st, lambda: f"{name} failed ({st}): {self.lib.gcsadmm_last_error(h).decode()}")
 
     def _stream(self):
-        return C.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
+        return self.torch.cuda.current_stream(self.device).cuda_stream
 
     def close(self):
         if getattr(self, "h", None):
-            self.lib.gcsadmm_destroy(self.h)
+            self._call("gcsadmm_destroy", select=False)
             self.h = None
 
     def __del__(self):
@@ -236,40 +133,28 @@ class DeviceSolver:
             for t in (self.copy, self.mu, self.zedge, self.xv, self.zv, self.yv):
                 t.zero_()
         self.trace = self.torch.zeros(max_it, 6, dtype=self.torch.float64, device=self.device)
-        with self.torch.cuda.device(self.device):
-            self._check(self.lib.gcsadmm_reset(self.h, C.byref(self.params), self._stream()), "gcsadmm_reset")
+        self._call("gcsadmm_reset", C.byref(self.params), self._stream())
 
-    # (every call is made with the handle's device current: the stream handed over is torch's current stream OF THAT DEVICE, and a
-    #  null stream handle is bound by HIP to whatever device is current)
     def vertex_step(self):
-        with self.torch.cuda.device(self.device):
-            self._check(self.lib.gcsadmm_vertex_step(self.h, C.byref(self.state), self._stream()), "gcsadmm_vertex_step")
+        self._call("gcsadmm_vertex_step", C.byref(self.state), self._stream())
 
     def edge_step(self):
-        with self.torch.cuda.device(self.device):
-            self._check(self.lib.gcsadmm_edge_step(self.h, C.byref(self.state), C.c_void_p(self.sums.data_ptr()),
-                                                   self._stream()), "gcsadmm_edge_step")
+        self._call("gcsadmm_edge_step", C.byref(self.state), self.sums.data_ptr(), self._stream())
         return self.sums
 
     def control(self, sums=None):
         s = self.sums if sums is None else sums
-        with self.torch.cuda.device(self.device):
-            self._check(self.lib.gcsadmm_control(self.h, C.c_void_p(s.data_ptr()), C.c_void_p(self.trace.data_ptr()),
-                                                 self._stream()), "gcsadmm_control")
+        self._call("gcsadmm_control", s.data_ptr(), self.trace.data_ptr(), self._stream())
 
     def enqueue(self, k: int):
         """k iterations back to back, no host synchronisation."""
-        with self.torch.cuda.device(self.device):
-            self._check(self.lib.gcsadmm_run(self.h, C.byref(self.state), int(k), C.c_void_p(self.trace.data_ptr()),
-                                             self._stream()), "gcsadmm_run")
+        self._call("gcsadmm_run", C.byref(self.state), int(k), self.trace.data_ptr(), self._stream())
 
     def enqueue_timed(self, k: int):
         vm, em = C.c_float(0), C.c_float(0)
         vl, el = C.c_int32(0), C.c_int32(0)
-        with self.torch.cuda.device(self.device):
-            self._check(self.lib.gcsadmm_run_timed(self.h, C.byref(self.state), int(k), C.c_void_p(self.trace.data_ptr()),
-                                                   self._stream(), C.byref(vm), C.byref(vl), C.byref(em), C.byref(el)),
-                        "gcsadmm_run_timed")
+        self._call("gcsadmm_run_timed", C.byref(self.state), int(k), self.trace.data_ptr(), self._stream(),
+                   C.byref(vm), C.byref(vl), C.byref(em), C.byref(el))
         return dict(vertex_ms=vm.value, vertex_launches=vl.value, edge_ms=em.value, edge_launches=el.value)
 
     def vertex_prox(self, q, c, ipm_tol: float = 1e-10, ipm_max_iter: int = 60):
@@ -283,18 +168,15 @@ class DeviceSolver:
         xv = torch.zeros(V, 2 * n, dtype=torch.float64, device=self.device); zv = torch.zeros_like(xv)
         yv = torch.zeros(V, dtype=torch.float64, device=self.device)
         fails = C.c_int32(0)
-        self._check(self.lib.gcsadmm_vertex_prox(self.h, C.c_void_p(qd.data_ptr()), C.c_void_p(cd.data_ptr()), C.c_void_p(xv.data_ptr()),
-                                                 C.c_void_p(zv.data_ptr()), C.c_void_p(yv.data_ptr()), C.c_double(ipm_tol),
-                                                 C.c_int32(ipm_max_iter), C.byref(fails), self._stream()), "gcsadmm_vertex_prox")
+        self._call("gcsadmm_vertex_prox", qd.data_ptr(), cd.data_ptr(), xv.data_ptr(), zv.data_ptr(), yv.data_ptr(),
+                   float(ipm_tol), int(ipm_max_iter), C.byref(fails), self._stream(), select=False)
         return xv, zv, yv, fails.value
 
     # ---- vertex partition across GPUs -------------------------------------------------
     def unique_id(self) -> bytes:
         """128 bytes naming a new RCCL communicator (rank 0 creates it, the host distributes it)"""
         buf = (C.c_ubyte * 128)()
-        st = self.lib.gcsadmm_comm_unique_id(buf)
-        if st != 0:
-            raise GcsAdmmError(f"gcsadmm_comm_unique_id failed ({st}): {self.lib.gcsadmm_last_error(None).decode()}")
+        self._call("gcsadmm_comm_unique_id", buf, handle=False, select=False)
         return bytes(buf)
 
     def _halo_desc(self, send_idx, recv_idx):
@@ -302,115 +184,112 @@ class DeviceSolver:
         if self.edge_major:      # the lists are written in incidence columns
             sc = np.ascontiguousarray(self.col_of[sc].astype(np.int32)); rc = np.ascontiguousarray(self.col_of[rc].astype(np.int32))
         self._halo_keep = (peers, ptr, sc, rc)
-        return HaloDesc(len(peers), _np_ptr(peers), _np_ptr(ptr), _np_ptr(sc), _np_ptr(ptr), _np_ptr(rc))
+        return HaloDesc(len(peers), peers.ctypes.data, ptr.ctypes.data, sc.ctypes.data, ptr.ctypes.data, rc.ctypes.data)
 
     def check_halo(self, rank: int, world: int, send_idx, recv_idx):
         """The local checks of ``attach_comm`` alone (no collective): call on every rank and agree on the outcome first."""
-        self._check(self.lib.gcsadmm_check_halo(self.h, int(rank), int(world), C.byref(self._halo_desc(send_idx, recv_idx))), "gcsadmm_check_halo")
+        self._call("gcsadmm_check_halo", int(rank), int(world), C.byref(self._halo_desc(send_idx, recv_idx)), select=False)
 
     def attach_comm(self, rank: int, world: int, unique_id, send_idx, recv_idx):
         """Join the communicator (collective) and upload this partition's halo lists.  ``unique_id`` None: no communicator (the
         host moves the packed halo itself; ``enqueue_partitioned`` then works for world 1 only, without an all-reduce)."""
-        hd = self._halo_desc(send_idx, recv_idx)
         idb = (C.c_ubyte * 128).from_buffer_copy(unique_id) if unique_id is not None else None
-        with self.torch.cuda.device(self.device):
-            self._check(self.lib.gcsadmm_attach_comm(self.h, int(rank), int(world), idb, C.byref(hd)), "gcsadmm_attach_comm")
+        self._call("gcsadmm_attach_comm", int(rank), int(world), idb, C.byref(self._halo_desc(send_idx, recv_idx)))
         self.has_comm = unique_id is not None
 
     def enqueue_partitioned(self, k: int):
         """k iterations of the partitioned loop back to back on the current stream (every rank enqueues the same k)"""
-        with self.torch.cuda.device(self.device):
-            self._check(self.lib.gcsadmm_run_partitioned(self.h, C.byref(self.state), int(k), C.c_void_p(self.trace.data_ptr()),
-                                                         self._stream()), "gcsadmm_run_partitioned")
+        self._call("gcsadmm_run_partitioned", C.byref(self.state), int(k), self.trace.data_ptr(), self._stream())
 
     def enqueue_partitioned_timed(self, k: int):
         """k iterations of the partitioned loop with every stage bracketed by HIP events (collective); device ms per stage"""
         v, hl, e, r = (C.c_float(0) for _ in range(4))
-        with self.torch.cuda.device(self.device):
-            self._check(self.lib.gcsadmm_run_partitioned_timed(self.h, C.byref(self.state), int(k), C.c_void_p(self.trace.data_ptr()),
-                                                               self._stream(), C.byref(v), C.byref(hl), C.byref(e), C.byref(r)),
-                        "gcsadmm_run_partitioned_timed")
+        self._call("gcsadmm_run_partitioned_timed", C.byref(self.state), int(k), self.trace.data_ptr(), self._stream(),
+                   C.byref(v), C.byref(hl), C.byref(e), C.byref(r))
         return dict(vertex_ms=v.value, halo_ms=hl.value, edge_ms=e.value, reduce_ms=r.value)
 
     def set_overlap(self, mode: int = 0) -> int:
         """Schedule of the partitioned loop (include/gcsadmm.h gcsadmm_set_overlap): 0 automatic (overlapped when the partition has
         neighbours), 1 overlapped even without neighbours (tests), 2 serial.  Returns the number of boundary wavefronts (0: serial)."""
         n = C.c_int32(0)
-        with self.torch.cuda.device(self.device):
-            self._check(self.lib.gcsadmm_set_overlap(self.h, int(mode), C.byref(n)), "gcsadmm_set_overlap")
+        self._call("gcsadmm_set_overlap", int(mode), C.byref(n))
         return n.value
 
     def comm_count(self) -> int:
         """ranks of the attached RCCL communicator as RCCL reports them (0: none attached)"""
         n = C.c_int32(0)
-        self._check(self.lib.gcsadmm_comm_count(self.h, C.byref(n)), "gcsadmm_comm_count")
+        self._call("gcsadmm_comm_count", C.byref(n), select=False)
         return n.value
 
     def halo_pack(self):
-        self._check(self.lib.gcsadmm_halo_pack(self.h, C.byref(self.state), self._stream()), "gcsadmm_halo_pack")
+        self._call("gcsadmm_halo_pack", C.byref(self.state), self._stream(), select=False)
 
     def halo_unpack(self):
-        self._check(self.lib.gcsadmm_halo_unpack(self.h, C.byref(self.state), self._stream()), "gcsadmm_halo_unpack")
+        self._call("gcsadmm_halo_unpack", C.byref(self.state), self._stream(), select=False)
 
     def halo_exchange(self):
-        self._check(self.lib.gcsadmm_halo_exchange(self.h, C.byref(self.state), self._stream()), "gcsadmm_halo_exchange")
+        self._call("gcsadmm_halo_exchange", C.byref(self.state), self._stream(), select=False)
 
     def halo_buffers(self):
         """(send pointer, receive pointer, elements) of the packed halo buffers (device memory owned by the handle)"""
         a, b, n = C.c_void_p(), C.c_void_p(), C.c_int64(0)
-        self._check(self.lib.gcsadmm_halo_buffers(self.h, C.byref(a), C.byref(b), C.byref(n)), "gcsadmm_halo_buffers")
+        self._call("gcsadmm_halo_buffers", C.byref(a), C.byref(b), C.byref(n), select=False)
         return a.value, b.value, n.value
-
-    def solve_partitioned(self, chunk: int = 25, **params):
-        """The partitioned loop to its stop test: as ``solve`` but through gcsadmm_run_partitioned (collective)."""
-        self.reset(**params)
-        max_it = self.params.max_it
-        done = 0
-        while True:
-            k = min(chunk, max_it - done)
-            if k > 0:
-                self.enqueue_partitioned(k)
-                done += k
-            cb = self.read_control()
-            if cb.status != RUNNING or done >= max_it:
-                return cb
 
     def read_control(self) -> ControlBlock:
         cb = ControlBlock()
-        self._check(self.lib.gcsadmm_read_control(self.h, C.byref(cb), self._stream()), "gcsadmm_read_control")
+        self._call("gcsadmm_read_control", C.byref(cb), self._stream(), select=False)
         return cb
 
     def query(self):
         a, b, c, d, e = (C.c_int32(0) for _ in range(5))
-        self._check(self.lib.gcsadmm_query(self.h, C.byref(a), C.byref(b), C.byref(c), C.byref(d), C.byref(e)), "gcsadmm_query")
+        self._call("gcsadmm_query", C.byref(a), C.byref(b), C.byref(c), C.byref(d), C.byref(e), select=False)
         return dict(num_waves=a.value, lds_bytes=b.value, num_special=c.value, num_workgroup_vertices=d.value,
                     workgroup_lds_bytes=e.value)
 
     def query_workspace(self):
         """the split form of the workgroup program (``vertex_workspace``): its vertices, LDS per workgroup, device workspace bytes"""
         a, b, c = C.c_int32(0), C.c_int32(0), C.c_int64(0)
-        self._check(self.lib.gcsadmm_query_workspace(self.h, C.byref(a), C.byref(b), C.byref(c)), "gcsadmm_query_workspace")
+        self._call("gcsadmm_query_workspace", C.byref(a), C.byref(b), C.byref(c), select=False)
         return dict(num_split_vertices=a.value, split_lds_bytes=b.value, workspace_bytes=c.value)
 
     def unit_iterations(self):
         """Newton iterations of the last vertex step per dispatch unit (empty for handles with fewer than 512 units)."""
-        import numpy as np
-        with self.torch.cuda.device(self.device):
-            n = C.c_int32(0)
-            self._check(self.lib.gcsadmm_unit_iterations(self.h, None, 0, C.byref(n), self._stream()), "gcsadmm_unit_iterations")
-            out = np.zeros(n.value, np.int32)
-            if n.value:
-                self._check(self.lib.gcsadmm_unit_iterations(self.h, out.ctypes.data_as(C.c_void_p), n.value, C.byref(n), self._stream()),
-                            "gcsadmm_unit_iterations")
+        n = C.c_int32(0)
+        self._call("gcsadmm_unit_iterations", None, 0, C.byref(n), self._stream())
+        out = np.zeros(n.value, np.int32)
+        if n.value:
+            self._call("gcsadmm_unit_iterations", out.ctypes.data, n.value, C.byref(n), self._stream())
         return out
 
     def cost(self) -> float:
         eps = self.params.eps_edge if self.params is not None else 1e-4
-        self._check(self.lib.gcsadmm_cost(self.h, C.byref(self.state), C.c_double(eps), C.c_void_p(self._cost.data_ptr()),
-                                          self._stream()), "gcsadmm_cost")
+        self._call("gcsadmm_cost", C.byref(self.state), eps, self._cost.data_ptr(), self._stream(), select=False)
         return float(self._cost.item())
 
     # ------------------------------------------------------------------
+    def _loop(self, enqueue, chunk, params, clock=False):
+        """``reset(**params)``, then ``enqueue(k)`` (which may return device milliseconds to add up) in chunks of ``chunk`` iterations,
+        polling the device control block after each, to the stop test or max_it.  ``clock``: the device is idle when the wall clock
+        starts.  Returns (control block, wall seconds, device milliseconds)."""
+        self.reset(**params)
+        max_it, done, dev_ms = self.params.max_it, 0, 0.0
+        if clock:
+            self.torch.cuda.synchronize(self.device)
+        t0 = time.perf_counter()
+        while True:
+            k = min(chunk, max_it - done)
+            if k > 0:
+                dev_ms += enqueue(k) or 0.0
+                done += k
+            cb = self.read_control()
+            if cb.status != RUNNING or done >= max_it:
+                return cb, time.perf_counter() - t0, dev_ms
+
+    def solve_partitioned(self, chunk: int = 25, **params):
+        """The partitioned loop to its stop test: as ``solve`` but through gcsadmm_run_partitioned (collective)."""
+        return self._loop(self.enqueue_partitioned, chunk, params)[0]
+
     def solve(self, chunk: int = 25, timed: bool = False, **params):
         """Run the loop to its stop test (or max_it), polling the device control
         block every ``chunk`` iterations; returns the reference's record fields
@@ -420,30 +299,12 @@ class DeviceSolver:
         summed device time of the vertex-step and edge-step kernels -- the counterpart of the reference's
         ``solve_time``, which adds up SolveInParallel and the edge loop only (admm_solver_v3.py:489-491, 579-585,
         660, 677).  ``wall_time_s`` is the host wall time of the loop either way."""
-        import time
-        self.reset(**params)
-        max_it = self.params.max_it
-        done = 0
-        dev_ms = 0.0
-        self.torch.cuda.synchronize(self.device)
-        t0 = time.perf_counter()
-        while True:
-            k = min(chunk, max_it - done)
-            if k > 0:
-                if timed:
-                    tm = self.enqueue_timed(k)
-                    dev_ms += tm["vertex_ms"] + tm["edge_ms"]
-                else:
-                    self.enqueue(k)
-                done += k
-            cb = self.read_control()
-            if cb.status != RUNNING or done >= max_it:
-                break
-        wall = time.perf_counter() - t0
-        it = cb.it
-        k = min(it, max_it)
-        tr = self.trace[:k].cpu().numpy()
-        return dict(iterations=int(it), status=STATUS_NAME[cb.status],
+        def enqueue_timed(k):
+            tm = self.enqueue_timed(k)
+            return tm["vertex_ms"] + tm["edge_ms"]
+        cb, wall, dev_ms = self._loop(enqueue_timed if timed else self.enqueue, chunk, params, clock=True)
+        tr = self.trace[:min(cb.it, self.params.max_it)].cpu().numpy()
+        return dict(iterations=int(cb.it), status=STATUS_NAME[cb.status],
                     rho_seq=np.concatenate([[self.params.rho], tr[:, 0]]),
                     pri_res_seq=np.concatenate([[0.0], tr[:, 1]]),
                     dual_res_seq=np.concatenate([[0.0], tr[:, 2]]),

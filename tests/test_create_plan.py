@@ -15,7 +15,7 @@ from conftest import BENCHMARKS, star_case
 from gcs_admm_amd.build import T512
 from gcs_admm_amd.cases import load_fixture
 from gcs_admm_amd.graph import convert_pt_to_polytope, graph_from_sets, lattice_boxes
-from gcs_admm_amd.solver import GraphDesc
+from gcs_admm_amd.abi import graph_desc
 from test_gpu_configs import _region_row, _region_star
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -62,18 +62,9 @@ def _p(a):
 
 
 def descriptor(g, columns="incidence", dtype=0, **knobs):
-    """(GraphDesc, arrays it points into): what DeviceSolver.__init__ builds; knobs: vertex_program, wave_slots, wave_align,
-    wave_store_dl, wave_generic_rows, or any other field to override"""
-    E = g.num_edges
-    tail, head = g.edge_inc_tail.astype(np.int32), g.edge_inc_head.astype(np.int32)
-    NI = int(g.inc_ptr[-1])
-    if columns == "edge":
-        tail, head, NI = np.arange(E, dtype=np.int32), (E + np.arange(E)).astype(np.int32), 2 * E
-    keep = [np.ascontiguousarray(a) for a in (
-        g.inc_ptr.astype(np.int32), g.inc_edge.astype(np.int32), g.inc_out.astype(np.int32), tail, head, g.poly_ptr.astype(np.int32),
-        g.poly_A.astype(np.float64), g.poly_b.astype(np.float64), g.interior.astype(np.float64))]
-    d = GraphDesc(g.n, g.num_vertices, E, NI, *[_p(a) for a in keep[:9]], g.src, g.dst, dtype, 0, None, None, 0.0, 0.0,
-                  0, 0, 0, 0, 0, int(columns == "edge"))
+    """(GraphDesc, arrays it points into): what DeviceSolver.__init__ builds (abi.graph_desc); knobs: vertex_program, wave_slots,
+    wave_align, wave_store_dl, wave_generic_rows, or any other field to override"""
+    d, keep, _ = graph_desc(g, state_dtype=dtype, device=0, columns=columns, num_incidences=2 * g.num_edges if columns == "edge" else None)
     for k, v in knobs.items():
         setattr(d, k, v)
     return d, keep
