@@ -3,6 +3,7 @@
 from .graph import (GcsGraph, build_graph, convert_pt_to_polytope, delta, graph_from_sets,  # noqa: F401
                     lattice_boxes, polytopes_overlap)
 from .cases import load_fixture  # noqa: F401
+from .batch import BatchSolver  # noqa: F401  (many small problems in one set of launches; needs the GPU only when one is made)
 
 # Barrier parameter at which a vertex solve stops (gcsadmm_params.ipm_tol).  MOSEK's default relative gap behind the reference's
 # SolveInParallel (admm_solver_v3.py:490) is ~1e-8.  Swept on the oracle in round 4 (profiles/r04/README.md): 1e-9, 3e-9 and 5e-9 keep
@@ -12,4 +13,4 @@ from .cases import load_fixture  # noqa: F401
 IPM_TOL = 3e-9
 
 __all__ = ["GcsGraph", "build_graph", "convert_pt_to_polytope", "delta", "graph_from_sets", "lattice_boxes",
-           "polytopes_overlap", "load_fixture", "IPM_TOL"]
+           "polytopes_overlap", "load_fixture", "BatchSolver", "IPM_TOL"]

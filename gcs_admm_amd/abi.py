@@ -73,6 +73,13 @@ PROTOTYPES = {
     "gcsadmm_query_workspace": ([_p] * 4, _i),
     "gcsadmm_unit_iterations": ([_p, _p, _i, _p, _p], _i),
     "gcsadmm_run_timed": (_run_timed, _i),
+    # batches of handles (gcs_admm_amd/batch.py)
+    "gcsadmm_batch_create": ([_p, _i, _p], _i),
+    "gcsadmm_batch_destroy": ([_p], None),
+    "gcsadmm_batch_last_error": ([_p], C.c_char_p),
+    "gcsadmm_batch_bind": ([_p] * 4, _i),
+    "gcsadmm_batch_run": ([_p, _i, _p], _i),
+    "gcsadmm_batch_poll": ([_p] * 4, _i),
     "gcsadmm_vertex_prox": ([_p] * 6 + [_d, _i, _p, _p], _i),
     # vertex partitions across GPUs (RCCL)
     "gcsadmm_comm_unique_id": ([_p], _i),

@@ -1,0 +1,118 @@
+"""Many small problems in one set of launches: the host side of the batch entry points of include/gcsadmm.h.
+
+A small graph leaves most of an MI355X idle, and its vertex step is bound by dependent latency, so users with many small problems
+(many start / goal queries, many scenes) gain from occupancy: ``BatchSolver`` holds one ordinary ``DeviceSolver`` per graph and
+advances all of them with one vertex launch and one edge + control launch per iteration.  Every member keeps its own state, control
+block and trace, stops on its own, and computes bit for bit what the same solver computes when it is driven alone.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import time
+
+from . import abi
+from .abi import RUNNING, State
+from .solver import DeviceSolver
+
+
+class BatchSolver:
+    """``graphs``: GcsGraph instances of one space dimension, small enough for the workgroup program (fewer than 512 generic vertices
+    each).  ``members[i]`` is the ``DeviceSolver(graphs[i], program="workgroup256")`` of graph i: its state tensors, ``cost()``,
+    ``read_control()`` and rounding work per member as they do for a solver of its own."""
+
+    def __init__(self, graphs, state_dtype: str = "f64", device=None):
+        self.members = [DeviceSolver(g, state_dtype, device=device, program="workgroup256") for g in graphs]
+        self.b = None
+        self._init(self.members)
+
+    @classmethod
+    def of(cls, members):
+        """a batch over existing solvers (they stay the caller's and must outlive the batch)"""
+        self = cls.__new__(cls)
+        self.members, self.b = list(members), None
+        self._init(self.members)
+        return self
+
+    def _init(self, members):
+        import torch
+        self.torch, self.lib = torch, abi.load_library()
+        self.device = members[0].device if members else torch.device("cuda", torch.cuda.current_device())
+        handles = (C.c_void_p * max(len(members), 1))(*[m.h.value for m in members])
+        b = C.c_void_p()
+        self._call("gcsadmm_batch_create", handles, len(members), C.byref(b), batch=False)
+        self.b = b
+
+    # ------------------------------------------------------------------
+    def _call(self, name, *args, batch=True):
+        """The one call into the library, as DeviceSolver._call: ``name(self.b, *args)`` (``batch=False``: ``name(*args)``, and the error
+        text is the calling thread's) with the batch's device current; a status other than 0 raises GcsAdmmError."""
+        b = self.b if batch else None
+        with self.torch.cuda.device(self.device):
+            st = getattr(self.lib, name)(*((b,) if batch else ()), *args)
+        abi.check(st, lambda: f"{name} failed ({st}): {self.lib.gcsadmm_batch_last_error(b).decode()}")
+
+    def _stream(self):
+        return self.torch.cuda.current_stream(self.device).cuda_stream
+
+    def close(self):
+        """destroys the batch; the members stay usable on their own"""
+        if getattr(self, "b", None):
+            self._call("gcsadmm_batch_destroy")
+            self.b = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __len__(self):
+        return len(self.members)
+
+    # ------------------------------------------------------------------
+    def bind(self):
+        """hand the members' state and trace pointers and their parameters to the batch (after every member's ``reset``)"""
+        n = len(self.members)
+        states = (State * n)(*[m.state for m in self.members])
+        traces = (C.c_void_p * n)(*[None if m.trace is None else m.trace.data_ptr() for m in self.members])
+        self._call("gcsadmm_batch_bind", states, traces, self._stream())
+
+    def reset(self, params=None, **common):
+        """``DeviceSolver.reset`` on every member, then ``bind``.  ``common``: parameters of all members; ``params``: a list of one dict per
+        member that overrides them (rho, tau_incr, cold_start, ...: every field may differ between members)."""
+        per = params if params is not None else [{}] * len(self.members)
+        if len(per) != len(self.members):
+            raise ValueError("one parameter dict per member")
+        for m, p in zip(self.members, per):
+            m.reset(**{**common, **p})
+        self.bind()
+
+    def enqueue(self, k: int):
+        """up to k iterations of every member that is still running, back to back, no host synchronisation"""
+        self._call("gcsadmm_batch_run", int(k), self._stream())
+
+    def poll(self):
+        """(status, it) of every member, two lists, in one device-to-host copy (synchronises the stream)"""
+        n = len(self.members)
+        status, it = (C.c_int32 * n)(), (C.c_int32 * n)()
+        self._call("gcsadmm_batch_poll", status, it, self._stream())
+        return list(status), list(it)
+
+    def solve(self, chunk: int = 25, params=None, **common):
+        """Every member to its stop test (or its max_it) as ``DeviceSolver.solve`` runs one: enqueue ``chunk`` iterations, poll once, stop
+        when no member is running.  Returns one result per member in the shape ``DeviceSolver.solve`` returns; ``wall_time_s`` is the
+        wall time of the whole batch."""
+        self.reset(params, **common)
+        max_it, done = max(m.params.max_it for m in self.members), 0
+        self.torch.cuda.synchronize(self.device)
+        t0 = time.perf_counter()
+        while True:
+            k = min(chunk, max_it - done)
+            if k > 0:
+                self.enqueue(k)
+                done += k
+            status, _ = self.poll()
+            if all(s != RUNNING for s in status) or done >= max_it:
+                break
+        wall = time.perf_counter() - t0
+        return [m.record(m.read_control(), wall) for m in self.members]

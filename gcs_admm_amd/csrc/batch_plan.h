@@ -1,0 +1,81 @@
+// batch_plan.h -- what gcsadmm_batch_create decides before it allocates anything: which handles may share a set of launches, and the
+// geometry of those launches.  Host-only and HIP-free like create_plan.h, whose plans are its input, so that the rules and the
+// geometry can be tested on a machine without a GPU (tests/hostemu/batch_plan_emu.cpp, tests/test_batch_plan.py).
+//
+// A batch is a set of ordinary handles.  Its two kernels (vertex_wg_batch_kernel, edge_batch_kernel) pick the member by blockIdx.y and
+// run the device functions of the solo kernels on that member's own arguments, so a member is eligible exactly when ONE launch of ONE
+// instantiation of the in-LDS workgroup program does its whole vertex step, and one launch of the edge kernel its edge step.
+#pragma once
+#include <algorithm>
+#include <string>
+#include <vector>
+
+#include "create_plan.h"
+
+namespace gcsadmm_k {
+
+constexpr int BATCH_MAX_MEMBERS = 65535;     // members are rows of the launch grid (gridDim.y)
+
+// a member as the rules see it: the plan its create made, the descriptor's scalars and what its handle holds
+struct BatchMember {
+    const void *id;             // identity of the handle (a handle may appear once)
+    const CreatePlan *plan;
+    int n, dtype, device;
+    int n_wg, n_special, n_split;       // vertices on the in-LDS workgroup program, closed-form vertices, split-form vertices
+    int has_comm;               // a communicator / halo is attached (gcsadmm_attach_comm)
+};
+
+struct BatchPlan {
+    int count = 0, n = 0, dtype = 0, device = 0, box = 0;
+    // vertex launch: grid (vertex_grid_x, count), 256 threads, vertex_lds_bytes of dynamic LDS; member m uses the first vertex_grid[m] columns
+    int vertex_grid_x = 0, vertex_lds_bytes = 0;
+    // edge launch: grid (edge_grid_x, count), EDGE_BLOCK threads; member m uses the first edge_blocks[m] columns
+    int edge_grid_x = 0;
+    std::vector<int> vertex_grid, edge_blocks;
+};
+
+// the eligibility rules, in the order they are checked, and the launch geometry; `err` names the member and the reason
+inline gcsadmm_status make_batch_plan(const BatchMember *m, int count, BatchPlan &bp, std::string &err)
+{
+    auto fail = [&](gcsadmm_status st, int i, const char *why) {
+        err = i < 0 ? std::string(why) : "member " + std::to_string(i) + ": " + why;
+        return st;
+    };
+    bp = BatchPlan();
+    if (!m || count < 1) return fail(GCSADMM_ERR_BAD_ARG, -1, "a batch needs at least one member");
+    if (count > BATCH_MAX_MEMBERS) return fail(GCSADMM_ERR_UNSUPPORTED, -1, "a batch holds at most 65535 members");
+    for (int i = 0; i < count; ++i) {
+        if (!m[i].id || !m[i].plan) return fail(GCSADMM_ERR_BAD_ARG, i, "null handle");
+        for (int j = 0; j < i; ++j)
+            if (m[j].id == m[i].id) return fail(GCSADMM_ERR_BAD_ARG, i, "the handle appears twice in the batch");
+    }
+    for (int i = 0; i < count; ++i) {
+        const CreatePlan &p = *m[i].plan;
+        // one kernel instantiation serves the launch
+        if (m[i].device != m[0].device) return fail(GCSADMM_ERR_BAD_ARG, i, "members must be on the same device");
+        if (m[i].n != m[0].n) return fail(GCSADMM_ERR_UNSUPPORTED, i, "members must share the space dimension n");
+        if (m[i].dtype != m[0].dtype) return fail(GCSADMM_ERR_UNSUPPORTED, i, "members must share the state_dtype");
+        // one launch of the in-LDS workgroup program at 256 threads is the member's whole vertex step
+        if (p.n_waves() > 0) return fail(GCSADMM_ERR_UNSUPPORTED, i, "vertices on the wavefront program (create the handle with vertex_program = 3)");
+        if (p.wg_t512) return fail(GCSADMM_ERR_UNSUPPORTED, i, "the workgroup program runs with 512 threads (create the handle with vertex_program = 3)");
+        if (m[i].n_split > 0) return fail(GCSADMM_ERR_UNSUPPORTED, i, "vertices in the split form of the workgroup program (vertex_workspace)");
+        if (p.n_term > 0) return fail(GCSADMM_ERR_UNSUPPORTED, i, "a terminal that is a region");
+        if (p.wg_reorder || m[i].n_wg >= REORDER_MIN_UNITS) return fail(GCSADMM_ERR_UNSUPPORTED, i, "512 or more workgroup-program vertices (slowest-first dispatch)");
+        if (p.edge_unroll != 1) return fail(GCSADMM_ERR_UNSUPPORTED, i, "the edge step runs unrolled (a graph this large gains nothing from a batch)");
+        if (m[i].has_comm) return fail(GCSADMM_ERR_UNSUPPORTED, i, "a communicator is attached (partitioned handles run their own loop)");
+        if (p.wg_box != m[0].plan->wg_box) return fail(GCSADMM_ERR_UNSUPPORTED, i, "members must share the BOX choice of the workgroup program (plan.wg_box)");
+    }
+    bp.count = count; bp.n = m[0].n; bp.dtype = m[0].dtype; bp.device = m[0].device; bp.box = m[0].plan->wg_box;
+    for (int i = 0; i < count; ++i) {
+        const CreatePlan &p = *m[i].plan;
+        const int grid = m[i].n_wg + (m[i].n_special + 255) / 256;
+        bp.vertex_grid.push_back(grid);
+        bp.edge_blocks.push_back(p.edge_blocks);
+        bp.vertex_grid_x = std::max(bp.vertex_grid_x, grid);
+        bp.vertex_lds_bytes = std::max(bp.vertex_lds_bytes, std::max(p.wg_lds_bytes, 4 * MAX_SPECIAL_DEG * 8));
+        bp.edge_grid_x = std::max(bp.edge_grid_x, p.edge_blocks);
+    }
+    return GCSADMM_OK;
+}
+
+}  // namespace gcsadmm_k

@@ -13,6 +13,9 @@
 //   halo_pack / halo_unpack_kernel     messages of the cut edges' copies between vertex partitions (RCCL); in the overlapped
 //                        partitioned loop they and the transfer run on a second stream while the interior wavefronts are solved
 //   cost_kernel<T>       GCS_utils.py:184-211
+//   vertex_wg_batch_kernel<N,T> (vertex_wg.hip) / edge_batch_kernel<T,C> / batch_poll_kernel   the loop of a BATCH of handles
+//                        (gcsadmm_batch_run): the bodies of vertex_wg_kernel and edge_kernel on the member blockIdx.y names, each member
+//                        with its own arguments and control state, one vertex launch and one edge + control launch per iteration
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
 #include <rccl/rccl.h>
@@ -51,6 +54,7 @@ __device__ __forceinline__ void gcs_stamp(int k)
 #include "warm_start.h"
 #include "canonical_box.h"
 #include "create_plan.h"
+#include "batch_plan.h"
 
 namespace {
 
@@ -144,9 +148,12 @@ template <class T, int C> __host__ __device__ constexpr int edge_unroll() { retu
 // MODE 3: as MODE 2 without the control step (gcsadmm_run_partitioned): the last workgroup leaves the five sums and, in
 //         sums[5], this partition's inner-failure count for the all-reduce that follows.
 // C = coupled words per copy (2n+1), compile-time so that all C x 5 loads of an edge are in flight at once.
+// The body is a function of the arguments, the workgroup's index bx and the number of workgroups nblocks that share the edges, so that
+// the kernel that gets them from its kernarg segment and its grid (edge_kernel) and the one that reads them from a table
+// (edge_batch_kernel) run the same instructions on the same numbers.  red / is_last: the workgroup's LDS, declared by the kernel.
 template <class T, int MODE, int C, int U>
-__global__ __launch_bounds__(EDGE_BLOCK) void edge_kernel(EdgeArgs<T> a, gcsadmm_control_block *cb, double *sums, ControlParams cp,
-                                                          int *counters, double *trace, unsigned *ticket)
+__device__ __forceinline__ void edge_body(const EdgeArgs<T> &a, gcsadmm_control_block *cb, double *sums, const ControlParams &cp, int *counters,
+                                          double *trace, unsigned *ticket, const unsigned bx, const unsigned nblocks, double (*red)[5], int *is_last)
 {
     if (cb->status != GCSADMM_RUNNING) return;
     const double mu_scale = cb->mu_scale;
@@ -154,7 +161,7 @@ __global__ __launch_bounds__(EDGE_BLOCK) void edge_kernel(EdgeArgs<T> a, gcsadmm
     // a workgroup takes tiles of U x EDGE_BLOCK consecutive edges; a thread handles U edges of the tile, EDGE_BLOCK apart, and issues
     // the loads of all of them before the first use: U x 5C coalesced 4/8-byte loads in flight per thread (one edge per thread left
     // the stream latency-bound: 64 MB in 36 us on the 100k lattice)
-    for (int base = blockIdx.x * (U * EDGE_BLOCK); base < a.E; base += gridDim.x * (U * EDGE_BLOCK)) {
+    for (int base = bx * (U * EDGE_BLOCK); base < a.E; base += nblocks * (U * EDGE_BLOCK)) {
         int it[U], ih[U];
         T cu_[U][C], cw_[U][C], zo_[U][C], mu_[U][C], mw_[U][C];
 #pragma unroll
@@ -196,8 +203,6 @@ __global__ __launch_bounds__(EDGE_BLOCK) void edge_kernel(EdgeArgs<T> a, gcsadmm
             }
         }
     }
-    __shared__ double red[EDGE_BLOCK][5];
-    __shared__ int is_last;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
 #pragma unroll
     for (int k = 0; k < 5; ++k) {
@@ -208,8 +213,8 @@ __global__ __launch_bounds__(EDGE_BLOCK) void edge_kernel(EdgeArgs<T> a, gcsadmm
     if (threadIdx.x < 5) {
         double t = 0;
         for (int q = 0; q < EDGE_BLOCK / WAVE; ++q) t += red[q][threadIdx.x];
-        if (MODE >= 2) __hip_atomic_store(&a.partials[(size_t)blockIdx.x * 5 + threadIdx.x], t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        else a.partials[(size_t)blockIdx.x * 5 + threadIdx.x] = t;
+        if (MODE >= 2) __hip_atomic_store(&a.partials[(size_t)bx * 5 + threadIdx.x], t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        else a.partials[(size_t)bx * 5 + threadIdx.x] = t;
         if (MODE == 1) sums[threadIdx.x] = t;      // one workgroup: its partial is the sum (what finalize_kernel would produce)
     }
     if (MODE == 1) {
@@ -219,19 +224,18 @@ __global__ __launch_bounds__(EDGE_BLOCK) void edge_kernel(EdgeArgs<T> a, gcsadmm
     if (MODE >= 2) {
         // hand-off of the partials to the last workgroup (MI355X_MICROARCH.md, inter-workgroup visibility): write-through (sc1)
         // stores by the first wavefront, drained, then ONE agent-scope ticket add by a lane of that same wavefront; the
-        // workgroup whose add returns gridDim.x - 1 came last and reads every partial with sc1 loads.  (Measured alternative: an
+        // workgroup whose add returns nblocks - 1 came last and reads every partial with sc1 loads.  (Measured alternative: an
         // agent-scope ACQ_REL ticket add instead of the drain -- the release writes back the L2 of the XCD, which holds this
         // kernel's own 24 MB of stores: edge step 23.6 -> 33.4 us on the 100k lattice.  Only the five partials need to cross.)
         if (threadIdx.x < WAVE) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         if (threadIdx.x == 0) {
             const unsigned t = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            is_last = (t == gridDim.x - 1);
+            *is_last = (t == nblocks - 1);
         }
         __syncthreads();
-        if (!is_last) return;
-        const int nblocks = gridDim.x;
+        if (!*is_last) return;
         double acc[5] = {0, 0, 0, 0, 0};
-        for (int b = threadIdx.x; b < nblocks; b += EDGE_BLOCK)
+        for (int b = threadIdx.x; b < (int)nblocks; b += EDGE_BLOCK)
             for (int k = 0; k < 5; ++k) acc[k] += __hip_atomic_load(&a.partials[(size_t)b * 5 + k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         __syncthreads();       // red[][] above has been consumed by every thread
         for (int k = 0; k < 5; ++k) red[threadIdx.x][k] = acc[k];
@@ -249,6 +253,53 @@ __global__ __launch_bounds__(EDGE_BLOCK) void edge_kernel(EdgeArgs<T> a, gcsadmm
             __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);     // ready for the next launch
         }
     }
+}
+
+template <class T, int MODE, int C, int U>
+__global__ __launch_bounds__(EDGE_BLOCK) void edge_kernel(EdgeArgs<T> a, gcsadmm_control_block *cb, double *sums, ControlParams cp,
+                                                          int *counters, double *trace, unsigned *ticket)
+{
+    __shared__ double red[EDGE_BLOCK][5];
+    __shared__ int is_last;
+    edge_body<T, MODE, C, U>(a, cb, sums, cp, counters, trace, ticket, blockIdx.x, gridDim.x, red, &is_last);
+}
+
+// BATCH form (gcsadmm_batch_run): row blockIdx.y of the grid is member blockIdx.y of the batch.  The workgroup copies that member's entry
+// of the table -- what edge_kernel gets in its kernarg segment, plus the member's own number of workgroups -- through a uniform index
+// (scalar loads) and runs the body in the mode gcsadmm_run uses for that member: MODE 1 where one workgroup
+// holds all its edges, MODE 2 otherwise, with the member's nblocks in place of gridDim.x in the edge loop, the partials and the ticket
+// (each member has its own partials, sums, counters and ticket: its handle's).  The grid is as wide as the widest member; the
+// workgroups beyond a member's own leave before they touch its ticket or partials.  One edge per thread (U = 1: batch_plan.h).
+template <class T> struct EdgeBatchEntry {
+    EdgeArgs<T> a;
+    gcsadmm_control_block *cb;
+    double *sums;
+    ControlParams cp;
+    int *counters;
+    double *trace;      // may be null
+    unsigned *ticket;
+    int nblocks;
+};
+template <class T, int C>
+__global__ __launch_bounds__(EDGE_BLOCK) void edge_batch_kernel(const EdgeBatchEntry<T> *__restrict__ table)
+{
+    __shared__ double red[EDGE_BLOCK][5];
+    __shared__ int is_last;
+    // (read through the constant address space, as kernel arguments are: vertex_wg_batch_kernel has the reason)
+    __builtin_assume_dereferenceable(table + blockIdx.y, sizeof(EdgeBatchEntry<T>));
+    const EdgeBatchEntry<T> e = *(const EdgeBatchEntry<T> *)((const __attribute__((address_space(4))) EdgeBatchEntry<T> *)table + blockIdx.y);
+    if ((int)blockIdx.x >= e.nblocks) return;
+    if (e.nblocks == 1) edge_body<T, 1, C, 1>(e.a, e.cb, e.sums, e.cp, e.counters, e.trace, e.ticket, 0, 1, red, &is_last);
+    else edge_body<T, 2, C, 1>(e.a, e.cb, e.sums, e.cp, e.counters, e.trace, e.ticket, blockIdx.x, (unsigned)e.nblocks, red, &is_last);
+}
+
+// status and it of the members' control blocks, gathered for the one copy of gcsadmm_batch_poll: out[i] = status, out[count + i] = it
+__global__ __launch_bounds__(256) void batch_poll_kernel(const gcsadmm_control_block *const *cbs, int count, int *out)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= count) return;
+    out[i] = cbs[i]->status;
+    out[count + i] = cbs[i]->it;
 }
 
 // SLOWEST-FIRST DISPATCH.  A vertex-step launch ends when its slowest workgroup does, and with the warm start most solves take 3-5
@@ -381,6 +432,9 @@ struct gcsadmm_handle_s {
     gcsadmm_params params{};
     bool params_set = false;
     int vertex_steps = 0;     // vertex steps enqueued since the last reset
+    unsigned resets = 0;      // gcsadmm_reset calls: a batch's tables hold what the reset before its bind set (gcsadmm_batch_run compares)
+    gcsadmm_batch_s *batch = nullptr;      // the batch this handle is bound to (gcsadmm_batch_bind .. the batch's next bind or its destroy)
+    std::vector<gcsadmm_batch_s *> batches;      // the batches that list this handle as a member (gcsadmm_batch_create .. _destroy)
     int overlap_mode = 0;     // gcsadmm_set_overlap: 0 automatic, 1 forced (tests: works without peers), 2 off
     std::string err;
     void *comm = nullptr;     // ncclComm_t (gcsadmm_attach_comm)
@@ -418,6 +472,22 @@ struct gcsadmm_handle_s {
     int n_special() const { return (int)g.d_special_vtx.size(); }
     int n_wg() const { return (int)g.d_wg_vtx.size(); }       // vertices solved by the workgroup program (vertex_wg.hip)
     int n_split() const { return (int)g.d_split_vtx.size(); }
+};
+
+// A batch of handles (gcsadmm_batch_create): the members stay the caller's, the batch owns its plan (batch_plan.h) and the argument
+// tables of its two kernels.  Nothing of a member's loop state moves: the entries point at the members' own control blocks, counters,
+// partials, sums and tickets, which is why a member run in a batch and the same handle run alone produce the same bits.
+struct gcsadmm_batch_s {
+    int device = 0;
+    std::string err;
+    std::vector<gcsadmm_handle> members;
+    std::vector<unsigned> resets;       // members' reset counts at bind
+    BatchPlan plan;
+    bool bound = false;
+    DevBuf<char> d_vertex_table, d_edge_table;      // [count] WgBatchEntry<T> (vertex_wg_launch.h) / EdgeBatchEntry<T>
+    DevBuf<const gcsadmm_control_block *> d_cbs;    // [count] the members' control blocks (batch_poll_kernel)
+    DevBuf<int> d_poll;                             // [2 count] status, it
+    std::vector<int> poll_host;
 };
 
 // ---- RCCL, bound at run time ----
@@ -610,6 +680,17 @@ static gcsadmm_status launch_vertex(gcsadmm_handle h, const gcsadmm_state *st, h
     return GCSADMM_OK;
 }
 
+// the arguments of an edge-step launch (the kernarg of edge_kernel, or a member's entry of the batch table)
+template <class T> static EdgeArgs<T> make_edge_args(gcsadmm_handle h, const gcsadmm_state *st)
+{
+    EdgeArgs<T> a;
+    a.E = h->E; a.NI = h->NI; a.c = h->c;
+    a.edge_inc_tail = h->edge_major ? nullptr : h->g.d_edge_inc_tail.get(); a.edge_inc_head = h->edge_major ? nullptr : h->g.d_edge_inc_head.get();
+    a.inc_counted = h->g.d_inc_counted.get(); a.edge_counted = h->g.d_edge_counted.get();
+    a.copy = (const T *)st->copy; a.zedge = (T *)st->zedge; a.mu = (T *)st->mu; a.partials = h->loop.d_partials.get();
+    return a;
+}
+
 // with_control: the control step rides in the same launches (gcsadmm_run); trace may be null
 static gcsadmm_status launch_edge(gcsadmm_handle h, const gcsadmm_state *st, double *sums, hipStream_t s, bool with_control = false,
                                   double *trace = nullptr, bool sums6 = false)
@@ -618,11 +699,7 @@ static gcsadmm_status launch_edge(gcsadmm_handle h, const gcsadmm_state *st, dou
     const int edge_blocks = h->plan.edge_blocks;
     with_state(h, [&](auto t) {
         using T = decltype(t);
-        EdgeArgs<T> a;
-        a.E = h->E; a.NI = h->NI; a.c = h->c;
-        a.edge_inc_tail = h->edge_major ? nullptr : h->g.d_edge_inc_tail.get(); a.edge_inc_head = h->edge_major ? nullptr : h->g.d_edge_inc_head.get();
-        a.inc_counted = h->g.d_inc_counted.get(); a.edge_counted = h->g.d_edge_counted.get();
-        a.copy = (const T *)st->copy; a.zedge = (T *)st->zedge; a.mu = (T *)st->mu; a.partials = h->loop.d_partials.get();
+        const EdgeArgs<T> a = make_edge_args<T>(h, st);
         // one kernel instantiation per (state type, mode, words per copy)
         auto go = [&](auto mode, int blocks) {
             constexpr int M = decltype(mode)::value;
@@ -798,6 +875,60 @@ static gcsadmm_status ensure_events(gcsadmm_handle h, size_t count)
     return GCSADMM_OK;
 }
 
+// ---- batch of handles: host-side helpers (C++ linkage) ----
+// the members as batch_plan.h sees them, and its verdict
+static gcsadmm_status batch_plan_of(const std::vector<gcsadmm_handle> &members, BatchPlan &bp, std::string &err)
+{
+    std::vector<BatchMember> m;
+    for (gcsadmm_handle h : members)
+        m.push_back(h ? BatchMember{h, &h->plan, h->n, h->dtype, h->device, h->n_wg(), h->n_special(), h->n_split(), h->halo.attached() || h->comm != nullptr}
+                      : BatchMember{});
+    return make_batch_plan(m.data(), (int)m.size(), bp, err);
+}
+
+// the members are released from the batch: it cannot run until it is bound again
+static void batch_unbind(gcsadmm_batch_s *b)
+{
+    for (gcsadmm_handle h : b->members)
+        if (h && h->batch == b) h->batch = nullptr;
+    b->bound = false;
+}
+
+// a handle that is destroyed leaves the batches that list it: they keep a null member and refuse to be bound again
+static void batches_forget(gcsadmm_handle h)
+{
+    for (gcsadmm_batch_s *b : h->batches) {
+        batch_unbind(b);
+        std::replace(b->members.begin(), b->members.end(), h, (gcsadmm_handle) nullptr);
+    }
+}
+
+// one vertex launch and one edge + control launch for the whole batch
+static gcsadmm_status launch_batch_iteration(gcsadmm_batch_s *b, hipStream_t s)
+{
+    const BatchPlan &bp = b->plan;
+    if (bp.vertex_grid_x > 0)
+        gcsadmm_wg_launch_batch(WgBatchLaunch{bp.n, bp.dtype, bp.box, b->d_vertex_table.get(), (unsigned)bp.vertex_grid_x, (unsigned)bp.count, bp.vertex_lds_bytes}, s);
+    with_state_type(bp.dtype == GCSADMM_F64, [&](auto t) {
+        using T = decltype(t);
+        const auto *table = (const EdgeBatchEntry<T> *)b->d_edge_table.get();
+#define GCS_EDGE_BATCH(CC) hipLaunchKernelGGL((edge_batch_kernel<T, CC>), dim3(bp.edge_grid_x, bp.count), dim3(EDGE_BLOCK), 0, s, table)
+        switch (2 * bp.n + 1) {
+        case 3: GCS_EDGE_BATCH(3); break;
+        case 5: GCS_EDGE_BATCH(5); break;
+        case 7: GCS_EDGE_BATCH(7); break;
+        case 9: GCS_EDGE_BATCH(9); break;
+        case 11: GCS_EDGE_BATCH(11); break;
+        case 13: GCS_EDGE_BATCH(13); break;
+        case 15: GCS_EDGE_BATCH(15); break;
+        default: GCS_EDGE_BATCH(17);
+        }
+#undef GCS_EDGE_BATCH
+    });
+    HIPCHK(b, hipGetLastError());
+    return GCSADMM_OK;
+}
+
 extern "C" {
 
 const char *gcsadmm_last_error(gcsadmm_handle h) { return h ? h->err.c_str() : g_create_error.c_str(); }
@@ -806,6 +937,7 @@ void gcsadmm_destroy(gcsadmm_handle h)
 {
     if (!h) return;
     DeviceGuard device_guard_(h->device);      // the owners release on the handle's device
+    batches_forget(h);
     if (h->comm && rccl().ok()) (void)rccl().CommDestroy((ncclComm_t)h->comm);
     delete h;
 }
@@ -907,7 +1039,7 @@ gcsadmm_status gcsadmm_reset(gcsadmm_handle h, const gcsadmm_params *p, void *st
 {
     if (!h || !p) return GCSADMM_ERR_BAD_ARG;
     if (!(p->rho > 0) || p->max_it < 1 || !(p->ipm_tol > 0) || p->ipm_max_iter < 1) { h->err = "bad parameter"; return GCSADMM_ERR_BAD_ARG; }
-    h->params = *p; h->params_set = true;
+    h->params = *p; h->params_set = true; ++h->resets;
     gcsadmm_control_block cb{};
     cb.rho = p->rho; cb.mu_scale = 1.0; cb.it = 1; cb.status = GCSADMM_RUNNING;
     USE_DEVICE(h);
@@ -1292,6 +1424,135 @@ gcsadmm_status gcsadmm_unit_iterations(gcsadmm_handle h, int32_t *out, int32_t c
     if (n == 0 || !out) return GCSADMM_OK;
     HIPCHK(h, hipStreamSynchronize((hipStream_t)stream));
     HIPCHK(h, hipMemcpy(out, src, sizeof(int) * (size_t)(n < capacity ? n : capacity), hipMemcpyDeviceToHost));
+    return GCSADMM_OK;
+}
+
+// =================================================================================================
+// batch of handles (include/gcsadmm.h): many small problems advance in one set of launches
+// =================================================================================================
+const char *gcsadmm_batch_last_error(struct gcsadmm_batch_s *b) { return b ? b->err.c_str() : g_create_error.c_str(); }
+
+void gcsadmm_batch_destroy(struct gcsadmm_batch_s *b)
+{
+    if (!b) return;
+    DeviceGuard device_guard_(b->device);      // the owners release on the batch's device
+    batch_unbind(b);
+    for (gcsadmm_handle h : b->members)
+        if (h) h->batches.erase(std::remove(h->batches.begin(), h->batches.end(), b), h->batches.end());
+    delete b;
+}
+
+gcsadmm_status gcsadmm_batch_create(const gcsadmm_handle *members, int32_t count, struct gcsadmm_batch_s **out)
+{
+    if (out) *out = nullptr;
+    auto fail = [&](gcsadmm_status st, const std::string &msg) { g_create_error = msg; return st; };
+    if (!out) return fail(GCSADMM_ERR_BAD_ARG, "null output pointer");
+    if (!members || count < 1) return fail(GCSADMM_ERR_BAD_ARG, "a batch needs at least one member");
+    auto b = std::unique_ptr<gcsadmm_batch_s>(new (std::nothrow) gcsadmm_batch_s);
+    if (!b) return fail(GCSADMM_ERR_HIP, "out of host memory");
+    b->members.assign(members, members + count);
+    std::string msg;
+    const gcsadmm_status st = batch_plan_of(b->members, b->plan, msg);
+    if (st != GCSADMM_OK) return fail(st, msg);
+    b->device = b->plan.device;
+    DeviceGuard device_guard_(b->device);
+    hipError_t e = device_guard_.err;
+    if (e == hipSuccess) e = b->d_vertex_table.alloc(gcsadmm_wg_batch_entry_bytes(b->plan.dtype) * (size_t)count);
+    if (e == hipSuccess) e = b->d_edge_table.alloc((b->plan.dtype == GCSADMM_F64 ? sizeof(EdgeBatchEntry<double>) : sizeof(EdgeBatchEntry<float>)) * (size_t)count);
+    if (e == hipSuccess) e = b->d_cbs.alloc((size_t)count);
+    if (e == hipSuccess) e = b->d_poll.upload(nullptr, 2 * (size_t)count);
+    if (e == hipSuccess && b->plan.vertex_lds_bytes > 48 * 1024) e = gcsadmm_wg_set_batch_lds(b->plan.n, b->plan.dtype, b->plan.vertex_lds_bytes);
+    if (e != hipSuccess) return fail(GCSADMM_ERR_HIP, std::string("gcsadmm_batch_create: ") + hipGetErrorString(e));      // (b is released under the guard)
+    b->poll_host.resize(2 * (size_t)count);
+    for (gcsadmm_handle h : b->members) h->batches.push_back(b.get());
+    *out = b.release();
+    return GCSADMM_OK;
+}
+
+gcsadmm_status gcsadmm_batch_bind(struct gcsadmm_batch_s *b, const gcsadmm_state *states, double *const *traces_dev, void *stream)
+{
+    if (!b) return GCSADMM_ERR_BAD_ARG;
+    if (!states) { b->err = "null state array"; return GCSADMM_ERR_BAD_ARG; }
+    const int count = (int)b->members.size();
+    // the members may have changed since create (a communicator attached): the rules again, then what only a bind can check
+    BatchPlan bp;
+    gcsadmm_status st = batch_plan_of(b->members, bp, b->err);
+    if (st != GCSADMM_OK) return st;
+    for (int i = 0; i < count; ++i) {
+        gcsadmm_handle h = b->members[i];
+        const std::string who = "member " + std::to_string(i) + ": ";
+        if (!state_ok(h, &states[i])) { b->err = who + h->err; return GCSADMM_ERR_BAD_ARG; }
+        if (h->batch && h->batch != b) { b->err = who + "the handle is bound to another batch (destroy that batch, or bind it to other states, first)"; return GCSADMM_ERR_BAD_ARG; }
+    }
+    DeviceGuard device_guard_(b->device);
+    HIPCHK(b, device_guard_.err);
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(b, hipStreamSynchronize(s));      // launches of an earlier bind may still read the tables
+    batch_unbind(b);
+    b->plan = bp;
+    const size_t vbytes = gcsadmm_wg_batch_entry_bytes(bp.dtype);
+    std::vector<char> vtab(vbytes * (size_t)count);
+    std::vector<const gcsadmm_control_block *> cbs((size_t)count);
+    b->resets.assign((size_t)count, 0u);
+    for (int i = 0; i < count; ++i) {
+        gcsadmm_handle h = b->members[i];
+        gcsadmm_wg_batch_fill(make_wg_desc(h, &states[i], true), vtab.data() + vbytes * (size_t)i);
+        cbs[i] = h->loop.d_cb.get();
+        b->resets[i] = h->resets;
+    }
+    HIPCHK(b, hipMemcpy(b->d_vertex_table.get(), vtab.data(), vtab.size(), hipMemcpyHostToDevice));
+    HIPCHK(b, hipMemcpy(b->d_cbs.get(), cbs.data(), sizeof(cbs[0]) * cbs.size(), hipMemcpyHostToDevice));
+    const gcsadmm_status est = with_state_type(bp.dtype == GCSADMM_F64, [&](auto t) -> gcsadmm_status {
+        using T = decltype(t);
+        std::vector<EdgeBatchEntry<T>> etab((size_t)count);
+        for (int i = 0; i < count; ++i) {
+            gcsadmm_handle h = b->members[i];
+            etab[i] = EdgeBatchEntry<T>{make_edge_args<T>(h, &states[i]), h->loop.d_cb.get(), h->loop.d_sums.get(), control_params(h), h->loop.d_counters.get(),
+                                        traces_dev ? traces_dev[i] : nullptr, h->loop.d_ticket.get(), h->plan.edge_blocks};
+        }
+        HIPCHK(b, hipMemcpy(b->d_edge_table.get(), etab.data(), sizeof(etab[0]) * etab.size(), hipMemcpyHostToDevice));
+        return GCSADMM_OK;
+    });
+    if (est != GCSADMM_OK) return est;
+    for (gcsadmm_handle h : b->members) h->batch = b;
+    b->bound = true;
+    return GCSADMM_OK;
+}
+
+gcsadmm_status gcsadmm_batch_run(struct gcsadmm_batch_s *b, int32_t k, void *stream)
+{
+    if (!b || k < 0) return GCSADMM_ERR_BAD_ARG;
+    if (!b->bound) { b->err = "gcsadmm_batch_bind has not been called"; return GCSADMM_ERR_BAD_ARG; }
+    for (size_t i = 0; i < b->members.size(); ++i)      // (bound: every member is alive and bound to this batch)
+        if (b->members[i]->resets != b->resets[i]) {
+            b->err = "member " + std::to_string(i) + ": gcsadmm_reset was called after gcsadmm_batch_bind (bind again: the tables hold the parameters)";
+            return GCSADMM_ERR_BAD_ARG;
+        }
+    DeviceGuard device_guard_(b->device);
+    HIPCHK(b, device_guard_.err);
+    for (int i = 0; i < k; ++i) {
+        const gcsadmm_status st = launch_batch_iteration(b, (hipStream_t)stream);
+        if (st != GCSADMM_OK) return st;
+    }
+    return GCSADMM_OK;
+}
+
+gcsadmm_status gcsadmm_batch_poll(struct gcsadmm_batch_s *b, int32_t *status, int32_t *it, void *stream)
+{
+    if (!b) return GCSADMM_ERR_BAD_ARG;
+    if (!b->bound) { b->err = "gcsadmm_batch_bind has not been called"; return GCSADMM_ERR_BAD_ARG; }
+    DeviceGuard device_guard_(b->device);
+    HIPCHK(b, device_guard_.err);
+    hipStream_t s = (hipStream_t)stream;
+    const int count = (int)b->members.size();
+    hipLaunchKernelGGL(batch_poll_kernel, dim3((count + 255) / 256), dim3(256), 0, s, b->d_cbs.get(), count, b->d_poll.get());
+    HIPCHK(b, hipGetLastError());
+    HIPCHK(b, hipMemcpyAsync(b->poll_host.data(), b->d_poll.get(), sizeof(int) * 2 * (size_t)count, hipMemcpyDeviceToHost, s));
+    HIPCHK(b, hipStreamSynchronize(s));
+    for (int i = 0; i < count; ++i) {
+        if (status) status[i] = b->poll_host[i];
+        if (it) it[i] = b->poll_host[count + i];
+    }
     return GCSADMM_OK;
 }
 

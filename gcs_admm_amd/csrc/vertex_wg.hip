@@ -58,6 +58,34 @@ void gcsadmm_wg_launch_split(const WgLaunchDesc &d, const WgSplitArgs &w, hipStr
 {
     if (!dispatch_dim<2, 3, 6>(d.n, [&](auto nn) { launch_split<decltype(nn)::value>(d, w, s); })) gcsadmm_wg_launch_split_dims(d, w, s);
 }
+
+// the batch form (one launch for many handles), 256-thread build only
+hipError_t gcsadmm_wg_set_batch_lds_dims(int n, int dtype, int lds_bytes);
+void gcsadmm_wg_launch_batch_dims(const WgBatchLaunch &b, hipStream_t s);
+
+size_t gcsadmm_wg_batch_entry_bytes(int dtype) { return dtype == GCSADMM_F64 ? sizeof(WgBatchEntry<double>) : sizeof(WgBatchEntry<float>); }
+
+int gcsadmm_wg_batch_fill(const WgLaunchDesc &d, void *entry_host)
+{
+    const int grid_x = d.n_vtx + (d.n_special + WG_THREADS - 1) / WG_THREADS;
+    with_state(d.dtype, [&](auto t) {
+        using T = decltype(t);
+        *(WgBatchEntry<T> *)entry_host = WgBatchEntry<T>{in_lds_args<T>(d), SpecialArgs{d.n_special, d.special_vtx, d.special_kind}, d.step.cb, grid_x};
+    });
+    return grid_x;
+}
+
+hipError_t gcsadmm_wg_set_batch_lds(int n, int dtype, int lds_bytes)
+{
+    hipError_t e = hipSuccess;
+    if (dispatch_dim<2, 3, 6>(n, [&](auto nn) { e = set_lds<BatchKernels, decltype(nn)::value>(dtype, lds_bytes); })) return e;
+    return gcsadmm_wg_set_batch_lds_dims(n, dtype, lds_bytes);
+}
+
+void gcsadmm_wg_launch_batch(const WgBatchLaunch &b, hipStream_t s)
+{
+    if (!dispatch_dim<2, 3, 6>(b.n, [&](auto nn) { launch_batch<decltype(nn)::value>(b, s); })) gcsadmm_wg_launch_batch_dims(b, s);
+}
 #endif
 
 #ifdef GCS_WG_TIMING

@@ -39,4 +39,16 @@ void gcsadmm_wg_launch_split_dims(const WgLaunchDesc &d, const WgSplitArgs &w, h
 {
     dispatch_dim<1, 4, 5, 7, 8>(d.n, [&](auto nn) { launch_split<decltype(nn)::value>(d, w, s); });
 }
+
+hipError_t gcsadmm_wg_set_batch_lds_dims(int n, int dtype, int lds_bytes)
+{
+    hipError_t e = hipErrorInvalidValue;
+    dispatch_dim<1, 4, 5, 7, 8>(n, [&](auto nn) { e = set_lds<BatchKernels, decltype(nn)::value>(dtype, lds_bytes); });
+    return e;
+}
+
+void gcsadmm_wg_launch_batch_dims(const WgBatchLaunch &b, hipStream_t s)
+{
+    dispatch_dim<1, 4, 5, 7, 8>(b.n, [&](auto nn) { launch_batch<decltype(nn)::value>(b, s); });
+}
 #endif

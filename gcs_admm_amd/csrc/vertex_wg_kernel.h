@@ -38,14 +38,14 @@ __device__ unsigned long long g_wg_block_ticks[64], g_wg_block_iters[64];
 // instantiation at n = 6 needs three -- 47 KB of LDS fit three times -- and lands at 167 registers on its own; asking for three made
 // the allocator spill 56 B, tests/test_build.py checks both.)
 template <int N, bool BOX> constexpr int wg_min_blocks() { return GCS_WG_MIN_BLOCKS == 1 ? 1 : (N <= 3 ? 4 : 2); }
+// what one workgroup of a vertex-step launch does once it knows its arguments: workgroup bx of the launch solves its generic vertex, the
+// trailing workgroups take the closed-form vertices.  One body for the kernel that gets its arguments in the kernarg segment
+// (vertex_wg_kernel) and the one that reads them from a table (vertex_wg_batch_kernel): the same instructions on the same numbers.
 template <int N, class T, bool BOX>
-__global__ __launch_bounds__(WG_THREADS, (wg_min_blocks<N, BOX>())) void vertex_wg_kernel(gcs_wg::WgArgs<T> a, SpecialArgs sp, const gcsadmm_control_block *cb)
+__device__ __forceinline__ void vertex_wg_body(const gcs_wg::WgArgs<T> &a, const SpecialArgs &sp, double rho, double mu_scale, int bx, double *smem)
 {
-    extern __shared__ __attribute__((aligned(16))) double smem[];
-    if (cb->status != GCSADMM_RUNNING) return;
-    const double rho = cb->rho, mu_scale = cb->mu_scale;
-    if ((int)blockIdx.x >= a.n_vtx) {      // closed-form vertices, one per thread
-        const int i = ((int)blockIdx.x - a.n_vtx) * WG_THREADS + (int)threadIdx.x;
+    if (bx >= a.n_vtx) {      // closed-form vertices, one per thread
+        const int i = (bx - a.n_vtx) * WG_THREADS + (int)threadIdx.x;
         if (i < sp.count) {
             double *vals = smem + (sp.kind[i] == 2 ? 2 * MAX_SPECIAL_DEG : 0);   // source and target: own work arrays in LDS
             special_body<N, T>(a, sp, i, rho, mu_scale, vals, vals + MAX_SPECIAL_DEG);
@@ -56,20 +56,55 @@ __global__ __launch_bounds__(WG_THREADS, (wg_min_blocks<N, BOX>())) void vertex_
 #ifdef GCS_WG_BLOCKTIME
     const unsigned long long t_begin = __builtin_amdgcn_s_memtime();
 #endif
-    const int slot = a.order ? a.order[blockIdx.x] : (int)blockIdx.x;
+    const int slot = a.order ? a.order[bx] : bx;
     gcs_wg::wg_solve_vertex<N, T, BOX>(a, a.vtx[slot], rho, mu_scale, smem, status, iters);
     if (threadIdx.x == 0) {
         if (status != 0) atomicAdd(&a.counters[0], 1);
         atomicAdd(&a.counters[1], iters);
         if (a.unit_iters) a.unit_iters[slot] = iters;
 #ifdef GCS_WG_BLOCKTIME
-        if (blockIdx.x < 64) {      // whole-solve ticks and Newton iterations of the first 64 workgroups (which one ends the launch?)
-            g_wg_block_ticks[blockIdx.x] += __builtin_amdgcn_s_memtime() - t_begin;
-            g_wg_block_iters[blockIdx.x] += (unsigned long long)iters;
+        if (bx < 64) {      // whole-solve ticks and Newton iterations of the first 64 workgroups (which one ends the launch?)
+            g_wg_block_ticks[bx] += __builtin_amdgcn_s_memtime() - t_begin;
+            g_wg_block_iters[bx] += (unsigned long long)iters;
         }
 #endif
     }
 }
+
+template <int N, class T, bool BOX>
+__global__ __launch_bounds__(WG_THREADS, (wg_min_blocks<N, BOX>())) void vertex_wg_kernel(gcs_wg::WgArgs<T> a, SpecialArgs sp, const gcsadmm_control_block *cb)
+{
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    if (cb->status != GCSADMM_RUNNING) return;
+    vertex_wg_body<N, T, BOX>(a, sp, cb->rho, cb->mu_scale, (int)blockIdx.x, smem);
+}
+
+#if GCS_WG_THREADS == 256
+// BATCH form (gcsadmm_batch_run): one launch serves many handles.  Row blockIdx.y of the grid is member blockIdx.y of the batch: the
+// workgroup copies that member's entry of the table -- the arguments vertex_wg_kernel gets in its kernarg segment, the member's own
+// control block and the width of its own grid -- and runs the body above on it.  The index is uniform over the workgroup, so the entry
+// comes in through scalar loads and lives in scalar registers as kernel arguments do.  Workgroups beyond the member's own grid (the
+// launch is as wide as the widest member) and those of a member that has stopped leave at once: the whole workgroup, before any barrier
+// or LDS use.  Built in the 256-thread objects only.
+template <class T> struct WgBatchEntry {
+    gcs_wg::WgArgs<T> a;
+    SpecialArgs sp;
+    const gcsadmm_control_block *cb;
+    int grid_x;                 // workgroups of this member: n_vtx + ceil(n_special / 256)
+};
+template <int N, class T, bool BOX>
+__global__ __launch_bounds__(WG_THREADS, (wg_min_blocks<N, BOX>())) void vertex_wg_batch_kernel(const WgBatchEntry<T> *__restrict__ table)
+{
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    // the table is written by the host before the launch and by nobody during it: it is read through the constant address space, as
+    // kernel arguments are, so that the compiler may reload a field where it needs it instead of keeping all of them live (read as
+    // plain global memory the entry cost 90 more registers and 250 bytes of scratch per lane)
+    __builtin_assume_dereferenceable(table + blockIdx.y, sizeof(WgBatchEntry<T>));
+    const WgBatchEntry<T> e = *(const WgBatchEntry<T> *)((const __attribute__((address_space(4))) WgBatchEntry<T> *)table + blockIdx.y);
+    if ((int)blockIdx.x >= e.grid_x || e.cb->status != GCSADMM_RUNNING) return;
+    vertex_wg_body<N, T, BOX>(e.a, e.sp, e.cb->rho, e.cb->mu_scale, (int)blockIdx.x, smem);
+}
+#endif
 
 // SPLIT form of the same program (wg_solve_vertex<N, T, BOX, true>): workgroup b solves vtx[b] with its units in the device-memory slab
 // units + unit_off[b] and only the fixed block and the polytope in LDS.  No closed-form vertices (they ride in the launch above), no
@@ -95,6 +130,9 @@ __global__ __launch_bounds__(WG_THREADS, (wg_split_min_blocks<N, BOX>())) void v
 // Newton iteration); at n = 2 the loops it shortens are two terms long and it measured 1 % slower, so n = 2 has none.
 struct InLdsKernels { template <int N, class T, bool BOX> static constexpr auto kernel() { return vertex_wg_kernel<N, T, BOX>; } };
 struct SplitKernels { template <int N, class T, bool BOX> static constexpr auto kernel() { return vertex_wg_split_kernel<N, T, BOX>; } };
+#if GCS_WG_THREADS == 256
+struct BatchKernels { template <int N, class T, bool BOX> static constexpr auto kernel() { return vertex_wg_batch_kernel<N, T, BOX>; } };
+#endif
 template <int N> constexpr bool WG_HAS_BOX = N == 3 || N == 6;
 // the state type of a launch (WgLaunchDesc::dtype)
 template <class F> auto with_state(int dtype, F &&f) { return with_state_type(dtype == GCSADMM_F64, f); }
@@ -121,13 +159,20 @@ template <class K, int N> hipError_t set_lds(int dtype, int lds_bytes)
     });
 }
 
+// the typed arguments of an in-LDS launch (the kernarg of vertex_wg_kernel, or a member's entry of the batch table)
+template <class T> gcs_wg::WgArgs<T> in_lds_args(const WgLaunchDesc &d)
+{
+    gcs_wg::WgArgs<T> a;
+    static_cast<StepArgs<T> &>(a) = d.step.typed<T>();
+    a.n_vtx = d.n_vtx; a.vtx = d.vtx; a.order = d.order; a.unit_iters = d.unit_iters;
+    return a;
+}
+
 template <int N> void launch(const WgLaunchDesc &d, hipStream_t s)
 {
     with_state(d.dtype, [&](auto t) {
         using T = decltype(t);
-        gcs_wg::WgArgs<T> a;
-        static_cast<StepArgs<T> &>(a) = d.step.typed<T>();
-        a.n_vtx = d.n_vtx; a.vtx = d.vtx; a.order = d.order; a.unit_iters = d.unit_iters;
+        const gcs_wg::WgArgs<T> a = in_lds_args<T>(d);
         const SpecialArgs sp{d.n_special, d.special_vtx, d.special_kind};
         const unsigned grid = (unsigned)(d.n_vtx + (d.n_special + WG_THREADS - 1) / WG_THREADS);
         if (grid == 0) return;
@@ -135,6 +180,21 @@ template <int N> void launch(const WgLaunchDesc &d, hipStream_t s)
         launch_kernels<InLdsKernels, N, T>(d, a, grid, lds, sp, s);
     });
 }
+
+#if GCS_WG_THREADS == 256
+// one launch for the whole batch: grid (widest member, members), the LDS of the largest member
+template <int N> void launch_batch(const WgBatchLaunch &b, hipStream_t s)
+{
+    with_state(b.dtype, [&](auto t) {
+        using T = decltype(t);
+        const auto *table = (const WgBatchEntry<T> *)b.table;
+        if constexpr (WG_HAS_BOX<N>) {
+            if (b.box) { hipLaunchKernelGGL((vertex_wg_batch_kernel<N, T, true>), dim3(b.grid_x, b.count), dim3(WG_THREADS), b.lds_bytes, s, table); return; }
+        }
+        hipLaunchKernelGGL((vertex_wg_batch_kernel<N, T, false>), dim3(b.grid_x, b.count), dim3(WG_THREADS), b.lds_bytes, s, table);
+    });
+}
+#endif
 
 template <int N> void launch_split(const WgLaunchDesc &d, const WgSplitArgs &w, hipStream_t s)
 {

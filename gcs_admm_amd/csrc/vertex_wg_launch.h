@@ -25,6 +25,15 @@ struct WgSplitArgs {
     const long long *unit_off;      // [n_vtx] offsets in doubles
 };
 
+// one vertex-step launch for a batch of handles (vertex_wg_batch_kernel; 256-thread objects only): `table` is a device array of `count`
+// entries, one per member, laid out by gcsadmm_wg_batch_fill
+struct WgBatchLaunch {
+    int n, dtype, box;              // shared by the members: one kernel instantiation serves the launch
+    const void *table;
+    unsigned grid_x, count;         // workgroups of the widest member, members
+    int lds_bytes;                  // dynamic LDS of the largest member
+};
+
 }  // namespace gcsadmm_k
 
 // (LDS sizes of the program, gcsadmm_wg_lds_bytes / _t512 and gcsadmm_wg_has_box: create_plan.h, which is host-only)
@@ -42,6 +51,14 @@ void gcsadmm_wg_launch_t512(const gcsadmm_k::WgLaunchDesc &d, hipStream_t s);
 // d.unit_iters are unused
 hipError_t gcsadmm_wg_set_split_lds(int n, int dtype, int lds_bytes);
 void gcsadmm_wg_launch_split(const gcsadmm_k::WgLaunchDesc &d, const gcsadmm_k::WgSplitArgs &w, hipStream_t s);
+
+// the batch form: bytes of one table entry for that state type; fill the entry at `entry_host` from the member's in-LDS launch (d.step.cb
+// is the member's control block; the entry records the width of the member's own grid and returns it); raise the batch kernels' dynamic-LDS
+// limit; launch
+size_t gcsadmm_wg_batch_entry_bytes(int dtype);
+int gcsadmm_wg_batch_fill(const gcsadmm_k::WgLaunchDesc &d, void *entry_host);
+hipError_t gcsadmm_wg_set_batch_lds(int n, int dtype, int lds_bytes);
+void gcsadmm_wg_launch_batch(const gcsadmm_k::WgBatchLaunch &b, hipStream_t s);
 
 // PROX configuration of the workgroup program (gcsadmm_vertex_prox): every vertex of `vtx` solves the border-only problem with
 // the separable quadratic (q, c) [V][4n+1]; the two terminals (points) are closed form.  zedge / mu / copy of `d` are unused.

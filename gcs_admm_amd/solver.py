@@ -303,6 +303,10 @@ class DeviceSolver:
             tm = self.enqueue_timed(k)
             return tm["vertex_ms"] + tm["edge_ms"]
         cb, wall, dev_ms = self._loop(enqueue_timed if timed else self.enqueue, chunk, params, clock=True)
+        return self.record(cb, wall, dev_ms * 1e-3 if timed else None)
+
+    def record(self, cb, wall_time_s, device_time_s=None):
+        """what ``solve`` returns, from the final control block and the trace (batch.BatchSolver builds its members' results with it)"""
         tr = self.trace[:min(cb.it, self.params.max_it)].cpu().numpy()
         return dict(iterations=int(cb.it), status=STATUS_NAME[cb.status],
                     rho_seq=np.concatenate([[self.params.rho], tr[:, 0]]),
@@ -310,4 +314,4 @@ class DeviceSolver:
                     dual_res_seq=np.concatenate([[0.0], tr[:, 2]]),
                     eps_pri_seq=tr[:, 3], eps_dual_seq=tr[:, 4],
                     inner_failures=int(tr[:, 5].sum()), cost=self.cost(),
-                    wall_time_s=wall, device_time_s=(dev_ms * 1e-3 if timed else None))
+                    wall_time_s=wall_time_s, device_time_s=device_time_s)

@@ -205,6 +205,46 @@ gcsadmm_status gcsadmm_run_timed(gcsadmm_handle h, const gcsadmm_state *st, int3
                                  float *edge_ms, int32_t *edge_launches);
 
 /* ---------------------------------------------------------------------------------------------
+ * Batches of handles: many small problems advance in one set of launches.  A small graph leaves most of the chip idle (benchmark4:
+ * 43 workgroups on 256 CUs) and its workgroup program is bound by dependent latency, so the lever for users with MANY small problems
+ * (motion planning: many start / goal queries, many scenes) is occupancy.  A batch is a set of ordinary handles: its launches pick the
+ * member by the second grid coordinate and run the device functions of the solo kernels on that member's own arguments, control block,
+ * counters, sums and ticket.  Every member therefore stops on its own (the others go on; its workgroups leave at once), and its
+ * state, control block and trace are bit for bit those of the same handle driven alone by gcsadmm_run with the same parameters.
+ *
+ * The handles stay owned by the caller and stay usable on their own while no launch of the batch is in flight.  Destroy the batch before
+ * its members; a batch whose member was destroyed first can only be destroyed (gcsadmm_batch_bind refuses it).
+ * Call order: gcsadmm_create per member; gcsadmm_batch_create; then per solve gcsadmm_reset on every member, gcsadmm_batch_bind, and
+ * gcsadmm_batch_run / gcsadmm_batch_poll until no member is RUNNING; gcsadmm_read_control, gcsadmm_cost etc. per member as usual.
+ *
+ * Eligibility (checked at create and again at bind; a violation returns GCSADMM_ERR_UNSUPPORTED or GCSADMM_ERR_BAD_ARG and the text
+ * names the member and the reason): at least one member, at most 65535, no handle twice, all on one device; the same n and
+ * state_dtype; every generic vertex on the in-LDS workgroup program with 256 threads (handles created with vertex_program = 3) and
+ * the same BOX choice (all polytopes canonical boxes at n = 3, 6, or not); no vertices on the wavefront program or in the split form,
+ * no terminal that is a region, fewer than 512 workgroup-program vertices, an edge step that runs one edge per thread (always the case
+ * below 131 072 edges), no communicator attached.  Members may differ in graph, sizes, LDS bytes, column numbering, ownership masks and every
+ * field of gcsadmm_params.  Every member keeps its own copy of its graph's polytope data, also where members share a scene.
+ */
+typedef struct gcsadmm_batch_s gcsadmm_batch_s;
+
+gcsadmm_status gcsadmm_batch_create(const gcsadmm_handle *members, int32_t count, struct gcsadmm_batch_s **out);
+void gcsadmm_batch_destroy(struct gcsadmm_batch_s *b);
+const char *gcsadmm_batch_last_error(struct gcsadmm_batch_s *b);   /* b may be NULL: error of the calling thread's last failed create */
+
+/* After gcsadmm_reset of every member: record each member's state pointers (states[count]), trace pointer (traces_dev[count], device
+ * pointers as for gcsadmm_run; the array or any entry may be NULL) and parameters, build the per-member argument tables and upload
+ * them once.  Synchronises `stream`.  A member that is bound to another batch is refused until that batch is destroyed or bound anew
+ * without it; a gcsadmm_reset of a member after the bind makes gcsadmm_batch_run fail until the batch is bound again. */
+gcsadmm_status gcsadmm_batch_bind(struct gcsadmm_batch_s *b, const gcsadmm_state *states, double *const *traces_dev, void *stream);
+
+/* Enqueue up to k iterations of every member that is still RUNNING, with no host synchronisation: per iteration ONE vertex launch and
+ * ONE edge + control launch for the whole batch.  A member whose stop test has fired is left exactly as it stopped. */
+gcsadmm_status gcsadmm_batch_run(struct gcsadmm_batch_s *b, int32_t k, void *stream);
+
+/* status[count] and it[count] of the members' control blocks in one copy (either may be NULL; synchronises `stream`). */
+gcsadmm_status gcsadmm_batch_poll(struct gcsadmm_batch_s *b, int32_t *status, int32_t *it, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * The x-update of the reference's OTHER splittings: admm_solver_v1.py:334-383 (shared by v2) solves,
  * per vertex, the border-only problem -- no edge blocks -- whose consensus penalty (:350-367) is a separable quadratic in the
  * vertex's own unknowns:
