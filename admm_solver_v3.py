@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""``python admm_solver_v3.py --test_file <module in test_data/> [--show_plot <anything>]``
+"""``python admm_solver_v3.py --test_file <module in test_data/> [--show_plot <anything>] [--rounding {host,device}]``
 
 Same command line, case contract (``As, bs, n`` in a ``test_data`` module) and result record as the
 reference's admm_solver_v3.py (:28-60, :735-775); a name with no module may be a graph file ``test_data/<name>.npz``
@@ -28,6 +28,8 @@ def main(argv=None):
     parser.add_argument("--test_file", type=str, default=DEFAULT_TEST_FILE,
                         help="The name of the test file (in `test_data` folder) to use (e.g., 'benchmark2').")
     parser.add_argument("--show_plot", type=str, default=True, help="Whether to display plot.")
+    parser.add_argument("--rounding", choices=("host", "device"), default="host",
+                        help="Where the convex restrictions of the rounding step are solved (an addition to the reference's command line).")
     args = parser.parse_args(argv)
     print("=======================================================================")
     print(f"Running ADMM Solver v3 on {args.test_file}")
@@ -95,7 +97,7 @@ def main(argv=None):
     I_v_out = {v: [] for v in V}      # (one pass over E; edge order kept, as utils.py:75-80)
     for e in E:
         I_v_out[e[0]].append(e)
-    final_cost, x_v_rounded, y_v_rounded = rounding(y_e_e_sol, V, E, I_v_out, As, bs, n)   # N=5, M=20 (:759)
+    final_cost, x_v_rounded, y_v_rounded = rounding(y_e_e_sol, V, E, I_v_out, As, bs, n, restriction=args.rounding)   # N=5, M=20 (:759)
     print(f"{x_v_rounded=}\n")
     print(f"{y_v_rounded=}\n")
     if args.show_plot == True:  # noqa: E712  (string semantics on purpose)

@@ -106,6 +106,8 @@ PROTOTYPES = {
     "gcsadmm_scene_candidate_pairs": ([_p, _d, _p], _i),
     "gcsadmm_scene_overlaps": ([_p, _d, _p, _p], _i),
     "gcsadmm_scene_read_pairs": ([_p] * 5, _i),
+    # the rounding step's path restrictions on a resident scene (gcs_admm_amd/rounding.py)
+    "gcsadmm_scene_restrict_paths": ([_p, _i, _p, _p, _p, _d, _i, _p, _p, _p, _p], _i),
 }
 EXPORTS = list(PROTOTYPES)
 

@@ -21,6 +21,10 @@
 //
 // A gcsadmm_scene keeps the polytopes, the centres, the boxes and the pair list on the device from the first LP to the last; its
 // broad phase is sweep_kernel (box_sweep_core.h has the contract), so that only counts and the final pair list cross to the host.
+//
+// The resident regions also serve the step after the loop: path_restrict_kernel solves the convex restriction along fixed paths
+// (path_restrict_core.h: one 64-lane workgroup per path, a block-tridiagonal Newton system factored along the path), on the offsets
+// and sizes restrict_plan.h decides.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -37,6 +41,8 @@
 
 #include "polytope_lp_core.h"
 #include "box_sweep_core.h"
+#include "path_restrict_core.h"
+#include "restrict_plan.h"
 
 // the calling thread's last failure (gcsadmm_polytope_last_error)
 static thread_local std::string g_err;
@@ -160,6 +166,65 @@ __global__ __launch_bounds__(SWEEP_WAVE) void sweep_kernel(SortedBoxes B, double
     if (!FILL && lane == 0) count[k] = total;
 }
 
+// ---- path restrictions on the resident regions ----
+// executor of path_restrict_solve: one wavefront; reductions by shuffles in a fixed order (bit-reproducible, and the same whatever
+// else the launch holds); the barrier first waits for the wavefront's global accesses (the phases hand values over through the
+// workspace: vertex_wg.h WG_VM has the reason)
+struct RestrictExec {
+    __device__ __forceinline__ int tid() const { return (int)threadIdx.x; }
+    __device__ __forceinline__ int nthreads() const { return gcsadmm_k::RESTRICT_THREADS; }
+    __device__ __forceinline__ int task(int u, int) const { return u; }
+    __device__ __forceinline__ void sync()
+    {
+        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+        __syncthreads();
+    }
+    __device__ __forceinline__ void reduce3(double &mn, double &s1, double &s2)
+    {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            mn = fmin(mn, __shfl_xor(mn, off, 64));
+            s1 += __shfl_xor(s1, off, 64);
+            s2 += __shfl_xor(s2, off, 64);
+        }
+    }
+};
+
+struct RestrictArgs {
+    const int *poly_ptr;
+    const double *A, *b;
+    const int *path_ptr, *path_poly, *row_prefix;
+    const long long *ws_off;
+    double *ws;
+    const double *start;
+    double *points, *cost;
+    int *iterations, *status;
+    double tol;
+    int max_iter, num_paths;
+};
+
+template <int N>
+__global__ __launch_bounds__(gcsadmm_k::RESTRICT_THREADS) void path_restrict_kernel(RestrictArgs a)
+{
+    __shared__ gcs_restrict::PathShared<N> sh;
+    const int p = (int)blockIdx.x;
+    if (p >= a.num_paths) return;
+    const int first = a.path_ptr[p];
+    gcs_restrict::PathProblem pr;
+    pr.k = a.path_ptr[p + 1] - first;
+    pr.poly = a.path_poly + first;
+    pr.rowp = a.row_prefix + first + 2 * (size_t)p;
+    pr.poly_ptr = a.poly_ptr; pr.A = a.A; pr.b = a.b;
+    pr.start = a.start + (size_t)(first + p) * N;
+    pr.points = a.points + (size_t)(first + p) * N;
+    pr.tol = a.tol; pr.max_iter = a.max_iter;
+    RestrictExec ex;
+    double cost;
+    int iterations;
+    const int st = gcs_restrict::path_restrict_solve<N>(ex, pr, a.ws + a.ws_off[p], sh, &cost, &iterations);
+    if (threadIdx.x == 0) { a.cost[p] = cost; a.iterations[p] = iterations; a.status[p] = st; }
+}
+
 } // namespace gcsadmm_lp
 
 using namespace gcsadmm_lp;
@@ -171,6 +236,7 @@ struct gcsadmm_scene_s {
     int maxm = 0;                                      // most rows of one polytope
     DevBuf<int> ptr;                                   // the polytopes: CSR, rows, right-hand sides, norms of the rows (S points at them)
     DevBuf<double> A, b, nrm;
+    std::vector<int> h_ptr;                            // the CSR offsets on the host too (a resident scene's: restrict_plan.h reads them)
     Polys S{};
     DevBuf<double> w, cen, rad;                        // centre LPs: (x, r) records, centres [P][n], radii,
     DevBuf<int> st_c;                                  //   statuses
@@ -322,6 +388,14 @@ int launch_sweep(gcsadmm_scene_s *s, bool fill, double pad)
     return GCSADMM_OK;
 }
 
+template <int N>
+int launch_restrict(const gcsadmm_k::RestrictPlan &rp, const RestrictArgs &a)
+{
+    hipLaunchKernelGGL(path_restrict_kernel<N>, dim3((unsigned)rp.grid), dim3((unsigned)rp.threads), 0, 0, a);
+    LPCHK(hipGetLastError());
+    return GCSADMM_OK;
+}
+
 // ---- the three LP stages, on the scene's buffers: what both families of entry points run ----
 // centre LPs of all polytopes into w and st_c, then the centres and radii out of the records
 int run_centers(gcsadmm_scene_s *s)
@@ -437,6 +511,7 @@ int gcsadmm_scene_create(int n, int num_polytopes, const int *poly_ptr, const do
     int rc;
     try {
         rc = upload_scene(*s, guard, n, num_polytopes, poly_ptr, poly_A, poly_b, device);
+        if (rc == GCSADMM_OK) s->h_ptr.assign(poly_ptr, poly_ptr + num_polytopes + 1);
     } catch (const std::bad_alloc &) {
         g_err = "out of host memory"; rc = GCSADMM_ERR_NO_MEMORY;
     }
@@ -576,6 +651,46 @@ int gcsadmm_scene_read_pairs(gcsadmm_scene s, int *pair_a, int *pair_b, unsigned
     if ((overlap || status) && !s->have_overlaps) { g_err = "the resident pairs are not decided: call gcsadmm_scene_overlaps first"; return GCSADMM_ERR_BAD_ARG; }
     LPCHK(download(pair_a, s->pa)); LPCHK(download(pair_b, s->pb));
     return read_decisions(s, overlap, status);
+}
+
+static int restrict_paths(gcsadmm_scene s, int num_paths, const int *path_ptr, const int *path_poly, const double *start, double tol,
+                          int max_iter, double *points, double *cost, int *iterations, int *status)
+{
+    USE_SCENE(s);
+    gcsadmm_k::RestrictPlan rp;
+    if (int rc = gcsadmm_k::make_restrict_plan(s->n, s->P, s->h_ptr.data(), num_paths, path_ptr, path_poly, rp, g_err)) return rc;
+    if (!(tol > 0.0) || max_iter < 0) { g_err = "tol must be positive and max_iter non-negative"; return GCSADMM_ERR_BAD_ARG; }
+    if (num_paths == 0) return GCSADMM_OK;
+    if (!start) { g_err = "null start"; return GCSADMM_ERR_BAD_ARG; }
+    const size_t coords = (size_t)rp.total_points * s->n;
+    DevBuf<int> d_path_ptr, d_path_poly, d_prefix, d_iterations, d_status;
+    DevBuf<long long> d_ws_off;
+    DevBuf<double> d_ws, d_start, d_points, d_cost;
+    LPCHK(d_path_ptr.upload(path_ptr, (size_t)num_paths + 1));
+    LPCHK(d_path_poly.upload(path_poly, (size_t)rp.total_regions));
+    LPCHK(d_prefix.upload(rp.row_prefix.data(), rp.row_prefix.size()));
+    LPCHK(d_ws_off.upload(rp.ws_off.data(), rp.ws_off.size()));
+    LPCHK(d_start.upload(start, coords));
+    LPCHK(d_ws.alloc((size_t)rp.ws_doubles));
+    LPCHK(d_points.alloc(coords)); LPCHK(d_cost.alloc((size_t)num_paths));
+    LPCHK(d_iterations.alloc((size_t)num_paths)); LPCHK(d_status.alloc((size_t)num_paths));
+    const RestrictArgs a{s->ptr.get(), s->A.get(), s->b.get(), d_path_ptr.get(), d_path_poly.get(), d_prefix.get(), d_ws_off.get(), d_ws.get(),
+                         d_start.get(), d_points.get(), d_cost.get(), d_iterations.get(), d_status.get(), tol, max_iter, num_paths};
+    const int rc = for_dim(s->n, [&](auto N) { return launch_restrict<decltype(N)::value>(rp, a); });
+    if (rc != GCSADMM_OK) return rc;
+    LPCHK(download(points, d_points)); LPCHK(download(cost, d_cost)); LPCHK(download(iterations, d_iterations)); LPCHK(download(status, d_status));
+    LPCHK(hipStreamSynchronize(nullptr));
+    return GCSADMM_OK;
+}
+
+int gcsadmm_scene_restrict_paths(gcsadmm_scene s, int num_paths, const int *path_ptr, const int *path_poly, const double *start, double tol,
+                                 int max_iter, double *points, double *cost, int *iterations, int *status)
+{
+    try {
+        return restrict_paths(s, num_paths, path_ptr, path_poly, start, tol, max_iter, points, cost, iterations, status);
+    } catch (const std::bad_alloc &) {      // the plan's host arrays
+        g_err = "out of host memory"; return GCSADMM_ERR_NO_MEMORY;
+    }
 }
 
 } // extern "C"

@@ -1,7 +1,10 @@
 """Rounding of the relaxed edge activations to an s-t path and the convex restriction along it --
 the step that follows the ADMM loop in the reference (GCS_utils.py:92-181 ``rounding``,
 :17-89 ``solve_convex_restriction``; called at admm_solver_v3.py:759 with N=5, M=20, the case file's
-own N, M being ignored -- quirk Q5).  SURVEY.md section 8(f) item 1; runs once, on the host.
+own N, M being ignored -- quirk Q5).  SURVEY.md section 8(f) item 1; runs once, on the host by default.
+``restriction="device"`` solves all candidate paths side by side on the MI355X (csrc/path_restrict_core.h
+through ``gcsadmm_scene_restrict_paths``); the walk stays on the host, and ``rounding_many`` does the same
+for the candidates of many problems in one call per round.
 
 Differences from the reference, on purpose: the random walk is seeded (the reference draws from the
 unseeded global numpy generator, GCS_utils.py:131, so its runs are not reproducible), and the
@@ -89,12 +92,165 @@ def most_probable_path(y_e, I_v_out) -> Optional[List[Hashable]]:
     return path
 
 
-def rounding(y_e_sol, V, E, I_v_out, As, bs, n, N=5, M=20, seed=0):
+def path_point_regions(path):
+    """regions of every point of the polyline along ``path``: point j lies in path[j-1] and path[j] (the ends: in one region)"""
+    k = len(path)
+    return [(path[0],)] + [(path[j - 1], path[j]) for j in range(1, k)] + [(path[-1],)]
+
+
+def solve_path_restrictions(As, bs, n, paths, centers, restrict):
+    """``solve_path_restriction`` for many paths at once, on injected callables (tests run this logic without a GPU):
+    ``centers(polys) -> (centres, radii, status)`` are the Chebyshev-centre LPs of a list of polytopes, ``restrict(polys, paths,
+    starts) -> (points, cost, iterations, status)`` the restriction along paths of INDICES into ``polys`` (the contract of
+    ``DeviceScene.restrict_paths``).  The start points are the centres of the distinct one- or two-region intersections, from ONE
+    call of ``centers``; a radius <= 0 or a failed LP makes the path infeasible without solving it.  Returns ``(cost, xs)`` per
+    path in the shape of ``solve_path_restriction``; an infeasible path (no start, or status 1) gives ``(inf, None)``.  A solve
+    that FAILED (status -1: iteration limit, vanished step) says nothing about feasibility: it gives ``(inf, xs)`` with its last
+    iterate, so that the caller counts the path as visited, as the host loop does with whatever its solver returns, but never
+    prefers it."""
+    keys = list(As)
+    index = {v: i for i, v in enumerate(keys)}
+    polys = [(np.asarray(As[v], float), np.asarray(bs[v], float)) for v in keys]
+    inter = {}
+    for path in paths:
+        for reg in path_point_regions(path):
+            inter.setdefault(reg, len(inter))
+    out = [(float('inf'), None)] * len(paths)
+    if not inter:
+        return out
+    cen, rad, st = centers([(np.vstack([polys[index[v]][0] for v in reg]), np.hstack([polys[index[v]][1] for v in reg])) for reg in inter])
+    usable = (np.asarray(st) >= 0) & (np.asarray(rad) > 0)
+    live, starts = [], []
+    for p, path in enumerate(paths):
+        ids = [inter[reg] for reg in path_point_regions(path)]
+        if all(usable[i] for i in ids):
+            live.append(p); starts.append(np.asarray(cen)[ids])
+    if live:
+        pts, cost, _, status = restrict(polys, [[index[v] for v in paths[p]] for p in live], starts)
+        for i, p in enumerate(live):
+            if status[i] <= 0:
+                q = np.asarray(pts[i])
+                out[p] = (float(cost[i]) if status[i] == 0 else float('inf'), {v: np.concatenate([q[j], q[j + 1]]) for j, v in enumerate(paths[p])})
+    return out
+
+
+def solve_path_restrictions_device(As, bs, n, paths, device=0, scene=None):
+    """``(cost, xs)`` of ``solve_path_restriction`` for every path of ``paths``, solved side by side on the device: the start
+    points from one call of the centre LPs on a temporary scene of the distinct intersections, the restrictions from one call
+    of ``gcsadmm_scene_restrict_paths``.  ``scene``: a ``DeviceScene`` of the regions in the order of ``As`` (left open), so that
+    many calls reuse one upload.  There is no CPU fallback."""
+    from .scene import DeviceScene, PolytopeScene
+    own = scene is None
+
+    def restrict(polys, idx_paths, starts):
+        nonlocal scene
+        if scene is None:
+            scene = DeviceScene(polys, device)
+        return scene.restrict_paths(idx_paths, starts)
+    try:
+        return solve_path_restrictions(As, bs, n, paths, lambda polys: PolytopeScene(polys, device).centers(), restrict)
+    finally:
+        if own and scene is not None:
+            scene.close()
+
+
+class _Candidates:
+    """The candidate paths of ``rounding`` in the order the host loop visits them, handed out in rounds: the most probable path,
+    then seeded walks until N distinct paths are feasible or pending, or M draws are spent.  When a round comes back with
+    infeasible paths the next one goes on drawing with the remaining draws -- the draws and the list are the host loop's."""
+
+    def __init__(self, y_e_sol, I_v_out, N, M, seed):
+        self.y_e, self.I_out, self.N, self.draws_left = y_e_sol, I_v_out, N, M
+        self.rng = np.random.default_rng(seed)
+        self.seen, self.cands, self.started = set(), [], False
+
+    def next_round(self):
+        pending = []
+        if not self.started:
+            self.started = True
+            first = most_probable_path(self.y_e, self.I_out)
+            if first is not None:
+                self.seen.add(tuple(first)); pending.append(first)
+        while self.draws_left > 0 and len(self.cands) + len(pending) < self.N:
+            self.draws_left -= 1
+            pth = find_path_via_random_dfs(self.y_e, self.I_out, self.rng)
+            if pth is None or tuple(pth) in self.seen:
+                continue
+            self.seen.add(tuple(pth)); pending.append(pth)
+        return pending
+
+    def take(self, pending, results):
+        self.cands += [(cost, pth, xs) for pth, (cost, xs) in zip(pending, results) if xs is not None]
+
+
+def _rounded(cands, V, n):
+    cands = [c for c in cands if np.isfinite(c[0])]        # (a failed solve was a candidate of the walk, never a result)
+    if not cands:
+        print("Rounding failed to find any feasible paths.")
+        return float('inf'), None, None
+    cost, pth, xs = min(cands, key=lambda t: t[0])
+    return cost, {v: xs.get(v, np.zeros(2 * n)) for v in V}, {v: (1 if v in xs else 0) for v in V}
+
+
+def rounding_many(problems, N=5, M=20, device=0, solver=None):
+    """``rounding(..., restriction="device")`` for many problems at once (the members of a ``BatchSolver``, for instance):
+    ``problems`` is a list of dicts with the arguments of ``rounding`` (``y_e_sol, V, E, I_v_out, As, bs, n`` and optionally
+    ``seed``), all of one dimension n.  The candidates of every problem are solved in ONE call per round, on one scene over the
+    concatenated regions.  Returns the list of ``(cost, x_v_rounded, y_v_rounded)``, each exactly what ``rounding`` returns for
+    that problem alone.  ``solver``: as in ``rounding``, on the concatenated regions (keys ``(problem index, region key)``)."""
+    if not problems:
+        return []
+    n = problems[0]["n"]
+    if any(pr["n"] != n for pr in problems):
+        raise ValueError("rounding_many needs problems of one dimension n")
+    As = {(i, v): pr["As"][v] for i, pr in enumerate(problems) for v in pr["As"]}
+    bs = {(i, v): pr["bs"][v] for i, pr in enumerate(problems) for v in pr["As"]}
+    scene = None
+    if solver is None:
+        from .scene import DeviceScene
+        scene = DeviceScene([(np.asarray(As[k], float), np.asarray(bs[k], float)) for k in As], device)
+        solver = lambda As_, bs_, n_, paths: solve_path_restrictions_device(As_, bs_, n_, paths, device, scene)
+    try:
+        gens = [_Candidates(pr["y_e_sol"], pr["I_v_out"], N, M, pr.get("seed", 0)) for pr in problems]
+        while True:
+            rounds = [g.next_round() for g in gens]
+            if not any(rounds):
+                break
+            results = solver(As, bs, n, [[(i, v) for v in pth] for i, pend in enumerate(rounds) for pth in pend])
+            at = 0
+            for i, (g, pend) in enumerate(zip(gens, rounds)):
+                mine = [(cost, None if xs is None else {k[1]: x for k, x in xs.items()}) for cost, xs in results[at:at + len(pend)]]
+                g.take(pend, mine)
+                at += len(pend)
+    finally:
+        if scene is not None:
+            scene.close()
+    return [_rounded(g.cands, pr["V"], n) for g, pr in zip(gens, problems)]
+
+
+def rounding(y_e_sol, V, E, I_v_out, As, bs, n, N=5, M=20, seed=0, restriction="host", solver=None, device=0):
     """Up to M seeded random walks, at most N distinct paths, best restricted cost wins
     (GCS_utils.py:148-181); the deterministic most-probable path is tried first (an addition: it
     removes most of the run-to-run variation the reference's unseeded sampling has).  Returns
     (cost, x_v_rounded, y_v_rounded) with the reference's shapes: every vertex has an entry;
-    off-path vertices get x = 0, y = 0."""
+    off-path vertices get x = 0, y = 0.
+
+    ``restriction``: ``"host"`` (the default: one ``solve_path_restriction`` after the other, as before) or ``"device"``: the
+    same candidates from the same draws, collected first and solved in one call of ``solver(As, bs, n, paths) -> [(cost, xs)]``
+    (default ``solve_path_restrictions_device`` on ``device``); when paths come back infeasible, drawing goes on with the
+    remaining draws, so that for one seed the candidate list is the host's."""
+    if restriction not in ("host", "device"):
+        raise ValueError(f"restriction must be 'host' or 'device', not {restriction!r}")
+    if restriction == "device":
+        if solver is None:
+            solver = lambda As_, bs_, n_, paths: solve_path_restrictions_device(As_, bs_, n_, paths, device)
+        gen = _Candidates(y_e_sol, I_v_out, N, M, seed)
+        while True:
+            pending = gen.next_round()
+            if not pending:
+                break
+            gen.take(pending, solver(As, bs, n, pending))
+        return _rounded(gen.cands, V, n)
     rng = np.random.default_rng(seed)
     seen, cands = set(), []
     first = most_probable_path(y_e_sol, I_v_out)

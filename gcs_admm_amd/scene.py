@@ -206,6 +206,25 @@ class DeviceScene:
         return pa, pb, flags, st
 
 
+    def restrict_paths(self, paths, start, tol: float = 1e-10, max_iter: int = 100):
+        """The convex restriction along every path of ``paths`` (sequences of region indices, in order), all in one launch
+        (``gcsadmm_scene_restrict_paths``): path p has ``len(paths[p]) + 1`` points, point j in regions j - 1 and j of the path.
+        ``start[p]`` [k_p + 1, n] are start points strictly inside their rows.  Returns (points: a list of [k_p + 1, n] arrays, cost
+        [num_paths], Newton iterations, status): status 0 converged, 1 a start point is not strictly inside (an infeasible path), -1
+        failed; the cost is the polyline length, ``inf`` unless the status is 0.  Needs none of the other calls to have run."""
+        num = len(paths)
+        ptr = np.zeros(num + 1, np.int32)
+        ptr[1:] = np.cumsum([len(p) for p in paths])
+        poly = np.ascontiguousarray(np.concatenate([np.asarray(p, np.int64).ravel() for p in paths]) if num else np.zeros(0), np.int32)
+        x0 = np.ascontiguousarray(np.concatenate([np.asarray(s, float).reshape(-1, self.n) for s in start]) if num else np.zeros((0, self.n)))
+        if x0.shape[0] != int(ptr[-1]) + num:
+            raise ValueError("start needs len(path) + 1 points for every path")
+        pts = np.empty_like(x0); cost = np.empty(num); its = np.empty(num, np.int32); st = np.empty(num, np.int32)
+        self._call("gcsadmm_scene_restrict_paths", num, ptr.ctypes.data, poly.ctypes.data, x0.ctypes.data, float(tol), int(max_iter),
+                   pts.ctypes.data, cost.ctypes.data, its.ctypes.data, st.ctypes.data)
+        return [pts[int(ptr[p]) + p:int(ptr[p + 1]) + p + 1] for p in range(num)], cost, its, st
+
+
 def edge_arrays(pa, pb, flags):
     """both directions of every intersecting pair in the reference's double-loop order (by tail, then head), int32"""
     keep = np.asarray(flags) != 0

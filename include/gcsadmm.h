@@ -384,6 +384,22 @@ int gcsadmm_scene_overlaps(gcsadmm_scene s, double tol, int64_t *num_overlapping
 /* The resident pair list, num_pairs entries each; overlap and status need gcsadmm_scene_overlaps to have run. */
 int gcsadmm_scene_read_pairs(gcsadmm_scene s, int *pair_a, int *pair_b, unsigned char *overlap, int *status);
 
+/* The convex restriction along fixed paths through the resident regions (the rounding step after the loop; gcs_admm_amd/rounding.py),
+ * all paths of the call side by side, one 64-lane workgroup each (path_restrict_core.h).  Path p visits the k_p >= 1 regions
+ * path_poly[path_ptr[p] .. path_ptr[p + 1]) in order and has k_p + 1 points q_0 .. q_k: q_j lies in region j - 1 (j >= 1) and in
+ * region j (j <= k_p - 1); the sum of the segment lengths |q_{j+1} - q_j| is minimised.  A terminal that is a point is a region like
+ * any other (a box of half-width 1e-6).  start and points hold path p's points at offset (path_ptr[p] + p) * n; start must be strictly
+ * inside the rows of every point (the Chebyshev centres of the intersections, for instance).  tol > 0 is the stop on the barrier
+ * parameter mu, max_iter >= 0 the limit on Newton iterations.
+ * status[p]: 0 converged (mu <= tol); 1 a start point is not strictly inside its rows (treat the path as infeasible); -1 failed
+ * (iteration limit, non-finite iterate, vanished step above tol).  cost[p] is the polyline length recomputed from points, inf unless
+ * status[p] is 0; iterations[p] the Newton iterations taken.  One path's status never affects another's.  Needs none of the other
+ * scene calls to have run.  A region index out of range or a path without regions: GCSADMM_ERR_BAD_ARG; totals beyond 2^31 - 1
+ * (rows of one path, point coordinates of the call) or a workspace beyond 2^40 doubles: GCSADMM_ERR_UNSUPPORTED, before anything is
+ * allocated. */
+int gcsadmm_scene_restrict_paths(gcsadmm_scene s, int num_paths, const int *path_ptr, const int *path_poly, const double *start, double tol,
+                                 int max_iter, double *points, double *cost, int *iterations, int *status);
+
 #ifdef __cplusplus
 }
 #endif
