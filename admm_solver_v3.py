@@ -79,11 +79,12 @@ def main(argv=None):
     elif res["status"] == "diverged":
         print("BREAKING FOR Divergence")
     xv, zv, yv = dev.xv.cpu().numpy(), dev.zv.cpu().numpy(), dev.yv.cpu().numpy()
-    ye = dev.zedge[2 * n].cpu().numpy()
+    from gcs_admm_amd.rounding import rounding, rounding_problem
+    problem = rounding_problem(dev, As, bs)          # (the edge activations and the out-lists: one pass over E, edge order kept)
     x_v_sol = {v: xv[i] for i, v in enumerate(V)}
     y_v_sol = {v: float(yv[i]) for i, v in enumerate(V)}
     z_v_sol = {v: zv[i] for i, v in enumerate(V)}
-    y_e_e_sol = {e: float(ye[i]) for i, e in enumerate(E)}
+    y_e_e_sol, I_v_out = problem["y_e_sol"], problem["I_v_out"]
     cost = compute_cost(z_v_sol, y_e_e_sol)
     print(f"x_v: {x_v_sol}")
     print(f"y_v: {y_v_sol}")
@@ -93,10 +94,6 @@ def main(argv=None):
     print("===============================================================")
     print("POST-ROUNDING")
     print("===============================================================")
-    from gcs_admm_amd.rounding import rounding
-    I_v_out = {v: [] for v in V}      # (one pass over E; edge order kept, as utils.py:75-80)
-    for e in E:
-        I_v_out[e[0]].append(e)
     final_cost, x_v_rounded, y_v_rounded = rounding(y_e_e_sol, V, E, I_v_out, As, bs, n, restriction=args.rounding)   # N=5, M=20 (:759)
     print(f"{x_v_rounded=}\n")
     print(f"{y_v_rounded=}\n")

@@ -108,6 +108,9 @@ PROTOTYPES = {
     "gcsadmm_scene_read_pairs": ([_p] * 5, _i),
     # the rounding step's path restrictions on a resident scene (gcs_admm_amd/rounding.py)
     "gcsadmm_scene_restrict_paths": ([_p, _i, _p, _p, _p, _d, _i, _p, _p, _p, _p], _i),
+    # the regions under query points on a resident scene (gcs_admm_amd/queries.py)
+    "gcsadmm_scene_locate_points": ([_p, _i, _p, _d, _d, _p], _i),
+    "gcsadmm_scene_read_hits": ([_p] * 4, _i),
 }
 EXPORTS = list(PROTOTYPES)
 

@@ -25,6 +25,9 @@
 // The resident regions also serve the step after the loop: path_restrict_kernel solves the convex restriction along fixed paths
 // (path_restrict_core.h: one 64-lane workgroup per path, a block-tridiagonal Newton system factored along the path), on the offsets
 // and sizes restrict_plan.h decides.
+//
+// And the queries on a scene whose graph is decided: locate_kernel lists the regions under each start and goal point
+// (point_locate_core.h has the rule), so that a query costs no region-region LP.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -41,6 +44,7 @@
 
 #include "polytope_lp_core.h"
 #include "box_sweep_core.h"
+#include "point_locate_core.h"
 #include "path_restrict_core.h"
 #include "restrict_plan.h"
 
@@ -225,6 +229,46 @@ __global__ __launch_bounds__(gcsadmm_k::RESTRICT_THREADS) void path_restrict_ker
     if (threadIdx.x == 0) { a.cost[p] = cost; a.iterations[p] = iterations; a.status[p] = st; }
 }
 
+// ---- the regions under query points ----
+struct LocateArgs {
+    LocateRegions R;
+    const double *points;      // [num_points][N]
+    double margin;             // eps + 2 tol
+    int first_point;           // blockIdx.y counts from here (one launch takes at most 65 535 points)
+    long long chunks, limit;   // chunks of the P regions; length of the list
+    int *count;                // [num_points][chunks]
+    const long long *offset;   // [num_points][chunks]
+    int *hit_region;
+    unsigned char *hit_class;
+};
+
+// one 64-lane workgroup per (chunk of regions, point), one region per lane.  FILL = false: count[point][chunk] = regions of the chunk
+// that are not OUT; FILL = true: the same tests again, the hits written from offset[point][chunk] on in region order.
+template <int N, bool FILL>
+__global__ __launch_bounds__(LOCATE_WAVE) void locate_kernel(LocateArgs a)
+{
+    const long long chunk = blockIdx.x, q = (long long)a.first_point + blockIdx.y;
+    const int lane = threadIdx.x;
+    double p[N];
+#pragma unroll
+    for (int k = 0; k < N; ++k) p[k] = a.points[(size_t)q * N + k];      // the same address in every lane
+    const size_t cell = (size_t)(q * a.chunks + chunk);
+    long long pos = FILL ? a.offset[cell] : 0;
+    int total = 0;
+    for (int stride = 0; stride < LOCATE_CHUNK / LOCATE_WAVE; ++stride) {
+        const int region = locate_region(a.R.P, chunk, stride, lane);
+        const int cls = locate_lane<N>(a.R, region, p, a.margin);
+        const unsigned long long mask = __ballot(cls != LOCATE_OUT);
+        if (FILL) {
+            locate_store(a.hit_region, a.hit_class, pos, a.limit, mask, lane, region, cls);
+            pos += locate_hits(mask);
+        } else {
+            total += locate_hits(mask);
+        }
+    }
+    if (!FILL && lane == 0) a.count[cell] = total;
+}
+
 } // namespace gcsadmm_lp
 
 using namespace gcsadmm_lp;
@@ -250,6 +294,13 @@ struct gcsadmm_scene_s {
     DevBuf<unsigned long long> counts;                 //   and the two counts of them
     long long T = 0;
     bool have_centers = false, have_boxes = false, have_pairs = false, have_overlaps = false;
+    DevBuf<double> q_points;                           // queries (kept and grown from call to call): the points [num_points][n],
+    DevBuf<int> q_count;                               //   counts and
+    DevBuf<long long> q_offset;                        //   offsets per (point, chunk),
+    DevBuf<int> hit_region;                            //   the hit list
+    DevBuf<unsigned char> hit_class;
+    std::vector<int64_t> hit_ptr;                      //   and its segments per point (host: the scan runs there)
+    bool have_hits = false;
 };
 
 namespace {
@@ -393,6 +444,30 @@ int launch_restrict(const gcsadmm_k::RestrictPlan &rp, const RestrictArgs &a)
 {
     hipLaunchKernelGGL(path_restrict_kernel<N>, dim3((unsigned)rp.grid), dim3((unsigned)rp.threads), 0, 0, a);
     LPCHK(hipGetLastError());
+    return GCSADMM_OK;
+}
+
+// room for count elements in a buffer that outlives the call (the query buffers: a call with no more points or hits than an earlier
+// one allocates nothing)
+template <class T> hipError_t reserve(DevBuf<T> &buf, size_t count)
+{
+    if (buf && buf.size() >= count) return hipSuccess;
+    buf.reset();
+    return buf.alloc(count);
+}
+
+template <int N>
+int launch_locate(const LocateArgs &args, long long num_points, bool fill)
+{
+    constexpr long long SLAB = 65535;      // grid.y
+    for (long long q0 = 0; q0 < num_points; q0 += SLAB) {
+        LocateArgs a = args;
+        a.first_point = (int)q0;
+        const dim3 grid((unsigned)a.chunks, (unsigned)std::min(SLAB, num_points - q0));
+        if (fill) hipLaunchKernelGGL((locate_kernel<N, true>), grid, dim3(LOCATE_WAVE), 0, 0, a);
+        else hipLaunchKernelGGL((locate_kernel<N, false>), grid, dim3(LOCATE_WAVE), 0, 0, a);
+        LPCHK(hipGetLastError());
+    }
     return GCSADMM_OK;
 }
 
@@ -691,6 +766,72 @@ int gcsadmm_scene_restrict_paths(gcsadmm_scene s, int num_paths, const int *path
     } catch (const std::bad_alloc &) {      // the plan's host arrays
         g_err = "out of host memory"; return GCSADMM_ERR_NO_MEMORY;
     }
+}
+
+static int locate_points(gcsadmm_scene s, int num_points, const double *points, double eps, double tol, int64_t *num_hits)
+{
+    USE_SCENE(s);
+    if (num_points < 0 || (num_points > 0 && !points)) { g_err = "negative number of points or null points"; return GCSADMM_ERR_BAD_ARG; }
+    if (!(eps >= 0.0) || !(tol >= 0.0) || std::isinf(eps) || std::isinf(tol)) { g_err = "eps and tol must be finite and non-negative"; return GCSADMM_ERR_BAD_ARG; }
+    const size_t coords = (size_t)num_points * s->n;
+    for (size_t i = 0; i < coords; ++i)
+        if (!std::isfinite(points[i])) { g_err = "point with a NaN or an inf coordinate"; return GCSADMM_ERR_BAD_ARG; }
+    s->have_hits = false;
+    const long long Q = num_points, chunks = locate_chunks(s->P);
+    const size_t cells = (size_t)(Q * chunks);
+    std::vector<int> count(cells);
+    std::vector<long long> offset(cells);
+    std::vector<int64_t> hit_ptr((size_t)Q + 1, 0);
+    LocateArgs a{};
+    a.R = LocateRegions{s->P, s->ptr.get(), s->A.get(), s->b.get()};
+    a.margin = eps + 2.0 * tol;
+    a.chunks = chunks;
+    long long total = 0;
+    if (cells > 0) {
+        LPCHK(reserve(s->q_points, coords)); LPCHK(reserve(s->q_count, cells));
+        LPCHK(hipMemcpy(s->q_points.get(), points, sizeof(double) * coords, hipMemcpyHostToDevice));
+        a.points = s->q_points.get(); a.count = s->q_count.get();
+        int rc = for_dim(s->n, [&](auto N) { return launch_locate<decltype(N)::value>(a, Q, false); });
+        if (rc != GCSADMM_OK) return rc;
+        LPCHK(hipMemcpy(count.data(), s->q_count.get(), sizeof(int) * cells, hipMemcpyDeviceToHost));
+        if (!locate_scan(count.data(), Q, chunks, offset.data(), hit_ptr.data())) {      // before the list is allocated
+            g_err = "more than 2^31 - 1 hits"; return GCSADMM_ERR_UNSUPPORTED;
+        }
+        total = hit_ptr[(size_t)Q];
+    }
+    if (total > 0) {
+        LPCHK(reserve(s->hit_region, (size_t)total)); LPCHK(reserve(s->hit_class, (size_t)total)); LPCHK(reserve(s->q_offset, cells));
+        LPCHK(hipMemcpy(s->q_offset.get(), offset.data(), sizeof(long long) * cells, hipMemcpyHostToDevice));
+        a.offset = s->q_offset.get(); a.limit = total;
+        a.hit_region = s->hit_region.get(); a.hit_class = s->hit_class.get();
+        const int rc = for_dim(s->n, [&](auto N) { return launch_locate<decltype(N)::value>(a, Q, true); });
+        if (rc != GCSADMM_OK) return rc;
+    }
+    LPCHK(hipStreamSynchronize(nullptr));
+    s->hit_ptr.swap(hit_ptr);
+    s->have_hits = true;
+    if (num_hits) *num_hits = total;
+    return GCSADMM_OK;
+}
+
+int gcsadmm_scene_locate_points(gcsadmm_scene s, int num_points, const double *points, double eps, double tol, int64_t *num_hits)
+{
+    try {
+        return locate_points(s, num_points, points, eps, tol, num_hits);
+    } catch (const std::bad_alloc &) {      // the host arrays of the scan
+        g_err = "out of host memory"; return GCSADMM_ERR_NO_MEMORY;
+    }
+}
+
+int gcsadmm_scene_read_hits(gcsadmm_scene s, int64_t *hit_ptr, int *hit_region, unsigned char *hit_class)
+{
+    USE_SCENE(s);
+    if (!s->have_hits) { g_err = "no resident hit list: call gcsadmm_scene_locate_points first"; return GCSADMM_ERR_BAD_ARG; }
+    if (hit_ptr) std::copy(s->hit_ptr.begin(), s->hit_ptr.end(), hit_ptr);
+    const size_t total = (size_t)s->hit_ptr.back();      // (the buffers may be longer: they are kept from call to call)
+    if (hit_region && total) LPCHK(hipMemcpy(hit_region, s->hit_region.get(), sizeof(int) * total, hipMemcpyDeviceToHost));
+    if (hit_class && total) LPCHK(hipMemcpy(hit_class, s->hit_class.get(), total, hipMemcpyDeviceToHost));
+    return GCSADMM_OK;
 }
 
 } // extern "C"

@@ -1,0 +1,150 @@
+"""Many start / goal queries on one scene: the use case ``batch.py`` names for ``BatchSolver``.
+
+A query differs from the next one only in its two terminals, so the region graph -- the centre LPs, the box LPs, the sweep and every
+region-region overlap LP -- is decided ONCE, on a resident ``DeviceScene``.  Per call, ``locate_kernel`` (csrc/point_locate_core.h)
+lists the regions under every start and goal point; only hits in the band of about 1e-6 around a facet or a vertex go to a pair LP,
+all of them in one call.  The query graphs are the region graph plus the terminals' edges, in the order and with the arrays a
+from-scratch ``graph_from_sets_device`` on ``{'s', 't', regions}`` gives; ``solve`` takes them through ``BatchSolver`` and
+``rounding_many``.  There is no CPU fallback: the LPs and the locate call run on the device (tests inject stand-ins).
+"""
+from __future__ import annotations
+
+from typing import Dict, Hashable
+
+import numpy as np
+
+from .graph import _finish_graph, convert_pt_to_polytope, polytopes_overlap
+
+__all__ = ["SceneQueries"]
+
+IN, UNDECIDED = 1, 2      # hit classes of gcsadmm_scene_locate_points
+
+
+class SceneQueries:
+    """``As``, ``bs``: the regions alone, by key (a key ``'s'`` or ``'t'`` is refused: the terminals come with each query).  Opens one
+    ``DeviceScene`` and decides the region graph on it; release with ``close()`` or use as a context manager.
+
+    ``scene``: a prepared scene with the interface of ``DeviceScene`` (tests inject one; it is closed with the object).  ``pair_lp``:
+    ``(polys, pair_a, pair_b, tol, centers) -> (flags, status)``, the pair LPs of ``PolytopeScene.overlaps`` (default: those)."""
+
+    def __init__(self, As: Dict[Hashable, np.ndarray], bs: Dict[Hashable, np.ndarray], n: int, device: int = 0, scene=None, pair_lp=None):
+        from .scene import DeviceScene, PolytopeScene, build_graph_arrays_device
+        if 's' in As or 't' in As:
+            raise ValueError("SceneQueries takes the regions alone: the keys 's' and 't' belong to the queries")
+        self.n, self.device = int(n), int(device)
+        self.keys = list(As.keys())
+        self.polys = [(np.asarray(As[k], float).reshape(-1, self.n), np.asarray(bs[k], float).ravel()) for k in self.keys]
+        self._pair_lp = pair_lp or (lambda polys, pa, pb, tol, cen: PolytopeScene(polys, self.device).overlaps(pa, pb, tol, cen))
+        self.scene = scene if scene is not None else DeviceScene(self.polys, self.device)
+        try:
+            self.stats = {}
+            self.edge_tail, self.edge_head, self.centers = build_graph_arrays_device(
+                self.polys, self.device, scene=self.scene, stats=self.stats, names=self.keys, broad_phase="device")
+        except Exception:
+            self.close()
+            raise
+        self.centers = np.ascontiguousarray(self.centers, float)
+        self.last = {}      # counts of the last regions_at call: hits, undecided, redone_on_host
+
+    def close(self):
+        if getattr(self, "scene", None) is not None:
+            self.scene.close()
+            self.scene = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    # ------------------------------------------------------------------
+    def regions_at(self, points, eps: float = 1e-6, tol: float = 1e-9):
+        """The regions that meet the box ``[p - eps, p + eps]`` of each point, by the rule ``build_graph`` connects a terminal with: one
+        ascending int32 array of region indices per point.  One ``locate`` call for all points; its UNDECIDED hits, all of them, go
+        through ONE call of the pair LPs on a temporary scene of the point boxes and the distinct regions involved -- the point box first
+        in every pair, its LP started at p; an LP that reports status < 0 is decided by ``graph.polytopes_overlap``."""
+        if self.scene is None:
+            raise RuntimeError("the scene is closed")
+        pts = np.ascontiguousarray(points, float).reshape(-1, self.n)
+        Q = pts.shape[0]
+        hit_ptr, hit_region, hit_class = self.scene.locate(pts, eps, tol)
+        keep = hit_class == IN
+        und = np.nonzero(hit_class == UNDECIDED)[0]
+        redone = 0
+        if len(und):
+            point_of = np.repeat(np.arange(Q), np.diff(hit_ptr))[und]
+            qs, pa = np.unique(point_of, return_inverse=True)
+            rs, pb = np.unique(hit_region[und], return_inverse=True)
+            polys = [convert_pt_to_polytope(pts[q], eps) for q in qs] + [self.polys[r] for r in rs]
+            start = np.vstack([pts[qs], self.centers[rs]])
+            flags, status = self._pair_lp(polys, pa.astype(np.int32), (len(qs) + pb).astype(np.int32), tol, start)
+            flags = np.array(flags, copy=True)
+            for t in np.nonzero(np.asarray(status) < 0)[0]:
+                flags[t] = 1 if polytopes_overlap(*polys[pa[t]], *polys[len(qs) + pb[t]]) else 0
+                redone += 1
+            keep[und] = flags != 0
+        self.last = dict(hits=int(len(hit_region)), undecided=int(len(und)), redone_on_host=redone)
+        counts = np.bincount(np.repeat(np.arange(Q), np.diff(hit_ptr))[keep], minlength=Q)
+        return np.split(hit_region[keep].astype(np.int32), np.cumsum(counts)[:-1]) if Q else []
+
+    def graphs(self, starts, goals, eps: float = 1e-6, tol: float = 1e-9):
+        """One ``GcsGraph`` per query ``(starts[i], goals[i])``, keys ``['s', 't', *region keys]``: what ``graph_from_sets`` makes of the
+        sets ``{'s': box of the start, 't': box of the goal, regions}`` -- the region edges shifted by two, both directions of every
+        terminal-region hit, and both directions of s-t when the two boxes meet (the interval rule of ``graph.polytopes_overlap``), in
+        double-loop order.  ``interior`` is the point itself for a terminal and the scene's centre for a region.  A start or goal whose
+        box meets no region raises ValueError."""
+        S = np.ascontiguousarray(starts, float).reshape(-1, self.n)
+        G = np.ascontiguousarray(goals, float).reshape(-1, self.n)
+        if len(S) != len(G):
+            raise ValueError("one goal for every start")
+        B = len(S)
+        regs = self.regions_at(np.vstack([S, G]), eps, tol)
+        for i in range(B):
+            for which, r in (("start", regs[i]), ("goal", regs[B + i])):
+                if len(r) == 0:
+                    raise ValueError(f"query {i}: the {which} lies in no region")
+        box = lambda p: (p - eps, p + eps)      # the bounds graph._as_box reads off convert_pt_to_polytope(p, eps)
+        keys = ['s', 't'] + self.keys
+        out = []
+        for i in range(B):
+            rs, rt = regs[i].astype(np.int64) + 2, regs[B + i].astype(np.int64) + 2
+            (lo_s, hi_s), (lo_t, hi_t) = box(S[i]), box(G[i])
+            st = np.array([0], np.int64) if np.all(np.maximum(lo_s, lo_t) <= np.minimum(hi_s, hi_t) + 1e-9) else np.zeros(0, np.int64)
+            zs, zt = np.zeros(len(rs), np.int64), np.ones(len(rt), np.int64)
+            tail = np.concatenate([self.edge_tail.astype(np.int64) + 2, zs, rs, zt, rt, st, st + 1])
+            head = np.concatenate([self.edge_head.astype(np.int64) + 2, rs, zs, rt, zt, st + 1, st])
+            o = np.lexsort((head, tail))
+            polys = [convert_pt_to_polytope(S[i], eps), convert_pt_to_polytope(G[i], eps)] + self.polys
+            out.append(_finish_graph(self.n, keys, tail[o], head[o], polys, np.vstack([S[i], G[i], self.centers]), 0, 1))
+        return out
+
+    def solve(self, starts, goals, state_dtype: str = "f64", N: int = 5, M: int = 20, seeds=None, params=None, return_state: bool = False,
+              **common):
+        """Every query to its stop test in one ``BatchSolver`` (``params``: one dict per query, ``common``: parameters of all, as
+        ``BatchSolver.solve``), then rounded by ``rounding_many`` (``N``, ``M``: as ``rounding``; ``seeds``: one per query, default 0).
+        Returns one record per query: that of ``DeviceSolver.solve`` plus ``rounded_cost``, ``x_v_rounded``, ``y_v_rounded`` and
+        ``graph``; with ``return_state`` also ``trace`` and ``state``, host copies of the member's trace and of its six state arrays (the
+        batch and its members are closed on return)."""
+        from .batch import BatchSolver
+        from .graph import sets_of_graph
+        from .rounding import rounding_many, rounding_problem
+        graphs = self.graphs(starts, goals)
+        seeds = [0] * len(graphs) if seeds is None else list(seeds)
+        if len(seeds) != len(graphs):
+            raise ValueError("one seed per query")
+        batch = BatchSolver(graphs, state_dtype, device=self.device)
+        try:
+            records = batch.solve(params=params, **common)
+            problems = [rounding_problem(m, *sets_of_graph(g), seed=s) for m, g, s in zip(batch.members, graphs, seeds)]
+            for rec, m, g in zip(records, batch.members, graphs):
+                rec["graph"] = g
+                if return_state:
+                    rec["trace"] = m.trace.cpu().numpy()
+                    rec["state"] = {k: getattr(m, k).cpu().numpy() for k in ("copy", "mu", "zedge", "xv", "zv", "yv")}
+        finally:
+            batch.close()
+            for m in batch.members:
+                m.close()
+        for rec, (cost, x_v, y_v) in zip(records, rounding_many(problems, N=N, M=M, device=self.device)):
+            rec.update(rounded_cost=cost, x_v_rounded=x_v, y_v_rounded=y_v)
+        return records

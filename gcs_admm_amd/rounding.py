@@ -154,6 +154,18 @@ def solve_path_restrictions_device(As, bs, n, paths, device=0, scene=None):
             scene.close()
 
 
+def rounding_problem(dev, As, bs, seed=0):
+    """The arguments of ``rounding`` (one entry of ``rounding_many``'s ``problems``) for the problem solver ``dev`` has just run: the
+    relaxed edge activations y_e off its edge words, by edge key, and the out-lists in edge order (reference utils.py:75-80)."""
+    g = dev.g
+    V, E = g.keys, g.edges_as_keys()
+    ye = dev.zedge[2 * g.n].cpu().numpy()
+    I_v_out = {v: [] for v in V}
+    for e in E:
+        I_v_out[e[0]].append(e)
+    return dict(y_e_sol={e: float(ye[i]) for i, e in enumerate(E)}, V=V, E=E, I_v_out=I_v_out, As=As, bs=bs, n=g.n, seed=seed)
+
+
 class _Candidates:
     """The candidate paths of ``rounding`` in the order the host loop visits them, handed out in rounds: the most probable path,
     then seeded walks until N distinct paths are feasible or pending, or M draws are spent.  When a round comes back with

@@ -224,6 +224,20 @@ class DeviceScene:
                    pts.ctypes.data, cost.ctypes.data, its.ctypes.data, st.ctypes.data)
         return [pts[int(ptr[p]) + p:int(ptr[p + 1]) + p + 1] for p in range(num)], cost, its, st
 
+    def locate(self, points, eps: float = 1e-6, tol: float = 1e-9):
+        """The regions under each of ``points`` [Q, n] (``gcsadmm_scene_locate_points``, csrc/point_locate_core.h has the rule): a point
+        p stands for the box ``[p - eps, p + eps]``.  Returns ``(hit_ptr int64 [Q + 1], hit_region int32, hit_class uint8)``: the hits of
+        point q are ``hit_region[hit_ptr[q]:hit_ptr[q + 1]]``, region indices ascending, each of class 1 (IN: p lies in the region) or 2
+        (UNDECIDED: within about eps of a facet or just beyond a vertex; a pair LP decides it).  A region that is not listed does not
+        meet the box.  Needs none of the other calls to have run and leaves their resident results as they are."""
+        pts = np.ascontiguousarray(points, float).reshape(-1, self.n)
+        Q = pts.shape[0]
+        num = C.c_int64(0)
+        self._call("gcsadmm_scene_locate_points", Q, pts.ctypes.data, float(eps), float(tol), C.addressof(num))
+        hit_ptr = np.empty(Q + 1, np.int64); hit_region = np.empty(int(num.value), np.int32); hit_class = np.empty(int(num.value), np.uint8)
+        self._call("gcsadmm_scene_read_hits", hit_ptr.ctypes.data, hit_region.ctypes.data, hit_class.ctypes.data)
+        return hit_ptr, hit_region, hit_class
+
 
 def edge_arrays(pa, pb, flags):
     """both directions of every intersecting pair in the reference's double-loop order (by tail, then head), int32"""

@@ -400,6 +400,22 @@ int gcsadmm_scene_read_pairs(gcsadmm_scene s, int *pair_a, int *pair_b, unsigned
 int gcsadmm_scene_restrict_paths(gcsadmm_scene s, int num_paths, const int *path_ptr, const int *path_poly, const double *start, double tol,
                                  int max_iter, double *points, double *cost, int *iterations, int *status);
 
+/* Queries on a scene whose graph is decided: the regions under each of num_points points (starts and goals), without a region-region
+ * LP.  A point p stands for the box [p - eps, p + eps] (a terminal of a query); region r is listed for it unless some row a_i x <= b_i
+ * has a_i.p - b_i > (eps + 2 tol) sum_k |a_ik| + 2^-40 (sum_k |a_ik p_k| + |b_i|), which puts the pair LP's r* below -tol.  A listed
+ * hit is of class 1 (IN: p lies in the region, every row with 2^-40 (...) to spare) or 2 (UNDECIDED: within about eps of a facet, or just
+ * beyond an acute vertex -- decide these with gcsadmm_polytope_overlaps).  locate_kernel (csrc/point_locate_core.h): one 64-lane
+ * workgroup per (chunk of regions, point), a count pass and a fill pass, no atomics; the list is ordered by point, then by region
+ * index, and is the same on every run.  It stays resident until the next call.  points[num_points][n] are host doubles.  Needs none of
+ * the other scene calls to have run and disturbs none of their resident results.  A NaN or inf coordinate, a negative num_points,
+ * eps < 0, tol < 0 or null points: GCSADMM_ERR_BAD_ARG (a list made earlier stays); more than 2^31 - 1 hits:
+ * GCSADMM_ERR_UNSUPPORTED, before the list is allocated.  num_points = 0 gives an empty list. */
+int gcsadmm_scene_locate_points(gcsadmm_scene s, int num_points, const double *points, double eps, double tol, int64_t *num_hits);
+
+/* The resident hit list: the hits of point q are hit_region / hit_class [hit_ptr[q] .. hit_ptr[q + 1]).  Before a
+ * gcsadmm_scene_locate_points call has produced a list: GCSADMM_ERR_BAD_ARG. */
+int gcsadmm_scene_read_hits(gcsadmm_scene s, int64_t *hit_ptr, int *hit_region, unsigned char *hit_class);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,80 @@
+"""Measurement for many start / goal queries on one scene (gcs_admm_amd/queries.py, locate_kernel in csrc/polytope_lp.hip): seconds per
+query graph from ``SceneQueries.graphs`` against a from-scratch ``graph_from_sets_device(..., broad_phase="device")`` on the same sets,
+the ``locate`` call alone, and the share of UNDECIDED hits.  Scenes: the generator of tools/bench_overlap.py, P = 1 000 and 20 000 at
+n = 2 and one at n = 6; Q = 2 B points for B = 1, 8, 64 queries.  Medians of five, the two sides alternated in every repetition, after a
+warm-up of both; every time is a host clock around calls that end in a copy from the device.  A from-scratch build costs the same
+whatever B is, so each repetition builds the first ``--scratch`` queries of the line from scratch (default 2) and compares those: the
+edge arrays must be equal, or the run stops.  One JSON line per (scene, B).
+
+  python tools/query_bench.py [--regions 1000 20000] [--regions6 1000] [--batches 1 8 64] [--scratch 2]
+"""
+import argparse, json, os, sys, time
+import numpy as np
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import torch  # noqa: F401  (HIP runtime first, see abi.load_library)
+from bench_overlap import scene_polys
+from gcs_admm_amd.graph import convert_pt_to_polytope
+from gcs_admm_amd.queries import SceneQueries
+from gcs_admm_amd.scene import graph_from_sets_device
+
+ARRAYS = ("edge_tail", "edge_head", "inc_ptr", "inc_edge", "inc_out", "edge_inc_tail", "edge_inc_head", "poly_ptr")
+
+
+def from_scratch(As, bs, n, s, t):
+    sets_A = {'s': convert_pt_to_polytope(s)[0], 't': convert_pt_to_polytope(t)[0], **As}
+    sets_b = {'s': convert_pt_to_polytope(s)[1], 't': convert_pt_to_polytope(t)[1], **bs}
+    return graph_from_sets_device(sets_A, sets_b, n, broad_phase="device")
+
+
+def measure(n, P, batches, scratch, repeats=5):
+    rng = np.random.default_rng(n)
+    polys = scene_polys(rng, n, P, 3 + n)
+    As = {p: A for p, (A, _) in enumerate(polys)}
+    bs = {p: b for p, (_, b) in enumerate(polys)}
+    t0 = time.perf_counter()
+    sq = SceneQueries(As, bs, n)
+    t_scene = time.perf_counter() - t0
+    with sq:
+        for B in batches:
+            # starts and goals inside regions: the generator's regions hold a ball of radius 0.5 around their Chebyshev centre
+            jitter = np.zeros((2 * B, n)); jitter[:, :2] = rng.uniform(-0.2, 0.2, (2 * B, min(n, 2)))
+            pts = sq.centers[rng.integers(0, P, 2 * B)] + jitter
+            S, G = pts[:B], pts[B:]
+            k = min(B, scratch)
+            sq.graphs(S, G); from_scratch(As, bs, n, S[0], G[0])          # warm-up of both sides at this shape
+            t_q, t_f, t_l = [], [], []
+            for _ in range(repeats):
+                t0 = time.perf_counter(); graphs = sq.graphs(S, G); t_q.append((time.perf_counter() - t0) / B)
+                last = dict(sq.last)
+                t0 = time.perf_counter(); refs = [from_scratch(As, bs, n, S[i], G[i]) for i in range(k)]; t_f.append((time.perf_counter() - t0) / k)
+                t0 = time.perf_counter(); sq.scene.locate(pts); t_l.append(time.perf_counter() - t0)
+                for g, ref in zip(graphs, refs):
+                    if g.keys != ref.keys or not all(np.array_equal(getattr(g, f), getattr(ref, f)) for f in ARRAYS):
+                        raise SystemExit(f"n = {n}, P = {P}, B = {B}: a query graph differs from its from-scratch build")
+            q, f = float(np.median(t_q)), float(np.median(t_f))
+            print(json.dumps({"metric": "seconds_per_query_graph", "n": n, "regions": P, "queries": B, "points": 2 * B,
+                              "rows_per_region": int(polys[0][0].shape[0]), "region_edges": int(len(sq.edge_tail)),
+                              "queries_s_per_graph": q, "from_scratch_s_per_graph": f, "ratio": f / q,
+                              "queries_s_per_graph_spread": [float(min(t_q)), float(max(t_q))],
+                              "from_scratch_s_per_graph_spread": [float(min(t_f)), float(max(t_f))],
+                              "locate_call_s": float(np.median(t_l)), "hits": last["hits"], "undecided": last["undecided"],
+                              "undecided_share": last["undecided"] / max(last["hits"], 1), "from_scratch_builds_compared": k,
+                              "scene_setup_s": t_scene, "edges_equal": True}), flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--regions", type=int, nargs="*", default=[1000, 20000])
+    ap.add_argument("--regions6", type=int, default=1000)
+    ap.add_argument("--batches", type=int, nargs="*", default=[1, 8, 64])
+    ap.add_argument("--scratch", type=int, default=2)
+    args = ap.parse_args()
+    for P in args.regions:
+        measure(2, P, args.batches, args.scratch)
+    if args.regions6:
+        measure(6, args.regions6, args.batches, args.scratch)
+
+
+if __name__ == "__main__":
+    main()
