@@ -67,6 +67,7 @@ PROTOTYPES = {
     "gcsadmm_edge_step": ([_p] * 4, _i),
     "gcsadmm_control": ([_p] * 4, _i),
     "gcsadmm_run": (_run, _i),
+    "gcsadmm_set_fused_tail": ([_p, _i], _i),
     "gcsadmm_read_control": ([_p] * 3, _i),
     "gcsadmm_cost": ([_p, _p, _d, _p, _p], _i),
     "gcsadmm_query": ([_p] * 6, _i),

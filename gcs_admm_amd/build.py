@@ -21,9 +21,9 @@ UNITS = [(MAIN, "gcsadmm.o", []), (WG, "vertex_wg.o", []), (WG, "vertex_wg_t512.
          (LP, "polytope_lp.o", []), (TERM, "terminal_region.o", [])]
 HDR = os.path.join(ROOT, "include", "gcsadmm.h")
 _c = lambda *names: [os.path.join(CSRC, f) for f in names]
-DEPS = [MAIN, HDR] + _c("vertex_program.h", "vertex_program.inc", "vertex_kernel.h", "special_vertex.h", "vertex_wg_launch.h", "canonical_box.h", "create_plan.h", "batch_plan.h", "warm_start.h", "terminal_launch.h", "step_args.h", "gcs_math.h", "hip_owners.h")
+DEPS = [MAIN, HDR] + _c("vertex_program.h", "vertex_program.inc", "vertex_kernel.h", "special_vertex.h", "vertex_wg_launch.h", "canonical_box.h", "create_plan.h", "batch_plan.h", "warm_start.h", "terminal_launch.h", "step_args.h", "gcs_math.h", "hip_owners.h", "edge_step.h")
 UNIT_DEPS = {LP: [LP, HDR] + _c("polytope_lp_core.h", "box_sweep_core.h", "point_locate_core.h", "path_restrict_core.h", "restrict_plan.h", "hip_owners.h", "step_args.h", "gcs_math.h"),
-             WG: [WG, HDR] + _c("vertex_wg.h", "vertex_wg_kernel.h", "vertex_wg_launch.h", "special_vertex.h", "gcs_math.h", "warm_start.h", "step_args.h")}
+             WG: [WG, HDR] + _c("vertex_wg.h", "vertex_wg_kernel.h", "vertex_wg_launch.h", "special_vertex.h", "gcs_math.h", "warm_start.h", "step_args.h", "edge_step.h")}
 UNIT_DEPS[WGD] = [WGD] + UNIT_DEPS[WG][1:]
 UNIT_DEPS[TERM] = [TERM, HDR] + _c("terminal_region.h", "terminal_launch.h", "gcs_math.h", "warm_start.h", "step_args.h")
 OUT = os.path.join(HERE, "libgcsadmm.so")

@@ -24,7 +24,7 @@ long long gcsadmm_terminal_record_doubles(int n, int facets, int live_edges);
 
 namespace gcsadmm_k {
 
-constexpr int EDGE_BLOCK = 256;          // threads per workgroup of the edge kernel
+// (EDGE_BLOCK, threads per workgroup of the edge kernel: step_args.h)
 constexpr int REORDER_MIN_UNITS = 512;   // launches with fewer units run all at once: no slowest-first dispatch (reorder_kernel)
 constexpr int LDS_CU_BYTES = 160 * 1024;
 
@@ -67,6 +67,9 @@ struct CreatePlan {
     std::vector<int> col_vertex;             // [max(NI, 1)] vertex of that column, -1: a ghost column
     double nx = 0, nmu = 0;
     int edge_unroll = 1, edge_blocks = 1;
+    // gcsadmm_run may run the edge and control steps as the tail of the workgroup program's launch (vertex_wg_kernel.h): one launch
+    // per iteration instead of two
+    int fused_tail = 0;
     int n_waves() const { return (int)wave_slot_ptr.size() - 1; }
 };
 
@@ -308,6 +311,11 @@ inline gcsadmm_status make_create_plan(const gcsadmm_graph_desc &g, CreatePlan &
     p.edge_unroll = edge_unroll_rt(g.state_dtype, 2 * n + 1, E);
     const int tile = EDGE_BLOCK * p.edge_unroll;     // edges per workgroup and pass
     p.edge_blocks = std::max(1, std::min((E + tile - 1) / tile, 2048));
+    // FUSED TAIL: all edges fit one edge workgroup; the vertex step is ONE launch of the in-LDS workgroup program (no wavefront
+    // program, no split vertices, no region terminal -- its kernel joins from an auxiliary stream after the vertex launch); and the
+    // handle is whole (a partition has ghost columns or ownership masks, and its edge step waits for the halo exchange)
+    const bool partitioned = g.num_incidences > g.inc_ptr[V] || g.inc_counted != nullptr || g.edge_counted != nullptr;
+    p.fused_tail = p.edge_blocks == 1 && E <= EDGE_BLOCK && p.n_waves() == 0 && p.split_vtx.empty() && p.n_term == 0 && !p.wg_vtx.empty() && !partitioned;
     return GCSADMM_OK;
 }
 

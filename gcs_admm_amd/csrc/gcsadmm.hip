@@ -55,6 +55,7 @@ __device__ __forceinline__ void gcs_stamp(int k)
 #include "canonical_box.h"
 #include "create_plan.h"
 #include "batch_plan.h"
+#include "edge_step.h"
 
 namespace {
 
@@ -62,197 +63,12 @@ using namespace gcs;
 using namespace gcsadmm_k;
 
 // -------------------------------------------------------------------------------------------------
-// edge kernel: one thread per directed edge, all c coupled words
+// edge and control kernels: the bodies are edge_step.h's (EdgeArgs<T>, ControlParams, edge_body<T, MODE, C, U>, control_body)
 // -------------------------------------------------------------------------------------------------
-template <class T> struct EdgeArgs {
-    int E, NI, c;
-    const int *edge_inc_tail, *edge_inc_head;
-    const uint8_t *inc_counted, *edge_counted;   // may be null
-    const T *copy;
-    T *zedge, *mu;
-    double *partials;    // [gridDim.x][5]
-};
-
-__device__ __forceinline__ double wave_sum(double v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
-}
-
-// dual update mu_scale * mu + r with the product rounded ON ITS OWN: left to the compiler the line contracts into an fma, and for a
-// mu_scale that is not a power of two (tau_incr = 3) the result then differs from the two-rounding value in a few percent of the words --
-// by up to one ulp of mu_new, which the per-word bound of tests/loop_reference.py does not always have room for.  With a power of two
-// (every default run) the product is exact and both forms give the same bits.
-__device__ __forceinline__ double scaled_plus(double scale, double x, double r)
-{
-#pragma clang fp contract(off)
-    return scale * x + r;
-}
-
-struct ControlParams {
-    double tau_incr, tau_decr, nu, eps_abs, eps_rel, nx, nmu;
-    int it_rho_limit, max_it;
-};
-
-// admm_solver_v3.py:697-733 on the five (globally reduced) sums; one thread
-// global_fails: the inner-failure count comes with the (all-reduced) sums as sums[5] instead of from this handle's counter
-__device__ void control_body(gcsadmm_control_block *cb, const double *sums, const ControlParams &p, int *counters, double *trace,
-                             bool global_fails = false)
-{
-    if (cb->status != GCSADMM_RUNNING) return;
-    double s[5];
-    for (int k = 0; k < 5; ++k) { s[k] = sums[k]; cb->sums[k] = s[k]; }
-    const int it = cb->it;
-    double rho = cb->rho;
-    const int fails = global_fails ? (int)(sums[5] + 0.5) : counters[0], iters = counters[1];
-    counters[0] = 0; counters[1] = 0;
-    cb->inner_failures = fails; cb->inner_iters = iters;
-    const double tot = s[0] + s[1] + s[2] + s[3] + s[4];
-    if (!(fabs(tot) <= 1.7976931348623157e308)) {   // non-finite iterate (NaN or an overflowed total): admm_solver_v3.py:662-664, 679-681
-        cb->status = GCSADMM_DIVERGED;
-        return;
-    }
-    const double pri = sqrt(s[0]), dual = rho * sqrt(2.0 * s[1]);
-    double mu_scale = 1.0;
-    if (pri >= p.nu * dual && it < p.it_rho_limit) { rho *= p.tau_incr; mu_scale = 1.0 / p.tau_incr; }
-    else if (dual >= p.nu * pri && it < p.it_rho_limit) { rho *= 1.0 / p.tau_decr; mu_scale = p.tau_incr; }
-    const double eps_pri = sqrt(p.nx) * p.eps_abs + p.eps_rel * fmax(sqrt(s[2]), sqrt(2.0 * s[3]));
-    const double eps_dual = sqrt(p.nmu) * p.eps_abs + p.eps_rel * mu_scale * sqrt(s[4]);
-    cb->rho = rho; cb->mu_scale = mu_scale;
-    cb->pri = pri; cb->dual = dual; cb->eps_pri = eps_pri; cb->eps_dual = eps_dual;
-    if (trace) {
-        double *tr = trace + (size_t)(it - 1) * 6;
-        tr[0] = rho; tr[1] = pri; tr[2] = dual; tr[3] = eps_pri; tr[4] = eps_dual; tr[5] = (double)fails;
-    }
-    if (pri < eps_pri && dual < eps_dual) { cb->status = GCSADMM_CONVERGED; return; }
-    cb->it = it + 1;
-    if (it + 1 > p.max_it) cb->status = GCSADMM_MAX_IT;
-}
-
 __global__ void control_kernel(gcsadmm_control_block *cb, const double *sums, ControlParams p, int *counters, double *trace, bool global_fails)
 {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     control_body(cb, sums, p, counters, trace, global_fails);
-}
-
-// edges a thread of the edge kernel has in flight at once on LARGE graphs (registers: U x 5C words); which graphs use it:
-// edge_unroll_rt (create_plan.h)
-template <class T, int C> __host__ __device__ constexpr int edge_unroll() { return sizeof(T) == 4 ? (C <= 7 ? 4 : 2) : (C <= 7 ? 2 : 1); }
-
-// MODE 0: partial sums per workgroup only (gcsadmm_edge_step: the caller all-reduces / finalizes);
-// MODE 1: single workgroup (at most EDGE_BLOCK edges, gcsadmm_run on small graphs): the workgroup also does the final
-//         reduction and the control step;
-// MODE 2: any grid (gcsadmm_run): the LAST workgroup to finish -- told by an agent-scope ticket counter -- reduces all the
-//         partials in the fixed order of finalize_kernel and runs the control step: one launch per edge step instead of two;
-// MODE 3: as MODE 2 without the control step (gcsadmm_run_partitioned): the last workgroup leaves the five sums and, in
-//         sums[5], this partition's inner-failure count for the all-reduce that follows.
-// C = coupled words per copy (2n+1), compile-time so that all C x 5 loads of an edge are in flight at once.
-// The body is a function of the arguments, the workgroup's index bx and the number of workgroups nblocks that share the edges, so that
-// the kernel that gets them from its kernarg segment and its grid (edge_kernel) and the one that reads them from a table
-// (edge_batch_kernel) run the same instructions on the same numbers.  red / is_last: the workgroup's LDS, declared by the kernel.
-template <class T, int MODE, int C, int U>
-__device__ __forceinline__ void edge_body(const EdgeArgs<T> &a, gcsadmm_control_block *cb, double *sums, const ControlParams &cp, int *counters,
-                                          double *trace, unsigned *ticket, const unsigned bx, const unsigned nblocks, double (*red)[5], int *is_last)
-{
-    if (cb->status != GCSADMM_RUNNING) return;
-    const double mu_scale = cb->mu_scale;
-    double s[5] = {0, 0, 0, 0, 0};
-    // a workgroup takes tiles of U x EDGE_BLOCK consecutive edges; a thread handles U edges of the tile, EDGE_BLOCK apart, and issues
-    // the loads of all of them before the first use: U x 5C coalesced 4/8-byte loads in flight per thread (one edge per thread left
-    // the stream latency-bound: 64 MB in 36 us on the 100k lattice)
-    for (int base = bx * (U * EDGE_BLOCK); base < a.E; base += nblocks * (U * EDGE_BLOCK)) {
-        int it[U], ih[U];
-        T cu_[U][C], cw_[U][C], zo_[U][C], mu_[U][C], mw_[U][C];
-#pragma unroll
-        for (int q = 0; q < U; ++q) {
-            const int e = base + q * EDGE_BLOCK + (int)threadIdx.x, ee = e < a.E ? e : a.E - 1;     // (tail of the last tile: a valid edge, result unused)
-            // edge-major columns (null index arrays): the two columns of edge e are e and E + e, every access below is a stream
-            it[q] = a.edge_inc_tail ? a.edge_inc_tail[ee] : ee; ih[q] = a.edge_inc_head ? a.edge_inc_head[ee] : a.E + ee;
-#pragma unroll
-            for (int w = 0; w < C; ++w) {
-                cu_[q][w] = a.copy[(size_t)w * a.NI + it[q]]; cw_[q][w] = a.copy[(size_t)w * a.NI + ih[q]];
-                zo_[q][w] = a.zedge[(size_t)w * a.E + ee];
-                mu_[q][w] = a.mu[(size_t)w * a.NI + it[q]]; mw_[q][w] = a.mu[(size_t)w * a.NI + ih[q]];
-            }
-        }
-#pragma unroll
-        for (int q = 0; q < U; ++q) {
-            const int e = base + q * EDGE_BLOCK + (int)threadIdx.x;
-            if (e >= a.E) break;
-            const double we = a.edge_counted ? (double)a.edge_counted[e] : 1.0;
-            const double wt = a.inc_counted ? (double)a.inc_counted[it[q]] : 1.0;
-            const double wh = a.inc_counted ? (double)a.inc_counted[ih[q]] : 1.0;
-#pragma unroll
-            for (int w = 0; w < C; ++w) {
-                const double cu = (double)cu_[q][w], cw = (double)cw_[q][w], zo = (double)zo_[q][w];
-                const T zn_t = (T)(0.5 * (cu + cw));
-                const double zn = (double)zn_t;
-                const double ru = cu - zn, rw = cw - zn;
-                const T mu_u_t = (T)scaled_plus(mu_scale, (double)mu_[q][w], ru);
-                const T mu_w_t = (T)scaled_plus(mu_scale, (double)mw_[q][w], rw);
-                a.mu[(size_t)w * a.NI + it[q]] = mu_u_t;
-                a.mu[(size_t)w * a.NI + ih[q]] = mu_w_t;
-                a.zedge[(size_t)w * a.E + e] = zn_t;
-                const double mu_u = (double)mu_u_t, mu_w = (double)mu_w_t;
-                s[0] += wt * ru * ru + wh * rw * rw;
-                s[1] += we * (zn - zo) * (zn - zo);
-                s[2] += wt * cu * cu + wh * cw * cw;
-                s[3] += we * zn * zn;
-                s[4] += wt * mu_u * mu_u + wh * mu_w * mu_w;
-            }
-        }
-    }
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < 5; ++k) {
-        const double t = wave_sum(s[k]);
-        if (lane == 0) red[wv][k] = t;
-    }
-    __syncthreads();
-    if (threadIdx.x < 5) {
-        double t = 0;
-        for (int q = 0; q < EDGE_BLOCK / WAVE; ++q) t += red[q][threadIdx.x];
-        if (MODE >= 2) __hip_atomic_store(&a.partials[(size_t)bx * 5 + threadIdx.x], t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        else a.partials[(size_t)bx * 5 + threadIdx.x] = t;
-        if (MODE == 1) sums[threadIdx.x] = t;      // one workgroup: its partial is the sum (what finalize_kernel would produce)
-    }
-    if (MODE == 1) {
-        __syncthreads();
-        if (threadIdx.x == 0) control_body(cb, sums, cp, counters, trace);
-    }
-    if (MODE >= 2) {
-        // hand-off of the partials to the last workgroup (MI355X_MICROARCH.md, inter-workgroup visibility): write-through (sc1)
-        // stores by the first wavefront, drained, then ONE agent-scope ticket add by a lane of that same wavefront; the
-        // workgroup whose add returns nblocks - 1 came last and reads every partial with sc1 loads.  (Measured alternative: an
-        // agent-scope ACQ_REL ticket add instead of the drain -- the release writes back the L2 of the XCD, which holds this
-        // kernel's own 24 MB of stores: edge step 23.6 -> 33.4 us on the 100k lattice.  Only the five partials need to cross.)
-        if (threadIdx.x < WAVE) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if (threadIdx.x == 0) {
-            const unsigned t = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            *is_last = (t == nblocks - 1);
-        }
-        __syncthreads();
-        if (!*is_last) return;
-        double acc[5] = {0, 0, 0, 0, 0};
-        for (int b = threadIdx.x; b < (int)nblocks; b += EDGE_BLOCK)
-            for (int k = 0; k < 5; ++k) acc[k] += __hip_atomic_load(&a.partials[(size_t)b * 5 + k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __syncthreads();       // red[][] above has been consumed by every thread
-        for (int k = 0; k < 5; ++k) red[threadIdx.x][k] = acc[k];
-        __syncthreads();
-        for (int off = EDGE_BLOCK / 2; off > 0; off >>= 1) {
-            if ((int)threadIdx.x < off)
-                for (int k = 0; k < 5; ++k) red[threadIdx.x][k] += red[threadIdx.x + off][k];
-            __syncthreads();
-        }
-        if (threadIdx.x < 5) sums[threadIdx.x] = red[0][threadIdx.x];
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            if (MODE == 2) control_body(cb, sums, cp, counters, trace);
-            else sums[5] = (double)counters[0];
-            __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);     // ready for the next launch
-        }
-    }
 }
 
 template <class T, int MODE, int C, int U>
@@ -436,6 +252,7 @@ struct gcsadmm_handle_s {
     gcsadmm_batch_s *batch = nullptr;      // the batch this handle is bound to (gcsadmm_batch_bind .. the batch's next bind or its destroy)
     std::vector<gcsadmm_batch_s *> batches;      // the batches that list this handle as a member (gcsadmm_batch_create .. _destroy)
     int overlap_mode = 0;     // gcsadmm_set_overlap: 0 automatic, 1 forced (tests: works without peers), 2 off
+    int fused_tail_mode = 1;  // gcsadmm_set_fused_tail: 0 two launches per iteration, 1 automatic (one where the plan allows it)
     std::string err;
     void *comm = nullptr;     // ncclComm_t (gcsadmm_attach_comm)
     int rank = 0, world = 1;
@@ -472,6 +289,8 @@ struct gcsadmm_handle_s {
     int n_special() const { return (int)g.d_special_vtx.size(); }
     int n_wg() const { return (int)g.d_wg_vtx.size(); }       // vertices solved by the workgroup program (vertex_wg.hip)
     int n_split() const { return (int)g.d_split_vtx.size(); }
+    // gcsadmm_run runs the edge and control steps as the tail of the vertex launch (a handle attached to a communicator does not)
+    bool fuses() const { return plan.fused_tail && fused_tail_mode != 0 && !halo.attached(); }
 };
 
 // A batch of handles (gcsadmm_batch_create): the members stay the caller's, the batch owns its plan (batch_plan.h) and the argument
@@ -629,7 +448,13 @@ static VertexLaunchDesc make_launch_desc(gcsadmm_handle h, const gcsadmm_state *
 
 // part: -1 the whole vertex step; 0 / 1 the boundary / interior wavefronts of the overlapped partitioned loop (handles whose generic
 // vertices are all on the wavefront program; the closed-form vertices ride with the boundary part)
-static gcsadmm_status launch_vertex(gcsadmm_handle h, const gcsadmm_state *st, hipStream_t s, int part = -1, bool reorder = false)
+// fused_trace (gcsadmm_run on a handle that fuses, h->fuses()): the launch also runs the edge and control steps; the trace may be null
+static gcsadmm_status launch_vertex(gcsadmm_handle h, const gcsadmm_state *st, hipStream_t s, int part = -1, bool reorder = false,
+                                    bool fused = false, double *fused_trace = nullptr);
+template <class T> static EdgeArgs<T> make_edge_args(gcsadmm_handle h, const gcsadmm_state *st);
+static WgTailDesc make_wg_tail(gcsadmm_handle h, const gcsadmm_state *st, double *trace);
+
+static gcsadmm_status launch_vertex(gcsadmm_handle h, const gcsadmm_state *st, hipStream_t s, int part, bool reorder, bool fused, double *fused_trace)
 {
     const auto &g = h->g;
     const int n_waves = h->plan.n_waves();
@@ -664,8 +489,10 @@ static gcsadmm_status launch_vertex(gcsadmm_handle h, const gcsadmm_state *st, h
     const bool special_on_wave = n_waves > 0;
     if (n_waves > 0) launch_waves(make_launch_desc(h, st));
     if (h->n_wg() > 0 || (!special_on_wave && h->n_special() > 0)) {
-        if (h->plan.wg_t512) gcsadmm_wg_launch_t512(make_wg_desc(h, st, !special_on_wave), s);
-        else gcsadmm_wg_launch(make_wg_desc(h, st, !special_on_wave), s);
+        WgLaunchDesc d = make_wg_desc(h, st, !special_on_wave);
+        if (fused) d.tail = make_wg_tail(h, st, fused_trace);
+        if (h->plan.wg_t512) gcsadmm_wg_launch_t512(d, s);
+        else gcsadmm_wg_launch(d, s);
     }
     if (h->n_split() > 0) {      // the vertices too large for LDS: the split form, units in the handle's workspace
         WgLaunchDesc d = make_wg_desc(h, st, false);
@@ -689,6 +516,18 @@ template <class T> static EdgeArgs<T> make_edge_args(gcsadmm_handle h, const gcs
     a.inc_counted = h->g.d_inc_counted.get(); a.edge_counted = h->g.d_edge_counted.get();
     a.copy = (const T *)st->copy; a.zedge = (T *)st->zedge; a.mu = (T *)st->mu; a.partials = h->loop.d_partials.get();
     return a;
+}
+
+// the fused tail of the in-LDS launch (gcsadmm_run on handles that fuse): what launch_edge would hand edge_kernel MODE 1, beside make_wg_desc
+static WgTailDesc make_wg_tail(gcsadmm_handle h, const gcsadmm_state *st, double *trace)
+{
+    WgTailDesc t;
+    t.enabled = 1;
+    const EdgeArgs<char> a = make_edge_args<char>(h, st);      // (untyped: the launch casts the three state pointers back)
+    t.edge = EdgeArgs<void>{a.E, a.NI, a.c, a.edge_inc_tail, a.edge_inc_head, a.inc_counted, a.edge_counted, a.copy, a.zedge, a.mu, a.partials};
+    t.cb = h->loop.d_cb.get(); t.sums = h->loop.d_sums.get(); t.cp = control_params(h);
+    t.counters = h->loop.d_counters.get(); t.trace = trace; t.ticket = h->loop.d_ticket.get();
+    return t;
 }
 
 // with_control: the control step rides in the same launches (gcsadmm_run); trace may be null
@@ -1085,8 +924,13 @@ gcsadmm_status gcsadmm_run(gcsadmm_handle h, const gcsadmm_state *st, int32_t k,
 {
     if (!state_ok(h, st) || k < 0) return GCSADMM_ERR_BAD_ARG;
     USE_DEVICE(h);      // (the edge launches below are issued from here, not through an entry point that guards for itself)
+    const bool fused = h->fuses();
     for (int i = 0; i < k; ++i) {
         gcsadmm_status s;
+        if (fused) {      // small graphs: the last vertex workgroup runs the edge and control steps, one launch per iteration
+            if ((s = launch_vertex(h, st, (hipStream_t)stream, -1, false, true, trace_dev)) != GCSADMM_OK) return s;
+            continue;
+        }
         if ((s = gcsadmm_vertex_step(h, st, stream)) != GCSADMM_OK) return s;
         // edge step and control step in two launches (one when all edges fit a single workgroup)
         if ((s = launch_edge(h, st, h->loop.d_sums.get(), (hipStream_t)stream, true, trace_dev)) != GCSADMM_OK) return s;
@@ -1276,6 +1120,13 @@ gcsadmm_status gcsadmm_run_partitioned_timed(gcsadmm_handle h, const gcsadmm_sta
     }
     *vertex_ms = (float)acc[0]; *halo_ms = (float)acc[1]; *edge_ms = (float)acc[2]; *reduce_ms = (float)acc[3];
     return GCSADMM_OK;
+}
+
+int32_t gcsadmm_set_fused_tail(gcsadmm_handle h, int32_t mode)
+{
+    if (!h) return 0;
+    h->fused_tail_mode = mode != 0;
+    return h->fuses() ? 1 : 0;
 }
 
 gcsadmm_status gcsadmm_set_overlap(gcsadmm_handle h, int32_t mode, int32_t *boundary_units)

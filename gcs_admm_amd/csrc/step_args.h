@@ -12,6 +12,18 @@ struct gcsadmm_control_block;
 namespace gcsadmm_k {
 
 constexpr int MAX_SPECIAL_DEG = 256;   // degree limit of the closed-form vertices (special_vertex.h): their work arrays are this long
+constexpr int EDGE_BLOCK = 256;        // threads per workgroup of the edge kernel = edges the single-workgroup edge step holds
+// FUSED TAIL (vertex_wg_kernel.h): LDS of the edge step the last workgroup of a vertex-step launch runs -- red[EDGE_BLOCK / 64][5] and
+// the "came last" flag, in the dynamic segment the launch asks for
+constexpr int FUSED_TAIL_LDS_BYTES = (EDGE_BLOCK / 64 * 5 + 1) * 8;
+// dynamic LDS of a workgroup-program launch: the largest vertex of the plan, the work arrays of the closed-form workgroups, the tail
+constexpr int wg_launch_lds_bytes(int plan_lds_bytes, bool fused_tail)
+{
+    int b = 4 * MAX_SPECIAL_DEG * 8;
+    if (plan_lds_bytes > b) b = plan_lds_bytes;
+    if (fused_tail && FUSED_TAIL_LDS_BYTES > b) b = FUSED_TAIL_LDS_BYTES;
+    return b;
+}
 
 struct StepArgsBase {
     const int *inc_ptr;         // [V+1]
@@ -30,7 +42,21 @@ struct StepArgsBase {
     // warm start (warm_start.h): the records of the handle's workspace, warm + warm_ptr[v]; nullptr = every solve starts cold
     double *warm = nullptr;
     const long long *warm_ptr = nullptr;
+    // 1: the launch hands its copy columns to a reader in the SAME launch (the fused tail of vertex_wg_kernel): the solves store them
+    // write-through (store_copy below).  Uniform over the launch; 0 everywhere else.
+    int publish = 0;
 };
+
+// a word of the state's copy columns: a plain store, or for a publishing launch an agent-scope relaxed atomic store (sc1, write-through:
+// it leaves the XCD's L2, so that an sc1 load of another workgroup of the launch finds it once the storing wavefront has drained)
+template <class T> GCS_HD void store_copy(T *p, T v, int publish)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    if (publish) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); return; }
+#endif
+    (void)publish;
+    *p = v;
+}
 
 // the state columns: zedge [2n+1][E], mu and copy [2n+1][NI], of the handle's state type (f64 / f32)
 template <class T> struct StepArgs : StepArgsBase {

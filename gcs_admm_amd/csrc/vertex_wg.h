@@ -1713,7 +1713,7 @@ GCS_HD void wg_solve_vertex(const WgArgs<T> &a, int v, double rho, double mu_sca
         if (w == 2 * N) val = yy;
         else if (w < N) val = out ? p[w] + yy * CEN[w] : un[W::TF + w];     // incoming: the free word keeps its target
         else val = out ? p[w] + yy * CEN[w - N] : p[w - N] + yy * CEN[w - N];
-        a.copy[(size_t)w * a.NI + inc] = (T)val;
+        gcsadmm_k::store_copy(&a.copy[(size_t)w * a.NI + inc], (T)val, a.publish);      // (write-through where the launch has a fused tail)
     }
     WG_FOR_AT(k, NX, plo.at(NX)) {
         const int c = k < N ? k : k - N;

@@ -71,12 +71,81 @@ __device__ __forceinline__ void vertex_wg_body(const gcs_wg::WgArgs<T> &a, const
     }
 }
 
+// FUSED TAIL (graphs whose edges fit one edge workgroup, CreatePlan::fused_tail): the iteration is ONE launch.  Every workgroup of the
+// launch, once its vertices are solved, PUBLISHES -- its copy columns were stored write-through (sc1: store_copy, step_args.h), every
+// wavefront drains its stores (s_waitcnt vmcnt(0)), one workgroup barrier -- and ARRIVES: thread 0, whose counter adds are drained too,
+// makes one relaxed agent-scope add on the handle's ticket.  (The trailing workgroups of the closed-form vertices keep their plain
+// stores -- as sc1 stores inside special_body's divergent loops they cost every instantiation 3-4 vector registers of spilled scalars
+// across the Newton loop, and the n = 6 BOX instantiation its third wavefront per SIMD -- and thread 0 writes them back with one
+// agent-scope release before its add.  Those workgroups are done within a few microseconds of a launch that lasts as long as its
+// slowest interior-point solve, so the release is never on the critical path.)  The workgroup whose add returns gridDim.x - 1 came last: every other
+// workgroup has published, so it runs edge_kernel's MODE 1 body (edge_step.h) on threads 0 .. EDGE_BLOCK - 1 with sc1 loads of the
+// copies, then the control step, and leaves the ticket at 0.  Nobody waits for anybody: no spin, no flag poll, no cooperative launch,
+// and no fence in a workgroup that solves -- the hand-off is MI355X_MICROARCH.md's "sc1 stores, drain, counter add; the last adder reads with sc1 loads", the
+// one edge_kernel MODE 2 uses for its partials (a release fence would write back the XCD's L2: 3.5 us, more than the launch saved).
+// zedge and mu were written by the previous launch and are read by plain loads; the tail's own stores to them are read by the next.
+template <class T> struct WgTail {
+    int enabled;
+    EdgeArgs<T> edge;
+    gcsadmm_control_block *cb;
+    double *sums;
+    ControlParams cp;
+    int *counters;
+    double *trace;
+    unsigned *ticket;
+};
+
+template <class T, int C>
+__device__ __forceinline__ void wg_fused_tail(const WgTail<T> &t, double mu_scale, bool closed_form, double *smem)
+{
+    // the edge's two state columns do not depend on the solves: loaded while the stores drain
+    const EdgePre pre = edge_prefetch(t.edge, mu_scale);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // this wavefront's copy stores (and thread 0's counter adds) have left
+    __syncthreads();                                         // every wavefront's have; and the LDS of the solve is free
+    double(*red)[5] = (double(*)[5])smem;
+    int *is_last = (int *)(smem + EDGE_BLOCK / EDGE_WAVE * 5);
+    if (threadIdx.x == 0) {
+        if (closed_form) {      // plain stores: written back by one release, drained
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        }
+        const unsigned k = __hip_atomic_fetch_add(t.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        *is_last = (k == gridDim.x - 1);
+    }
+    __syncthreads();
+    if (!*is_last) return;
+    edge_body<T, 1, C, 1, EdgeInTail>(t.edge, t.cb, t.sums, t.cp, t.counters, t.trace, t.ticket, 0, 1, red, is_last, pre);
+    if (threadIdx.x == 0) __hip_atomic_store(t.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);     // ready for the next launch
+}
+
+// REGISTERS: the kernel reads its tail block LATE.  The Newton loop's scalar registers already spill into vector lanes, and nothing of the
+// tail may be live in it.  So after the solve the kernel takes the address of its own kernarg segment, makes it opaque, and reads the
+// block (twenty words) -- and through it the dual scale for the tail -- from there through the constant address space: scalar loads
+// where they are needed (vertex_wg_batch_kernel reads its table the same way, for the same reason).  Every instantiation keeps the
+// register count it had without the tail, except n = 2 f64 (97 -> 115, the tail's own loads: same occupancy class).
+template <class T> constexpr size_t wg_tail_kernarg_offset()
+{
+    static_assert(alignof(gcs_wg::WgArgs<T>) == 8 && alignof(SpecialArgs) == 8 && alignof(WgTail<T>) == 8, "kernarg layout: every argument starts on 8 bytes");
+    return sizeof(gcs_wg::WgArgs<T>) + sizeof(SpecialArgs) + sizeof(const gcsadmm_control_block *);
+}
+
 template <int N, class T, bool BOX>
-__global__ __launch_bounds__(WG_THREADS, (wg_min_blocks<N, BOX>())) void vertex_wg_kernel(gcs_wg::WgArgs<T> a, SpecialArgs sp, const gcsadmm_control_block *cb)
+__global__ __launch_bounds__(WG_THREADS, (wg_min_blocks<N, BOX>())) void vertex_wg_kernel(gcs_wg::WgArgs<T> a, SpecialArgs sp, const gcsadmm_control_block *cb,
+                                                                                 WgTail<T> /* read late, below */)
 {
     extern __shared__ __attribute__((aligned(16))) double smem[];
     if (cb->status != GCSADMM_RUNNING) return;
     vertex_wg_body<N, T, BOX>(a, sp, cb->rho, cb->mu_scale, (int)blockIdx.x, smem);
+    typedef const __attribute__((address_space(4))) char *KernargPtr;
+    KernargPtr kp = (KernargPtr)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(kp));
+    typedef const __attribute__((address_space(4))) WgTail<T> *TailPtr;
+    TailPtr tp = (TailPtr)(kp + wg_tail_kernarg_offset<T>());
+    if (!tp->enabled) return;      // (uniform over the launch: a kernel argument)
+    const WgTail<T> tail = *(const WgTail<T> *)tp;
+    // the dual scale the launch started with: the control block is not written before the tail's own control step
+    const double mu_scale = __hip_atomic_load(&tail.cb->mu_scale, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    wg_fused_tail<T, 2 * N + 1>(tail, mu_scale, (int)blockIdx.x >= a.n_vtx, smem);
 }
 
 #if GCS_WG_THREADS == 256
@@ -138,13 +207,14 @@ template <int N> constexpr bool WG_HAS_BOX = N == 3 || N == 6;
 template <class F> auto with_state(int dtype, F &&f) { return with_state_type(dtype == GCSADMM_F64, f); }
 
 // one launch of family K: `extra` is the kernel's second argument (the closed-form vertices / the split form's workspace)
-template <class K, int N, class T, class X>
-void launch_kernels(const WgLaunchDesc &d, const gcs_wg::WgArgs<T> &a, unsigned grid, int lds, const X &extra, hipStream_t s)
+// (`more`: the kernel's arguments after the control block -- the in-LDS family's tail)
+template <class K, int N, class T, class X, class... More>
+void launch_kernels(const WgLaunchDesc &d, const gcs_wg::WgArgs<T> &a, unsigned grid, int lds, const X &extra, hipStream_t s, const More &...more)
 {
     if constexpr (WG_HAS_BOX<N>) {
-        if (d.box) { hipLaunchKernelGGL((K::template kernel<N, T, true>()), dim3(grid), dim3(WG_THREADS), lds, s, a, extra, d.step.cb); return; }
+        if (d.box) { hipLaunchKernelGGL((K::template kernel<N, T, true>()), dim3(grid), dim3(WG_THREADS), lds, s, a, extra, d.step.cb, more...); return; }
     }
-    hipLaunchKernelGGL((K::template kernel<N, T, false>()), dim3(grid), dim3(WG_THREADS), lds, s, a, extra, d.step.cb);
+    hipLaunchKernelGGL((K::template kernel<N, T, false>()), dim3(grid), dim3(WG_THREADS), lds, s, a, extra, d.step.cb, more...);
 }
 
 // raise the dynamic-LDS limit of family K's instantiations (needed above 48 KB)
@@ -168,16 +238,25 @@ template <class T> gcs_wg::WgArgs<T> in_lds_args(const WgLaunchDesc &d)
     return a;
 }
 
+// the typed tail of an in-LDS launch (its last kernel argument)
+template <class T> WgTail<T> in_lds_tail(const WgTailDesc &d)
+{
+    const EdgeArgs<void> &e = d.edge;
+    return WgTail<T>{d.enabled,
+                     EdgeArgs<T>{e.E, e.NI, e.c, e.edge_inc_tail, e.edge_inc_head, e.inc_counted, e.edge_counted, (const T *)e.copy, (T *)e.zedge, (T *)e.mu, e.partials},
+                     d.cb, d.sums, d.cp, d.counters, d.trace, d.ticket};
+}
+
 template <int N> void launch(const WgLaunchDesc &d, hipStream_t s)
 {
     with_state(d.dtype, [&](auto t) {
         using T = decltype(t);
-        const gcs_wg::WgArgs<T> a = in_lds_args<T>(d);
+        gcs_wg::WgArgs<T> a = in_lds_args<T>(d);
+        a.publish = d.tail.enabled;      // the copies go out write-through exactly when the launch has a reader for them
         const SpecialArgs sp{d.n_special, d.special_vtx, d.special_kind};
         const unsigned grid = (unsigned)(d.n_vtx + (d.n_special + WG_THREADS - 1) / WG_THREADS);
         if (grid == 0) return;
-        const int lds = std::max(d.lds_bytes, (int)(4 * MAX_SPECIAL_DEG * sizeof(double)));
-        launch_kernels<InLdsKernels, N, T>(d, a, grid, lds, sp, s);
+        launch_kernels<InLdsKernels, N, T>(d, a, grid, wg_launch_lds_bytes(d.lds_bytes, d.tail.enabled != 0), sp, s, in_lds_tail<T>(d.tail));
     });
 }
 

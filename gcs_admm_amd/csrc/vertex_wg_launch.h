@@ -3,10 +3,25 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "edge_step.h"
 #include "gcsadmm.h"
 #include "step_args.h"
 
 namespace gcsadmm_k {
+
+// FUSED TAIL of an in-LDS launch (vertex_wg_kernel.h): what the last workgroup to finish needs to run the single-workgroup edge step and
+// the control step -- the arguments edge_kernel MODE 1 gets (state untyped, as in StepDesc) and the handle's arrival counter.
+// enabled = 0 (every launch but gcsadmm_run's on a handle whose plan has fused_tail): the launch is the vertex step alone.
+struct WgTailDesc {
+    int enabled = 0;
+    EdgeArgs<void> edge{};
+    gcsadmm_control_block *cb = nullptr;      // writable: the control step's
+    double *sums = nullptr;
+    ControlParams cp{};
+    int *counters = nullptr;
+    double *trace = nullptr;                  // may be null
+    unsigned *ticket = nullptr;
+};
 
 struct WgLaunchDesc {
     StepDesc step;
@@ -17,6 +32,7 @@ struct WgLaunchDesc {
     int box;                        // every vertex of the launch is a canonical axis-aligned box (canonical_box.h): BOX instantiation
     const int *order;               // slowest-first dispatch (reorder_kernel): workgroup b solves vtx[order[b]]; may be null
     int *unit_iters;                // [n_vtx] Newton iterations of each vertex's last solve; may be null
+    WgTailDesc tail;                // in-LDS launch only
 };
 
 // the split form's device-memory workspace: the units of vtx[b] of the launch at units + unit_off[b] (256-byte aligned slabs)

@@ -150,6 +150,12 @@ class DeviceSolver:
         """k iterations back to back, no host synchronisation."""
         self._call("gcsadmm_run", C.byref(self.state), int(k), self.trace.data_ptr(), self._stream())
 
+    def set_fused_tail(self, mode: int = 1) -> bool:
+        """Launches per iteration of ``enqueue`` (include/gcsadmm.h gcsadmm_set_fused_tail): 0 two (vertex step; edge + control step),
+        1 automatic -- one on small graphs, where the last vertex workgroup runs the edge and control steps.  Same numbers either
+        way.  Returns whether ``enqueue`` fuses on this handle."""
+        return bool(self.lib.gcsadmm_set_fused_tail(self.h, int(mode)))
+
     def enqueue_timed(self, k: int):
         vm, em = C.c_float(0), C.c_float(0)
         vl, el = C.c_int32(0), C.c_int32(0)

@@ -177,6 +177,13 @@ gcsadmm_status gcsadmm_control(gcsadmm_handle h, const double *sums_dev, double 
  * stop test fires the remaining enqueued kernels exit immediately. */
 gcsadmm_status gcsadmm_run(gcsadmm_handle h, const gcsadmm_state *st, int32_t k, double *trace_dev, void *stream);
 
+/* Small graphs -- all edges in one edge workgroup (at most 256), every generic vertex on the in-LDS workgroup program, no region
+ * terminal, no ghost columns or ownership masks -- run an iteration of gcsadmm_run as ONE launch: the last vertex workgroup to finish
+ * runs the edge and control steps as the tail of the vertex launch (same numbers bit for bit).  mode 0: two launches per iteration
+ * (vertex step; edge + control step); 1: automatic, the default.  Returns 1 when gcsadmm_run fuses on this handle, 0 when it does not
+ * (larger graphs, a handle attached to a communicator, mode 0).  Every other entry point keeps its launches. */
+int32_t gcsadmm_set_fused_tail(gcsadmm_handle h, int32_t mode);
+
 /* Copy the control block to the host (synchronises `stream`). */
 gcsadmm_status gcsadmm_read_control(gcsadmm_handle h, gcsadmm_control_block *out, void *stream);
 
