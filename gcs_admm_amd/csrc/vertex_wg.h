@@ -311,6 +311,19 @@ GCS_HD int wg_uniform(int x)
 #endif
 }
 
+// a workgroup-uniform integer made opaque in its scalar register (identity on the host): the scalar counterpart of wg_tid().  What is
+// derived from it afterwards is no longer invariant across the Newton loop, so the compiler recomputes it in the region that uses it (one
+// or two scalar instructions) instead of keeping it live in a scalar register or a spill lane for the whole loop (DESIGN.md section 4,
+// "scalar budget of the Newton loop").
+GCS_HD void wg_opaque(int &x)
+{
+#if WG_DEVICE
+    asm volatile("" : "+s"(x));
+#else
+    (void)x;
+#endif
+}
+
 template <bool VM = false> GCS_HD Red3 wg_reduce(Red3 v, double *red, int &phase)
 {
 #if WG_DEVICE
@@ -580,18 +593,45 @@ GCS_HD void wg_solve_vertex(const WgArgs<T> &a, int v, double rho, double mu_sca
     constexpr bool CONE_PAIR = N <= GCS_WG_CONE_PAIR_MAXN;      // the cone's two step bounds on two lanes side by side (solve_tail); at n = 6 the
                                                                 // second lane costs the BOX instantiation two registers (167 -> 169: its third workgroup per CU)
     const bool prox = a.prox_q != nullptr;       // border-only problem with a separable quadratic (no blocks, no sides)
-    const int lo = a.inc_ptr[v], d = prox ? 0 : a.inc_ptr[v + 1] - lo, d_in = prox ? 0 : a.deg_in[v], d_out = d - d_in;
-    const bool sides = d > 0;
-    const int p0 = a.poly_ptr[v], m = a.poly_ptr[v + 1] - p0;
-    const int U = d + 1, R = 4 * m, m2 = 2 * m;
-    const int US = W::unit_stride(m);
+    const int lo = a.inc_ptr[v], p0 = a.poly_ptr[v];
+    // THE THREE SIZES of the sub-problem, and what is derived from them.  Not const: WG_REGION() (the head of every region of the Newton
+    // loop) makes the three opaque and derives the rest again, so that none of it -- nor any product, bound or Place start computed from
+    // it -- is invariant across the loop (wg_opaque, above).
+    int d = prox ? 0 : a.inc_ptr[v + 1] - lo, d_in = prox ? 0 : a.deg_in[v], m = a.poly_ptr[v + 1] - p0;
+    int d_out, U, R, m2, US, oR1, oR2;      // (oLAM, oR1, oR2: facet-row arrays of a unit: duals, two work arrays)
+    bool sides;
+    double *PA;
+    const double *A, *BC;
+    constexpr int oLAM = W::ROWS;
+    auto derive = [&] {
+        d_out = d - d_in; sides = d > 0;
+        U = d + 1; R = 4 * m; m2 = 2 * m;
+        US = W::unit_stride(m);
+        oR1 = W::ROWS + R; oR2 = W::ROWS + 2 * R;
+        PA = sm + W::FIXED + (SPLIT ? 0 : pad2(U * US));
+        A = PA; BC = PA + pad2(m * N);
+    };
+    // (not at n = 6 and n = 1: at n = 6 the freed scalars let the scheduler stretch the vector live ranges -- the BOX instantiation went
+    //  from 167 to 228 vector registers and lost its third wavefront per SIMD, the generic one from 169 to 173 -- and n = 1 lost its fifth)
+    constexpr bool REGION_OPAQUE = N != 6 && N != 1;
+    if constexpr (REGION_OPAQUE) { d = wg_uniform(d); d_in = wg_uniform(d_in); m = wg_uniform(m); }      // (in scalar registers whatever loaded them)
+    derive();
+    // (The LDS pointer is NOT treated this way: with `sm` opaque as well the n = 2 kernels have no reload from a spill lane left in the loop
+    //  -- four sm + W::... addresses of the Hessian entry tasks remain otherwise, five reloads per iteration -- but every LDS access then adds
+    //  its base in a vector instruction instead of carrying it in its offset field: 35 170 ticks per Newton iteration on benchmark4 against
+    //  33 860 without, parent 35 075; profiles/wg_scalars/README.md.)
+#define WG_REGION()                                                                                                            \
+    do {                                                                                                                       \
+        if constexpr (REGION_OPAQUE) {                                                                                         \
+            gcs_wg::wg_opaque(d); gcs_wg::wg_opaque(d_in); gcs_wg::wg_opaque(m);                                               \
+            derive();                                                                                                          \
+        }                                                                                                                      \
+    } while (0)
     const float inv_m2 = 1.0f / (float)m2;
     double *const UB = SPLIT ? units : sm + W::FIXED;
     auto UN = [&](int u) -> double * { return UB + u * US; };       // base of unit u
     constexpr bool WG_VM = SPLIT;      // (WG_SYNC, WG_WAVE_SYNC and wg_reduce wait for the units' global accesses)
-    const int oLAM = W::ROWS, oR1 = W::ROWS + R, oR2 = W::ROWS + 2 * R;   // facet-row arrays of a unit: duals, two work arrays
-    double *const PA = sm + W::FIXED + (SPLIT ? 0 : pad2(U * US));
-    const double *A = PA, *BC = PA + pad2(m * N), *CEN = sm + W::CEN;
+    const double *CEN = sm + W::CEN;
     double *SOC = sm + W::SOC, *SC = sm + W::SC;
     int red_phase = 0;
     WG_STAMP_INIT();
@@ -753,19 +793,19 @@ GCS_HD void wg_solve_vertex(const WgArgs<T> &a, int v, double rho, double mu_sca
         }
         WG_ARRIVE(30);
         WG_SYNC();
-        WG_STAMP(30);
+        WG_STAMP(30); WG_REGION();
         { Place pl; bg_tasks(pl); }
         WG_ARRIVE(31);
         WG_SYNC();
-        WG_STAMP(31);
+        WG_STAMP(31); WG_REGION();
         { Place pl; v_tasks(pl); }
         WG_ARRIVE(32);
         WG_SYNC();
-        WG_STAMP(32);
+        WG_STAMP(32); WG_REGION();
         { Place pl; rhs_tasks(pl, wk); }
         WG_ARRIVE(33);
         WG_SYNC();
-        WG_STAMP(33);
+        WG_STAMP(33); WG_REGION();
     };
     // the cone's part of a direction, as soon as (d zeta, dt) exist: slack direction xs = (dt, d z1 - d z2) and dual direction
     // dl = kappa - lambda - W^{-2} xs (kappa = 0 for the affine direction)
@@ -789,7 +829,7 @@ GCS_HD void wg_solve_vertex(const WgArgs<T> &a, int v, double rho, double mu_sca
         WG_WAVE0() wave_ldl_solve<NB1>(sm + W::M, sm + W::PIVM, sm + W::RHS, sm + W::SOL);
         WG_ARRIVE(34);
         WG_SYNC();
-        WG_STAMP(34);
+        WG_STAMP(34); WG_REGION();
         // solution back in (x, z1, z2, y_v): dz1 = du + dz2
         auto dzeta = [&](int i) { return i < N ? sm[W::SOL + NX + i] + sm[W::SOL + NX + N + i] : sm[W::SOL + NX + i]; };
         Place plw;
@@ -813,7 +853,7 @@ GCS_HD void wg_solve_vertex(const WgArgs<T> &a, int v, double rho, double mu_sca
         }
         WG_ARRIVE(36);
         WG_SYNC();
-        WG_STAMP(36);
+        WG_STAMP(36); WG_REGION();
         // the cone, beside the pipeline below.  Two lanes of the last wavefront form the cone's directions (both the same values) and
         // then ONE step bound each, side by side: lane 0 the slack side, lane 1 the dual side (a square root and two reciprocal chains
         // each).  (Round 4, measured and rejected: a third lane on another wavefront forming the corrector's second-order cone term
@@ -885,7 +925,7 @@ GCS_HD void wg_solve_vertex(const WgArgs<T> &a, int v, double rho, double mu_sca
         }
         WG_ARRIVE(39);
         WG_SYNC();
-        WG_STAMP(39);
+        WG_STAMP(39); WG_REGION();
     };
 
     int status = -1, it = 0, it_total = 0, stalled = 0;
@@ -901,6 +941,7 @@ GCS_HD void wg_solve_vertex(const WgArgs<T> &a, int v, double rho, double mu_sca
         continue;                                                                                                              \
     }
     for (it = 0;; ++it) {
+    WG_REGION();
     if (init_pending) {
     // ---- start point: the record's iterate, or the strictly feasible point of oracle_solve_vertex ----
         init_pending = false; stalled = 0; saved = false;
@@ -1016,7 +1057,7 @@ GCS_HD void wg_solve_vertex(const WgArgs<T> &a, int v, double rho, double mu_sca
         }
         WG_ARRIVE(1);
         const Red3 r0 = wg_reduce<WG_VM>(Red3{bad ? -1.0 : 1.0, acc, 0.0}, sm + W::RED, red_phase);
-        WG_STAMP(1);
+        WG_STAMP(1); WG_REGION();
         // (workgroup-uniform scalars go to scalar registers: the branches on them are then scalar branches, not EXEC-masked regions)
         const double gap = wg_uniform(r0.s1);
         const double mu = wg_uniform(r0.mn < 0.0 ? 0.0 / 0.0 : gap * inv_deg);
@@ -1177,7 +1218,7 @@ GCS_HD void wg_solve_vertex(const WgArgs<T> &a, int v, double rho, double mu_sca
         }
         WG_ARRIVE(2);
         WG_SYNC();
-        WG_STAMP(2);
+        WG_STAMP(2); WG_REGION();
         if (wg_uniform(SC[SC_CONEFAIL]) != 0.0) {
             status = gcs_math::boundary_status(mu, a.ipm_tol, use_warm);
             if (status == 0) break;
@@ -1273,7 +1314,7 @@ GCS_HD void wg_solve_vertex(const WgArgs<T> &a, int v, double rho, double mu_sca
         }
         WG_ARRIVE(3);
         WG_SYNC();
-        WG_STAMP(3);
+        WG_STAMP(3); WG_REGION();
         if constexpr (BOX) {
             // 1 / s of the y pivot (every thread of the unit forms it: no region of its own), the last entry of BW, and
             // BQ = X_e' BW (B_e X_e = diag(BD XD) + BRS BW BQ' is never formed)
@@ -1289,12 +1330,12 @@ GCS_HD void wg_solve_vertex(const WgArgs<T> &a, int v, double rho, double mu_sca
             }
             WG_ARRIVE(4);
             WG_SYNC();
-            WG_STAMP(4);
+            WG_STAMP(4); WG_REGION();
             if (!first_warm) {      // affine solve, head 1/4 (a re-centring iteration has no affine solve: none of its four head steps)
                 { Place plx; te_tasks(plx, false); }
                 WG_SYNC();
             }
-            WG_STAMP(5);
+            WG_STAMP(5); WG_REGION();
         } else {
         WG_FOR(t, d * NW * NW) {
             const int u = 1 + t / (NW * NW), ij = t - (u - 1) * (NW * NW), i = ij / NW, j = ij - i * NW;
@@ -1307,7 +1348,7 @@ GCS_HD void wg_solve_vertex(const WgArgs<T> &a, int v, double rho, double mu_sca
         }
         WG_ARRIVE(4);
         WG_SYNC();
-        WG_STAMP(4);
+        WG_STAMP(4); WG_REGION();
         Place plx;
         WG_FOR_AT(t, d * NW * NX, plx.at(d * NW * NX)) {     // B_e X_e, written over the (now dead) factor of the block
             const int u = 1 + t / (NW * NX), ic = t - (u - 1) * (NW * NX), i = ic / NX, c = ic - i * NX, h = c / N;
@@ -1320,7 +1361,7 @@ GCS_HD void wg_solve_vertex(const WgArgs<T> &a, int v, double rho, double mu_sca
         if (!first_warm) te_tasks(plx, false);            // affine solve, head 1/4
         WG_ARRIVE(5);
         WG_SYNC();
-        WG_STAMP(5);
+        WG_STAMP(5); WG_REGION();
         }
         // ================= side sums: Bs, BXs, X'BX, equality residuals =================
         Place plq;
@@ -1408,7 +1449,7 @@ GCS_HD void wg_solve_vertex(const WgArgs<T> &a, int v, double rho, double mu_sca
         if (!first_warm) bg_tasks(plq);                   // affine solve, head 2/4
         WG_ARRIVE(6);
         WG_SYNC();
-        WG_STAMP(6);
+        WG_STAMP(6); WG_REGION();
         // ================= sides: factor, invert, Y_s = Bs^{-1} BXs (over the dead factor) =================
         Place ply;
         if (sides) {
@@ -1416,7 +1457,7 @@ GCS_HD void wg_solve_vertex(const WgArgs<T> &a, int v, double rho, double mu_sca
             WG_FIRST_WAVES(sd, 2) wave_ldl<NW>(sm + W::BS + sd * NW * NW, sm + W::PIVS + sd * NW);
             WG_ARRIVE(7);
             WG_SYNC();
-            WG_STAMP(7);
+            WG_STAMP(7); WG_REGION();
             WG_FOR(t, 2 * NW) {
                 const int s = t / NW, c = t - s * NW;
                 ldl_inverse_col<NW, (!BOX && NW > 9)>(sm + W::BS + s * NW * NW, sm + W::PIVS + s * NW, c, sm + W::BSI + s * NW * NW, NW);
@@ -1439,7 +1480,7 @@ GCS_HD void wg_solve_vertex(const WgArgs<T> &a, int v, double rho, double mu_sca
         if (!first_warm) v_tasks(ply);                    // affine solve, head 3/4
         WG_ARRIVE(9);
         WG_SYNC();
-        WG_STAMP(9);
+        WG_STAMP(9); WG_REGION();
         // ================= reduced border matrix in the (x, u, z2, y_v) variables =================
         // One region: every entry of the lower triangle directly in the new variables.  The change of variables (u, z2) =
         // (z1 - z2, z2) -- columns / rows of z2 gain those of z1; the cone term Su then sits on u alone (with the cone inactive
@@ -1493,11 +1534,11 @@ GCS_HD void wg_solve_vertex(const WgArgs<T> &a, int v, double rho, double mu_sca
         }
         WG_ARRIVE(10);
         WG_SYNC();
-        WG_STAMP(10);
+        WG_STAMP(10); WG_REGION();
         WG_WAVE0() wave_ldl<NB1>(sm + W::M, sm + W::PIVM);      // L D L' inside one wavefront; no explicit inverse
         WG_ARRIVE(11);
         WG_SYNC();
-        WG_STAMP(11);
+        WG_STAMP(11); WG_REGION();
         WG_STAMP(12);
         double rmax = 0.0, c1 = 0.0, c2 = 0.0, amax_cone = 1e300;
         double sigmu;
@@ -1514,7 +1555,7 @@ GCS_HD void wg_solve_vertex(const WgArgs<T> &a, int v, double rho, double mu_sca
             sigmu = mu_ref;
             WG_ARRIVE(14);
             WG_SYNC();
-            WG_STAMP(14);
+            WG_STAMP(14); WG_REGION();
         } else {
         // ================= affine direction (kappa = 0) =================
         solve_tail(SC_DTA, false);      // the head of the affine solve rode in the factorisation regions above
@@ -1543,7 +1584,7 @@ GCS_HD void wg_solve_vertex(const WgArgs<T> &a, int v, double rho, double mu_sca
         WG_CONE() { amax_cone = fmin(SC[SC_AMAXC], SC[SC_AMAXC2]); c1 += SC[SC_C1C]; c2 += SC[SC_C2C]; }
         WG_ARRIVE(14);
         const Red3 rb = wg_reduce<WG_VM>(Red3{fmin(rmax > 0.0 ? rcp1(rmax) : 1e300, amax_cone), c1, c2}, sm + W::RED, red_phase);
-        WG_STAMP(14);
+        WG_STAMP(14); WG_REGION();
         {
             const double al = fmin(1.0, rb.mn);
             const double mu_aff = (gap + al * rb.s1 + al * al * rb.s2) * inv_deg;
@@ -1617,7 +1658,7 @@ GCS_HD void wg_solve_vertex(const WgArgs<T> &a, int v, double rho, double mu_sca
         }
         WG_ARRIVE(16);
         WG_SYNC();
-        WG_STAMP(16);
+        WG_STAMP(16); WG_REGION();
         solve_head(true);
         solve_tail(SC_DT, true);
         WG_STAMP(18);
@@ -1644,7 +1685,7 @@ GCS_HD void wg_solve_vertex(const WgArgs<T> &a, int v, double rho, double mu_sca
         WG_CONE() amax_cone = fmin(SC[SC_AMAXC], SC[SC_AMAXC2]);
         WG_ARRIVE(19);
         const Red3 rd = wg_reduce<WG_VM>(Red3{fmin(rmax > 0.0 ? rcp1(rmax) : 1e300, amax_cone), 0.0, 0.0}, sm + W::RED, red_phase);
-        WG_STAMP(19);
+        WG_STAMP(19); WG_REGION();
         WG_CONE() {      // step length with the cone guard (round-off must not push either cone point outside)
             double al = gcs_math::step_length(rd.mn);
             for (int tries = 0; tries < 40; ++tries) {
@@ -1658,7 +1699,7 @@ GCS_HD void wg_solve_vertex(const WgArgs<T> &a, int v, double rho, double mu_sca
         }
         WG_ARRIVE(20);
         WG_SYNC();
-        WG_STAMP(20);
+        WG_STAMP(20); WG_REGION();
         const double alpha = wg_uniform(SC[SC_ALPHA]);
         stalled = gcs_math::step_stalled(alpha);
         // ================= update =================
@@ -1686,9 +1727,10 @@ GCS_HD void wg_solve_vertex(const WgArgs<T> &a, int v, double rho, double mu_sca
         }
         WG_ARRIVE(21);
         WG_SYNC();
-        WG_STAMP(21);
+        WG_STAMP(21); WG_REGION();
     }
 #undef WG_FAIL_OR_RESTART
+#undef WG_REGION
     it_total += it;
     if (wrec != nullptr) {
         WG_ONE() {
