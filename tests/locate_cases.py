@@ -14,9 +14,10 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
+
+from gcs_admm_amd.native_build import build_library
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "gcs_admm_amd", "csrc")
@@ -181,14 +182,11 @@ def check_crafted(hits, names, polys, pts, expect):
 
 
 # ------------------------------------------------------------------------------------------- the host build
-def load_locate_emu(csrc=CSRC, out=None):
-    """tests/hostemu/locate_emu.cpp against the point_locate_core.h of `csrc`, rebuilt when a source is newer.  -ffp-contract=off:
+def load_locate_emu():
+    """tests/hostemu/locate_emu.cpp against csrc/point_locate_core.h, rebuilt when a source changes.  -ffp-contract=off:
     only the written fma calls fuse, as in the kernel"""
-    out = out or os.path.join(ROOT, "tests", "hostemu", "liblocateemu.so")
-    hdr = os.path.join(csrc, "point_locate_core.h")
-    if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(EMU_SRC), os.path.getmtime(hdr)):
-        subprocess.check_call(["g++", "-O1", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-I" + str(csrc), EMU_SRC, "-o", str(out)])
-    lib = C.CDLL(str(out))
+    out = build_library(os.path.join(ROOT, "tests", "hostemu", "liblocateemu.so"), [(EMU_SRC, [])], flags=["-O1", "-std=c++17", "-ffp-contract=off", "-fPIC", "-I" + CSRC])
+    lib = C.CDLL(out)
     lib.locate_emu_hits.restype = C.c_longlong
     lib.locate_emu_hits.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_double,
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong]

@@ -14,7 +14,6 @@ from __future__ import annotations
 import ctypes as C
 import functools
 import os
-import subprocess
 import sys
 from dataclasses import dataclass, field
 
@@ -24,6 +23,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 from gcs_admm_amd.graph import convert_pt_to_polytope   # noqa: E402
+from gcs_admm_amd.native_build import build_library     # noqa: E402
 from gcs_admm_amd.scene import SWEEP_PAD                 # noqa: E402
 from oracle import polytope_oracle as PO                 # noqa: E402
 
@@ -240,13 +240,10 @@ def reference(name, n):
 
 
 # ------------------------------------------------------------------------------------------- the host build
-def load_lp_emu(csrc=CSRC, out=None):
-    """tests/hostemu/lp_emu.cpp against the polytope_lp_core.h of `csrc`, rebuilt when a source is newer"""
-    out = out or os.path.join(ROOT, "tests", "hostemu", "liblpemu.so")
-    hdr = os.path.join(csrc, "polytope_lp_core.h")
-    if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(EMU_SRC), os.path.getmtime(hdr)):
-        subprocess.check_call(["g++", "-O1", "-std=c++17", "-fPIC", "-shared", "-I" + str(csrc), EMU_SRC, "-o", str(out)])
-    return C.CDLL(str(out))
+def load_lp_emu():
+    """tests/hostemu/lp_emu.cpp against csrc/polytope_lp_core.h, rebuilt when a source changes"""
+    out = build_library(os.path.join(ROOT, "tests", "hostemu", "liblpemu.so"), [(EMU_SRC, [])], flags=["-O1", "-std=c++17", "-fPIC", "-I" + CSRC])
+    return C.CDLL(out)
 
 
 class HostLP:

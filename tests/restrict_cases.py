@@ -24,19 +24,17 @@ that nothing of the order 1e-6 has to be allowed.  Deliberately outside: centres
 at n = 2), overlaps thinner than 1e-4 (the emulation needs about 80 of its 100 iterations at 1e-5)."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 
 from gcs_admm_amd.graph import chebyshev_center, convert_pt_to_polytope
+from gcs_admm_amd.native_build import build_library
 from gcs_admm_amd.rounding import solve_path_restriction
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(ROOT, "gcs_admm_amd", "csrc")
 SRC = os.path.join(HERE, "hostemu", "restrict_emu.cpp")
-DEPS = [SRC] + [os.path.join(CSRC, f) for f in ("path_restrict_core.h", "restrict_plan.h", "gcs_math.h", "step_args.h")] + \
-       [os.path.join(ROOT, "include", "gcsadmm.h")]
 LIB = os.path.join(HERE, "hostemu", "librestrictemu.so")
 TOL, MAX_ITER = 1e-10, 100
 OK, BAD_ARG, UNSUPPORTED = 0, 1, 2
@@ -448,10 +446,7 @@ def split_points(n, pp, flat):
 
 # ---- the host emulation ----
 def build_lib(out=LIB):
-    if os.path.exists(out) and os.path.getmtime(out) >= max(os.path.getmtime(d) for d in DEPS):
-        return out
-    subprocess.check_call(["g++", "-std=c++17", "-fPIC", "-O2", "-shared", "-I" + CSRC, "-I" + os.path.join(ROOT, "include"), SRC, "-o", out])
-    return out
+    return build_library(out, [(SRC, [])], flags=["-std=c++17", "-fPIC", "-O2", "-I" + CSRC, "-I" + os.path.join(ROOT, "include")])
 
 
 _lib = None

@@ -10,9 +10,10 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
+
+from gcs_admm_amd.native_build import build_library
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "gcs_admm_amd", "csrc")
@@ -84,13 +85,10 @@ def brute_force(lo, hi, pad):
 
 
 # ------------------------------------------------------------------------------------------- the host build
-def load_sweep_emu(csrc=CSRC, out=None):
-    """tests/hostemu/sweep_emu.cpp against the box_sweep_core.h of `csrc`, rebuilt when a source is newer"""
-    out = out or os.path.join(ROOT, "tests", "hostemu", "libsweepemu.so")
-    hdr = os.path.join(csrc, "box_sweep_core.h")
-    if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(EMU_SRC), os.path.getmtime(hdr)):
-        subprocess.check_call(["g++", "-O1", "-std=c++17", "-fPIC", "-shared", "-I" + str(csrc), EMU_SRC, "-o", str(out)])
-    lib = C.CDLL(str(out))
+def load_sweep_emu():
+    """tests/hostemu/sweep_emu.cpp against csrc/box_sweep_core.h, rebuilt when a source changes"""
+    out = build_library(os.path.join(ROOT, "tests", "hostemu", "libsweepemu.so"), [(EMU_SRC, [])], flags=["-O1", "-std=c++17", "-fPIC", "-I" + CSRC])
+    lib = C.CDLL(out)
     lib.sweep_emu_pairs.restype = C.c_longlong
     lib.sweep_emu_pairs.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_longlong]
     lib.sweep_emu_scan.restype = C.c_int

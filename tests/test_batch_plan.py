@@ -5,21 +5,17 @@ refusal with its message, and the registers and scratch of the two batch kernels
 computes with a batch is checked by test_gpu_batch.py."""
 import ctypes as C
 import os
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
 import test_create_plan as cp
-from gcs_admm_amd.build import T512
 from gcs_admm_amd.cases import load_fixture
 from gcs_admm_amd.graph import lattice_boxes
 from test_gpu_configs import _region_star
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "hostemu", "batch_plan_emu.cpp")
-DEPS = [SRC, os.path.join(cp.CSRC, "batch_plan.h")] + cp.DEPS[1:]
 LIB = os.path.join(HERE, "hostemu", "libbatchplanemu.so")
 OK, BAD_ARG, UNSUPPORTED = cp.OK, cp.BAD_ARG, cp.UNSUPPORTED
 WG256 = dict(vertex_program=3)       # what solver.DeviceSolver(program="workgroup256") asks for: the program a batch member runs
@@ -27,15 +23,7 @@ MAX_SPECIAL_DEG = 256                # step_args.h
 
 
 def build_lib(out=LIB):
-    if os.path.exists(out) and os.path.getmtime(out) >= max(os.path.getmtime(d) for d in DEPS):
-        return out
-    cxx = ["g++", "-std=c++17", "-fPIC", "-O1", "-I" + cp.CSRC, "-I" + os.path.join(cp.ROOT, "include")]
-    with tempfile.TemporaryDirectory() as tmp:
-        objs = [os.path.join(tmp, "sizes.o"), os.path.join(tmp, "sizes_t512.o")]
-        procs = [subprocess.Popen(cxx + ["-c", cp.SIZES, "-o", objs[0]]), subprocess.Popen(cxx + T512 + ["-c", cp.SIZES, "-o", objs[1]])]
-        assert all(p.wait() == 0 for p in procs)
-        subprocess.check_call(cxx + ["-shared", SRC] + objs + ["-o", out])
-    return out
+    return cp.build_shim(out, SRC)
 
 
 @pytest.fixture(scope="module")

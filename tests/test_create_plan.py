@@ -5,8 +5,6 @@ rules, the wavefront packing, the schedule knobs of include/gcsadmm.h, the regio
 messages.  What the GPU runs with these plans is checked by test_gpu_parity.py / test_gpu_configs.py."""
 import ctypes as C
 import os
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
@@ -16,31 +14,27 @@ from gcs_admm_amd.build import T512
 from gcs_admm_amd.cases import load_fixture
 from gcs_admm_amd.graph import convert_pt_to_polytope, graph_from_sets, lattice_boxes
 from gcs_admm_amd.abi import graph_desc
+from gcs_admm_amd.native_build import build_library
 from test_gpu_configs import _region_row, _region_star
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(ROOT, "gcs_admm_amd", "csrc")
 SRC, SIZES = os.path.join(HERE, "hostemu", "plan_emu.cpp"), os.path.join(HERE, "hostemu", "wg_sizes.cpp")
-DEPS = [SRC, SIZES, os.path.join(ROOT, "include", "gcsadmm.h")] + [os.path.join(CSRC, f) for f in (
-    "create_plan.h", "vertex_program.h", "vertex_program.inc", "vertex_wg.h", "terminal_region.h", "step_args.h", "warm_start.h",
-    "canonical_box.h", "gcs_math.h")]
 LIB = os.path.join(HERE, "hostemu", "libplanemu.so")
 OK, BAD_ARG, UNSUPPORTED = 0, 1, 2          # gcsadmm_status
 KB = 1024
 
 
+def build_shim(out, src, flags=("-O1",), extra=()):
+    """a plan shim: wg_sizes.cpp at 256 and at 512 threads (build.T512, as vertex_wg.hip is built), linked with ``src`` (compiled with
+    ``extra`` on top).  Every shim built with the same flags links the same two sizing objects: they are compiled once."""
+    cxx = ["-std=c++17", "-fPIC", "-I" + CSRC, "-I" + os.path.join(ROOT, "include")] + list(flags)
+    return build_library(out, [(SIZES, []), (SIZES, T512), (src, list(extra))], flags=cxx)
+
+
 def build_lib(out=LIB, flags=("-O1",)):
-    """the shim: wg_sizes.cpp at 256 and at 512 threads (build.T512, as vertex_wg.hip is built), linked with plan_emu.cpp"""
-    if os.path.exists(out) and os.path.getmtime(out) >= max(os.path.getmtime(d) for d in DEPS):
-        return out
-    cxx = ["g++", "-std=c++17", "-fPIC", "-I" + CSRC, "-I" + os.path.join(ROOT, "include")] + list(flags)
-    with tempfile.TemporaryDirectory() as tmp:
-        objs = [os.path.join(tmp, "sizes.o"), os.path.join(tmp, "sizes_t512.o")]
-        procs = [subprocess.Popen(cxx + ["-c", SIZES, "-o", objs[0]]), subprocess.Popen(cxx + T512 + ["-c", SIZES, "-o", objs[1]])]
-        subprocess.check_call(cxx + ["-shared", SRC] + objs + ["-o", out])
-        assert all(p.wait() == 0 for p in procs)
-    return out
+    return build_shim(out, SRC, flags)
 
 
 def load(path):

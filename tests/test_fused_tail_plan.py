@@ -4,17 +4,14 @@ in one edge workgroup, every generic vertex on the in-LDS workgroup program, no 
 by case, and the LDS request of the launch that carries the tail."""
 import ctypes as C
 import os
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
 from fused_tail_cases import EDGE_BLOCK, largest_fused_lattice, path3, smallest_unfused_lattice
-from gcs_admm_amd.build import T512
 from gcs_admm_amd.cases import load_fixture
 from gcs_admm_amd.graph import lattice_boxes
-from test_create_plan import CSRC, DEPS, HERE, ROOT, SIZES, descriptor
+from test_create_plan import HERE, build_shim, descriptor
 
 SRC = os.path.join(HERE, "hostemu", "fused_plan_emu.cpp")
 LIB = os.path.join(HERE, "hostemu", "libfusedplanemu.so")
@@ -22,15 +19,7 @@ LIB = os.path.join(HERE, "hostemu", "libfusedplanemu.so")
 
 @pytest.fixture(scope="module")
 def lib():
-    deps = [SRC, os.path.join(CSRC, "edge_step.h")] + DEPS[1:]
-    if not (os.path.exists(LIB) and os.path.getmtime(LIB) >= max(os.path.getmtime(d) for d in deps)):
-        cxx = ["g++", "-std=c++17", "-fPIC", "-O1", "-I" + CSRC, "-I" + os.path.join(ROOT, "include")]
-        with tempfile.TemporaryDirectory() as tmp:
-            objs = [os.path.join(tmp, "sizes.o"), os.path.join(tmp, "sizes_t512.o")]
-            procs = [subprocess.Popen(cxx + ["-c", SIZES, "-o", objs[0]]), subprocess.Popen(cxx + T512 + ["-c", SIZES, "-o", objs[1]])]
-            assert all(p.wait() == 0 for p in procs)
-            subprocess.check_call(cxx + ["-shared", SRC] + objs + ["-o", LIB])
-    lib = C.CDLL(LIB)
+    lib = C.CDLL(build_shim(LIB, SRC))
     lib.fused_plan_error.restype = C.c_char_p
     return lib
 

@@ -10,27 +10,26 @@ the worst case."""
 from gcs_admm_amd import IPM_TOL
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from gcs_admm_amd.cases import load_fixture
+from gcs_admm_amd.native_build import build_library
 from solve_agreement import Agreement, NewtonParity, oracle_step
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 
 
+def build_emu():
+    return build_library(os.path.join(HERE, "hostemu", "libemu.so"), [(os.path.join(HERE, "hostemu", "emu.cpp"), [])],
+                         flags=["-O1", "-std=c++17", "-fPIC", "-I" + os.path.join(ROOT, "gcs_admm_amd", "csrc")])
+
+
 @pytest.fixture(scope="module")
 def emu():
-    src = os.path.join(HERE, "hostemu", "emu.cpp")
-    out = os.path.join(HERE, "hostemu", "libemu.so")
-    hdr = os.path.join(ROOT, "gcs_admm_amd", "csrc", "vertex_program.h")
-    deps = [src, hdr, os.path.join(HERE, "hostemu", "emu_body.inc")] + [os.path.join(os.path.dirname(hdr), f) for f in ("vertex_program.inc", "warm_start.h", "step_args.h", "gcs_math.h")]
-    if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(d) for d in deps):
-        subprocess.check_call(["g++", "-O1", "-std=c++17", "-fPIC", "-shared", "-I" + os.path.dirname(hdr), src, "-o", out])
-    return C.CDLL(out)
+    return C.CDLL(build_emu())
 
 
 def _p(a):

@@ -4,7 +4,6 @@ equals the in-LDS form bit for bit (same layout, same arithmetic, same order) fo
 tasks of every region in ascending and in descending order; on hubs too large for LDS it matches the CPU oracle, warm and cold."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -12,6 +11,7 @@ import pytest
 from gcs_admm_amd import IPM_TOL
 from gcs_admm_amd.cases import load_fixture
 from gcs_admm_amd.graph import lattice_boxes
+from gcs_admm_amd.native_build import build_library
 from solve_agreement import Agreement, NewtonParity, oracle_step
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -22,13 +22,9 @@ CSRC = os.path.join(ROOT, "gcs_admm_amd", "csrc")
 @pytest.fixture(scope="module")
 def libs():
     src = os.path.join(HERE, "hostemu", "wg_split_emu.cpp")
-    deps = [src] + [os.path.join(CSRC, f) for f in ("vertex_wg.h", "gcs_math.h", "warm_start.h", "step_args.h")]
     out = {}
     for rev, name, flags in ((False, "libwgsplitemu.so", []), (True, "libwgsplitemu_rev.so", ["-DGCS_WG_REVERSE"])):
-        so = os.path.join(HERE, "hostemu", name)
-        if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(d) for d in deps):
-            subprocess.check_call(["g++", "-O1", "-std=c++17", "-fPIC", "-shared", "-I" + CSRC] + flags + [src, "-o", so])
-        lib = C.CDLL(so)
+        lib = C.CDLL(build_library(os.path.join(HERE, "hostemu", name), [(src, flags)], flags=["-O1", "-std=c++17", "-fPIC", "-I" + CSRC]))
         out[rev] = getattr(lib, "wg_split_emu_vertex_step_rev" if rev else "wg_split_emu_vertex_step")
     return out
 

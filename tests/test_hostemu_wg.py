@@ -7,13 +7,13 @@ order-dependent operations are the floating-point sums of the workgroup reductio
 from gcs_admm_amd import IPM_TOL
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from gcs_admm_amd.cases import load_fixture
 from gcs_admm_amd.graph import lattice_boxes
+from gcs_admm_amd.native_build import build_library
 from solve_agreement import Agreement, NewtonParity, oracle_step
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -21,17 +21,16 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(ROOT, "gcs_admm_amd", "csrc")
 
 
+def build_libs():
+    """[ascending, descending task order] (rebuilt when the program changes)"""
+    return [build_library(os.path.join(HERE, "hostemu", name), [(os.path.join(HERE, "hostemu", "wg_emu.cpp"), flags)],
+                          flags=["-O1", "-std=c++17", "-fPIC", "-I" + CSRC])
+            for name, flags in (("libwgemu.so", []), ("libwgemu_rev.so", ["-DGCS_WG_REVERSE"]))]
+
+
 @pytest.fixture(scope="module")
 def libs():
-    src = os.path.join(HERE, "hostemu", "wg_emu.cpp")
-    deps = [src] + [os.path.join(CSRC, f) for f in ("vertex_wg.h", "gcs_math.h", "warm_start.h", "step_args.h")]      # (rebuilt when the program changes)
-    out = []
-    for name, flags in (("libwgemu.so", []), ("libwgemu_rev.so", ["-DGCS_WG_REVERSE"])):
-        so = os.path.join(HERE, "hostemu", name)
-        if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(d) for d in deps):
-            subprocess.check_call(["g++", "-O1", "-std=c++17", "-fPIC", "-shared", "-I" + CSRC] + flags + [src, "-o", so])
-        out.append(C.CDLL(so))
-    return out
+    return [C.CDLL(so) for so in build_libs()]
 
 
 def _p(a):

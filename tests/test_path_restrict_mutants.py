@@ -18,15 +18,13 @@ Not every error moves a cost.  RESTRICT_REG = 1e-4 in place of 1e-10 passes ever
 method recomputes in every iteration correct that.  The contract holds the answers, not the way the iteration takes to them.  (An
 error in the residual itself is another matter: 1e-3 relative in one component of the right-hand side of ``direction`` sends the
 longer staircases of the old cases to status -1 already.)"""
-import ctypes as C
 import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 import restrict_cases as rc
+from mutant_build import build_mutants
 
 # (anchor in path_restrict_core.h, replacement): each anchor must occur exactly once
 MUTANTS = {
@@ -46,25 +44,10 @@ UNSEEN = ["large_reg"]
 
 @pytest.fixture(scope="module")
 def builds(tmp_path_factory):
-    base = tmp_path_factory.mktemp("restrict_mutants")
-    procs = {}
-    for name, subs in MUTANTS.items():
-        csrc = base / name
-        csrc.mkdir()
-        text = open(os.path.join(rc.CSRC, "path_restrict_core.h")).read()
-        for old, new in subs:
-            assert text.count(old) == 1, f"mutant {name}: anchor {old!r} does not occur exactly once in path_restrict_core.h -- update MUTANTS"
-            text = text.replace(old, new)
-        (csrc / "path_restrict_core.h").write_text(text)
-        shutil.copy(os.path.join(rc.CSRC, "restrict_plan.h"), csrc / "restrict_plan.h")      # it includes the core from its own directory
-        so = csrc / "librestrictemu.so"
-        procs[name] = (subprocess.Popen(["g++", "-O1", "-std=c++17", "-fPIC", "-shared", "-I" + str(csrc), "-I" + rc.CSRC,
-                                         "-I" + os.path.join(rc.ROOT, "include"), rc.SRC, "-o", str(so)]), so)
-    libs = {}
-    for name, (p, so) in procs.items():
-        assert p.wait() == 0, f"build of mutant {name} failed"
-        libs[name] = C.CDLL(str(so))
-        libs[name].restrict_emu_solve.argtypes = rc.emu().restrict_emu_solve.argtypes
+    libs = build_mutants(tmp_path_factory.mktemp("restrict_mutants"), "path_restrict_core.h", MUTANTS, rc.SRC,
+                         flags=["-I" + rc.CSRC, "-I" + os.path.join(rc.ROOT, "include")])
+    for lib in libs.values():
+        lib.restrict_emu_solve.argtypes = rc.emu().restrict_emu_solve.argtypes
     return libs
 
 

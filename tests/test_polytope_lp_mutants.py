@@ -4,14 +4,10 @@ copy of csrc/polytope_lp_core.h with one seeded error each must fail it, and the
   * 0.99 -> 0.5 in the step rule: still converges to the same answers, in more Newton steps than the bound allows;
   * the margin of the early dual bound dropped: touching regions 300 from the origin are decided "apart" on a dual bound that is
     only valid up to the dual residual times |x|."""
-import ctypes as C
-import os
-import shutil
-import subprocess
-
 import pytest
 
 import lp_cases as L
+from mutant_build import build_mutants
 
 # (anchor in polytope_lp_core.h, replacement): each anchor must occur exactly once
 MUTANTS = {
@@ -25,23 +21,7 @@ CASES = [(name, n) for n in (1, 2, 3) for name in ("touching", "scales", "mixed_
 
 @pytest.fixture(scope="module")
 def builds(tmp_path_factory):
-    base = tmp_path_factory.mktemp("lp_mutants")
-    procs = {}
-    for name, subs in MUTANTS.items():
-        csrc = base / name
-        csrc.mkdir()
-        text = open(os.path.join(L.CSRC, "polytope_lp_core.h")).read()
-        for old, new in subs:
-            assert text.count(old) == 1, f"mutant {name}: anchor {old!r} does not occur exactly once in polytope_lp_core.h -- update MUTANTS"
-            text = text.replace(old, new)
-        (csrc / "polytope_lp_core.h").write_text(text)
-        so = csrc / "liblpemu.so"
-        procs[name] = (subprocess.Popen(["g++", "-O1", "-std=c++17", "-fPIC", "-shared", "-I" + str(csrc), L.EMU_SRC, "-o", str(so)]), so)
-    libs = {}
-    for name, (p, so) in procs.items():
-        assert p.wait() == 0, f"build of mutant {name} failed"
-        libs[name] = C.CDLL(str(so))
-    return libs
+    return build_mutants(tmp_path_factory.mktemp("lp_mutants"), "polytope_lp_core.h", MUTANTS, L.EMU_SRC)
 
 
 def _violations(lib):

@@ -8,20 +8,17 @@ benchmark1:
   * NT scaling eta x 1.01: a wrong but convergent Newton direction, seen in the iteration counts (totals +2.4 % / +7.4 % warm,
     +1.2 % / +2.0 % cold, per-vertex counts equal in 0.44 - 0.85 of the solves).
 The clean copy passes the contract.  The four builds compile in parallel (~45 s of CPU time in all)."""
-import ctypes as C
 import os
-import shutil
-import subprocess
 
 import pytest
 
 from gcs_admm_amd import IPM_TOL
 from gcs_admm_amd.cases import load_fixture
+from mutant_build import build_mutants
 from solve_agreement import Agreement, NewtonParity, oracle_step
 from test_hostemu_wg import WarmRecords, wg_step
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-CSRC = os.path.join(os.path.dirname(HERE), "gcs_admm_amd", "csrc")
 
 # (anchor in gcs_math.h, replacement): each anchor must occur exactly once
 MUTANTS = {
@@ -35,25 +32,7 @@ STEPS = 12
 
 @pytest.fixture(scope="module")
 def builds(tmp_path_factory):
-    base = tmp_path_factory.mktemp("mutants")
-    procs = {}
-    for name, subs in MUTANTS.items():
-        csrc = base / name / "csrc"
-        shutil.copytree(CSRC, csrc)
-        hdr = csrc / "gcs_math.h"
-        text = hdr.read_text()
-        for old, new in subs:
-            assert text.count(old) == 1, f"mutant {name}: anchor {old!r} does not occur exactly once in gcs_math.h -- update MUTANTS"
-            text = text.replace(old, new)
-        hdr.write_text(text)
-        so = base / name / "libwgemu.so"
-        procs[name] = (subprocess.Popen(["g++", "-O1", "-std=c++17", "-fPIC", "-shared", "-I" + str(csrc),
-                                         os.path.join(HERE, "hostemu", "wg_emu.cpp"), "-o", str(so)]), so)
-    libs = {}
-    for name, (p, so) in procs.items():
-        assert p.wait() == 0, f"build of mutant {name} failed"
-        libs[name] = C.CDLL(str(so))
-    return libs
+    return build_mutants(tmp_path_factory.mktemp("mutants"), "gcs_math.h", MUTANTS, os.path.join(HERE, "hostemu", "wg_emu.cpp"))
 
 
 def _run(oracle_lib, lib, name, cold):

@@ -168,14 +168,11 @@ def test_a_point_terminal_is_the_limit_of_a_small_region():
 @pytest.fixture(scope="module")
 def term_emu():
     import os
-    import subprocess
+    from gcs_admm_amd.native_build import build_library
     here = os.path.dirname(os.path.abspath(__file__))
     csrc = os.path.join(os.path.dirname(here), "gcs_admm_amd", "csrc")
-    src, out = os.path.join(here, "hostemu", "term_emu.cpp"), os.path.join(here, "hostemu", "libtermemu.so")
-    deps = [src] + [os.path.join(csrc, f) for f in ("terminal_region.h", "gcs_math.h", "warm_start.h", "step_args.h")]
-    if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(d) for d in deps):
-        subprocess.check_call(["g++", "-O1", "-std=c++17", "-fPIC", "-shared", "-I" + csrc, src, "-o", out])
-    return C.CDLL(out)
+    return C.CDLL(build_library(os.path.join(here, "hostemu", "libtermemu.so"), [(os.path.join(here, "hostemu", "term_emu.cpp"), [])],
+                                flags=["-O1", "-std=c++17", "-fPIC", "-I" + csrc]))
 
 
 def emu_terminal(lib, n, A, b, cen, d, d_in, is_src, T, rho, tol=IPM_TOL, warm=None):

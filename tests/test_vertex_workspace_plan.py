@@ -3,22 +3,17 @@ of the workgroup program (edge blocks in a device-memory workspace), the workspa
 the split fields added (tests/hostemu/plan_ws_emu.cpp); descriptors and plans are read as in test_create_plan.py."""
 import ctypes as C
 import os
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
 from conftest import BENCHMARKS, star_case
-from gcs_admm_amd.build import T512
 from gcs_admm_amd.cases import load_fixture
 from gcs_admm_amd.graph import graph_from_sets, lattice_boxes
-from test_create_plan import BAD_ARG, DEPS, KB, OK, SIZES, UNSUPPORTED, descriptor, make, _p
+from test_create_plan import BAD_ARG, KB, OK, UNSUPPORTED, build_shim, descriptor, make, _p
 from test_gpu_vertex_workspace import hub_case
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-CSRC = os.path.join(ROOT, "gcs_admm_amd", "csrc")
 SRC = os.path.join(HERE, "hostemu", "plan_ws_emu.cpp")
 LIB = os.path.join(HERE, "hostemu", "libplanwsemu.so")
 OLD_MSG = "a vertex sub-problem (degree x facets) does not fit the 160 KB of LDS of a CU"
@@ -27,15 +22,7 @@ POLY_MSG = "a vertex's border system and polytope do not fit the 160 KB of LDS o
 
 @pytest.fixture(scope="module")
 def lib():
-    deps = DEPS + [SRC]
-    if not os.path.exists(LIB) or os.path.getmtime(LIB) < max(os.path.getmtime(d) for d in deps):
-        cxx = ["g++", "-std=c++17", "-O1", "-fPIC", "-I" + CSRC, "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(HERE, "hostemu")]
-        with tempfile.TemporaryDirectory() as tmp:
-            objs = [os.path.join(tmp, "sizes.o"), os.path.join(tmp, "sizes_t512.o")]
-            subprocess.check_call(cxx + ["-c", SIZES, "-o", objs[0]])
-            subprocess.check_call(cxx + T512 + ["-c", SIZES, "-o", objs[1]])
-            subprocess.check_call(cxx + ["-shared", SRC] + objs + ["-o", LIB])
-    lib = C.CDLL(LIB)
+    lib = C.CDLL(build_shim(LIB, SRC, extra=["-I" + os.path.join(HERE, "hostemu")]))
     lib.plan_emu_error.restype = C.c_char_p
     lib.plan_emu_get.restype = C.c_double
     lib.plan_emu_vec.restype = C.c_longlong

@@ -3,22 +3,21 @@ vertex program's own source compiled for the host with a counting scalar type.  
 ``roofline_fp``; never part of the product path."""
 import ctypes as C
 import os
-import subprocess
+import sys
 
 import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+from gcs_admm_amd.native_build import build_library   # noqa: E402
 CSRC = os.path.join(ROOT, "gcs_admm_amd", "csrc")
 LIB = os.path.join(HERE, "libwgflops.so")
 
 
 def build(force=False):
-    src = os.path.join(HERE, "wg_flops.cpp")
-    deps = [src, os.path.join(CSRC, "vertex_wg.h"), os.path.join(CSRC, "gcs_math.h"), os.path.join(CSRC, "step_args.h")]
-    if force or not os.path.exists(LIB) or os.path.getmtime(LIB) < max(os.path.getmtime(d) for d in deps):
-        subprocess.check_call(["g++", "-O1", "-std=c++17", "-fPIC", "-shared", "-I" + CSRC, src, "-o", LIB])
-    return LIB
+    return build_library(LIB, [(os.path.join(HERE, "wg_flops.cpp"), [])], flags=["-O1", "-std=c++17", "-fPIC", "-I" + CSRC], force=force)
 
 
 def _p(a):
@@ -57,8 +56,6 @@ def count_vertex_step(g, zedge=None, mu=None, rho=1.0, ipm_tol=1e-9, max_vertice
 
 
 if __name__ == "__main__":
-    import sys
-    sys.path.insert(0, ROOT)
     from gcs_admm_amd.cases import load_fixture
     from gcs_admm_amd.graph import lattice_boxes
     for name, g in (("benchmark4", load_fixture("benchmark4")[1]), ("s10k", lattice_boxes(100, 100, seed=0)),

@@ -11,10 +11,8 @@ from oracle.oracle import Oracle
 from scale_demo import polygon_scene
 import test_hostemu as TW, test_hostemu_wg as TG
 
-emu = TW.emu.__wrapped__() if hasattr(TW.emu, "__wrapped__") else None
-wg = C.CDLL(os.path.join(ROOT, "tests", "hostemu", "libwgemu.so"))
-if emu is None:
-    emu = C.CDLL(os.path.join(ROOT, "tests", "hostemu", "libemu.so"))
+emu = C.CDLL(TW.build_emu())
+wg = C.CDLL(TG.build_libs()[0])
 for seed in map(int, sys.argv[1:]):
     rng = np.random.default_rng(100 + seed)
     As, bs = polygon_scene(5 + seed % 3, seed=seed, m=3 + seed % 5)
