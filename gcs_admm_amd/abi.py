@@ -112,6 +112,11 @@ PROTOTYPES = {
     # the regions under query points on a resident scene (gcs_admm_amd/queries.py)
     "gcsadmm_scene_locate_points": ([_p, _i, _p, _d, _d, _p], _i),
     "gcsadmm_scene_read_hits": ([_p] * 4, _i),
+    # the candidate paths of the rounding step, drawn on the device (gcs_admm_amd/walks.py)
+    "gcsadmm_walks_create": ([_i] + [_p] * 7 + [_i, _p], _i),
+    "gcsadmm_walks_destroy": ([_p], None),
+    "gcsadmm_walks_last_error": ([_p], C.c_char_p),
+    "gcsadmm_walks_sample": ([_p, _p, _i, _p, _i, _i, _i] + [_p] * 4, _i),
 }
 EXPORTS = list(PROTOTYPES)
 

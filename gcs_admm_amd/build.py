@@ -15,11 +15,12 @@ WG = os.path.join(CSRC, "vertex_wg.hip")        # workgroup-cooperative vertex p
 WGD = os.path.join(CSRC, "vertex_wg_dims.hip")  # the same program for n = 1, 4, 5, 7, 8 (own object: the builds run in parallel)
 LP = os.path.join(CSRC, "polytope_lp.hip")      # batched tiny LPs for graph construction (own object, own dependencies)
 TERM = os.path.join(CSRC, "terminal_region.hip")  # x-update of terminals that are regions (own object)
+WALK = os.path.join(CSRC, "path_walk.hip")      # the rounding step's candidate walks (own object, own entry points)
 # (source, object name, extra flags)
 # vertex_wg.hip is built twice: 256 threads per workgroup, and 512 for launches of at most one workgroup per CU (own namespace and entry points)
 T512 = ["-DGCS_WG_THREADS=512", "-Dgcs_wg=gcs_wg_t512", "-DGCS_WG_SYM(name)=name##_t512"]
 UNITS = [(MAIN, "gcsadmm.o", []), (WG, "vertex_wg.o", []), (WG, "vertex_wg_t512.o", T512), (WGD, "vertex_wg_dims.o", []), (WGD, "vertex_wg_dims_t512.o", T512),
-         (LP, "polytope_lp.o", []), (TERM, "terminal_region.o", [])]
+         (LP, "polytope_lp.o", []), (TERM, "terminal_region.o", []), (WALK, "path_walk.o", [])]
 OUT = os.path.join(HERE, "libgcsadmm.so")
 
 

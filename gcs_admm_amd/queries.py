@@ -119,15 +119,20 @@ class SceneQueries:
         return out
 
     def solve(self, starts, goals, state_dtype: str = "f64", N: int = 5, M: int = 20, seeds=None, params=None, return_state: bool = False,
-              **common):
+              walk: str = "host", **common):
         """Every query to its stop test in one ``BatchSolver`` (``params``: one dict per query, ``common``: parameters of all, as
         ``BatchSolver.solve``), then rounded by ``rounding_many`` (``N``, ``M``: as ``rounding``; ``seeds``: one per query, default 0).
+        ``walk``: ``"host"`` (the default: the walks of ``rounding``, on a host copy of every query's activations) or ``"device"``
+        (``rounding_members``: the walks of all queries drawn on the device while the activations are still there, by the rule of
+        ``walks.walk_reference`` -- other draws than the host's for the same seed).
         Returns one record per query: that of ``DeviceSolver.solve`` plus ``rounded_cost``, ``x_v_rounded``, ``y_v_rounded`` and
         ``graph``; with ``return_state`` also ``trace`` and ``state``, host copies of the member's trace and of its six state arrays (the
         batch and its members are closed on return)."""
         from .batch import BatchSolver
         from .graph import sets_of_graph
-        from .rounding import rounding_many, rounding_problem
+        from .rounding import rounding_many, rounding_members, rounding_problem
+        if walk not in ("host", "device"):
+            raise ValueError(f"walk must be 'host' or 'device', not {walk!r}")
         graphs = self.graphs(starts, goals)
         seeds = [0] * len(graphs) if seeds is None else list(seeds)
         if len(seeds) != len(graphs):
@@ -135,7 +140,10 @@ class SceneQueries:
         batch = BatchSolver(graphs, state_dtype, device=self.device)
         try:
             records = batch.solve(params=params, **common)
-            problems = [rounding_problem(m, *sets_of_graph(g), seed=s) for m, g, s in zip(batch.members, graphs, seeds)]
+            if walk == "device":
+                rounded = rounding_members(batch.members, graphs, N=N, M=M, seeds=seeds, device=self.device)
+            else:
+                problems = [rounding_problem(m, *sets_of_graph(g), seed=s) for m, g, s in zip(batch.members, graphs, seeds)]
             for rec, m, g in zip(records, batch.members, graphs):
                 rec["graph"] = g
                 if return_state:
@@ -145,6 +153,8 @@ class SceneQueries:
             batch.close()
             for m in batch.members:
                 m.close()
-        for rec, (cost, x_v, y_v) in zip(records, rounding_many(problems, N=N, M=M, device=self.device)):
+        if walk == "host":
+            rounded = rounding_many(problems, N=N, M=M, device=self.device)
+        for rec, (cost, x_v, y_v) in zip(records, rounded):
             rec.update(rounded_cost=cost, x_v_rounded=x_v, y_v_rounded=y_v)
         return records

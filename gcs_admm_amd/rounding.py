@@ -3,8 +3,11 @@ the step that follows the ADMM loop in the reference (GCS_utils.py:92-181 ``roun
 :17-89 ``solve_convex_restriction``; called at admm_solver_v3.py:759 with N=5, M=20, the case file's
 own N, M being ignored -- quirk Q5).  SURVEY.md section 8(f) item 1; runs once, on the host by default.
 ``restriction="device"`` solves all candidate paths side by side on the MI355X (csrc/path_restrict_core.h
-through ``gcsadmm_scene_restrict_paths``); the walk stays on the host, and ``rounding_many`` does the same
-for the candidates of many problems in one call per round.
+through ``gcsadmm_scene_restrict_paths``), and ``rounding_many`` does the same for the candidates of many
+problems in one call per round.  In ``rounding`` and ``rounding_many`` the walk runs on the host, on one dict
+entry per edge; ``rounding_members`` draws the walks of all members of a batch on the device instead
+(``walks.DeviceWalks``, csrc/path_walk_core.h: a rule of its own with a counter-based generator, not the host's
+draws) and builds no per-edge Python object.
 
 Differences from the reference, on purpose: the random walk is seeded (the reference draws from the
 unseeded global numpy generator, GCS_utils.py:131, so its runs are not reproducible), and the
@@ -224,20 +227,101 @@ def rounding_many(problems, N=5, M=20, device=0, solver=None):
         solver = lambda As_, bs_, n_, paths: solve_path_restrictions_device(As_, bs_, n_, paths, device, scene)
     try:
         gens = [_Candidates(pr["y_e_sol"], pr["I_v_out"], N, M, pr.get("seed", 0)) for pr in problems]
-        while True:
-            rounds = [g.next_round() for g in gens]
-            if not any(rounds):
-                break
-            results = solver(As, bs, n, [[(i, v) for v in pth] for i, pend in enumerate(rounds) for pth in pend])
-            at = 0
-            for i, (g, pend) in enumerate(zip(gens, rounds)):
-                mine = [(cost, None if xs is None else {k[1]: x for k, x in xs.items()}) for cost, xs in results[at:at + len(pend)]]
-                g.take(pend, mine)
-                at += len(pend)
+        _solve_rounds(gens, As, bs, n, solver)
     finally:
         if scene is not None:
             scene.close()
     return [_rounded(g.cands, pr["V"], n) for g, pr in zip(gens, problems)]
+
+
+def _solve_rounds(gens, As, bs, n, solver):
+    """round after round of the candidate generators of many problems, each round's paths in ONE ``solver`` call on the concatenated
+    regions (keys ``(problem index, region key)``), until no generator has a path left"""
+    while True:
+        rounds = [g.next_round() for g in gens]
+        if not any(rounds):
+            break
+        results = solver(As, bs, n, [[(i, v) for v in pth] for i, pend in enumerate(rounds) for pth in pend])
+        at = 0
+        for g, pend in zip(gens, rounds):
+            mine = [(cost, None if xs is None else {k[1]: x for k, x in xs.items()}) for cost, xs in results[at:at + len(pend)]]
+            g.take(pend, mine)
+            at += len(pend)
+
+
+class _DrawnCandidates:
+    """``_Candidates`` on walks that are drawn already (``paths[w]``, ``status[w]`` of walks 0 .. M, by vertex key): the same
+    accounting -- walk 0 first, then draws 1 .. M in order, a draw spent on every walk looked at, dead ends, overruns and duplicates
+    skipped, at most N paths feasible or pending, and drawing goes on after a round with infeasible paths."""
+
+    def __init__(self, paths, status, N, M):
+        self.paths, self.status, self.N, self.M = paths, status, N, min(M, len(paths) - 1)
+        self.next, self.seen, self.cands = 0, set(), []
+
+    def next_round(self):
+        pending = []
+        while self.next <= self.M and (self.next == 0 or len(self.cands) + len(pending) < self.N):
+            w, self.next = self.next, self.next + 1
+            pth = self.paths[w]
+            if self.status[w] != 0 or tuple(pth) in self.seen:
+                continue
+            self.seen.add(tuple(pth)); pending.append(pth)
+        return pending
+
+    def take(self, pending, results):
+        self.cands += [(cost, pth, xs) for pth, (cost, xs) in zip(pending, results) if xs is not None]
+
+
+def device_sampler(device=0):
+    """the sampler of ``rounding_members``: walks 0 .. count - 1 of every member from ONE ``DeviceWalks.sample`` call on the members'
+    activation rows ``zedge[2 n]``, where the solver left them"""
+    def sample(members, graphs, seeds, count):
+        from .walks import DeviceWalks
+        with DeviceWalks(graphs, device) as walks:
+            return walks.sample([m.zedge[2 * g.n] for m, g in zip(members, graphs)], seeds, 0, count)
+    return sample
+
+
+def rounding_members(members, graphs, N=5, M=20, seeds=None, device=0, sampler=None, solver=None):
+    """The rounding step for the members of a batch with the walks drawn on the device: ``members[i]`` is the solver that has just run
+    ``graphs[i]`` (its activations are read on the device; nothing per edge comes to the host), all of one dimension n.
+    ``sampler(members, graphs, seeds, count) -> [(paths, status)]`` per member, paths as arrays of vertex indices (default:
+    ``device_sampler(device)``), is called ONCE, for walks 0 .. M.  The candidates of a member are its walk 0 and then its draws
+    1 .. M in order, without dead ends, overruns and duplicates, at most N feasible or pending at any time, as in ``rounding``; the
+    restrictions go through ``solver`` (as in ``rounding_many``: default ``solve_path_restrictions_device`` on one scene over the
+    concatenated regions), one call per round for all members.  Returns ``(cost, x_v_rounded, y_v_rounded)`` per member, in the
+    shape of ``rounding``; a member without a successful walk gives ``(inf, None, None)``.
+
+    The walks follow the rule of ``walks.walk_reference``, not the host generator's draws: for one seed the candidates differ from
+    those of ``rounding``.  An activation below 2^-40 counts as absent (the host walk: 1e-15)."""
+    from .graph import sets_of_graph
+    if not graphs:
+        return []
+    if len(members) != len(graphs):
+        raise ValueError("one graph per member")
+    n = graphs[0].n
+    if any(g.n != n for g in graphs):
+        raise ValueError("rounding_members needs problems of one dimension n")
+    seeds = [0] * len(graphs) if seeds is None else list(seeds)
+    if len(seeds) != len(graphs):
+        raise ValueError("one seed per member")
+    drawn = (sampler or device_sampler(device))(members, graphs, seeds, M + 1)
+    gens = [_DrawnCandidates([[g.keys[v] for v in pth] for pth in paths], status, N, M) for g, (paths, status) in zip(graphs, drawn)]
+    As, bs = {}, {}
+    for i, g in enumerate(graphs):      # per vertex: views into the graph's polytope CSR
+        A_i, b_i = sets_of_graph(g)
+        As.update(((i, v), A) for v, A in A_i.items()); bs.update(((i, v), b) for v, b in b_i.items())
+    scene = None
+    if solver is None:
+        from .scene import DeviceScene
+        scene = DeviceScene([(np.asarray(As[k], float), np.asarray(bs[k], float)) for k in As], device)
+        solver = lambda As_, bs_, n_, paths: solve_path_restrictions_device(As_, bs_, n_, paths, device, scene)
+    try:
+        _solve_rounds(gens, As, bs, n, solver)
+    finally:
+        if scene is not None:
+            scene.close()
+    return [_rounded(gen.cands, g.keys, n) for gen, g in zip(gens, graphs)]
 
 
 def rounding(y_e_sol, V, E, I_v_out, As, bs, n, N=5, M=20, seed=0, restriction="host", solver=None, device=0):

@@ -423,6 +423,34 @@ int gcsadmm_scene_locate_points(gcsadmm_scene s, int num_points, const double *p
  * gcsadmm_scene_locate_points call has produced a list: GCSADMM_ERR_BAD_ARG. */
 int gcsadmm_scene_read_hits(gcsadmm_scene s, int64_t *hit_ptr, int *hit_region, unsigned char *hit_class);
 
+/* ---- the candidate paths of the rounding step, drawn on the device (gcs_admm_amd/walks.py; csrc/path_walk_core.h has the rule) ----
+ * After the loop, rounding draws s-t walks on the relaxed edge activations y_e.  walk_kernel draws them where the solver left y: one
+ * 64-lane workgroup per (walk, problem), the visited set a bitmap in LDS, the draws from a counter-based generator (splitmix64 on
+ * (walk, position)), so that every walk is independent of every other: walks 0 .. 15 in one call equal walks 0 .. 7 and 8 .. 15 in two.
+ * Walk 0 is the most probable path (the largest activation at every step, the last entry among equals); walk w >= 1 picks out-list
+ * entry k with probability proportional to its weight floor(min(y, 2) 2^40) (0 for y <= 0, NaN and heads already on the path).
+ * Status of a walk: 0 reached dst, 1 dead end (no entry of positive weight), 2 the path would need more than max_len vertices; the
+ * vertices walked so far are returned in every case.
+ *
+ * B problems, concatenated.  Problem i has vertex_off[i+1]-vertex_off[i] vertices and edge_off[i+1]-edge_off[i] edges; its out_ptr (V_i + 1
+ * entries, local offsets 0 .. E_i) starts at out_ptr + vertex_off[i] + i, its out_head / out_edge (local ids) at edge_off[i].  Host pointers,
+ * checked (monotone CSR, ids in range, src / dst in range, degree and vertex limits) and uploaded once.  A violation returns
+ * GCSADMM_ERR_BAD_ARG; more than 524288 vertices in one problem (the bitmap is 64 KB of LDS) or an out-degree above 2^22 (the total
+ * weight of an out-list stays within 64 bits) GCSADMM_ERR_UNSUPPORTED; the text names the problem and the reason. */
+typedef struct gcsadmm_walks_s gcsadmm_walks_s;
+int gcsadmm_walks_create(int num_problems, const int64_t *vertex_off, const int64_t *edge_off, const int *out_ptr, const int *out_head,
+                         const int *out_edge, const int *src, const int *dst, int device, struct gcsadmm_walks_s **out);
+void gcsadmm_walks_destroy(struct gcsadmm_walks_s *w);
+const char *gcsadmm_walks_last_error(struct gcsadmm_walks_s *w);      /* NULL: the calling thread's last failed create */
+/* Walks walk_first .. walk_first + num_walks - 1 of every problem.  y_dev: host array [B] of DEVICE pointers to E_i activations of
+ * state_dtype (a row of zedge); seed[B] (the bits are taken as unsigned).  Enqueues on `stream` behind the work that wrote y, then
+ * synchronises it.  Host outputs: path_vtx[B][num_walks][max_len] (entries beyond a path's length unspecified), path_len[B][num_walks],
+ * status[B][num_walks] (0 / 1 / 2).  num_walks = 0 or no problems: nothing is done.  Negative walk_first or num_walks, max_len < 1, a
+ * null array or a null activation pointer: GCSADMM_ERR_BAD_ARG; B * num_walks * max_len above 2^31 - 1 or more than 65535 problems:
+ * GCSADMM_ERR_UNSUPPORTED, before anything is allocated.  The object stays usable after a refused call. */
+int gcsadmm_walks_sample(struct gcsadmm_walks_s *w, const void *const *y_dev, int state_dtype, const int64_t *seed, int walk_first,
+                         int num_walks, int max_len, void *stream, int *path_vtx, int *path_len, int *status);
+
 #ifdef __cplusplus
 }
 #endif
