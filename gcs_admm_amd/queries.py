@@ -9,6 +9,7 @@ from-scratch ``graph_from_sets_device`` on ``{'s', 't', regions}`` gives; ``solv
 """
 from __future__ import annotations
 
+import contextlib
 from typing import Dict, Hashable
 
 import numpy as np
@@ -138,23 +139,29 @@ class SceneQueries:
         if len(seeds) != len(graphs):
             raise ValueError("one seed per query")
         batch = BatchSolver(graphs, state_dtype, device=self.device)
-        try:
-            records = batch.solve(params=params, **common)
-            if walk == "device":
-                rounded = rounding_members(batch.members, graphs, N=N, M=M, seeds=seeds, device=self.device)
-            else:
-                problems = [rounding_problem(m, *sets_of_graph(g), seed=s) for m, g, s in zip(batch.members, graphs, seeds)]
+
+        def close():
+            batch.close()
+            for m in batch.members:
+                m.close()
+
+        def keep(records):
             for rec, m, g in zip(records, batch.members, graphs):
                 rec["graph"] = g
                 if return_state:
                     rec["trace"] = m.trace.cpu().numpy()
                     rec["state"] = {k: getattr(m, k).cpu().numpy() for k in ("copy", "mu", "zedge", "xv", "zv", "yv")}
-        finally:
-            batch.close()
-            for m in batch.members:
-                m.close()
-        if walk == "host":
-            rounded = rounding_many(problems, N=N, M=M, device=self.device)
+        with contextlib.ExitStack() as members_open:
+            members_open.callback(close)
+            records = batch.solve(params=params, **common)
+            if walk == "device":         # the walks read the activations where the members hold them
+                rounded = rounding_members(batch.members, graphs, N=N, M=M, seeds=seeds, device=self.device)
+                keep(records)
+            else:                        # the host walks read a copy of them; the batch is closed before the rounding
+                problems = [rounding_problem(m, *sets_of_graph(g), seed=s) for m, g, s in zip(batch.members, graphs, seeds)]
+                keep(records)
+                members_open.close()
+                rounded = rounding_many(problems, N=N, M=M, device=self.device)
         for rec, (cost, x_v, y_v) in zip(records, rounded):
             rec.update(rounded_cost=cost, x_v_rounded=x_v, y_v_rounded=y_v)
         return records

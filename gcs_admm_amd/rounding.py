@@ -2,12 +2,16 @@
 the step that follows the ADMM loop in the reference (GCS_utils.py:92-181 ``rounding``,
 :17-89 ``solve_convex_restriction``; called at admm_solver_v3.py:759 with N=5, M=20, the case file's
 own N, M being ignored -- quirk Q5).  SURVEY.md section 8(f) item 1; runs once, on the host by default.
-``restriction="device"`` solves all candidate paths side by side on the MI355X (csrc/path_restrict_core.h
-through ``gcsadmm_scene_restrict_paths``), and ``rounding_many`` does the same for the candidates of many
-problems in one call per round.  In ``rounding`` and ``rounding_many`` the walk runs on the host, on one dict
-entry per edge; ``rounding_members`` draws the walks of all members of a batch on the device instead
-(``walks.DeviceWalks``, csrc/path_walk_core.h: a rule of its own with a counter-based generator, not the host's
-draws) and builds no per-edge Python object.
+
+Every entry point is the same three pieces.  The candidate rule (``_Candidates``: walk 0, then up to M draws, dead ends and
+duplicates skipped, at most N paths feasible or pending) over an iterator of walks; the round loop (``_solve_rounds``: the pending
+paths of all problems in one solver call per round); the result rule (``_rounded``: the cheapest candidate of finite cost).  They
+differ in where walks and solves come from.  ``rounding``: host walks (``_host_walks``: lazy, seeded, one dict entry per edge),
+solved by ``solve_path_restriction`` one after the other (``restriction="host"``) or side by side on the MI355X
+(``"device"``: csrc/path_restrict_core.h through ``gcsadmm_scene_restrict_paths``).  ``rounding_many``: host walks of many
+problems, solved on one scene over the concatenated regions.  ``rounding_members``: the same, on walks that the device has drawn
+for all members of a batch in one call (``_drawn_walks`` on ``walks.DeviceWalks``, csrc/path_walk_core.h: a rule of its own with a
+counter-based generator, not the host's draws), with no per-edge Python object.
 
 Differences from the reference, on purpose: the random walk is seeded (the reference draws from the
 unseeded global numpy generator, GCS_utils.py:131, so its runs are not reproducible), and the
@@ -17,6 +21,7 @@ points q_0 .. q_{k+1} with q_j, q_{j+1} in P_{v_j}, and the cost is the polyline
 """
 from __future__ import annotations
 
+import contextlib
 from typing import Dict, Hashable, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -48,10 +53,8 @@ def find_path_via_random_dfs(y_e: Dict[Tuple[Hashable, Hashable], float], I_v_ou
 def solve_path_restriction(As, bs, n: int, path: Sequence[Hashable]):
     """Shortest polyline through the regions of ``path`` in order.  Returns (cost, {v: x_v (2n)})
     or (inf, None) when consecutive regions do not intersect."""
-    k = len(path)
-    # point j lies in P_{path[j-1]} and P_{path[j]} (ends: only one region)
-    regions = [[path[0]]] + [[path[j - 1], path[j]] for j in range(1, k)] + [[path[-1]]]
-    npts = k + 1
+    regions = path_point_regions(path)
+    npts = len(path) + 1
     q0 = []
     for reg in regions:
         A = np.vstack([np.asarray(As[v], float) for v in reg]); b = np.hstack([np.asarray(bs[v], float) for v in reg])
@@ -169,33 +172,57 @@ def rounding_problem(dev, As, bs, seed=0):
     return dict(y_e_sol={e: float(ye[i]) for i, e in enumerate(E)}, V=V, E=E, I_v_out=I_v_out, As=As, bs=bs, n=g.n, seed=seed)
 
 
-class _Candidates:
-    """The candidate paths of ``rounding`` in the order the host loop visits them, handed out in rounds: the most probable path,
-    then seeded walks until N distinct paths are feasible or pending, or M draws are spent.  When a round comes back with
-    infeasible paths the next one goes on drawing with the remaining draws -- the draws and the list are the host loop's."""
+def _host_walks(y_e_sol, I_v_out, M, seed):
+    """walk 0 (the most probable path), then the M seeded draws, each made only when it is asked for; a dead end is ``None``"""
+    yield most_probable_path(y_e_sol, I_v_out)
+    rng = np.random.default_rng(seed)
+    for _ in range(M):
+        yield find_path_via_random_dfs(y_e_sol, I_v_out, rng)
 
-    def __init__(self, y_e_sol, I_v_out, N, M, seed):
-        self.y_e, self.I_out, self.N, self.draws_left = y_e_sol, I_v_out, N, M
-        self.rng = np.random.default_rng(seed)
+
+def _drawn_walks(paths, status, keys, M):
+    """walks 0 .. M that are drawn already (``paths[w]`` of vertex indices, ``status[w]``), by vertex key; a dead end or an overrun is
+    ``None``"""
+    for w in range(min(M, len(paths) - 1) + 1):
+        yield [keys[v] for v in paths[w]] if status[w] == 0 else None
+
+
+class _Candidates:
+    """THE candidate rule of the rounding step, over an iterator of walks (walk 0 first, then the draws; a path or ``None``), handed
+    out in rounds: walk 0 whatever N is, then draws while fewer than N distinct paths are feasible or pending; every walk looked at is
+    spent, dead ends and duplicates are skipped.  When a round comes back with infeasible paths the next one goes on with the
+    remaining draws, so the paths are those of a loop that solves each one before it draws the next."""
+
+    def __init__(self, walks, N):
+        self.walks, self.N = walks, N
         self.seen, self.cands, self.started = set(), [], False
 
     def next_round(self):
         pending = []
-        if not self.started:
+        while not self.started or len(self.cands) + len(pending) < self.N:
             self.started = True
-            first = most_probable_path(self.y_e, self.I_out)
-            if first is not None:
-                self.seen.add(tuple(first)); pending.append(first)
-        while self.draws_left > 0 and len(self.cands) + len(pending) < self.N:
-            self.draws_left -= 1
-            pth = find_path_via_random_dfs(self.y_e, self.I_out, self.rng)
-            if pth is None or tuple(pth) in self.seen:
-                continue
-            self.seen.add(tuple(pth)); pending.append(pth)
+            try:
+                pth = next(self.walks)
+            except StopIteration:
+                break
+            if pth is not None and tuple(pth) not in self.seen:
+                self.seen.add(tuple(pth)); pending.append(pth)
         return pending
 
     def take(self, pending, results):
         self.cands += [(cost, pth, xs) for pth, (cost, xs) in zip(pending, results) if xs is not None]
+
+
+def _solve_rounds(cands, solve):
+    """round after round of the candidates of many problems, each round's paths in ONE call ``solve([(problem index, path)]) ->
+    [(cost, xs)]``, until no problem has a path left"""
+    while True:
+        rounds = [c.next_round() for c in cands]
+        if not any(rounds):
+            return
+        results = iter(solve([(i, pth) for i, pend in enumerate(rounds) for pth in pend]))
+        for c, pend in zip(cands, rounds):
+            c.take(pend, [next(results) for _ in pend])
 
 
 def _rounded(cands, V, n):
@@ -220,56 +247,30 @@ def rounding_many(problems, N=5, M=20, device=0, solver=None):
         raise ValueError("rounding_many needs problems of one dimension n")
     As = {(i, v): pr["As"][v] for i, pr in enumerate(problems) for v in pr["As"]}
     bs = {(i, v): pr["bs"][v] for i, pr in enumerate(problems) for v in pr["As"]}
-    scene = None
-    if solver is None:
-        from .scene import DeviceScene
-        scene = DeviceScene([(np.asarray(As[k], float), np.asarray(bs[k], float)) for k in As], device)
-        solver = lambda As_, bs_, n_, paths: solve_path_restrictions_device(As_, bs_, n_, paths, device, scene)
-    try:
-        gens = [_Candidates(pr["y_e_sol"], pr["I_v_out"], N, M, pr.get("seed", 0)) for pr in problems]
-        _solve_rounds(gens, As, bs, n, solver)
-    finally:
-        if scene is not None:
-            scene.close()
-    return [_rounded(g.cands, pr["V"], n) for g, pr in zip(gens, problems)]
+    cands = [_Candidates(_host_walks(pr["y_e_sol"], pr["I_v_out"], M, pr.get("seed", 0)), N) for pr in problems]
+    return _round_batch(cands, [pr["V"] for pr in problems], As, bs, n, device, solver)
 
 
-def _solve_rounds(gens, As, bs, n, solver):
-    """round after round of the candidate generators of many problems, each round's paths in ONE ``solver`` call on the concatenated
-    regions (keys ``(problem index, region key)``), until no generator has a path left"""
-    while True:
-        rounds = [g.next_round() for g in gens]
-        if not any(rounds):
-            break
-        results = solver(As, bs, n, [[(i, v) for v in pth] for i, pend in enumerate(rounds) for pth in pend])
-        at = 0
-        for g, pend in zip(gens, rounds):
-            mine = [(cost, None if xs is None else {k[1]: x for k, x in xs.items()}) for cost, xs in results[at:at + len(pend)]]
-            g.take(pend, mine)
-            at += len(pend)
+@contextlib.contextmanager
+def _scene_solver(As, bs, device, solver=None):
+    """``solver``, or in its absence the device solver on ONE scene of the regions in the order of ``As``, open for the block"""
+    if solver is not None:
+        yield solver
+        return
+    from .scene import DeviceScene
+    with contextlib.closing(DeviceScene([(np.asarray(As[k], float), np.asarray(bs[k], float)) for k in As], device)) as scene:
+        yield lambda As_, bs_, n_, paths: solve_path_restrictions_device(As_, bs_, n_, paths, device, scene)
 
 
-class _DrawnCandidates:
-    """``_Candidates`` on walks that are drawn already (``paths[w]``, ``status[w]`` of walks 0 .. M, by vertex key): the same
-    accounting -- walk 0 first, then draws 1 .. M in order, a draw spent on every walk looked at, dead ends, overruns and duplicates
-    skipped, at most N paths feasible or pending, and drawing goes on after a round with infeasible paths."""
-
-    def __init__(self, paths, status, N, M):
-        self.paths, self.status, self.N, self.M = paths, status, N, min(M, len(paths) - 1)
-        self.next, self.seen, self.cands = 0, set(), []
-
-    def next_round(self):
-        pending = []
-        while self.next <= self.M and (self.next == 0 or len(self.cands) + len(pending) < self.N):
-            w, self.next = self.next, self.next + 1
-            pth = self.paths[w]
-            if self.status[w] != 0 or tuple(pth) in self.seen:
-                continue
-            self.seen.add(tuple(pth)); pending.append(pth)
-        return pending
-
-    def take(self, pending, results):
-        self.cands += [(cost, pth, xs) for pth, (cost, xs) in zip(pending, results) if xs is not None]
+def _round_batch(cands, Vs, As, bs, n, device, solver):
+    """the rounds of many problems on their concatenated regions ``As``, ``bs`` (keys ``(problem index, region key)``: the solver gets
+    paths of such keys, the candidates get their points back by region key), and every problem's result"""
+    with _scene_solver(As, bs, device, solver) as run:
+        def solve(jobs):
+            results = run(As, bs, n, [[(i, v) for v in pth] for i, pth in jobs])
+            return [(cost, None if xs is None else {k[1]: x for k, x in xs.items()}) for cost, xs in results]
+        _solve_rounds(cands, solve)
+    return [_rounded(c.cands, V, n) for c, V in zip(cands, Vs)]
 
 
 def device_sampler(device=0):
@@ -306,22 +307,12 @@ def rounding_members(members, graphs, N=5, M=20, seeds=None, device=0, sampler=N
     if len(seeds) != len(graphs):
         raise ValueError("one seed per member")
     drawn = (sampler or device_sampler(device))(members, graphs, seeds, M + 1)
-    gens = [_DrawnCandidates([[g.keys[v] for v in pth] for pth in paths], status, N, M) for g, (paths, status) in zip(graphs, drawn)]
+    cands = [_Candidates(_drawn_walks(paths, status, g.keys, M), N) for g, (paths, status) in zip(graphs, drawn)]
     As, bs = {}, {}
     for i, g in enumerate(graphs):      # per vertex: views into the graph's polytope CSR
         A_i, b_i = sets_of_graph(g)
         As.update(((i, v), A) for v, A in A_i.items()); bs.update(((i, v), b) for v, b in b_i.items())
-    scene = None
-    if solver is None:
-        from .scene import DeviceScene
-        scene = DeviceScene([(np.asarray(As[k], float), np.asarray(bs[k], float)) for k in As], device)
-        solver = lambda As_, bs_, n_, paths: solve_path_restrictions_device(As_, bs_, n_, paths, device, scene)
-    try:
-        _solve_rounds(gens, As, bs, n, solver)
-    finally:
-        if scene is not None:
-            scene.close()
-    return [_rounded(gen.cands, g.keys, n) for gen, g in zip(gens, graphs)]
+    return _round_batch(cands, [g.keys for g in graphs], As, bs, n, device, solver)
 
 
 def rounding(y_e_sol, V, E, I_v_out, As, bs, n, N=5, M=20, seed=0, restriction="host", solver=None, device=0):
@@ -331,44 +322,16 @@ def rounding(y_e_sol, V, E, I_v_out, As, bs, n, N=5, M=20, seed=0, restriction="
     (cost, x_v_rounded, y_v_rounded) with the reference's shapes: every vertex has an entry;
     off-path vertices get x = 0, y = 0.
 
-    ``restriction``: ``"host"`` (the default: one ``solve_path_restriction`` after the other, as before) or ``"device"``: the
-    same candidates from the same draws, collected first and solved in one call of ``solver(As, bs, n, paths) -> [(cost, xs)]``
-    (default ``solve_path_restrictions_device`` on ``device``); when paths come back infeasible, drawing goes on with the
-    remaining draws, so that for one seed the candidate list is the host's."""
+    The candidates come in rounds (``_Candidates``), each round solved in one call of ``solver(As, bs, n, paths) -> [(cost, xs)]``;
+    when paths come back infeasible, drawing goes on with the remaining draws, so that for one seed the paths are those of a loop
+    that solves one after the other.  ``restriction``: ``"host"`` (the default: ``solve_path_restriction`` path by path, whatever
+    ``solver`` is) or ``"device"`` (``solver``, default ``solve_path_restrictions_device`` on ``device``)."""
     if restriction not in ("host", "device"):
         raise ValueError(f"restriction must be 'host' or 'device', not {restriction!r}")
-    if restriction == "device":
-        if solver is None:
-            solver = lambda As_, bs_, n_, paths: solve_path_restrictions_device(As_, bs_, n_, paths, device)
-        gen = _Candidates(y_e_sol, I_v_out, N, M, seed)
-        while True:
-            pending = gen.next_round()
-            if not pending:
-                break
-            gen.take(pending, solver(As, bs, n, pending))
-        return _rounded(gen.cands, V, n)
-    rng = np.random.default_rng(seed)
-    seen, cands = set(), []
-    first = most_probable_path(y_e_sol, I_v_out)
-    if first is not None:
-        seen.add(tuple(first))
-        cost, xs = solve_path_restriction(As, bs, n, first)
-        if xs is not None:
-            cands.append((cost, first, xs))
-    for _ in range(M):
-        if len(cands) >= N:
-            break
-        pth = find_path_via_random_dfs(y_e_sol, I_v_out, rng)
-        if pth is None or tuple(pth) in seen:
-            continue
-        seen.add(tuple(pth))
-        cost, xs = solve_path_restriction(As, bs, n, pth)
-        if xs is not None:
-            cands.append((cost, pth, xs))
-    if not cands:
-        print("Rounding failed to find any feasible paths.")
-        return float('inf'), None, None
-    cost, pth, xs = min(cands, key=lambda t: t[0])
-    x_v = {v: xs.get(v, np.zeros(2 * n)) for v in V}
-    y_v = {v: (1 if v in xs else 0) for v in V}
-    return cost, x_v, y_v
+    if restriction == "host":
+        solver = lambda As_, bs_, n_, paths: [solve_path_restriction(As_, bs_, n_, p) for p in paths]
+    elif solver is None:
+        solver = lambda As_, bs_, n_, paths: solve_path_restrictions_device(As_, bs_, n_, paths, device)
+    cands = _Candidates(_host_walks(y_e_sol, I_v_out, M, seed), N)
+    _solve_rounds([cands], lambda jobs: solver(As, bs, n, [pth for _, pth in jobs]))
+    return _rounded(cands.cands, V, n)
