@@ -112,6 +112,10 @@ PROTOTYPES = {
     # the regions under query points on a resident scene (gcs_admm_amd/queries.py)
     "gcsadmm_scene_locate_points": ([_p, _i, _p, _d, _d, _p], _i),
     "gcsadmm_scene_read_hits": ([_p] * 4, _i),
+    # edits of a decided scene
+    "gcsadmm_scene_add_regions": ([_p, _i, _p, _p, _p, _d, _d] + [_p] * 6, _i),
+    "gcsadmm_scene_remove_regions": ([_p, _i, _p, _p], _i),
+    "gcsadmm_scene_read_regions": ([_p] * 7, _i),
     # the candidate paths of the rounding step, drawn on the device (gcs_admm_amd/walks.py)
     "gcsadmm_walks_create": ([_i] + [_p] * 7 + [_i, _p], _i),
     "gcsadmm_walks_destroy": ([_p], None),

@@ -28,6 +28,10 @@
 //
 // And the queries on a scene whose graph is decided: locate_kernel lists the regions under each start and goal point
 // (point_locate_core.h has the rule), so that a query costs no region-region LP.
+//
+// A decided scene can grow and shrink (gcsadmm_scene_add_regions, gcsadmm_scene_remove_regions; scene_edit_core.h has the contract):
+// the LPs of the new regions and of their pairs alone, cross_kernel for the new boxes against all boxes, and a merge that leaves the
+// pair list a scene built from scratch on the edited set would have.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -45,6 +49,7 @@
 #include "polytope_lp_core.h"
 #include "box_sweep_core.h"
 #include "point_locate_core.h"
+#include "scene_edit_core.h"
 #include "path_restrict_core.h"
 #include "restrict_plan.h"
 
@@ -88,13 +93,15 @@ __global__ __launch_bounds__(WAVE) void ball_kernel(Polys S, int count, const in
 }
 
 template <int N>
-__global__ __launch_bounds__(WAVE) void bounds_kernel(Polys S, const double *centers, int maxm, double *lo, double *hi, int *out_status)
+// polytopes first .. first + count - 1; out_status counts from `first` (lo, hi and centers are the scene's arrays)
+__global__ __launch_bounds__(WAVE) void bounds_kernel(Polys S, int first, int count, const double *centers, int maxm, double *lo, double *hi,
+                                                     int *out_status)
 {
     extern __shared__ double smem[];
     double *lam = smem, *dlam = smem + (size_t)maxm * WAVE;
     const int t = blockIdx.x * WAVE + threadIdx.x, lane = threadIdx.x;
-    if (t >= S.P * 2 * N) return;
-    const int p = t / (2 * N), j = t % (2 * N), k = j >> 1, upper = j & 1;
+    if (t >= count * 2 * N) return;
+    const int p = first + t / (2 * N), j = t % (2 * N), k = j >> 1, upper = j & 1;
     double xk;
     const int st = bound_lp<N>(S, p, centers + (size_t)p * N, k, upper, lam, dlam, lane, xk, nullptr);
     (upper ? hi : lo)[(size_t)p * N + k] = xk;
@@ -269,6 +276,77 @@ __global__ __launch_bounds__(LOCATE_WAVE) void locate_kernel(LocateArgs a)
     if (!FILL && lane == 0) a.count[cell] = total;
 }
 
+// ---- edits of a decided scene (scene_edit_core.h) ----
+__global__ void edit_rank_kernel(EditRanks E)
+{
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t < E.P + E.K) edit_rank(E, t);
+}
+
+// one 64-lane workgroup per (chunk of targets, sweeping box), one target per lane.  FILL = false: count[box][chunk] = targets of the
+// chunk that pair with the box; FILL = true: the same tests again, the pairs written from offset[box][chunk] on in target order.
+template <int N, bool FILL>
+__global__ __launch_bounds__(SWEEP_WAVE) void cross_kernel(CrossSide c, double pad)
+{
+    const long long chunk = blockIdx.x;
+    const int k = c.first + (int)blockIdx.y, lane = threadIdx.x;
+    SweepBox<N> bk;
+    sweep_load_box<N>(c.S, k, pad, bk);
+    int w0, w1;
+    cross_window<N>(c, k, bk, w0, w1);
+    const size_t cell = (size_t)(c.cell0 + (long long)k * c.chunks + chunk);
+    int total = 0;
+    if (cross_chunk_live(chunk, w0, w1)) {      // (the same in every lane)
+        const int re = cross_sweeper_rank(c, k, w0);
+        long long pos = FILL ? c.offset[cell] : 0;
+        for (int stride = 0; stride < EDIT_CHUNK / SWEEP_WAVE; ++stride) {
+            int j;
+            const bool hit = cross_hit<N>(c, bk, w0, w1, chunk, stride, lane, pad, j);
+            const unsigned long long mask = __ballot(hit);
+            if (FILL) {
+                if (hit) cross_store(c, pos + sweep_rank(mask, lane), re, j);
+                pos += sweep_hits(mask);
+            } else {
+                total += sweep_hits(mask);
+            }
+        }
+    }
+    if (!FILL && lane == 0) c.count[cell] = total;
+}
+
+__global__ void merge_count_kernel(EditMerge m)
+{
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r < m.P + m.K) merge_count(m, r);
+}
+__global__ void merge_move_old_kernel(EditMerge m)
+{
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t < m.T_old) merge_move_old(m, t);
+}
+__global__ void merge_move_new_kernel(EditMerge m)
+{
+    const long long x = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (x < m.T_new) merge_move_new(m, x);
+}
+
+template <bool FILL> __global__ void remove_segment_kernel(EditRemove e)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < e.P) remove_segment<FILL>(e, i);
+}
+template <class V> __global__ void compact_rows_kernel(const V *src, V *dst, const int *newidx, int width, int P)
+{
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p < P) remove_compact_row(src, dst, newidx, width, p);
+}
+__global__ void compact_polys_kernel(const int *ptr, const int *new_ptr, const int *newidx, int n, int P, const double *A, const double *b,
+                                     const double *nrm, double *A2, double *b2, double *nrm2)
+{
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p < P) remove_compact_poly(ptr, new_ptr, newidx, n, p, A, b, nrm, A2, b2, nrm2);
+}
+
 } // namespace gcsadmm_lp
 
 using namespace gcsadmm_lp;
@@ -411,15 +489,16 @@ int launch_ball(const gcsadmm_scene_s &s, long count, const int *d_pa, const int
 }
 
 template <int N>
-int launch_bounds(const gcsadmm_scene_s &s, const double *d_centers, double *d_lo, double *d_hi, int *d_status)
+int launch_bounds(const gcsadmm_scene_s &s, int first, int polys, const double *d_centers, double *d_lo, double *d_hi, int *d_status)
 {
     const int rows_max = bounds_rows(s.maxm, N);
     const size_t lds = lds_bytes(rows_max);
     if (lds > LDS_MAX_BYTES) { g_err = "too many facet rows per LP for LDS"; return GCSADMM_ERR_UNSUPPORTED; }
     LPCHK(hipFuncSetAttribute((const void *)bounds_kernel<N>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    const long count = (long)s.S.P * 2 * N;
+    const long count = (long)polys * 2 * N;
     if (count > 0)
-        hipLaunchKernelGGL(bounds_kernel<N>, dim3((unsigned)((count + WAVE - 1) / WAVE)), dim3(WAVE), lds, 0, s.S, d_centers, rows_max, d_lo, d_hi, d_status);
+        hipLaunchKernelGGL(bounds_kernel<N>, dim3((unsigned)((count + WAVE - 1) / WAVE)), dim3(WAVE), lds, 0, s.S, first, polys, d_centers, rows_max, d_lo,
+                           d_hi, d_status);
     LPCHK(hipGetLastError());
     return GCSADMM_OK;
 }
@@ -487,7 +566,7 @@ int run_centers(gcsadmm_scene_s *s)
 // the 2n bound LPs of every polytope, started at cen, into lo, hi and st_b: what the LPs left (a failed side is not opened here)
 int run_bounds(gcsadmm_scene_s *s)
 {
-    return for_dim(s->n, [&](auto N) { return launch_bounds<decltype(N)::value>(*s, s->cen.get(), s->lo.get(), s->hi.get(), s->st_b.get()); });
+    return for_dim(s->n, [&](auto N) { return launch_bounds<decltype(N)::value>(*s, 0, s->P, s->cen.get(), s->lo.get(), s->hi.get(), s->st_b.get()); });
 }
 
 // one LP per pair of pa, pb into flag and st_o; x0: the scene's centres (LP t starts at x0[pa[t]]), or nullptr (least-squares points)
@@ -832,6 +911,360 @@ int gcsadmm_scene_read_hits(gcsadmm_scene s, int64_t *hit_ptr, int *hit_region, 
     if (hit_region && total) LPCHK(hipMemcpy(hit_region, s->hit_region.get(), sizeof(int) * total, hipMemcpyDeviceToHost));
     if (hit_class && total) LPCHK(hipMemcpy(hit_class, s->hit_class.get(), total, hipMemcpyDeviceToHost));
     return GCSADMM_OK;
+}
+
+} // extern "C"
+
+// ---- edits of a decided scene: everything is built in a scene of its own beside the resident one, and takes its place at the end ----
+namespace {
+
+// a new buffer of `count` elements with the first `old` ones of src (device) and `fresh` host elements behind them
+template <class T> hipError_t grown(DevBuf<T> &dst, const DevBuf<T> &src, size_t old, const T *fresh, size_t count)
+{
+    hipError_t e = dst.alloc(count);
+    if (e == hipSuccess && old > 0) e = hipMemcpy(dst.get(), src.get(), sizeof(T) * old, hipMemcpyDeviceToDevice);
+    if (e == hipSuccess && fresh && count > old) e = hipMemcpy(dst.get() + old, fresh, sizeof(T) * (count - old), hipMemcpyHostToDevice);
+    return e;
+}
+template <class T> hipError_t put(DevBuf<T> &dst, const T *src, size_t count) { return grown(dst, dst, 0, src, count); }
+// the first `count` elements of src into a buffer that is already there
+template <class T> hipError_t carry(DevBuf<T> &dst, const DevBuf<T> &src, size_t count)
+{
+    return count > 0 ? hipMemcpy(dst.get(), src.get(), sizeof(T) * count, hipMemcpyDeviceToDevice) : hipSuccess;
+}
+template <class T> hipError_t fetch(T *dst, const T *src, size_t count)
+{
+    return count > 0 ? hipMemcpy(dst, src, sizeof(T) * count, hipMemcpyDeviceToHost) : hipSuccess;
+}
+
+template <int N> int launch_cross(const CrossSide &side, int sweepers, double pad, bool fill)
+{
+    constexpr int SLAB = 65535;      // grid.y
+    if (side.chunks <= 0) return GCSADMM_OK;
+    for (int k0 = 0; k0 < sweepers; k0 += SLAB) {
+        CrossSide c = side;
+        c.first = k0;
+        const dim3 grid((unsigned)c.chunks, (unsigned)std::min(SLAB, sweepers - k0));
+        if (fill) hipLaunchKernelGGL((cross_kernel<N, true>), grid, dim3(SWEEP_WAVE), 0, 0, c, pad);
+        else hipLaunchKernelGGL((cross_kernel<N, false>), grid, dim3(SWEEP_WAVE), 0, 0, c, pad);
+        LPCHK(hipGetLastError());
+    }
+    return GCSADMM_OK;
+}
+
+// the edited scene takes the place of the resident one (nothing here can fail)
+void commit_regions(gcsadmm_scene_s *s, gcsadmm_scene_s &nx, std::vector<int> &h_ptr)
+{
+    std::swap(s->ptr, nx.ptr); std::swap(s->A, nx.A); std::swap(s->b, nx.b); std::swap(s->nrm, nx.nrm);
+    std::swap(s->w, nx.w); std::swap(s->cen, nx.cen); std::swap(s->rad, nx.rad); std::swap(s->st_c, nx.st_c);
+    std::swap(s->lo, nx.lo); std::swap(s->hi, nx.hi); std::swap(s->st_b, nx.st_b);
+    std::swap(s->lo0, nx.lo0); std::swap(s->slo, nx.slo); std::swap(s->shi, nx.shi);
+    std::swap(s->order, nx.order); std::swap(s->count, nx.count); std::swap(s->offset, nx.offset);
+    s->h_ptr.swap(h_ptr);
+    s->P = nx.P; s->maxm = nx.maxm;
+    s->S = Polys{s->n, s->P, s->ptr.get(), s->A.get(), s->b.get(), s->nrm.get()};
+    s->have_hits = false;
+}
+void commit_pairs(gcsadmm_scene_s *s, gcsadmm_scene_s &nx, long long T)
+{
+    std::swap(s->pa, nx.pa); std::swap(s->pb, nx.pb); std::swap(s->flag, nx.flag); std::swap(s->st_o, nx.st_o);
+    s->T = T;
+}
+
+} // namespace
+
+extern "C" {
+
+static int add_regions(gcsadmm_scene s, int K, const int *poly_ptr, const double *A, const double *b, double pad, double tol, double *centers,
+                       double *radii, int *center_status, int64_t *num_new_pairs, int64_t *num_overlapping, int64_t *num_undecided)
+{
+    USE_SCENE(s);
+    if (!s->have_centers) { g_err = "no resident centres: call gcsadmm_scene_centers first"; return GCSADMM_ERR_BAD_ARG; }
+    if (!s->have_boxes) { g_err = "no resident boxes: call gcsadmm_scene_bounds or gcsadmm_scene_set_boxes first"; return GCSADMM_ERR_BAD_ARG; }
+    if (!s->have_pairs) { g_err = "no resident pairs: call gcsadmm_scene_candidate_pairs first"; return GCSADMM_ERR_BAD_ARG; }
+    if (!s->have_overlaps) { g_err = "the resident pairs are not decided: call gcsadmm_scene_overlaps first"; return GCSADMM_ERR_BAD_ARG; }
+    if (K < 0 || !poly_ptr || (K > 0 && (!A || !b))) { g_err = "negative number of regions or null polytope array"; return GCSADMM_ERR_BAD_ARG; }
+    if (!(pad == pad)) { g_err = "pad is NaN"; return GCSADMM_ERR_BAD_ARG; }
+    if (poly_ptr[0] != 0) { g_err = "poly_ptr[0] != 0"; return GCSADMM_ERR_BAD_ARG; }
+    const int n = s->n, P = s->P;
+    const size_t un = (size_t)n, uP = (size_t)P, uK = (size_t)K;
+    gcsadmm_scene_s nx;
+    nx.n = n; nx.device = s->device; nx.maxm = s->maxm;
+    for (int p = 0; p < K; ++p) {
+        const int m = poly_ptr[p + 1] - poly_ptr[p];
+        if (m < 1) { g_err = "polytope without rows"; return GCSADMM_ERR_BAD_ARG; }
+        nx.maxm = std::max(nx.maxm, m);
+    }
+    const size_t old_rows = (size_t)s->h_ptr[uP], new_rows = (size_t)poly_ptr[K];
+    if ((long long)P + K > INT32_MAX || (long long)old_rows + (long long)new_rows > INT32_MAX) {
+        g_err = "more than 2^31 - 1 regions or rows"; return GCSADMM_ERR_UNSUPPORTED;
+    }
+    std::vector<double> nrm(new_rows);
+    for (size_t r = 0; r < new_rows; ++r) {
+        double sq = 0;
+        for (int k = 0; k < n; ++k) sq += A[r * un + k] * A[r * un + k];
+        if (!(sq > 0.0)) { g_err = "zero facet normal"; return GCSADMM_ERR_BAD_ARG; }
+        nrm[r] = std::sqrt(sq);
+    }
+    if (num_new_pairs) *num_new_pairs = 0;
+    if (num_overlapping) *num_overlapping = 0;
+    if (num_undecided) *num_undecided = 0;
+    if (K == 0) return GCSADMM_OK;
+    nx.P = P + K;
+    std::vector<int> h_ptr(s->h_ptr), appended(uK);
+    for (int p = 1; p <= K; ++p) h_ptr.push_back((int)old_rows + poly_ptr[p]);
+    for (int p = 0; p < K; ++p) appended[p] = P + p;
+
+    // the polytopes and the results of the resident regions
+    LPCHK(put(nx.ptr, h_ptr.data(), h_ptr.size()));
+    LPCHK(grown(nx.A, s->A, old_rows * un, A, (old_rows + new_rows) * un));
+    LPCHK(grown(nx.b, s->b, old_rows, b, old_rows + new_rows));
+    LPCHK(grown(nx.nrm, s->nrm, old_rows, nrm.data(), old_rows + new_rows));
+    nx.S = Polys{n, nx.P, nx.ptr.get(), nx.A.get(), nx.b.get(), nx.nrm.get()};
+    int rc = alloc_buffers(&nx, BUF_CEN | BUF_CENTRE_LP | BUF_BOXES | BUF_RESIDENT);
+    if (rc != GCSADMM_OK) return rc;
+    LPCHK(carry(nx.w, s->w, uP * (un + 1))); LPCHK(carry(nx.cen, s->cen, uP * un)); LPCHK(carry(nx.rad, s->rad, uP)); LPCHK(carry(nx.st_c, s->st_c, uP));
+    LPCHK(carry(nx.lo, s->lo, uP * un)); LPCHK(carry(nx.hi, s->hi, uP * un)); LPCHK(carry(nx.st_b, s->st_b, uP * 2 * un));
+
+    // centre LPs of the new regions; a region without a centre or without interior ends the call, the resident scene untouched
+    DevBuf<int> d_appended;
+    LPCHK(put(d_appended, appended.data(), uK));
+    rc = for_dim(n, [&](auto N) {
+        return launch_ball<decltype(N)::value>(nx, K, d_appended.get(), nullptr, nullptr, centre_rows(nx.maxm), 0.0, 0, nx.w.get() + uP * (un + 1), nullptr,
+                                               nx.st_c.get() + uP);
+    });
+    if (rc != GCSADMM_OK) return rc;
+    hipLaunchKernelGGL(split_centres_kernel, dim3(blocks_of(K)), dim3(TB), 0, 0, nx.w.get() + uP * (un + 1), n, K, nx.cen.get() + uP * un, nx.rad.get() + uP);
+    LPCHK(hipGetLastError());
+    std::vector<double> rad(uK);
+    std::vector<int> st_c(uK);
+    LPCHK(fetch(rad.data(), nx.rad.get() + uP, uK)); LPCHK(fetch(st_c.data(), nx.st_c.get() + uP, uK));
+    if (centers) LPCHK(fetch(centers, nx.cen.get() + uP * un, uK * un));
+    if (radii) std::copy(rad.begin(), rad.end(), radii);
+    if (center_status) std::copy(st_c.begin(), st_c.end(), center_status);
+    for (int p = 0; p < K; ++p) {
+        if (st_c[p] < 0) { g_err = "centre LP did not converge for new region " + std::to_string(p); return GCSADMM_ERR_BAD_ARG; }
+        if (!(rad[p] > 0.0)) { g_err = "new region " + std::to_string(p) + " has no interior"; return GCSADMM_ERR_BAD_ARG; }
+    }
+
+    // their boxes, failed sides opened
+    rc = for_dim(n, [&](auto N) {
+        return launch_bounds<decltype(N)::value>(nx, P, K, nx.cen.get(), nx.lo.get(), nx.hi.get(), nx.st_b.get() + uP * 2 * un);
+    });
+    if (rc != GCSADMM_OK) return rc;
+    hipLaunchKernelGGL(open_failed_sides_kernel, dim3(blocks_of((long)K * 2 * n)), dim3(TB), 0, 0, nx.st_b.get() + uP * 2 * un, n, K, nx.lo.get() + uP * un,
+                       nx.hi.get() + uP * un);
+    LPCHK(hipGetLastError());
+
+    // sweep order of the new boxes (sorted on the host, as the resident ones were), ranks of all boxes, the merged sweep arrays
+    std::vector<double> lo_new(uK * un), alo0(uK);
+    LPCHK(fetch(lo_new.data(), nx.lo.get() + uP * un, uK * un));
+    for (int p = 0; p < K; ++p) {
+        alo0[p] = lo_new[(size_t)p * un];
+        if (!(alo0[p] == alo0[p])) { g_err = "new box with a NaN lower bound"; return GCSADMM_ERR_BAD_ARG; }
+    }
+    std::vector<int> aorder(uK);
+    sweep_order(alo0.data(), K, aorder.data());
+    DevBuf<int> d_aorder, d_arank, d_inv, d_oldpos;
+    DevBuf<double> aslo, ashi;
+    LPCHK(put(d_aorder, aorder.data(), uK));
+    LPCHK(d_arank.alloc(uK)); LPCHK(d_inv.alloc(uP + uK)); LPCHK(d_oldpos.alloc(uP + uK));
+    LPCHK(aslo.alloc(uK * un)); LPCHK(ashi.alloc(uK * un));
+    hipLaunchKernelGGL(sweep_gather_kernel, dim3(blocks_of(K)), dim3(TB), 0, 0, nx.lo.get() + uP * un, nx.hi.get() + uP * un, d_aorder.get(), n, K, aslo.get(),
+                       ashi.get());
+    const EditRanks ranks{P, K, s->slo.get(), aslo.get(), s->order.get(), d_aorder.get(), d_arank.get(), nx.order.get(), d_inv.get(),
+                          d_oldpos.get()};
+    hipLaunchKernelGGL(edit_rank_kernel, dim3(blocks_of(nx.P)), dim3(TB), 0, 0, ranks);
+    hipLaunchKernelGGL(sweep_gather_kernel, dim3(blocks_of(nx.P)), dim3(TB), 0, 0, nx.lo.get(), nx.hi.get(), nx.order.get(), n, nx.P, nx.slo.get(), nx.shi.get());
+    LPCHK(hipGetLastError());
+
+    // cross sweep, count pass: the new boxes over all boxes behind them (F), the resident boxes over the new boxes behind them (B)
+    CrossSide F{}, B{};
+    F.S = SortedBoxes{K, aslo.get(), ashi.get(), d_aorder.get()}; F.T = SortedBoxes{nx.P, nx.slo.get(), nx.shi.get(), nx.order.get()};
+    F.srank = d_arank.get(); F.chunks = edit_chunks(nx.P); F.cell0 = 0;
+    B.S = SortedBoxes{P, s->slo.get(), s->shi.get(), s->order.get()}; B.T = F.S;
+    B.trank = d_arank.get(); B.chunks = edit_chunks(K); B.cell0 = (long long)K * F.chunks;
+    F.norder = B.norder = nx.order.get();
+    const long long cells = B.cell0 + (long long)P * B.chunks;
+    if (cells > INT32_MAX) { g_err = "more than 2^31 - 1 cells of the cross sweep: add fewer regions per call"; return GCSADMM_ERR_UNSUPPORTED; }
+    DevBuf<int> d_cells;
+    LPCHK(d_cells.alloc((size_t)cells));
+    F.count = B.count = d_cells.get();
+    auto cross = [&](bool fill) {
+        int r = for_dim(n, [&](auto N) { return launch_cross<decltype(N)::value>(F, K, pad, fill); });
+        if (r == GCSADMM_OK) r = for_dim(n, [&](auto N) { return launch_cross<decltype(N)::value>(B, P, pad, fill); });
+        return r;
+    };
+    if ((rc = cross(false)) != GCSADMM_OK) return rc;
+    std::vector<int> cell_count((size_t)cells);
+    std::vector<long long> cell_off((size_t)cells + 1);
+    LPCHK(fetch(cell_count.data(), d_cells.get(), (size_t)cells));
+    if (!edit_scan(cell_count.data(), cells, cell_off.data()) || cell_off[(size_t)cells] + s->T > (long long)INT32_MAX) {      // before anything is allocated
+        g_err = "more than 2^31 - 1 candidate pairs"; return GCSADMM_ERR_UNSUPPORTED;
+    }
+    const long long Tn = cell_off[(size_t)cells], T = s->T + Tn;
+
+    // fill pass, then the LPs of the new pairs, each from the centre of its first region
+    DevBuf<long long> d_cell_off;
+    DevBuf<int> rank_e, rank_l, npa, npb, nst;
+    DevBuf<unsigned char> nflag;
+    LPCHK(put(d_cell_off, cell_off.data(), cell_off.size()));
+    LPCHK(rank_e.alloc((size_t)Tn)); LPCHK(rank_l.alloc((size_t)Tn)); LPCHK(npa.alloc((size_t)Tn)); LPCHK(npb.alloc((size_t)Tn));
+    LPCHK(nst.alloc((size_t)Tn)); LPCHK(nflag.alloc((size_t)Tn));
+    F.offset = B.offset = d_cell_off.get(); F.limit = B.limit = Tn;
+    F.rank_e = B.rank_e = rank_e.get(); F.rank_l = B.rank_l = rank_l.get(); F.pair_a = B.pair_a = npa.get(); F.pair_b = B.pair_b = npb.get();
+    if (Tn > 0 && (rc = cross(true)) != GCSADMM_OK) return rc;
+    rc = for_dim(n, [&](auto N) {
+        return launch_ball<decltype(N)::value>(nx, (long)Tn, npa.get(), npb.get(), nx.cen.get(), overlap_rows(nx.maxm), tol, 1, nullptr, nflag.get(), nst.get());
+    });
+    if (rc != GCSADMM_OK) return rc;
+    unsigned long long decided[2] = {0, 0};
+    LPCHK(hipMemcpy(s->counts.get(), decided, sizeof(decided), hipMemcpyHostToDevice));
+    if (Tn > 0)
+        hipLaunchKernelGGL(count_decisions_kernel, dim3(blocks_of((long)Tn)), dim3(TB), 0, 0, nflag.get(), nst.get(), (long)Tn, s->counts.get());
+    LPCHK(hipGetLastError());
+    LPCHK(download(decided, s->counts));
+
+    // merge: counts by rank, scan, every pair to its place
+    EditMerge m{};
+    m.P = P; m.K = K; m.T_old = s->T; m.T_new = Tn; m.chunks_f = F.chunks; m.chunks_b = B.chunks; m.cell_off = d_cell_off.get();
+    m.oldpos = d_oldpos.get(); m.inv = d_inv.get(); m.count_old = s->count.get(); m.offset_old = s->offset.get();
+    m.pa_old = s->pa.get(); m.pb_old = s->pb.get(); m.st_old = s->st_o.get(); m.flag_old = s->flag.get();
+    m.rank_e = rank_e.get(); m.rank_l = rank_l.get(); m.pa_new = npa.get(); m.pb_new = npb.get(); m.st_new = nst.get(); m.flag_new = nflag.get();
+    m.count = nx.count.get();
+    hipLaunchKernelGGL(merge_count_kernel, dim3(blocks_of(nx.P)), dim3(TB), 0, 0, m);
+    LPCHK(hipGetLastError());
+    std::vector<int> count((size_t)nx.P);
+    std::vector<long long> offset((size_t)nx.P);
+    LPCHK(fetch(count.data(), nx.count.get(), (size_t)nx.P));
+    long long total = 0;
+    if (!sweep_scan(count.data(), nx.P, offset.data(), &total) || total != T) { g_err = "the merged pair list does not add up"; return GCSADMM_ERR_HIP; }
+    LPCHK(hipMemcpy(nx.offset.get(), offset.data(), sizeof(long long) * offset.size(), hipMemcpyHostToDevice));
+    if ((rc = alloc_buffers(&nx, BUF_PAIRS, (size_t)T)) != GCSADMM_OK) return rc;
+    m.offset = nx.offset.get(); m.pa = nx.pa.get(); m.pb = nx.pb.get(); m.st = nx.st_o.get(); m.flag = nx.flag.get();
+    if (m.T_old > 0) hipLaunchKernelGGL(merge_move_old_kernel, dim3(blocks_of((long)m.T_old)), dim3(TB), 0, 0, m);
+    if (Tn > 0) hipLaunchKernelGGL(merge_move_new_kernel, dim3(blocks_of((long)Tn)), dim3(TB), 0, 0, m);
+    LPCHK(hipGetLastError());
+    LPCHK(hipStreamSynchronize(nullptr));
+
+    commit_regions(s, nx, h_ptr);
+    commit_pairs(s, nx, T);
+    if (num_new_pairs) *num_new_pairs = Tn;
+    if (num_overlapping) *num_overlapping = (int64_t)decided[0];
+    if (num_undecided) *num_undecided = (int64_t)decided[1];
+    return GCSADMM_OK;
+}
+
+int gcsadmm_scene_read_regions(gcsadmm_scene s, double *centers, double *radii, int *center_status, double *lo, double *hi, int *box_status)
+{
+    USE_SCENE(s);
+    if ((centers || radii || center_status) && !s->have_centers) { g_err = "no resident centres: call gcsadmm_scene_centers first"; return GCSADMM_ERR_BAD_ARG; }
+    if ((lo || hi) && !s->have_boxes) { g_err = "no resident boxes: call gcsadmm_scene_bounds or gcsadmm_scene_set_boxes first"; return GCSADMM_ERR_BAD_ARG; }
+    if (int rc = read_centers(s, centers, radii, center_status)) return rc;
+    return read_boxes(s, lo, hi, box_status);
+}
+
+int gcsadmm_scene_add_regions(gcsadmm_scene s, int num_new, const int *poly_ptr, const double *poly_A, const double *poly_b,
+                              double pad, double tol, double *centers, double *radii, int *center_status,
+                              int64_t *num_new_pairs, int64_t *num_overlapping, int64_t *num_undecided)
+{
+    try {
+        return add_regions(s, num_new, poly_ptr, poly_A, poly_b, pad, tol, centers, radii, center_status, num_new_pairs, num_overlapping, num_undecided);
+    } catch (const std::bad_alloc &) {      // the host arrays of the checks, the sort and the scans
+        g_err = "out of host memory"; return GCSADMM_ERR_NO_MEMORY;
+    }
+}
+
+static int remove_regions(gcsadmm_scene s, int R, const int *regions, int64_t *num_pairs_left)
+{
+    USE_SCENE(s);
+    if (R < 0 || (R > 0 && !regions)) { g_err = "negative number of regions or null index array"; return GCSADMM_ERR_BAD_ARG; }
+    const int n = s->n, P = s->P;
+    const size_t un = (size_t)n, uP = (size_t)P;
+    std::vector<int> newidx(uP);
+    int Q = 0;
+    if (!remove_renumber(P, R, regions, newidx.data(), &Q)) { g_err = "region index out of range or given twice"; return GCSADMM_ERR_BAD_ARG; }
+    if (num_pairs_left) *num_pairs_left = s->have_pairs ? s->T : 0;
+    if (R == 0) return GCSADMM_OK;
+    const size_t uQ = (size_t)Q;
+    gcsadmm_scene_s nx;
+    nx.n = n; nx.P = Q; nx.device = s->device;
+    std::vector<int> h_ptr(1, 0);
+    for (int p = 0; p < P; ++p) {
+        if (newidx[p] < 0) continue;
+        const int m = s->h_ptr[(size_t)p + 1] - s->h_ptr[p];
+        nx.maxm = std::max(nx.maxm, m);
+        h_ptr.push_back(h_ptr.back() + m);
+    }
+    const size_t rows = (size_t)h_ptr.back();
+
+    // the polytopes and the per-region results: row p to row newidx[p]
+    DevBuf<int> d_newidx;
+    LPCHK(put(d_newidx, newidx.data(), uP));
+    LPCHK(put(nx.ptr, h_ptr.data(), h_ptr.size()));
+    LPCHK(nx.A.alloc(rows * un)); LPCHK(nx.b.alloc(rows)); LPCHK(nx.nrm.alloc(rows));
+    nx.S = Polys{n, Q, nx.ptr.get(), nx.A.get(), nx.b.get(), nx.nrm.get()};
+    int rc = alloc_buffers(&nx, BUF_CEN | BUF_CENTRE_LP | BUF_BOXES | BUF_RESIDENT);
+    if (rc != GCSADMM_OK) return rc;
+    const dim3 grid(blocks_of(P)), block(TB);
+    hipLaunchKernelGGL(compact_polys_kernel, grid, block, 0, 0, s->ptr.get(), nx.ptr.get(), d_newidx.get(), n, P, s->A.get(), s->b.get(), s->nrm.get(),
+                       nx.A.get(), nx.b.get(), nx.nrm.get());
+    auto compact = [&](auto &src, auto &dst, int width) {
+        using V = std::remove_pointer_t<decltype(src.get())>;
+        hipLaunchKernelGGL(compact_rows_kernel<V>, grid, block, 0, 0, (const V *)src.get(), dst.get(), (const int *)d_newidx.get(), width, P);
+    };
+    compact(s->w, nx.w, n + 1); compact(s->cen, nx.cen, n); compact(s->rad, nx.rad, 1); compact(s->st_c, nx.st_c, 1);
+    compact(s->lo, nx.lo, n); compact(s->hi, nx.hi, n); compact(s->st_b, nx.st_b, 2 * n);
+    LPCHK(hipGetLastError());
+
+    // the pair list: the segments of the old sweep order, without the removed boxes and their pairs
+    long long T = 0;
+    DevBuf<int> d_kept;
+    DevBuf<long long> d_dst;
+    if (s->have_pairs) {
+        LPCHK(d_kept.alloc(uP));
+        EditRemove e{};
+        e.P = P; e.newidx = d_newidx.get(); e.order = s->order.get(); e.count_old = s->count.get(); e.offset_old = s->offset.get();
+        e.pa_old = s->pa.get(); e.pb_old = s->pb.get(); e.st_old = s->st_o.get(); e.flag_old = s->flag.get(); e.kept = d_kept.get();
+        hipLaunchKernelGGL(remove_segment_kernel<false>, grid, block, 0, 0, e);
+        LPCHK(hipGetLastError());
+        std::vector<int> kept(uP), order(uP), new_order, new_count;
+        std::vector<long long> dst(uP, 0), new_offset;
+        LPCHK(fetch(kept.data(), d_kept.get(), uP)); LPCHK(fetch(order.data(), s->order.get(), uP));
+        for (int i = 0; i < P; ++i) {
+            dst[i] = T;
+            if (newidx[order[i]] < 0) continue;
+            new_order.push_back(newidx[order[i]]); new_count.push_back(kept[i]); new_offset.push_back(T);
+            T += kept[i];
+        }
+        if (Q > 0) {
+            LPCHK(hipMemcpy(nx.order.get(), new_order.data(), sizeof(int) * uQ, hipMemcpyHostToDevice));
+            LPCHK(hipMemcpy(nx.count.get(), new_count.data(), sizeof(int) * uQ, hipMemcpyHostToDevice));
+            LPCHK(hipMemcpy(nx.offset.get(), new_offset.data(), sizeof(long long) * uQ, hipMemcpyHostToDevice));
+        }
+        LPCHK(put(d_dst, dst.data(), uP));
+        if ((rc = alloc_buffers(&nx, BUF_PAIRS, (size_t)T)) != GCSADMM_OK) return rc;
+        e.dst = d_dst.get(); e.pa = nx.pa.get(); e.pb = nx.pb.get(); e.st = nx.st_o.get(); e.flag = nx.flag.get();
+        hipLaunchKernelGGL(remove_segment_kernel<true>, grid, block, 0, 0, e);
+        if (Q > 0)
+            hipLaunchKernelGGL(sweep_gather_kernel, dim3(blocks_of(Q)), block, 0, 0, nx.lo.get(), nx.hi.get(), nx.order.get(), n, Q, nx.slo.get(), nx.shi.get());
+        LPCHK(hipGetLastError());
+    }
+    LPCHK(hipStreamSynchronize(nullptr));
+
+    commit_regions(s, nx, h_ptr);
+    if (s->have_pairs) commit_pairs(s, nx, T);
+    if (num_pairs_left) *num_pairs_left = T;
+    return GCSADMM_OK;
+}
+
+int gcsadmm_scene_remove_regions(gcsadmm_scene s, int num_removed, const int *regions, int64_t *num_pairs_left)
+{
+    try {
+        return remove_regions(s, num_removed, regions, num_pairs_left);
+    } catch (const std::bad_alloc &) {      // the host arrays of the renumbering and the scan
+        g_err = "out of host memory"; return GCSADMM_ERR_NO_MEMORY;
+    }
 }
 
 } // extern "C"

@@ -5,7 +5,7 @@ region-region overlap LP -- is decided ONCE, on a resident ``DeviceScene``.  Per
 lists the regions under every start and goal point; only hits in the band of about 1e-6 around a facet or a vertex go to a pair LP,
 all of them in one call.  The query graphs are the region graph plus the terminals' edges, in the order and with the arrays a
 from-scratch ``graph_from_sets_device`` on ``{'s', 't', regions}`` gives; ``solve`` takes them through ``BatchSolver`` and
-``rounding_many``.  There is no CPU fallback: the LPs and the locate call run on the device (tests inject stand-ins).
+``rounding_many``.  The scene is not frozen: ``add_regions`` and ``remove_regions`` edit it in place, and only the LPs of what is new run.  There is no CPU fallback: the LPs and the locate call run on the device (tests inject stand-ins).
 """
 from __future__ import annotations
 
@@ -39,8 +39,9 @@ class SceneQueries:
         self.scene = scene if scene is not None else DeviceScene(self.polys, self.device)
         try:
             self.stats = {}
+            self._pairs = {}      # the decided pair list with the host's decisions in it: pa, pb, flags, status
             self.edge_tail, self.edge_head, self.centers = build_graph_arrays_device(
-                self.polys, self.device, scene=self.scene, stats=self.stats, names=self.keys, broad_phase="device")
+                self.polys, self.device, scene=self.scene, stats=self.stats, names=self.keys, broad_phase="device", pairs_out=self._pairs)
         except Exception:
             self.close()
             raise
@@ -59,6 +60,79 @@ class SceneQueries:
         self.close()
 
     # ------------------------------------------------------------------
+    def _take_pairs(self, pa, pb, flags, status, edit):
+        from .scene import edge_arrays
+        self._pairs = dict(pa=pa, pb=pb, flags=flags, status=status)
+        self.edge_tail, self.edge_head = edge_arrays(pa, pb, flags)
+        self.stats.update(candidate_pairs=int(len(pa)), overlaps_redone_on_host=int((status < 0).sum()), **edit)
+
+    def add_regions(self, As: Dict[Hashable, np.ndarray], bs: Dict[Hashable, np.ndarray], tol: float = 1e-9):
+        """Add the regions ``As``, ``bs`` (new keys, in the dictionary's order, behind the old ones) without rebuilding the graph: the
+        scene runs the LPs of the new regions and of the pairs they form (``DeviceScene.add_regions``), and the object is afterwards
+        what a new ``SceneQueries`` on the joined dictionaries is.  The rules of construction hold: a centre LP with status < 0 raises
+        GcsAdmmError and a radius <= 0 ValueError, both naming the keys and leaving the object as it was; a new pair whose LP reports
+        status < 0 is decided by ``graph.polytopes_overlap``.  Pairs that were there keep their decision, the host's included.
+        ``stats`` receives the LPs this edit ran: ``edit_centre_lps``, ``edit_bound_lps``, ``edit_pair_lps``."""
+        from .abi import GcsAdmmError
+        from .scene import check_centres
+        if self.scene is None:
+            raise RuntimeError("the scene is closed")
+        new_keys = list(As.keys())
+        if 's' in As or 't' in As:
+            raise ValueError("SceneQueries takes the regions alone: the keys 's' and 't' belong to the queries")
+        known = set(self.keys)
+        twice = [k for k in new_keys if k in known]
+        if twice:
+            raise ValueError(f"regions {twice[:5]} are in the scene already")
+        polys = [(np.asarray(As[k], float).reshape(-1, self.n), np.asarray(bs[k], float).ravel()) for k in new_keys]
+        P_old = len(self.keys)
+        try:
+            cen, _, _, counts = self.scene.add_regions(polys, tol=tol)
+        except GcsAdmmError as e:
+            if getattr(e, "results", None) is not None:      # name the regions as construction does
+                check_centres(e.results[1], e.results[2], lambda idx: [new_keys[i] for i in idx])
+            raise
+        pa, pb, flags, status = self.scene.pairs()
+        new = pb >= P_old
+        old = self._pairs
+        if not (np.array_equal(pa[~new], old["pa"]) and np.array_equal(pb[~new], old["pb"])):
+            raise RuntimeError("the scene's pair list lost its order")
+        flags = np.array(flags, copy=True)
+        flags[~new] = old["flags"]
+        for t in np.nonzero(new & (status < 0))[0]:
+            (A1, b1), (A2, b2) = (self.polys + polys)[pa[t]], (self.polys + polys)[pb[t]]
+            flags[t] = 1 if polytopes_overlap(A1, b1, A2, b2) else 0
+        self.keys = self.keys + new_keys
+        self.polys = self.polys + polys
+        self.centers = np.ascontiguousarray(np.vstack([self.centers, np.asarray(cen, float).reshape(-1, self.n)]))
+        self._take_pairs(pa, pb, flags, status, dict(edit_centre_lps=len(polys), edit_bound_lps=2 * self.n * len(polys),
+                                                     edit_pair_lps=int(counts["new_pairs"])))
+
+    def remove_regions(self, keys):
+        """Take the regions ``keys`` out (``DeviceScene.remove_regions``): no LP runs, and the object is afterwards what a new
+        ``SceneQueries`` on the remaining dictionaries is.  An unknown key or one given twice raises ValueError before any device call."""
+        if self.scene is None:
+            raise RuntimeError("the scene is closed")
+        keys = list(keys)
+        where = {k: i for i, k in enumerate(self.keys)}
+        unknown = [k for k in keys if k not in where]
+        if unknown or len(set(keys)) != len(keys):
+            raise ValueError(f"regions {unknown[:5]} are not in the scene" if unknown else "a region is given twice")
+        gone = np.array([where[k] for k in keys], np.int64)
+        self.scene.remove_regions(gone)
+        stays = np.ones(len(self.keys), bool)
+        stays[gone] = False
+        newidx = np.cumsum(stays) - 1
+        old = self._pairs
+        keep = stays[old["pa"]] & stays[old["pb"]]
+        pa, pb, _, status = self.scene.pairs()
+        if not (np.array_equal(pa, newidx[old["pa"][keep]]) and np.array_equal(pb, newidx[old["pb"][keep]])):
+            raise RuntimeError("the scene's pair list lost its order")
+        self.keys = [k for k, s in zip(self.keys, stays) if s]
+        self.polys = [p for p, s in zip(self.polys, stays) if s]
+        self.centers = np.ascontiguousarray(self.centers[stays])
+        self._take_pairs(pa, pb, old["flags"][keep], status, dict(edit_centre_lps=0, edit_bound_lps=0, edit_pair_lps=0))
+
     def regions_at(self, points, eps: float = 1e-6, tol: float = 1e-9):
         """The regions that meet the box ``[p - eps, p + eps]`` of each point, by the rule ``build_graph`` connects a terminal with: one
         ascending int32 array of region indices per point.  One ``locate`` call for all points; its UNDECIDED hits, all of them, go

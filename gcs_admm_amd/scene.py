@@ -124,7 +124,8 @@ def candidate_pairs(lo: np.ndarray, hi: np.ndarray, pad: float = SWEEP_PAD):
 class DeviceScene:
     """The regions of a ``PolytopeScene`` resident on the device (``gcsadmm_scene``): uploaded once; the centres, the boxes and the
     pair list stay there between the calls, and the broad phase runs there.  Call order: ``centers``, ``bounds`` (or ``set_boxes``),
-    ``candidate_pairs``, ``overlaps``, ``pairs``.  There is no CPU fallback.  Release with ``close()`` or use as a context manager."""
+    ``candidate_pairs``, ``overlaps``, ``pairs``; a decided scene then takes ``add_regions`` and ``remove_regions`` in any order.  There is
+    no CPU fallback.  Release with ``close()`` or use as a context manager."""
 
     def __init__(self, polys: Sequence[Tuple[np.ndarray, np.ndarray]], device: int = 0):
         host = PolytopeScene(polys, device)
@@ -238,6 +239,57 @@ class DeviceScene:
         self._call("gcsadmm_scene_read_hits", hit_ptr.ctypes.data, hit_region.ctypes.data, hit_class.ctypes.data)
         return hit_ptr, hit_region, hit_class
 
+    def regions(self):
+        """The resident results per region as they are, no LP run (``gcsadmm_scene_read_regions``; after ``centers`` and ``bounds``):
+        ``(centres [P, n], radii [P], LP status [P], lo [P, n], hi [P, n], LP status [P, 2n])``."""
+        cen = np.empty((self.P, self.n)); rad = np.empty(self.P); st_c = np.empty(self.P, np.int32)
+        lo = np.empty((self.P, self.n)); hi = np.empty((self.P, self.n)); st_b = np.empty((self.P, 2 * self.n), np.int32)
+        self._call("gcsadmm_scene_read_regions", cen.ctypes.data, rad.ctypes.data, st_c.ctypes.data, lo.ctypes.data, hi.ctypes.data, st_b.ctypes.data)
+        return cen, rad, st_c, lo, hi, st_b
+
+    def add_regions(self, polys, pad: float = SWEEP_PAD, tol: float = 1e-9):
+        """Append ``polys`` to a decided scene (``gcsadmm_scene_add_regions``; after ``overlaps``) as regions ``P .. P + len(polys) - 1``.
+        Only the LPs of the new regions and of the pairs they form run; afterwards every resident result is that of a scene created
+        on the whole list (``pad``, ``tol``: those of ``candidate_pairs`` and ``overlaps``).  Returns ``(centres [K, n], radii [K], LP
+        status [K], counts)`` of the new regions, ``counts = dict(new_pairs, overlapping, undecided)`` of the new pairs.  A new region
+        whose centre LP reports status < 0 or whose radius is <= 0 is refused, the scene unchanged: the GcsAdmmError carries
+        ``results = (centres, radii, status)``."""
+        K = len(polys)
+        ptr = np.zeros(K + 1, np.int32)
+        ptr[1:] = np.cumsum([np.asarray(A).shape[0] for A, _ in polys])
+        A = np.ascontiguousarray(np.vstack([np.asarray(A, float).reshape(-1, self.n) for A, _ in polys])) if K else np.zeros((0, self.n))
+        b = np.ascontiguousarray(np.hstack([np.asarray(b, float).ravel() for _, b in polys])) if K else np.zeros(0)
+        cen = np.zeros((K, self.n)); rad = np.ones(K); st = np.zeros(K, np.int32)
+        new = C.c_int64(0); over = C.c_int64(0); und = C.c_int64(0)
+        try:
+            self._call("gcsadmm_scene_add_regions", K, ptr.ctypes.data, A.ctypes.data, b.ctypes.data, float(pad), float(tol), cen.ctypes.data,
+                       rad.ctypes.data, st.ctypes.data, C.addressof(new), C.addressof(over), C.addressof(und))
+        except GcsAdmmError as e:
+            e.results = (cen, rad, st)
+            raise
+        self.P += K
+        self.num_pairs += int(new.value)
+        return cen, rad, st, dict(new_pairs=int(new.value), overlapping=int(over.value), undecided=int(und.value))
+
+    def remove_regions(self, indices):
+        """Take the regions ``indices`` (distinct, in range) out of the scene, in any state of it (``gcsadmm_scene_remove_regions``):
+        the others keep their order and are renumbered without gaps, and what is resident is compacted -- a pair stays iff both its
+        regions stay.  Returns the length of the pair list afterwards."""
+        idx = np.ascontiguousarray(indices, np.int32).ravel()
+        left = C.c_int64(0)
+        self._call("gcsadmm_scene_remove_regions", len(idx), idx.ctypes.data, C.addressof(left))
+        self.P -= len(idx)
+        self.num_pairs = int(left.value)
+        return self.num_pairs
+
+
+def check_centres(rad, st_c, name=lambda idx: idx.tolist()):
+    """the rule of graph construction for centre LPs: one that did not converge raises GcsAdmmError, a region without interior ValueError"""
+    if np.any(st_c < 0):
+        raise GcsAdmmError(f"centre LP did not converge for regions {name(np.nonzero(st_c < 0)[0][:8])} (of {int((st_c < 0).sum())})")
+    if np.any(rad <= 0):
+        raise ValueError(f"regions without interior: {name(np.nonzero(rad <= 0)[0][:5])}")
+
 
 def edge_arrays(pa, pb, flags):
     """both directions of every intersecting pair in the reference's double-loop order (by tail, then head), int32"""
@@ -249,7 +301,8 @@ def edge_arrays(pa, pb, flags):
 
 
 def build_graph_arrays_device(polys: Sequence[Tuple[np.ndarray, np.ndarray]], device: int = 0, tol: float = 1e-9, scene=None,
-                              stats: dict | None = None, names: Sequence[Hashable] | None = None, broad_phase: str = "device"):
+                              stats: dict | None = None, names: Sequence[Hashable] | None = None, broad_phase: str = "device",
+                              pairs_out: dict | None = None):
     """``utils.build_graph`` (reference utils.py:31-82) with the LPs on the device, arrays in and out: ``polys[p] = (A_p, b_p)``;
     returns ``(edge_tail, edge_head, centres)``, int32 region indices in the reference's double-loop order.
 
@@ -262,23 +315,18 @@ def build_graph_arrays_device(polys: Sequence[Tuple[np.ndarray, np.ndarray]], de
     ``stats`` (optional dict) receives the counts.  ``broad_phase``: ``"host"`` (the batch LP calls of a PolytopeScene around the numpy
     sweep) or ``"device"`` (a resident DeviceScene: no host sweep, no copies between the steps) -- the same edges.  ``scene``: a
     prepared scene of that kind (tests inject one; a DeviceScene is left open).  ``names``: what to call the regions in an error
-    message (default: their indices)."""
+    message (default: their indices).  ``pairs_out`` (optional dict) receives the decided pair list, host decisions included:
+    ``pa``, ``pb``, ``flags``, ``status``."""
     if broad_phase not in ("host", "device"):
         raise ValueError(f"broad_phase must be 'host' or 'device', not {broad_phase!r}")
     name = (lambda idx: [names[i] for i in idx]) if names is not None else (lambda idx: idx.tolist())
-
-    def check_centres(rad, st_c):
-        if np.any(st_c < 0):
-            raise GcsAdmmError(f"centre LP did not converge for regions {name(np.nonzero(st_c < 0)[0][:8])} (of {int((st_c < 0).sum())})")
-        if np.any(rad <= 0):
-            raise ValueError(f"regions without interior: {name(np.nonzero(rad <= 0)[0][:5])}")
 
     # the two call sequences to (cen, st_b, pa, pb, flags, st_o); everything after them is common
     if broad_phase == "host":
         if scene is None:
             scene = PolytopeScene(polys, device)
         cen, rad, st_c = scene.centers()
-        check_centres(rad, st_c)
+        check_centres(rad, st_c, name)
         lo, hi, st_b = scene.bounds(cen)
         # the batch call opens nothing; status layout of bounds_kernel (polytope_lp.hip): [P][n][2] = (min, max) per axis
         st_b = np.asarray(st_b).reshape(lo.shape + (2,))
@@ -290,7 +338,7 @@ def build_graph_arrays_device(polys: Sequence[Tuple[np.ndarray, np.ndarray]], de
             scene = DeviceScene(polys, device)
         try:
             cen, rad, st_c = scene.centers()
-            check_centres(rad, st_c)
+            check_centres(rad, st_c, name)
             _, _, st_b = scene.bounds()          # failed sides are opened on the device
             scene.candidate_pairs()
             scene.overlaps(tol)
@@ -307,6 +355,8 @@ def build_graph_arrays_device(polys: Sequence[Tuple[np.ndarray, np.ndarray]], de
             flags[t] = 1 if polytopes_overlap(np.asarray(A1, float), np.asarray(b1, float), np.asarray(A2, float), np.asarray(b2, float)) else 0
     if stats is not None:
         stats.update(bounds_opened=int((np.asarray(st_b) < 0).sum()), overlaps_redone_on_host=int(len(redo)), candidate_pairs=int(len(pa)))
+    if pairs_out is not None:
+        pairs_out.update(pa=np.asarray(pa), pb=np.asarray(pb), flags=np.asarray(flags), status=np.asarray(st_o))
     tail, head = edge_arrays(pa, pb, flags)
     return tail, head, cen
 

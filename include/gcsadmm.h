@@ -358,7 +358,8 @@ int gcsadmm_polytope_overlaps(int n, int num_polytopes, const int *poly_ptr, con
  * list stay on the device from the first LP to the last.  The broad phase -- sort-and-sweep over the first coordinate of the
  * boxes -- runs on the device too (sweep_kernel; csrc/box_sweep_core.h has its contract: the pair list of
  * gcs_admm_amd.scene.candidate_pairs, element for element).  The call order is centers, bounds (or set_boxes), candidate_pairs,
- * overlaps, read_pairs; a call whose input is not resident yet returns GCSADMM_ERR_BAD_ARG.  All pointers are HOST pointers; every
+ * overlaps, read_pairs, and from then on add_regions and remove_regions in any order, each leaving a decided scene; a call whose input
+ * is not resident yet returns GCSADMM_ERR_BAD_ARG.  All pointers are HOST pointers; every
  * output pointer may be NULL.  Every call works on the scene's device and hands the caller's current device back; calls on one
  * scene are not re-entrant.  Text of the calling thread's last failure: gcsadmm_polytope_last_error().
  */
@@ -422,6 +423,35 @@ int gcsadmm_scene_locate_points(gcsadmm_scene s, int num_points, const double *p
 /* The resident hit list: the hits of point q are hit_region / hit_class [hit_ptr[q] .. hit_ptr[q + 1]).  Before a
  * gcsadmm_scene_locate_points call has produced a list: GCSADMM_ERR_BAD_ARG. */
 int gcsadmm_scene_read_hits(gcsadmm_scene s, int64_t *hit_ptr, int *hit_region, unsigned char *hit_class);
+
+/* Edits of a scene whose graph is decided (csrc/scene_edit_core.h has the contract): afterwards every resident result -- centres, radii,
+ * boxes, statuses, the pair list with its flags and statuses -- is what the call order above gives on a scene created from the edited
+ * list of regions, element for element and bit for bit, and restrict_paths and locate_points see the edited regions.  A hit list made
+ * before an edit is dropped.
+ *
+ * add_regions appends num_new regions (poly_ptr[0] = 0, rows of new region p: poly_ptr[p] .. poly_ptr[p+1]) as regions P .. P+num_new-1.
+ * It needs centers, bounds (or set_boxes), candidate_pairs and overlaps to have run (otherwise GCSADMM_ERR_BAD_ARG, the text names the
+ * missing call), and runs only what is new: num_new centre LPs, 2 n num_new bound LPs (failed sides opened), the new boxes against all
+ * boxes (cross_kernel: one 64-lane workgroup per (chunk of boxes, sweeping box), count and fill, no atomics) with the pad given --
+ * use that of candidate_pairs --, and the pair LPs of the pairs this finds, each from the centre of its first region.  Their flags and
+ * statuses are merged into the pair list; the pairs that were there keep theirs.  centers[num_new][n], radii[num_new],
+ * center_status[num_new]; num_new_pairs, num_overlapping and num_undecided count the new pairs.  A region without rows, a zero normal, a
+ * centre LP with status < 0 or a radius <= 0: GCSADMM_ERR_BAD_ARG (centers, radii and center_status are filled in the last two cases);
+ * more than 2^31 - 1 pairs in all: GCSADMM_ERR_UNSUPPORTED, before the list is allocated.  After any failure the scene is exactly as
+ * before.
+ *
+ * remove_regions takes the regions regions[0 .. num_removed) out; the others keep their order and are renumbered without gaps.  Any
+ * state of the scene is accepted, and what is resident is compacted: a pair stays iff both its regions stay.  An index out of range or
+ * given twice: GCSADMM_ERR_BAD_ARG, the scene unchanged.  num_pairs_left: length of the pair list afterwards (0 if there is none).
+ *
+ * read_regions copies the resident centres, radii, boxes and their LP statuses out as they are -- no LP runs (after edits: to see what
+ * the scene holds).  centers[P][n], radii[P], center_status[P] need centers to have run, lo[P][n] and hi[P][n] resident boxes;
+ * box_status[P][n][2] is that of the bounds LPs (unspecified for boxes that were set by hand). */
+int gcsadmm_scene_add_regions(gcsadmm_scene s, int num_new, const int *poly_ptr, const double *poly_A, const double *poly_b,
+                              double pad, double tol, double *centers, double *radii, int *center_status,
+                              int64_t *num_new_pairs, int64_t *num_overlapping, int64_t *num_undecided);
+int gcsadmm_scene_remove_regions(gcsadmm_scene s, int num_removed, const int *regions, int64_t *num_pairs_left);
+int gcsadmm_scene_read_regions(gcsadmm_scene s, double *centers, double *radii, int *center_status, double *lo, double *hi, int *box_status);
 
 /* ---- the candidate paths of the rounding step, drawn on the device (gcs_admm_amd/walks.py; csrc/path_walk_core.h has the rule) ----
  * After the loop, rounding draws s-t walks on the relaxed edge activations y_e.  walk_kernel draws them where the solver left y: one
