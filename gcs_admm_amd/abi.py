@@ -116,6 +116,10 @@ PROTOTYPES = {
     "gcsadmm_scene_add_regions": ([_p, _i, _p, _p, _p, _d, _d] + [_p] * 6, _i),
     "gcsadmm_scene_remove_regions": ([_p, _i, _p, _p], _i),
     "gcsadmm_scene_read_regions": ([_p] * 7, _i),
+    # the region graph of a decided scene and the query graphs of a batch from it (csrc/query_graph_core.h)
+    "gcsadmm_scene_build_region_graph": ([_p] * 3, _i),
+    "gcsadmm_scene_read_region_graph": ([_p] * 5, _i),
+    "gcsadmm_scene_query_graphs": ([_p, _i, _p, _p, _p, _i] + [_p] * 8, _i),
     # the candidate paths of the rounding step, drawn on the device (gcs_admm_amd/walks.py)
     "gcsadmm_walks_create": ([_i] + [_p] * 7 + [_i, _p], _i),
     "gcsadmm_walks_destroy": ([_p], None),

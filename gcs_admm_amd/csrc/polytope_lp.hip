@@ -32,6 +32,9 @@
 // A decided scene can grow and shrink (gcsadmm_scene_add_regions, gcsadmm_scene_remove_regions; scene_edit_core.h has the contract):
 // the LPs of the new regions and of their pairs alone, cross_kernel for the new boxes against all boxes, and a merge that leaves the
 // pair list a scene built from scratch on the edited set would have.
+// The query graphs of a batch are assembled here as well (gcsadmm_scene_build_region_graph, gcsadmm_scene_query_graphs;
+// query_graph_core.h has the contract): the region graph from the resident pair list without a sort, then one kernel that writes every
+// entry of every query graph's index arrays from its closed form.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -50,6 +53,7 @@
 #include "box_sweep_core.h"
 #include "point_locate_core.h"
 #include "scene_edit_core.h"
+#include "query_graph_core.h"
 #include "path_restrict_core.h"
 #include "restrict_plan.h"
 
@@ -347,6 +351,44 @@ __global__ void compact_polys_kernel(const int *ptr, const int *new_ptr, const i
     if (p < P) remove_compact_poly(ptr, new_ptr, newidx, n, p, A, b, nrm, A2, b2, nrm2);
 }
 
+// ---- the region graph and the query graphs of a decided scene (query_graph_core.h) ----
+__global__ void region_count_kernel(RegionBuild g)
+{
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t < g.T) region_count(g, t);
+}
+__global__ void region_scatter_kernel(RegionBuild g)
+{
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t < g.T) region_scatter(g, t);
+}
+__global__ void region_place_kernel(RegionBuild g, long long E)
+{
+    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p < E) region_place(g, p);
+}
+__global__ void region_reverse_kernel(RegionBuild g, long long E)
+{
+    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p < E) region_reverse(g, p);
+}
+
+struct QueryGraphArgs {
+    RegionGraph g;
+    QueryBatch q;             // device copies of the caller's arrays
+    QueryArrays out;          // the chunk's buffers: they begin with query `first`
+    int first;                // blockIdx.y counts queries from here
+    long long items;          // the most work items of one query of the call
+};
+// one thread per work item of one query (query_item): blockIdx.y the query of the chunk, blockIdx.x * 256 + threadIdx.x the item
+__global__ __launch_bounds__(256) void query_graph_kernel(QueryGraphArgs a)
+{
+    const int i = a.first + (int)blockIdx.y;
+    const long long x = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (x >= a.items) return;
+    query_item(a.g, query_terms(a.q, i), query_arrays(a.out, a.q, a.g.P, a.first, i), x);
+}
+
 } // namespace gcsadmm_lp
 
 using namespace gcsadmm_lp;
@@ -379,6 +421,14 @@ struct gcsadmm_scene_s {
     DevBuf<unsigned char> hit_class;
     std::vector<int64_t> hit_ptr;                      //   and its segments per point (host: the scan runs there)
     bool have_hits = false;
+    DevBuf<long long> g_row_ptr;                       // region graph of the decided pairs (query_graph_core.h): rows [P + 1],
+    DevBuf<int> g_tail, g_head, g_rev;                 //   edges by (tail, head) and the id of each one's opposite edge
+    long long g_edges = 0;
+    bool have_graph = false;                           //   (an edit or a new narrow phase ends it)
+    DevBuf<long long> qg_term_ptr, qg_edge_off;        // query graphs (kept and grown from call to call): the caller's arrays
+    DevBuf<int> qg_term_region;
+    DevBuf<unsigned char> qg_st;
+    DevBuf<int> qg_edge_tail, qg_edge_head, qg_inc_ptr, qg_inc_edge, qg_inc_out, qg_edge_inc_tail, qg_edge_inc_head;      //   one chunk of results
 };
 
 namespace {
@@ -730,7 +780,7 @@ static int candidate_pairs(gcsadmm_scene s, double pad, int64_t *num_pairs)
     if (!s->have_boxes) { g_err = "no resident boxes: call gcsadmm_scene_bounds or gcsadmm_scene_set_boxes first"; return GCSADMM_ERR_BAD_ARG; }
     if (!(pad == pad)) { g_err = "pad is NaN"; return GCSADMM_ERR_BAD_ARG; }
     const int n = s->n, P = s->P;
-    s->have_pairs = s->have_overlaps = false;
+    s->have_pairs = s->have_overlaps = s->have_graph = false;
     s->T = 0;
     // sort on the host (P log P on P doubles; a device radix sort would order -0.0 before +0.0 and change the order of ties)
     std::vector<double> lo0((size_t)P);
@@ -780,7 +830,7 @@ int gcsadmm_scene_overlaps(gcsadmm_scene s, double tol, int64_t *num_overlapping
     USE_SCENE(s);
     if (!s->have_pairs) { g_err = "no resident pairs: call gcsadmm_scene_candidate_pairs first"; return GCSADMM_ERR_BAD_ARG; }
     if (!s->have_centers) { g_err = "no resident centres: call gcsadmm_scene_centers first"; return GCSADMM_ERR_BAD_ARG; }
-    s->have_overlaps = false;
+    s->have_overlaps = s->have_graph = false;
     const int rc = run_overlaps(s, s->cen.get(), tol);
     if (rc != GCSADMM_OK) return rc;
     if (num_overlapping || num_undecided) {      // counted where the flags are: two numbers come back, the arrays stay for read_pairs
@@ -963,12 +1013,13 @@ void commit_regions(gcsadmm_scene_s *s, gcsadmm_scene_s &nx, std::vector<int> &h
     s->h_ptr.swap(h_ptr);
     s->P = nx.P; s->maxm = nx.maxm;
     s->S = Polys{s->n, s->P, s->ptr.get(), s->A.get(), s->b.get(), s->nrm.get()};
-    s->have_hits = false;
+    s->have_hits = s->have_graph = false;
 }
 void commit_pairs(gcsadmm_scene_s *s, gcsadmm_scene_s &nx, long long T)
 {
     std::swap(s->pa, nx.pa); std::swap(s->pb, nx.pb); std::swap(s->flag, nx.flag); std::swap(s->st_o, nx.st_o);
     s->T = T;
+    s->have_graph = false;
 }
 
 } // namespace
@@ -1263,6 +1314,128 @@ int gcsadmm_scene_remove_regions(gcsadmm_scene s, int num_removed, const int *re
     try {
         return remove_regions(s, num_removed, regions, num_pairs_left);
     } catch (const std::bad_alloc &) {      // the host arrays of the renumbering and the scan
+        g_err = "out of host memory"; return GCSADMM_ERR_NO_MEMORY;
+    }
+}
+
+} // extern "C"
+
+// ---- the region graph of a decided scene, and the query graphs of a batch from it (query_graph_core.h) ----
+extern "C" {
+
+static int build_region_graph(gcsadmm_scene s, const unsigned char *overlap, int64_t *num_edges)
+{
+    USE_SCENE(s);
+    if (!s->have_pairs || !s->have_overlaps) { g_err = "the resident pairs are not decided: call gcsadmm_scene_overlaps first"; return GCSADMM_ERR_BAD_ARG; }
+    const int P = s->P;
+    const long long T = s->T;
+    DevBuf<unsigned char> d_flag;
+    DevBuf<int> d_count;
+    if (overlap) LPCHK(put(d_flag, overlap, (size_t)T));
+    LPCHK(d_count.upload(nullptr, (size_t)P));
+    RegionBuild g{};
+    g.P = P; g.T = T; g.pa = s->pa.get(); g.pb = s->pb.get(); g.flag = overlap ? d_flag.get() : s->flag.get(); g.count = d_count.get();
+    if (T > 0) hipLaunchKernelGGL(region_count_kernel, dim3(blocks_of((long)T)), dim3(TB), 0, 0, g);
+    LPCHK(hipGetLastError());
+    std::vector<int> count((size_t)P);
+    std::vector<long long> row_ptr((size_t)P + 1);
+    LPCHK(fetch(count.data(), d_count.get(), (size_t)P));
+    if (!region_scan(count.data(), P, row_ptr.data())) {      // before the graph is allocated
+        g_err = "too many region edges: a query graph's incidences would not fit 32-bit indices"; return GCSADMM_ERR_UNSUPPORTED;
+    }
+    const long long E = row_ptr[(size_t)P];
+    DevBuf<long long> d_row_ptr;
+    DevBuf<int> unsorted, tail, head, rev;
+    LPCHK(put(d_row_ptr, row_ptr.data(), row_ptr.size()));
+    LPCHK(unsorted.alloc((size_t)E)); LPCHK(tail.alloc((size_t)E)); LPCHK(head.alloc((size_t)E)); LPCHK(rev.alloc((size_t)E));
+    LPCHK(hipMemset(d_count.get(), 0, sizeof(int) * std::max<size_t>((size_t)P, 1)));
+    g.row_ptr = d_row_ptr.get(); g.unsorted = unsorted.get(); g.tail = tail.get(); g.head = head.get(); g.rev = rev.get();
+    if (E > 0) {
+        hipLaunchKernelGGL(region_scatter_kernel, dim3(blocks_of((long)T)), dim3(TB), 0, 0, g);
+        hipLaunchKernelGGL(region_place_kernel, dim3(blocks_of((long)E)), dim3(TB), 0, 0, g, E);
+        hipLaunchKernelGGL(region_reverse_kernel, dim3(blocks_of((long)E)), dim3(TB), 0, 0, g, E);
+    }
+    LPCHK(hipGetLastError());
+    LPCHK(hipStreamSynchronize(nullptr));
+    std::swap(s->g_row_ptr, d_row_ptr); std::swap(s->g_tail, tail); std::swap(s->g_head, head); std::swap(s->g_rev, rev);
+    s->g_edges = E;
+    s->have_graph = true;
+    if (num_edges) *num_edges = E;
+    return GCSADMM_OK;
+}
+
+int gcsadmm_scene_build_region_graph(gcsadmm_scene s, const unsigned char *overlap, int64_t *num_edges)
+{
+    try {
+        return build_region_graph(s, overlap, num_edges);
+    } catch (const std::bad_alloc &) {      // the host arrays of the scan
+        g_err = "out of host memory"; return GCSADMM_ERR_NO_MEMORY;
+    }
+}
+
+int gcsadmm_scene_read_region_graph(gcsadmm_scene s, int64_t *row_ptr, int *edge_tail, int *edge_head, int *reverse)
+{
+    USE_SCENE(s);
+    if (!s->have_graph) { g_err = "no resident region graph: call gcsadmm_scene_build_region_graph first"; return GCSADMM_ERR_BAD_ARG; }
+    static_assert(sizeof(int64_t) == sizeof(long long), "row_ptr is kept as long long");
+    LPCHK(download((long long *)row_ptr, s->g_row_ptr));
+    LPCHK(download(edge_tail, s->g_tail)); LPCHK(download(edge_head, s->g_head)); LPCHK(download(reverse, s->g_rev));
+    return GCSADMM_OK;
+}
+
+static int query_graphs(gcsadmm_scene s, int B, const int64_t *term_ptr, const int *term_region, const unsigned char *st_adjacent, int chunk_queries,
+                        const int64_t *edge_off, int *edge_tail, int *edge_head, int *inc_ptr, int *inc_edge, int *inc_out, int *edge_inc_tail,
+                        int *edge_inc_head)
+{
+    USE_SCENE(s);
+    static_assert(QUERY_BAD_ARG == GCSADMM_ERR_BAD_ARG && QUERY_UNSUPPORTED == GCSADMM_ERR_UNSUPPORTED && QUERY_OK == GCSADMM_OK, "query_check returns the ABI's codes");
+    if (!s->have_graph) {
+        g_err = "no resident region graph, or one from before an edit: call gcsadmm_scene_build_region_graph first"; return GCSADMM_ERR_BAD_ARG;
+    }
+    const int P = s->P;
+    const QueryBatch host{B, (const long long *)term_ptr, term_region, st_adjacent, (const long long *)edge_off};
+    long long max_items = 0;
+    if (const int rc = query_check(P, s->g_edges, host, chunk_queries, g_err, &max_items)) return rc;
+    if (B == 0) return GCSADMM_OK;
+    if (!edge_tail || !edge_head || !inc_ptr || !inc_edge || !inc_out || !edge_inc_tail || !edge_inc_head) { g_err = "null output array"; return GCSADMM_ERR_BAD_ARG; }
+    const size_t points = 2 * (size_t)B, hits = (size_t)host.term_ptr[points], V1 = (size_t)P + 3;
+    LPCHK(reserve(s->qg_term_ptr, points + 1)); LPCHK(reserve(s->qg_term_region, hits)); LPCHK(reserve(s->qg_st, (size_t)B)); LPCHK(reserve(s->qg_edge_off, (size_t)B + 1));
+    LPCHK(hipMemcpy(s->qg_term_ptr.get(), host.term_ptr, sizeof(long long) * (points + 1), hipMemcpyHostToDevice));
+    if (hits > 0) LPCHK(hipMemcpy(s->qg_term_region.get(), term_region, sizeof(int) * hits, hipMemcpyHostToDevice));
+    LPCHK(hipMemcpy(s->qg_st.get(), st_adjacent, (size_t)B, hipMemcpyHostToDevice));
+    LPCHK(hipMemcpy(s->qg_edge_off.get(), host.edge_off, sizeof(long long) * ((size_t)B + 1), hipMemcpyHostToDevice));
+    QueryGraphArgs a{};
+    a.g = RegionGraph{P, s->g_edges, s->g_row_ptr.get(), s->g_tail.get(), s->g_head.get(), s->g_rev.get()};
+    a.q = QueryBatch{B, s->qg_term_ptr.get(), s->qg_term_region.get(), s->qg_st.get(), s->qg_edge_off.get()};
+    a.items = max_items;
+    const int chunk = query_chunk(P, s->g_edges, chunk_queries);
+    for (int first = 0; first < B; first += chunk) {
+        const int count = std::min(chunk, B - first);
+        const size_t at = (size_t)host.edge_off[first], E = (size_t)(host.edge_off[first + count] - host.edge_off[first]);
+        LPCHK(reserve(s->qg_edge_tail, E)); LPCHK(reserve(s->qg_edge_head, E)); LPCHK(reserve(s->qg_inc_ptr, (size_t)count * V1));
+        LPCHK(reserve(s->qg_inc_edge, 2 * E)); LPCHK(reserve(s->qg_inc_out, 2 * E)); LPCHK(reserve(s->qg_edge_inc_tail, E)); LPCHK(reserve(s->qg_edge_inc_head, E));
+        a.out = QueryArrays{s->qg_edge_tail.get(), s->qg_edge_head.get(), s->qg_inc_ptr.get(), s->qg_inc_edge.get(), s->qg_inc_out.get(),
+                            s->qg_edge_inc_tail.get(), s->qg_edge_inc_head.get()};
+        a.first = first;
+        hipLaunchKernelGGL(query_graph_kernel, dim3((unsigned)((max_items + 255) / 256), (unsigned)count), dim3(256), 0, 0, a);
+        LPCHK(hipGetLastError());
+        LPCHK(fetch(edge_tail + at, a.out.edge_tail, E)); LPCHK(fetch(edge_head + at, a.out.edge_head, E));
+        LPCHK(fetch(inc_ptr + (size_t)first * V1, a.out.inc_ptr, (size_t)count * V1));
+        LPCHK(fetch(inc_edge + 2 * at, a.out.inc_edge, 2 * E)); LPCHK(fetch(inc_out + 2 * at, a.out.inc_out, 2 * E));
+        LPCHK(fetch(edge_inc_tail + at, a.out.edge_inc_tail, E)); LPCHK(fetch(edge_inc_head + at, a.out.edge_inc_head, E));
+    }
+    LPCHK(hipStreamSynchronize(nullptr));
+    return GCSADMM_OK;
+}
+
+int gcsadmm_scene_query_graphs(gcsadmm_scene s, int num_queries, const int64_t *term_ptr, const int *term_region, const unsigned char *st_adjacent,
+                               int chunk_queries, const int64_t *edge_off, int *edge_tail, int *edge_head, int *inc_ptr, int *inc_edge, int *inc_out,
+                               int *edge_inc_tail, int *edge_inc_head)
+{
+    try {
+        return query_graphs(s, num_queries, term_ptr, term_region, st_adjacent, chunk_queries, edge_off, edge_tail, edge_head, inc_ptr, inc_edge, inc_out,
+                            edge_inc_tail, edge_inc_head);
+    } catch (const std::bad_alloc &) {      // the text of a refusal
         g_err = "out of host memory"; return GCSADMM_ERR_NO_MEMORY;
     }
 }

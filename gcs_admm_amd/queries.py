@@ -5,7 +5,8 @@ region-region overlap LP -- is decided ONCE, on a resident ``DeviceScene``.  Per
 lists the regions under every start and goal point; only hits in the band of about 1e-6 around a facet or a vertex go to a pair LP,
 all of them in one call.  The query graphs are the region graph plus the terminals' edges, in the order and with the arrays a
 from-scratch ``graph_from_sets_device`` on ``{'s', 't', regions}`` gives; ``solve`` takes them through ``BatchSolver`` and
-``rounding_many``.  The scene is not frozen: ``add_regions`` and ``remove_regions`` edit it in place, and only the LPs of what is new run.  There is no CPU fallback: the LPs and the locate call run on the device (tests inject stand-ins).
+``rounding_many``.  By default the graphs are assembled on the host (a sort over all edges per query); ``assemble="device"`` takes them
+from one kernel call on the scene's own region graph (csrc/query_graph_core.h), the same arrays.  The scene is not frozen: ``add_regions`` and ``remove_regions`` edit it in place, and only the LPs of what is new run.  There is no CPU fallback: the LPs and the locate call run on the device (tests inject stand-ins).
 """
 from __future__ import annotations
 
@@ -14,7 +15,7 @@ from typing import Dict, Hashable
 
 import numpy as np
 
-from .graph import _finish_graph, convert_pt_to_polytope, polytopes_overlap
+from .graph import GcsGraph, _finish_graph, convert_pt_to_polytope, polytopes_overlap
 
 __all__ = ["SceneQueries"]
 
@@ -47,6 +48,8 @@ class SceneQueries:
             raise
         self.centers = np.ascontiguousarray(self.centers, float)
         self.last = {}      # counts of the last regions_at call: hits, undecided, redone_on_host
+        # assemble="device" alone: is the scene's region graph that of _pairs?  The regions' stacked polytope CSR (rows int64, A, b)
+        self._graph_resident, self._stacked = False, None
 
     def close(self):
         if getattr(self, "scene", None) is not None:
@@ -64,6 +67,7 @@ class SceneQueries:
         from .scene import edge_arrays
         self._pairs = dict(pa=pa, pb=pb, flags=flags, status=status)
         self.edge_tail, self.edge_head = edge_arrays(pa, pb, flags)
+        self._graph_resident = False
         self.stats.update(candidate_pairs=int(len(pa)), overlaps_redone_on_host=int((status < 0).sum()), **edit)
 
     def add_regions(self, As: Dict[Hashable, np.ndarray], bs: Dict[Hashable, np.ndarray], tol: float = 1e-9):
@@ -104,6 +108,10 @@ class SceneQueries:
             flags[t] = 1 if polytopes_overlap(A1, b1, A2, b2) else 0
         self.keys = self.keys + new_keys
         self.polys = self.polys + polys
+        if self._stacked is not None:      # extended by the new rows
+            rows, A, b = self._stacked
+            self._stacked = (np.concatenate([rows, rows[-1] + np.cumsum([len(q) for _, q in polys], dtype=np.int64)]),
+                             np.concatenate([A] + [p for p, _ in polys]), np.concatenate([b] + [q for _, q in polys]))
         self.centers = np.ascontiguousarray(np.vstack([self.centers, np.asarray(cen, float).reshape(-1, self.n)]))
         self._take_pairs(pa, pb, flags, status, dict(edit_centre_lps=len(polys), edit_bound_lps=2 * self.n * len(polys),
                                                      edit_pair_lps=int(counts["new_pairs"])))
@@ -130,6 +138,10 @@ class SceneQueries:
             raise RuntimeError("the scene's pair list lost its order")
         self.keys = [k for k, s in zip(self.keys, stays) if s]
         self.polys = [p for p, s in zip(self.polys, stays) if s]
+        if self._stacked is not None:      # compacted: the rows of the regions that stay
+            rows, A, b = self._stacked
+            keep_rows = np.repeat(stays, np.diff(rows))
+            self._stacked = (np.concatenate([[0], np.cumsum(np.diff(rows)[stays])]).astype(np.int64), A[keep_rows], b[keep_rows])
         self.centers = np.ascontiguousarray(self.centers[stays])
         self._take_pairs(pa, pb, old["flags"][keep], status, dict(edit_centre_lps=0, edit_bound_lps=0, edit_pair_lps=0))
 
@@ -162,12 +174,51 @@ class SceneQueries:
         counts = np.bincount(np.repeat(np.arange(Q), np.diff(hit_ptr))[keep], minlength=Q)
         return np.split(hit_region[keep].astype(np.int32), np.cumsum(counts)[:-1]) if Q else []
 
-    def graphs(self, starts, goals, eps: float = 1e-6, tol: float = 1e-9):
+    def _assemble_on_device(self, S, G, regs, eps):
+        """the graphs of ``graphs`` from ONE ``query_graphs`` call: the scene's region graph (built on first use and after an edit, with
+        the host's decisions in it when an LP left a pair undecided) merged with every query's terminal edges by a kernel, the arrays
+        taken as they come; the polytope CSR is the regions' stacked one behind the two point boxes"""
+        B = len(S)
+        if not self._graph_resident:
+            undecided = np.any(np.asarray(self._pairs["status"]) < 0)
+            self.scene.build_region_graph(self._pairs["flags"] if undecided else None)
+            self._graph_resident = True
+        if self._stacked is None:
+            rows = np.zeros(len(self.polys) + 1, np.int64)
+            rows[1:] = np.cumsum([len(b) for _, b in self.polys])
+            self._stacked = (rows, np.ascontiguousarray(np.vstack([A for A, _ in self.polys]).reshape(-1, self.n)) if self.polys else np.zeros((0, self.n)),
+                             np.ascontiguousarray(np.hstack([b for _, b in self.polys])) if self.polys else np.zeros(0))
+        rows, A_all, b_all = self._stacked
+        term_ptr = np.zeros(2 * B + 1, np.int64)
+        term_ptr[1:] = np.cumsum([len(r) for r in regs])
+        term_region = np.concatenate(regs) if regs else np.zeros(0, np.int32)
+        st = np.array([np.all(np.maximum(S[i] - eps, G[i] - eps) <= np.minimum(S[i] + eps, G[i] + eps) + 1e-9) for i in range(B)], np.uint8)
+        arrays = self.scene.query_graphs(term_ptr, term_region, st)
+        keys = ['s', 't'] + self.keys
+        poly_ptr = np.concatenate([[0, 2 * self.n, 4 * self.n], rows[1:] + 4 * self.n]).astype(np.int32)
+        out = []
+        for i in range(B):
+            (A_s, b_s), (A_t, b_t) = convert_pt_to_polytope(S[i], eps), convert_pt_to_polytope(G[i], eps)
+            tail, head, inc_ptr, inc_edge, inc_out, inc_tail, inc_head = arrays[i]
+            out.append(GcsGraph(n=self.n, keys=list(keys), edge_tail=tail, edge_head=head, inc_ptr=inc_ptr, inc_edge=inc_edge, inc_out=inc_out,
+                                edge_inc_tail=inc_tail, edge_inc_head=inc_head, poly_ptr=poly_ptr.copy(),
+                                poly_A=np.concatenate([np.asarray(A_s, float).reshape(-1, self.n), np.asarray(A_t, float).reshape(-1, self.n), A_all]),
+                                poly_b=np.concatenate([np.asarray(b_s, float).ravel(), np.asarray(b_t, float).ravel(), b_all]),
+                                interior=np.concatenate([S[i][None], G[i][None], self.centers]), src=0, dst=1))
+        return out
+
+    def graphs(self, starts, goals, eps: float = 1e-6, tol: float = 1e-9, assemble: str = "host"):
         """One ``GcsGraph`` per query ``(starts[i], goals[i])``, keys ``['s', 't', *region keys]``: what ``graph_from_sets`` makes of the
         sets ``{'s': box of the start, 't': box of the goal, regions}`` -- the region edges shifted by two, both directions of every
         terminal-region hit, and both directions of s-t when the two boxes meet (the interval rule of ``graph.polytopes_overlap``), in
         double-loop order.  ``interior`` is the point itself for a terminal and the scene's centre for a region.  A start or goal whose
-        box meets no region raises ValueError."""
+        box meets no region raises ValueError.
+
+        ``assemble``: ``"host"`` (the default: one ``lexsort`` over all edges and ``graph._finish_graph`` per query) or ``"device"`` (the
+        region graph is built once on the scene, where the pair list lives, and ONE kernel call writes the index arrays of all queries
+        -- csrc/query_graph_core.h --; every field of every graph is the host path's, dtype, shape and bytes)."""
+        if assemble not in ("host", "device"):
+            raise ValueError(f"assemble must be 'host' or 'device', not {assemble!r}")
         S = np.ascontiguousarray(starts, float).reshape(-1, self.n)
         G = np.ascontiguousarray(goals, float).reshape(-1, self.n)
         if len(S) != len(G):
@@ -178,6 +229,8 @@ class SceneQueries:
             for which, r in (("start", regs[i]), ("goal", regs[B + i])):
                 if len(r) == 0:
                     raise ValueError(f"query {i}: the {which} lies in no region")
+        if assemble == "device":
+            return self._assemble_on_device(S, G, regs, eps)
         box = lambda p: (p - eps, p + eps)      # the bounds graph._as_box reads off convert_pt_to_polytope(p, eps)
         keys = ['s', 't'] + self.keys
         out = []
@@ -194,12 +247,12 @@ class SceneQueries:
         return out
 
     def solve(self, starts, goals, state_dtype: str = "f64", N: int = 5, M: int = 20, seeds=None, params=None, return_state: bool = False,
-              walk: str = "host", **common):
+              walk: str = "host", assemble: str = "host", **common):
         """Every query to its stop test in one ``BatchSolver`` (``params``: one dict per query, ``common``: parameters of all, as
         ``BatchSolver.solve``), then rounded by ``rounding_many`` (``N``, ``M``: as ``rounding``; ``seeds``: one per query, default 0).
         ``walk``: ``"host"`` (the default: the walks of ``rounding``, on a host copy of every query's activations) or ``"device"``
         (``rounding_members``: the walks of all queries drawn on the device while the activations are still there, by the rule of
-        ``walks.walk_reference`` -- other draws than the host's for the same seed).
+        ``walks.walk_reference`` -- other draws than the host's for the same seed).  ``assemble``: as ``graphs`` (the same graphs either way).
         Returns one record per query: that of ``DeviceSolver.solve`` plus ``rounded_cost``, ``x_v_rounded``, ``y_v_rounded`` and
         ``graph``; with ``return_state`` also ``trace`` and ``state``, host copies of the member's trace and of its six state arrays (the
         batch and its members are closed on return)."""
@@ -208,7 +261,7 @@ class SceneQueries:
         from .rounding import rounding_many, rounding_members, rounding_problem
         if walk not in ("host", "device"):
             raise ValueError(f"walk must be 'host' or 'device', not {walk!r}")
-        graphs = self.graphs(starts, goals)
+        graphs = self.graphs(starts, goals, assemble=assemble)
         seeds = [0] * len(graphs) if seeds is None else list(seeds)
         if len(seeds) != len(graphs):
             raise ValueError("one seed per query")

@@ -282,6 +282,66 @@ class DeviceScene:
         self.num_pairs = int(left.value)
         return self.num_pairs
 
+    def build_region_graph(self, flags=None) -> int:
+        """The region graph of the decided pairs, made and kept on the device (``gcsadmm_scene_build_region_graph``; after ``overlaps``):
+        ``edge_arrays(pa, pb, flags)`` with its rows and reverse edges, without a sort.  ``flags``: host decisions [num_pairs] that take
+        the place of the resident flags for this graph (default: the resident flags).  Returns the number of directed edges.  A new
+        ``candidate_pairs`` or ``overlaps`` and every edit end the graph."""
+        f = None if flags is None else np.ascontiguousarray(flags, np.uint8).ravel()
+        if f is not None and len(f) != self.num_pairs:
+            raise ValueError(f"flags must be [{self.num_pairs}]")
+        num = C.c_int64(0)
+        self._call("gcsadmm_scene_build_region_graph", f.ctypes.data if f is not None else None, C.addressof(num))
+        self.num_region_edges = int(num.value)
+        return self.num_region_edges
+
+    def region_graph(self):
+        """``(row_ptr int64 [P + 1], edge_tail, edge_head, reverse int32 [E_R])`` of the resident region graph: the edges with tail u are
+        ``row_ptr[u]:row_ptr[u + 1]``, heads ascending; ``reverse[p]`` is the id of the opposite edge."""
+        row_ptr = np.empty(self.P + 1, np.int64)
+        self._call("gcsadmm_scene_read_region_graph", row_ptr.ctypes.data, None, None, None)
+        E = int(row_ptr[-1])
+        tail = np.empty(E, np.int32); head = np.empty(E, np.int32); rev = np.empty(E, np.int32)
+        self._call("gcsadmm_scene_read_region_graph", None, tail.ctypes.data, head.ctypes.data, rev.ctypes.data)
+        return row_ptr, tail, head, rev
+
+    def query_graphs(self, term_ptr, term_region, st_adjacent, chunk_queries: int = 0):
+        """The index arrays of the query graphs of a batch from one kernel (``gcsadmm_scene_query_graphs``; csrc/query_graph_core.h has
+        the rule; after ``build_region_graph``).  ``B = len(st_adjacent)`` queries; points ``0 .. B-1`` are the starts and ``B .. 2B-1``
+        the goals, point q lies in the regions ``term_region[term_ptr[q]:term_ptr[q + 1]]`` (ascending), ``st_adjacent[i]`` says whether
+        the two point boxes of query i meet.  Returns one tuple ``(edge_tail, edge_head, inc_ptr, inc_edge, inc_out, edge_inc_tail,
+        edge_inc_head)`` per query, int32 views into seven flat arrays: what ``graph._finish_graph`` makes of the merged edge list, vertex
+        0 the start, 1 the goal, r + 2 region r.  ``chunk_queries``: queries per launch (0: the library bounds its workspace)."""
+        return query_graph_views(self.P, self.num_region_edges, term_ptr, term_region, st_adjacent,
+                                 lambda *arrays: self._call("gcsadmm_scene_query_graphs", *arrays), chunk_queries)
+
+
+def query_graph_views(P, region_edges, term_ptr, term_region, st_adjacent, call, chunk_queries=0):
+    """the flat arrays of ``gcsadmm_scene_query_graphs`` around ``call(num_queries, term_ptr, term_region, st_adjacent, chunk_queries,
+    edge_off, *seven outputs)`` (addresses), cut into one tuple of views per query"""
+    ptr = np.ascontiguousarray(term_ptr, np.int64).ravel()
+    reg = np.ascontiguousarray(term_region, np.int32).ravel()
+    st = np.ascontiguousarray(st_adjacent, np.uint8).ravel()
+    B = len(st)
+    if len(ptr) != 2 * B + 1:
+        raise ValueError("term_ptr needs 2 B + 1 entries: the starts, then the goals")
+    hits = np.diff(ptr)
+    edge_off = np.zeros(B + 1, np.int64)
+    edge_off[1:] = np.cumsum(region_edges + 2 * (hits[:B] + hits[B:]) + 2 * (st != 0))
+    E = int(edge_off[-1])
+    edge = [np.empty(E, np.int32) for _ in range(4)]            # edge_tail, edge_head, edge_inc_tail, edge_inc_head
+    inc = [np.empty(2 * E, np.int32) for _ in range(2)]         # inc_edge, inc_out
+    inc_ptr = np.empty(B * (P + 3), np.int32)
+    flat = (edge[0], edge[1], inc_ptr, inc[0], inc[1], edge[2], edge[3])
+    call(B, ptr.ctypes.data, reg.ctypes.data, st.ctypes.data, int(chunk_queries), edge_off.ctypes.data, *(a.ctypes.data for a in flat))
+    out = []
+    for i in range(B):
+        e0, e1 = int(edge_off[i]), int(edge_off[i + 1])
+        cut = (slice(e0, e1), slice(e0, e1), slice(i * (P + 3), (i + 1) * (P + 3)), slice(2 * e0, 2 * e1), slice(2 * e0, 2 * e1), slice(e0, e1),
+               slice(e0, e1))
+        out.append(tuple(a[c] for a, c in zip(flat, cut)))
+    return out
+
 
 def check_centres(rad, st_c, name=lambda idx: idx.tolist()):
     """the rule of graph construction for centre LPs: one that did not converge raises GcsAdmmError, a region without interior ValueError"""

@@ -453,6 +453,41 @@ int gcsadmm_scene_add_regions(gcsadmm_scene s, int num_new, const int *poly_ptr,
 int gcsadmm_scene_remove_regions(gcsadmm_scene s, int num_removed, const int *regions, int64_t *num_pairs_left);
 int gcsadmm_scene_read_regions(gcsadmm_scene s, double *centers, double *radii, int *center_status, double *lo, double *hi, int *box_status);
 
+/* The query graphs of a batch, assembled on the device (csrc/query_graph_core.h has the contract and every closed form): a query graph
+ * is the region graph with the few edges of its two terminals merged in, so no entry of it needs a sort.
+ *
+ * build_region_graph makes the region graph from the resident pair list, and keeps it resident: the directed edges, both directions of
+ * every pair with a non-zero flag, sorted by (tail, head) -- gcs_admm_amd.scene.edge_arrays element for element --, row_ptr[P + 1] and
+ * for every edge the id of the opposite one.  It needs gcsadmm_scene_overlaps to have run (otherwise GCSADMM_ERR_BAD_ARG).  overlap:
+ * num_pairs host flags that take the place of the resident flags for this graph only (a host that decided the pairs with status < 0
+ * itself passes its decisions; the resident flags stay as they are), or NULL: the resident flags.  Count, host scan, scatter, then
+ * every head to "number of smaller heads in its row": no sort, any degree, the same arrays on every run.  num_edges: E_R.  The graph
+ * ends with the next gcsadmm_scene_candidate_pairs or gcsadmm_scene_overlaps and with every add_regions or remove_regions that changes
+ * the scene.  A query graph on P regions has at most E_R + 4 P + 2 edges; if twice that exceeds 2^31 - 1: GCSADMM_ERR_UNSUPPORTED,
+ * before the graph is allocated (a graph built earlier stays).
+ *
+ * read_region_graph copies it out: row_ptr[P + 1], edge_tail[E_R], edge_head[E_R], reverse[E_R].  No graph: GCSADMM_ERR_BAD_ARG.
+ *
+ * query_graphs writes the seven index arrays of gcsadmm_graph_desc for num_queries queries, element for element what
+ * gcs_admm_amd.queries.SceneQueries.graphs builds on the host: vertex 0 is the start, 1 the goal, r + 2 region r.  Points
+ * 0 .. num_queries-1 are the starts and num_queries .. 2 num_queries-1 the goals; point q lies in the regions
+ * term_region[term_ptr[q] .. term_ptr[q+1]), strictly ascending (term_ptr[0] = 0; an empty list is a vertex without edges);
+ * st_adjacent[i] is 1 iff the boxes of start and goal i meet.  Query i has E_i = E_R + 2 (a + b) + 2 st_adjacent[i] edges, a and b
+ * the lengths of its two lists; edge_off[num_queries + 1] must step by exactly that.  Its edge arrays begin at edge_off[i], its
+ * incidence arrays (inc_edge, inc_out) at 2 edge_off[i], its inc_ptr (P + 3 entries) at i (P + 3).  One launch of query_graph_kernel
+ * serves chunk_queries queries (0: the library chooses), every entry written once by a plain store; the device workspace is the
+ * caller's four small arrays plus 4 (8 E + P + 3) bytes per query of one chunk (at most 65 535), and with chunk_queries = 0 the
+ * library keeps that within 256 MiB (or one query, if one is larger).  The result does not depend on chunk_queries.
+ * Everything is checked on the host before any launch: no region graph or one from before an edit, term_ptr not non-decreasing, a
+ * list that is not strictly ascending or leaves [0, P), a st_adjacent other than 0 or 1, an edge_off that does not step by E_i,
+ * negative num_queries or chunk_queries, a null array: GCSADMM_ERR_BAD_ARG; more than 2^31 - 1 hits or 2^30 queries:
+ * GCSADMM_ERR_UNSUPPORTED.  A refused call writes no output and changes nothing resident. */
+int gcsadmm_scene_build_region_graph(gcsadmm_scene s, const unsigned char *overlap, int64_t *num_edges);
+int gcsadmm_scene_read_region_graph(gcsadmm_scene s, int64_t *row_ptr, int *edge_tail, int *edge_head, int *reverse);
+int gcsadmm_scene_query_graphs(gcsadmm_scene s, int num_queries, const int64_t *term_ptr, const int *term_region,
+                               const unsigned char *st_adjacent, int chunk_queries, const int64_t *edge_off, int *edge_tail, int *edge_head,
+                               int *inc_ptr, int *inc_edge, int *inc_out, int *edge_inc_tail, int *edge_inc_head);
+
 /* ---- the candidate paths of the rounding step, drawn on the device (gcs_admm_amd/walks.py; csrc/path_walk_core.h has the rule) ----
  * After the loop, rounding draws s-t walks on the relaxed edge activations y_e.  walk_kernel draws them where the solver left y: one
  * 64-lane workgroup per (walk, problem), the visited set a bitmap in LDS, the draws from a counter-based generator (splitmix64 on
