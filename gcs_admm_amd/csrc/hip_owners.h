@@ -16,6 +16,16 @@ struct HipRelease {
 };
 using Stream = std::unique_ptr<std::remove_pointer_t<hipStream_t>, HipRelease>;
 using Event = std::unique_ptr<std::remove_pointer_t<hipEvent_t>, HipRelease>;
+// Copies: typed, counted in elements, the direction in the name.  A count of 0 or a null pointer (an array the caller does not want, a
+// buffer the call never needed) copies nothing.
+template <class T> hipError_t copy_elements(T *dst, const T *src, size_t count, hipMemcpyKind kind)
+{
+    return (count > 0 && dst && src) ? hipMemcpy(dst, src, sizeof(T) * count, kind) : hipSuccess;
+}
+template <class T> hipError_t to_device(T *dst, const T *src, size_t count) { return copy_elements(dst, src, count, hipMemcpyHostToDevice); }
+template <class T> hipError_t to_host(T *dst, const T *src, size_t count) { return copy_elements(dst, src, count, hipMemcpyDeviceToHost); }
+template <class T> hipError_t on_device(T *dst, const T *src, size_t count) { return copy_elements(dst, src, count, hipMemcpyDeviceToDevice); }
+
 template <class T> class DevBuf {
     std::unique_ptr<T, HipRelease> p_;
     size_t count_ = 0;
@@ -40,7 +50,12 @@ public:
         return src ? hipMemcpy(get(), src, bytes, hipMemcpyHostToDevice) : hipMemset(get(), 0, bytes);
     }
     hipError_t zero(hipStream_t s) const { return size() ? hipMemsetAsync(get(), 0, size() * sizeof(T), s) : hipSuccess; }
+    // a new buffer with `count` host elements in it (reads none for a count of 0)
+    hipError_t put(const T *src, size_t count) { const hipError_t e = alloc(count); return e == hipSuccess ? to_device(get(), src, count) : e; }
+    // room for `count` elements in a buffer that is kept from call to call and only ever grows
+    hipError_t reserve(size_t count) { return p_ && count_ >= count ? hipSuccess : (reset(), alloc(count)); }
 };
+template <class T> hipError_t to_host(T *dst, const DevBuf<T> &src) { return to_host(dst, src.get(), src.size()); }      // all of a buffer
 // fills an empty Stream / Event through the HIP call that creates one with flags
 template <class O> static hipError_t create_owned(O &owner, hipError_t (*create)(typename O::pointer *, unsigned), unsigned flags)
 {

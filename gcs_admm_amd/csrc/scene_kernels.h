@@ -1,0 +1,335 @@
+// scene_kernels.h -- the device side of polytope_lp.hip: the __global__ wrappers around the *_core.h headers (which have the rules and
+// the contracts) with their argument and executor structs.  Included by polytope_lp.hip alone, the one translation unit of the scene.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "polytope_lp_core.h"
+#include "box_sweep_core.h"
+#include "point_locate_core.h"
+#include "scene_edit_core.h"
+#include "query_graph_core.h"
+#include "path_restrict_core.h"
+#include "restrict_plan.h"
+
+namespace gcsadmm_lp {
+
+// ---- kernels (LDS: lam[maxm][64], dlam[maxm][64]) ----
+template <int N>
+__global__ __launch_bounds__(WAVE) void ball_kernel(Polys S, int count, const int *pa, const int *pb, const double *x0s,
+                                                   int maxm, double tol, int early, double *out_w, unsigned char *out_flag, int *out_status)
+{
+    extern __shared__ double smem[];
+    double *lam = smem, *dlam = smem + (size_t)maxm * WAVE;
+    const int t = blockIdx.x * WAVE + threadIdx.x, lane = threadIdx.x;
+    if (t >= count) return;
+    const int p = pa ? pa[t] : t, q = pb ? pb[t] : -1;
+    Rows<N, true> R(S, p, q);
+    double w[N + 1], c[N + 1];
+#pragma unroll
+    for (int k = 0; k < N; ++k) c[k] = 0.0;
+    c[N] = -1.0;
+    ball_start<N>(R, x0s ? x0s + (size_t)p * N : nullptr, w);
+    int iters = 0;
+    const int st = lp_ipm<N, true>(R, c, w, lam, dlam, lane, early != 0, tol, &iters);
+    if (out_w) {
+#pragma unroll
+        for (int k = 0; k <= N; ++k) out_w[(size_t)t * (N + 1) + k] = w[k];
+    }
+    if (out_flag) out_flag[t] = (st == 1) ? 1 : (st == 2 ? 0 : (w[N] >= -tol ? 1 : 0));
+    if (out_status) out_status[t] = st;
+}
+
+template <int N>
+// polytopes first .. first + count - 1; out_status counts from `first` (lo, hi and centers are the scene's arrays)
+__global__ __launch_bounds__(WAVE) void bounds_kernel(Polys S, int first, int count, const double *centers, int maxm, double *lo, double *hi,
+                                                     int *out_status)
+{
+    extern __shared__ double smem[];
+    double *lam = smem, *dlam = smem + (size_t)maxm * WAVE;
+    const int t = blockIdx.x * WAVE + threadIdx.x, lane = threadIdx.x;
+    if (t >= count * 2 * N) return;
+    const int p = first + t / (2 * N), j = t % (2 * N), k = j >> 1, upper = j & 1;
+    double xk;
+    const int st = bound_lp<N>(S, p, centers + (size_t)p * N, k, upper, lam, dlam, lane, xk, nullptr);
+    (upper ? hi : lo)[(size_t)p * N + k] = xk;
+    if (out_status) out_status[t] = st;
+}
+
+// ---- the resident scene's own kernels ----
+// centres [P][n] and radii [P] out of the ball LPs' (x, r) records
+__global__ void split_centres_kernel(const double *w, int n, int P, double *centers, double *radii)
+{
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= P) return;
+    for (int k = 0; k < n; ++k) centers[(size_t)p * n + k] = w[(size_t)p * (n + 1) + k];
+    radii[p] = w[(size_t)p * (n + 1) + n];
+}
+
+// a side whose bounds LP did not converge is an interior iterate, a box that is too small: open it (status layout [P][n][(min, max)])
+__global__ void open_failed_sides_kernel(const int *status, int n, int P, double *lo, double *hi)
+{
+    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (long)P * 2 * n || status[t] >= 0) return;
+    const long side = t >> 1;          // p * n + k
+    if (t & 1) hi[side] = INFINITY;
+    else lo[side] = -INFINITY;
+}
+
+// counts[0] = pairs flagged as overlapping, counts[1] = pairs whose LP reports status < 0: one add per wavefront and counter
+__global__ void count_decisions_kernel(const unsigned char *flag, const int *status, long T, unsigned long long *counts)
+{
+    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const unsigned long long over = __ballot(t < T && flag[t] != 0), undecided = __ballot(t < T && status[t] < 0);
+    if ((threadIdx.x & (SWEEP_WAVE - 1)) == 0) {
+        if (over) atomicAdd(&counts[0], (unsigned long long)__popcll(over));
+        if (undecided) atomicAdd(&counts[1], (unsigned long long)__popcll(undecided));
+    }
+}
+
+__global__ void first_lower_bounds_kernel(const double *lo, int n, int P, double *lo0)
+{
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p < P) lo0[p] = lo[(size_t)p * n];
+}
+
+__global__ void sweep_gather_kernel(const double *lo, const double *hi, const int *order, int n, int P, double *slo, double *shi)
+{
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t < P) sweep_gather(lo, hi, order, n, P, t, slo, shi);
+}
+
+// one wavefront per box of the sweep order.  FILL = false: count[k] = pairs of box k; FILL = true: the same tests again, the pairs
+// written from offset[k] on in window order.
+template <int N, bool FILL>
+__global__ __launch_bounds__(SWEEP_WAVE) void sweep_kernel(SortedBoxes B, double pad, int *count, const long long *offset, int *pair_a, int *pair_b)
+{
+    const int k = blockIdx.x, lane = threadIdx.x;
+    SweepBox<N> bk;
+    sweep_load_box<N>(B, k, pad, bk);
+    const int end = sweep_window_end(B.lo, B.P, bk.hip[0]);
+    const int ok = FILL ? B.order[k] : 0;
+    long long pos = FILL ? offset[k] : 0;
+    int total = 0;
+    for (int j0 = k + 1; j0 < end; j0 += SWEEP_WAVE) {
+        const int j = j0 + lane;
+        const bool hit = j < end && sweep_test<N>(B, bk, j, pad);
+        const unsigned long long mask = __ballot(hit);
+        if (FILL) {
+            if (hit) sweep_store_pair(pair_a, pair_b, pos + sweep_rank(mask, lane), ok, B.order[j]);
+            pos += sweep_hits(mask);
+        } else {
+            total += sweep_hits(mask);
+        }
+    }
+    if (!FILL && lane == 0) count[k] = total;
+}
+
+// ---- path restrictions on the resident regions ----
+// executor of path_restrict_solve: one wavefront; reductions by shuffles in a fixed order (bit-reproducible, and the same whatever
+// else the launch holds); the barrier first waits for the wavefront's global accesses (the phases hand values over through the
+// workspace: vertex_wg.h WG_VM has the reason)
+struct RestrictExec {
+    __device__ __forceinline__ int tid() const { return (int)threadIdx.x; }
+    __device__ __forceinline__ int nthreads() const { return gcsadmm_k::RESTRICT_THREADS; }
+    __device__ __forceinline__ int task(int u, int) const { return u; }
+    __device__ __forceinline__ void sync()
+    {
+        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+        __syncthreads();
+    }
+    __device__ __forceinline__ void reduce3(double &mn, double &s1, double &s2)
+    {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            mn = fmin(mn, __shfl_xor(mn, off, 64));
+            s1 += __shfl_xor(s1, off, 64);
+            s2 += __shfl_xor(s2, off, 64);
+        }
+    }
+};
+
+struct RestrictArgs {
+    const int *poly_ptr;
+    const double *A, *b;
+    const int *path_ptr, *path_poly, *row_prefix;
+    const long long *ws_off;
+    double *ws;
+    const double *start;
+    double *points, *cost;
+    int *iterations, *status;
+    double tol;
+    int max_iter, num_paths;
+};
+
+template <int N>
+__global__ __launch_bounds__(gcsadmm_k::RESTRICT_THREADS) void path_restrict_kernel(RestrictArgs a)
+{
+    __shared__ gcs_restrict::PathShared<N> sh;
+    const int p = (int)blockIdx.x;
+    if (p >= a.num_paths) return;
+    const int first = a.path_ptr[p];
+    gcs_restrict::PathProblem pr;
+    pr.k = a.path_ptr[p + 1] - first;
+    pr.poly = a.path_poly + first;
+    pr.rowp = a.row_prefix + first + 2 * (size_t)p;
+    pr.poly_ptr = a.poly_ptr; pr.A = a.A; pr.b = a.b;
+    pr.start = a.start + (size_t)(first + p) * N;
+    pr.points = a.points + (size_t)(first + p) * N;
+    pr.tol = a.tol; pr.max_iter = a.max_iter;
+    RestrictExec ex;
+    double cost;
+    int iterations;
+    const int st = gcs_restrict::path_restrict_solve<N>(ex, pr, a.ws + a.ws_off[p], sh, &cost, &iterations);
+    if (threadIdx.x == 0) { a.cost[p] = cost; a.iterations[p] = iterations; a.status[p] = st; }
+}
+
+// ---- the regions under query points ----
+struct LocateArgs {
+    LocateRegions R;
+    const double *points;      // [num_points][N]
+    double margin;             // eps + 2 tol
+    int first_point;           // blockIdx.y counts from here (one launch takes at most 65 535 points)
+    long long chunks, limit;   // chunks of the P regions; length of the list
+    int *count;                // [num_points][chunks]
+    const long long *offset;   // [num_points][chunks]
+    int *hit_region;
+    unsigned char *hit_class;
+};
+
+// one 64-lane workgroup per (chunk of regions, point), one region per lane.  FILL = false: count[point][chunk] = regions of the chunk
+// that are not OUT; FILL = true: the same tests again, the hits written from offset[point][chunk] on in region order.
+template <int N, bool FILL>
+__global__ __launch_bounds__(LOCATE_WAVE) void locate_kernel(LocateArgs a)
+{
+    const long long chunk = blockIdx.x, q = (long long)a.first_point + blockIdx.y;
+    const int lane = threadIdx.x;
+    double p[N];
+#pragma unroll
+    for (int k = 0; k < N; ++k) p[k] = a.points[(size_t)q * N + k];      // the same address in every lane
+    const size_t cell = (size_t)(q * a.chunks + chunk);
+    long long pos = FILL ? a.offset[cell] : 0;
+    int total = 0;
+    for (int stride = 0; stride < LOCATE_CHUNK / LOCATE_WAVE; ++stride) {
+        const int region = locate_region(a.R.P, chunk, stride, lane);
+        const int cls = locate_lane<N>(a.R, region, p, a.margin);
+        const unsigned long long mask = __ballot(cls != LOCATE_OUT);
+        if (FILL) {
+            locate_store(a.hit_region, a.hit_class, pos, a.limit, mask, lane, region, cls);
+            pos += locate_hits(mask);
+        } else {
+            total += locate_hits(mask);
+        }
+    }
+    if (!FILL && lane == 0) a.count[cell] = total;
+}
+
+// ---- edits of a decided scene (scene_edit_core.h) ----
+__global__ void edit_rank_kernel(EditRanks E)
+{
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t < E.P + E.K) edit_rank(E, t);
+}
+
+// one 64-lane workgroup per (chunk of targets, sweeping box), one target per lane.  FILL = false: count[box][chunk] = targets of the
+// chunk that pair with the box; FILL = true: the same tests again, the pairs written from offset[box][chunk] on in target order.
+template <int N, bool FILL>
+__global__ __launch_bounds__(SWEEP_WAVE) void cross_kernel(CrossSide c, double pad)
+{
+    const long long chunk = blockIdx.x;
+    const int k = c.first + (int)blockIdx.y, lane = threadIdx.x;
+    SweepBox<N> bk;
+    sweep_load_box<N>(c.S, k, pad, bk);
+    int w0, w1;
+    cross_window<N>(c, k, bk, w0, w1);
+    const size_t cell = (size_t)(c.cell0 + (long long)k * c.chunks + chunk);
+    int total = 0;
+    if (cross_chunk_live(chunk, w0, w1)) {      // (the same in every lane)
+        const int re = cross_sweeper_rank(c, k, w0);
+        long long pos = FILL ? c.offset[cell] : 0;
+        for (int stride = 0; stride < EDIT_CHUNK / SWEEP_WAVE; ++stride) {
+            int j;
+            const bool hit = cross_hit<N>(c, bk, w0, w1, chunk, stride, lane, pad, j);
+            const unsigned long long mask = __ballot(hit);
+            if (FILL) {
+                if (hit) cross_store(c, pos + sweep_rank(mask, lane), re, j);
+                pos += sweep_hits(mask);
+            } else {
+                total += sweep_hits(mask);
+            }
+        }
+    }
+    if (!FILL && lane == 0) c.count[cell] = total;
+}
+
+__global__ void merge_count_kernel(EditMerge m)
+{
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r < m.P + m.K) merge_count(m, r);
+}
+__global__ void merge_move_old_kernel(EditMerge m)
+{
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t < m.T_old) merge_move_old(m, t);
+}
+__global__ void merge_move_new_kernel(EditMerge m)
+{
+    const long long x = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (x < m.T_new) merge_move_new(m, x);
+}
+
+template <bool FILL> __global__ void remove_segment_kernel(EditRemove e)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < e.P) remove_segment<FILL>(e, i);
+}
+template <class V> __global__ void compact_rows_kernel(const V *src, V *dst, const int *newidx, int width, int P)
+{
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p < P) remove_compact_row(src, dst, newidx, width, p);
+}
+__global__ void compact_polys_kernel(const int *ptr, const int *new_ptr, const int *newidx, int n, int P, const double *A, const double *b,
+                                     const double *nrm, double *A2, double *b2, double *nrm2)
+{
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p < P) remove_compact_poly(ptr, new_ptr, newidx, n, p, A, b, nrm, A2, b2, nrm2);
+}
+
+// ---- the region graph and the query graphs of a decided scene (query_graph_core.h) ----
+__global__ void region_count_kernel(RegionBuild g)
+{
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t < g.T) region_count(g, t);
+}
+__global__ void region_scatter_kernel(RegionBuild g)
+{
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t < g.T) region_scatter(g, t);
+}
+__global__ void region_place_kernel(RegionBuild g, long long E)
+{
+    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p < E) region_place(g, p);
+}
+__global__ void region_reverse_kernel(RegionBuild g, long long E)
+{
+    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p < E) region_reverse(g, p);
+}
+
+struct QueryGraphArgs {
+    RegionGraph g;
+    QueryBatch q;             // device copies of the caller's arrays
+    QueryArrays out;          // the chunk's buffers: they begin with query `first`
+    int first;                // blockIdx.y counts queries from here
+    long long items;          // the most work items of one query of the call
+};
+// one thread per work item of one query (query_item): blockIdx.y the query of the chunk, blockIdx.x * 256 + threadIdx.x the item
+__global__ __launch_bounds__(256) void query_graph_kernel(QueryGraphArgs a)
+{
+    const int i = a.first + (int)blockIdx.y;
+    const long long x = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (x >= a.items) return;
+    query_item(a.g, query_terms(a.q, i), query_arrays(a.out, a.q, a.g.P, a.first, i), x);
+}
+
+} // namespace gcsadmm_lp

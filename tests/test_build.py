@@ -129,14 +129,14 @@ def test_every_launching_entry_point_selects_the_handles_device():
 
 
 def test_device_resources_are_released_by_their_owners_alone():
-    """Ownership rule of the host code of the handle and of the scene (csrc/gcsadmm.hip, csrc/polytope_lp.hip, and csrc/hip_owners.h,
-    which has the owners): a device allocation, a stream and an event each belong to an owning type (DevBuf, Stream, Event) whose
+    """Ownership rule of the host code of the handle and of the scene (csrc/gcsadmm.hip, csrc/polytope_lp.hip with the headers split from
+    it, and csrc/hip_owners.h, which has the owners): a device allocation, a stream and an event each belong to an owning type (DevBuf, Stream, Event) whose
     destructor releases it, so hipFree, hipStreamDestroy and hipEventDestroy are each written exactly once -- in the owners' releasing
     functor -- and hipMalloc only inside DevBuf.  A buffer added to the handle or the scene as a raw pointer and freed by hand fails here."""
     import os
     import re
     from gcs_admm_amd import build
-    src = "".join(open(os.path.join(build.CSRC, f)).read() for f in ("hip_owners.h", "gcsadmm.hip", "polytope_lp.hip"))
+    src = "".join(open(os.path.join(build.CSRC, f)).read() for f in ("hip_owners.h", "gcsadmm.hip", "polytope_lp.hip", "scene_kernels.h", "scene_stage.h"))
     for call in ("hipFree(", "hipStreamDestroy(", "hipEventDestroy("):
         assert src.count(call) == 1, (call, src.count(call))
     m = re.search(r"\nstruct HipRelease \{\n.*?\n\};\n", src, re.S)
