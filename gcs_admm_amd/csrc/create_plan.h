@@ -25,10 +25,10 @@ long long gcsadmm_terminal_record_doubles(int n, int facets, int live_edges);
 namespace gcsadmm_k {
 
 // (EDGE_BLOCK, threads per workgroup of the edge kernel: step_args.h)
-constexpr int REORDER_MIN_UNITS = 512;   // launches with fewer units run all at once: no slowest-first dispatch (reorder_kernel)
+constexpr int REORDER_MIN_UNITS = 512;   // launches with fewer units run all at once: no slowest-first dispatch (reorder_kernel, loop_kernels.h)
 constexpr int LDS_CU_BYTES = 160 * 1024;
 
-// edges a thread of the edge kernel has in flight at once on LARGE graphs (edge_unroll<T, C>() in gcsadmm.hip); graphs that would not
+// edges a thread of the edge kernel has in flight at once on LARGE graphs (edge_unroll<T, C>() in edge_step.h); graphs that would not
 // fill the chip with such tiles (fewer than 256 workgroups: one per CU) keep one edge per thread
 inline int edge_unroll_rt(int dtype, int c, int E)
 {

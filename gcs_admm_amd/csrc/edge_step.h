@@ -1,6 +1,6 @@
 // edge_step.h -- the edge step (z-update, dual update, five partial norms: admm_solver_v3.py:543-614) and the control step
 // (admm_solver_v3.py:697-733) as device functions, shared by the objects that run them: gcsadmm.hip (edge_kernel, edge_batch_kernel,
-// control_kernel) and the workgroup program's objects, where on small graphs the last vertex workgroup to finish runs the single-workgroup
+// control_kernel: loop_kernels.h) and the workgroup program's objects, where on small graphs the last vertex workgroup to finish runs the single-workgroup
 // edge step as the tail of the vertex launch (vertex_wg_kernel.h, FUSED TAIL).  One body, so that every caller runs the same
 // instructions on the same numbers in the same order.
 #pragma once
@@ -26,6 +26,11 @@ template <class T> struct EdgeArgs {
     T *zedge, *mu;
     double *partials;    // [gridDim.x][5]
 };
+// the same arguments with the state pointers as another type (host side: the handle's dtype picks T at launch, as StepDesc::typed)
+template <class U, class V> EdgeArgs<U> retype(const EdgeArgs<V> &a)
+{
+    return EdgeArgs<U>{a.E, a.NI, a.c, a.edge_inc_tail, a.edge_inc_head, a.inc_counted, a.edge_counted, (const U *)a.copy, (U *)a.zedge, (U *)a.mu, a.partials};
+}
 
 __device__ __forceinline__ double wave_sum(double v)
 {

@@ -1,6 +1,8 @@
-// gcsadmm.hip -- gfx950 kernels and C ABI (include/gcsadmm.h) of the ADMM iteration loop.
+// gcsadmm.hip -- C ABI (include/gcsadmm.h) of the ADMM iteration loop: the handle and batch structs, the launch descriptors and
+// helpers, the entry points.  Its kernels are in loop_kernels.h, the RCCL binding in rccl_api.h, the host-only rules of a vertex
+// partition in halo_plan.h (as those of create and of a batch are in create_plan.h and batch_plan.h).
 //
-// Kernels (one HIP stream, launched back to back, no host round trip inside the loop):
+// Kernels of the loop (one HIP stream, launched back to back, no host round trip inside the loop):
 //   vertex_kernel<2,T>   x-update, wavefront program (n = 2, degree <= 63): one wavefront per workgroup, several vertices
 //                        per wavefront, program in vertex_program.inc   (admm_solver_v3.py:352-540)
 //   vertex_wg_kernel<N,T> (vertex_wg.hip) x-update, workgroup program: one 256-thread workgroup per vertex, any n / degree
@@ -17,8 +19,6 @@
 //                        (gcsadmm_batch_run): the bodies of vertex_wg_kernel and edge_kernel on the member blockIdx.y names, each member
 //                        with its own arguments and control state, one vertex launch and one edge + control launch per iteration
 #include <hip/hip_runtime.h>
-#include <dlfcn.h>
-#include <rccl/rccl.h>
 
 #include <algorithm>
 #include <cmath>
@@ -56,169 +56,16 @@ __device__ __forceinline__ void gcs_stamp(int k)
 #include "create_plan.h"
 #include "batch_plan.h"
 #include "edge_step.h"
-
-namespace {
-
-using namespace gcs;
-using namespace gcsadmm_k;
-
-// -------------------------------------------------------------------------------------------------
-// edge and control kernels: the bodies are edge_step.h's (EdgeArgs<T>, ControlParams, edge_body<T, MODE, C, U>, control_body)
-// -------------------------------------------------------------------------------------------------
-__global__ void control_kernel(gcsadmm_control_block *cb, const double *sums, ControlParams p, int *counters, double *trace, bool global_fails)
-{
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    control_body(cb, sums, p, counters, trace, global_fails);
-}
-
-template <class T, int MODE, int C, int U>
-__global__ __launch_bounds__(EDGE_BLOCK) void edge_kernel(EdgeArgs<T> a, gcsadmm_control_block *cb, double *sums, ControlParams cp,
-                                                          int *counters, double *trace, unsigned *ticket)
-{
-    __shared__ double red[EDGE_BLOCK][5];
-    __shared__ int is_last;
-    edge_body<T, MODE, C, U>(a, cb, sums, cp, counters, trace, ticket, blockIdx.x, gridDim.x, red, &is_last);
-}
-
-// BATCH form (gcsadmm_batch_run): row blockIdx.y of the grid is member blockIdx.y of the batch.  The workgroup copies that member's entry
-// of the table -- what edge_kernel gets in its kernarg segment, plus the member's own number of workgroups -- through a uniform index
-// (scalar loads) and runs the body in the mode gcsadmm_run uses for that member: MODE 1 where one workgroup
-// holds all its edges, MODE 2 otherwise, with the member's nblocks in place of gridDim.x in the edge loop, the partials and the ticket
-// (each member has its own partials, sums, counters and ticket: its handle's).  The grid is as wide as the widest member; the
-// workgroups beyond a member's own leave before they touch its ticket or partials.  One edge per thread (U = 1: batch_plan.h).
-template <class T> struct EdgeBatchEntry {
-    EdgeArgs<T> a;
-    gcsadmm_control_block *cb;
-    double *sums;
-    ControlParams cp;
-    int *counters;
-    double *trace;      // may be null
-    unsigned *ticket;
-    int nblocks;
-};
-template <class T, int C>
-__global__ __launch_bounds__(EDGE_BLOCK) void edge_batch_kernel(const EdgeBatchEntry<T> *__restrict__ table)
-{
-    __shared__ double red[EDGE_BLOCK][5];
-    __shared__ int is_last;
-    // (read through the constant address space, as kernel arguments are: vertex_wg_batch_kernel has the reason)
-    __builtin_assume_dereferenceable(table + blockIdx.y, sizeof(EdgeBatchEntry<T>));
-    const EdgeBatchEntry<T> e = *(const EdgeBatchEntry<T> *)((const __attribute__((address_space(4))) EdgeBatchEntry<T> *)table + blockIdx.y);
-    if ((int)blockIdx.x >= e.nblocks) return;
-    if (e.nblocks == 1) edge_body<T, 1, C, 1>(e.a, e.cb, e.sums, e.cp, e.counters, e.trace, e.ticket, 0, 1, red, &is_last);
-    else edge_body<T, 2, C, 1>(e.a, e.cb, e.sums, e.cp, e.counters, e.trace, e.ticket, blockIdx.x, (unsigned)e.nblocks, red, &is_last);
-}
-
-// status and it of the members' control blocks, gathered for the one copy of gcsadmm_batch_poll: out[i] = status, out[count + i] = it
-__global__ __launch_bounds__(256) void batch_poll_kernel(const gcsadmm_control_block *const *cbs, int count, int *out)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= count) return;
-    out[i] = cbs[i]->status;
-    out[count + i] = cbs[i]->it;
-}
-
-// SLOWEST-FIRST DISPATCH.  A vertex-step launch ends when its slowest workgroup does, and with the warm start most solves take 3-5
-// Newton iterations while a few take 15: on the 10k lattice (1 654 wavefronts on 1 024 one-wavefront-per-SIMD slots) a slow
-// wavefront that happens to start in the second round ends the launch at 21 iteration times instead of 17.  Every few ADMM
-// iterations the units (wavefronts / workgroups) are re-ordered by the Newton iterations of their last launch, descending: a
-// counting sort by one workgroup.  The order among equal counts is arbitrary (atomics); it affects scheduling only, never results.
-constexpr int REORDER_BINS = 64, REORDER_THREADS = 1024, REORDER_EVERY = 8;     // (REORDER_MIN_UNITS: create_plan.h)
-// ids (may be null): the units to order are ids[0 .. n) instead of 0 .. n (the boundary / interior subsets of a partition's overlapped loop)
-__global__ __launch_bounds__(REORDER_THREADS) void reorder_kernel(int n, const int *iters, int *order, const gcsadmm_control_block *cb, const int *ids = nullptr)
-{
-    if (cb->status != GCSADMM_RUNNING) return;
-    __shared__ int cnt[REORDER_BINS], off[REORDER_BINS];
-    if (threadIdx.x < REORDER_BINS) cnt[threadIdx.x] = 0;
-    __syncthreads();
-    auto unit = [&](int i) { return ids ? ids[i] : i; };
-    auto key = [&](int i) { const int k = iters[unit(i)]; return k < 0 ? 0 : (k >= REORDER_BINS ? REORDER_BINS - 1 : k); };
-    for (int i = threadIdx.x; i < n; i += REORDER_THREADS) atomicAdd(&cnt[key(i)], 1);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int run = 0;
-        for (int b = REORDER_BINS - 1; b >= 0; --b) { off[b] = run; run += cnt[b]; }
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < n; i += REORDER_THREADS) order[atomicAdd(&off[key(i)], 1)] = unit(i);
-}
-
-// fixed-order reduction of the per-workgroup partials -> sums[5]
-__global__ __launch_bounds__(256) void finalize_kernel(const double *partials, int nblocks, double *sums,
-                                                      const gcsadmm_control_block *cb)
-{
-    if (cb->status != GCSADMM_RUNNING) return;
-    __shared__ double red[256][5];
-    double s[5] = {0, 0, 0, 0, 0};
-    for (int b = threadIdx.x; b < nblocks; b += 256)
-        for (int k = 0; k < 5; ++k) s[k] += partials[(size_t)b * 5 + k];
-    for (int k = 0; k < 5; ++k) red[threadIdx.x][k] = s[k];
-    __syncthreads();
-    for (int off = 128; off > 0; off >>= 1) {
-        if ((int)threadIdx.x < off)
-            for (int k = 0; k < 5; ++k) red[threadIdx.x][k] += red[threadIdx.x + off][k];
-        __syncthreads();
-    }
-    if (threadIdx.x < 5) sums[threadIdx.x] = red[0][threadIdx.x];
-}
-
-// halo of a vertex partition: copies of the cut edges' coupled words, packed per neighbour as [c][columns of that peer]
-// (one contiguous message per peer).  base[j] / stride[j]: where column j of the flat send (recv) list sits in the buffer.
-template <class T>
-__global__ __launch_bounds__(256) void halo_pack_kernel(int c, int ncols, int NI, const int *cols, const int *base, const int *stride,
-                                                        const T *copy, T *buf, const gcsadmm_control_block *cb)
-{
-    if (cb->status != GCSADMM_RUNNING) return;
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= c * ncols) return;
-    const int w = t / ncols, j = t - w * ncols;
-    buf[base[j] + w * stride[j]] = copy[(size_t)w * NI + cols[j]];
-}
-template <class T>
-__global__ __launch_bounds__(256) void halo_unpack_kernel(int c, int ncols, int NI, const int *cols, const int *base, const int *stride,
-                                                          const T *buf, T *copy, const gcsadmm_control_block *cb)
-{
-    if (cb->status != GCSADMM_RUNNING) return;
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= c * ncols) return;
-    const int w = t / ncols, j = t - w * ncols;
-    copy[(size_t)w * NI + cols[j]] = buf[base[j] + w * stride[j]];
-}
-template <class T>
-__global__ __launch_bounds__(256) void cost_kernel(int V, int E, int n, const double *zv, const T *zedge,
-                                                   const uint8_t *edge_counted, double eps_edge, double *cost)
-{
-    // single workgroup, fixed order: this runs once after the loop
-    __shared__ double red[256];
-    double s = 0;
-    for (int v = threadIdx.x; v < V; v += 256) {
-        double q = 0;
-        for (int k = 0; k < n; ++k) { const double dlt = zv[(size_t)v * 2 * n + k] - zv[(size_t)v * 2 * n + n + k]; q += dlt * dlt; }
-        s += sqrt(q);
-    }
-    for (int e = threadIdx.x; e < E; e += 256)
-        s += eps_edge * (edge_counted ? (double)edge_counted[e] : 1.0) * (double)zedge[(size_t)(2 * n) * E + e];
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int off = 128; off > 0; off >>= 1) {
-        if ((int)threadIdx.x < off) red[threadIdx.x] += red[threadIdx.x + off];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) cost[0] = red[0];
-}
-
-
-} // namespace
+#include "halo_plan.h"
+#include "loop_kernels.h"
+#include "rccl_api.h"
 
 // =================================================================================================
 // host side
 // =================================================================================================
 // (the owners of the device resources -- DevBuf<T>, Stream, Event -- and the DeviceGuard: hip_owners.h)
-// vertex partition across GPUs (gcsadmm_attach_comm): halo index lists and message buffers
-struct Halo {
-    std::vector<int> peers, peer_cnt, peer_off;   // neighbour ranks; columns per peer; first column of each peer's block
-    std::vector<int> send_cols;       // host copy of the send list as validated at attach (the overlap split is derived from it)
-    int n_send = 0, n_recv = 0;       // halo columns sent / received per iteration
+// vertex partition across GPUs (gcsadmm_attach_comm): the halo lists and the message layout (halo_plan.h) with what is uploaded of them
+struct Halo : HaloPlan {
     DevBuf<int> d_send_cols, d_send_base, d_send_stride, d_recv_cols, d_recv_base, d_recv_stride;
     DevBuf<char> d_sendbuf, d_recvbuf;
     DevBuf<double> d_sums6;           // the five norms + the inner-failure count, all-reduced together
@@ -309,79 +156,46 @@ struct gcsadmm_batch_s {
     std::vector<int> poll_host;
 };
 
-// ---- RCCL, bound at run time ----
-// The library is not linked against librccl: a process that already carries an RCCL (PyTorch-ROCm ships its own copy with the
-// SONAME of /opt/rocm's) must not end up with two, and a single-GPU user needs none.  dlopen returns the copy that is already
-// loaded, or loads the system one.
-namespace {
-struct RcclApi {
-    void *lib = nullptr;
-    decltype(&ncclGetUniqueId) GetUniqueId = nullptr;
-    decltype(&ncclCommInitRank) CommInitRank = nullptr;
-    decltype(&ncclCommDestroy) CommDestroy = nullptr;
-    decltype(&ncclGroupStart) GroupStart = nullptr;
-    decltype(&ncclGroupEnd) GroupEnd = nullptr;
-    decltype(&ncclSend) Send = nullptr;
-    decltype(&ncclRecv) Recv = nullptr;
-    decltype(&ncclAllReduce) AllReduce = nullptr;
-    decltype(&ncclGetErrorString) GetErrorString = nullptr;
-    decltype(&ncclCommCount) CommCount = nullptr;
-    std::string err;
-    bool ok() const { return lib && GetUniqueId && CommInitRank && CommDestroy && GroupStart && GroupEnd && Send && Recv && AllReduce; }
-};
-RcclApi &rccl()
-{
-    static RcclApi api = [] {
-        RcclApi a;
-        for (const char *name : {"librccl.so.1", "librccl.so"}) {
-            a.lib = dlopen(name, RTLD_NOW | RTLD_GLOBAL);
-            if (a.lib) break;
-        }
-        if (!a.lib) {
-            const char *why = dlerror();      // (a second call would return NULL: the message is consumed)
-            a.err = std::string("dlopen(librccl): ") + (why ? why : "not found");
-            return a;
-        }
-#define RCCL_SYM(f) a.f = (decltype(a.f))dlsym(a.lib, "nccl" #f)
-        RCCL_SYM(GetUniqueId); RCCL_SYM(CommInitRank); RCCL_SYM(CommDestroy); RCCL_SYM(GroupStart); RCCL_SYM(GroupEnd);
-        RCCL_SYM(Send); RCCL_SYM(Recv); RCCL_SYM(AllReduce); RCCL_SYM(GetErrorString); RCCL_SYM(CommCount);
-#undef RCCL_SYM
-        if (!a.ok()) a.err = "librccl lacks an expected symbol";
-        return a;
-    }();
-    return api;
-}
-}  // namespace
-#define NCCLCHK(h, call)                                                                             \
-    do {                                                                                             \
-        ncclResult_t r_ = (call);                                                                    \
-        if (r_ != ncclSuccess) {                                                                     \
-            (h)->err = std::string(#call) + ": " + (rccl().GetErrorString ? rccl().GetErrorString(r_) : "RCCL error"); \
-            return GCSADMM_ERR_HIP;                                                                  \
-        }                                                                                            \
-    } while (0)
-
 
 static thread_local std::string g_create_error;      // gcsadmm_last_error(NULL): the calling thread's last failed create
 
-// every entry point holds the handle's device for the call (DeviceGuard, hip_owners.h)
-#define USE_DEVICE(h)                                                                               \
-    DeviceGuard device_guard_((h)->device);                                                          \
+// of one family with NCCLCHK (rccl_api.h): `obj` is the handle or batch whose err takes the text
+#define HIPCHK(obj, call)                                                                            \
     do {                                                                                             \
-        if (device_guard_.err != hipSuccess) {                                                       \
-            (h)->err = std::string("hipSetDevice: ") + hipGetErrorString(device_guard_.err);        \
+        hipError_t e_ = (call);                                                                      \
+        if (e_ != hipSuccess) {                                                                      \
+            (obj)->err = std::string(#call) + ": " + hipGetErrorString(e_);                          \
             return GCSADMM_ERR_HIP;                                                                  \
         }                                                                                            \
     } while (0)
 
-#define HIPCHK(h, call)                                                                              \
-    do {                                                                                             \
-        hipError_t e_ = (call);                                                                      \
-        if (e_ != hipSuccess) {                                                                      \
-            (h)->err = std::string(#call) + ": " + hipGetErrorString(e_);                            \
-            return GCSADMM_ERR_HIP;                                                                  \
-        }                                                                                            \
-    } while (0)
+// The one shim of the entry points: no exception crosses the C ABI, a failed host allocation (a plan, a table, an event of the pool,
+// the text of a refusal) is a status.  `err` takes its text: the object's, or g_create_error for the calls without one.
+template <class F> static gcsadmm_status entry(std::string &err, F &&body)
+{
+    try {
+        return body();
+    } catch (const std::bad_alloc &) {
+        try { err = "out of host memory"; } catch (...) { err.clear(); }
+        return GCSADMM_ERR_NO_MEMORY;
+    }
+}
+// ... of every call on a handle or a batch that reaches the device: a null object is refused, `args` checks the other arguments on the
+// host, then the object's device is held for `body` and the caller's is back on return (DeviceGuard, hip_owners.h)
+template <class O, class A, class F> static gcsadmm_status guarded_entry(O *obj, A &&args, F &&body)
+{
+    if (!obj) return GCSADMM_ERR_BAD_ARG;
+    return entry(obj->err, [&]() -> gcsadmm_status {
+        const gcsadmm_status refused = args();
+        if (refused != GCSADMM_OK) return refused;
+        DeviceGuard device_guard_(obj->device);
+        if (device_guard_.err != hipSuccess) { obj->err = std::string("hipSetDevice: ") + hipGetErrorString(device_guard_.err); return GCSADMM_ERR_HIP; }
+        return body();
+    });
+}
+template <class A, class F> static gcsadmm_status handle_entry(gcsadmm_handle h, A &&args, F &&body) { return guarded_entry(h, args, body); }
+template <class A, class F> static gcsadmm_status batch_entry(gcsadmm_batch_s *b, A &&args, F &&body) { return guarded_entry(b, args, body); }
+static gcsadmm_status bad_unless(bool ok) { return ok ? GCSADMM_OK : GCSADMM_ERR_BAD_ARG; }
 
 // f(double()) or f(float()): the one switch on the handle's state type
 template <class F> static auto with_state(const gcsadmm_handle_s *h, F &&f) { return with_state_type(h->dtype == GCSADMM_F64, f); }
@@ -393,12 +207,18 @@ static ControlParams control_params(const gcsadmm_handle_s *h)
     return ControlParams{p.tau_incr, p.tau_decr, p.nu, p.eps_abs, p.eps_rel, h->plan.nx, h->plan.nmu, p.it_rho_limit, p.max_it};
 }
 
-// the inputs every vertex-step launch shares (step_args.h)
-static StepDesc make_step(gcsadmm_handle h, const gcsadmm_state *st)
+// the inputs every vertex-step launch shares (step_args.h): the graph half (all the PROX solve reads: the rest stays zero) ...
+static StepDesc make_step_graph(gcsadmm_handle h)
 {
-    StepDesc a;
+    StepDesc a{};
     a.inc_ptr = h->g.d_inc_ptr.get(); a.deg_in = h->g.d_deg_in.get(); a.inc_edge = h->g.d_inc_edge.get(); a.poly_ptr = h->g.d_poly_ptr.get();
     a.poly_A = h->g.d_poly_A.get(); a.poly_bc = h->g.d_poly_bc.get(); a.center = h->g.d_center.get();
+    return a;
+}
+// ... and with the ADMM state, its column numbering, the loop's counters and the parameters of the run
+static StepDesc make_step(gcsadmm_handle h, const gcsadmm_state *st)
+{
+    StepDesc a = make_step_graph(h);
     a.E = h->E; a.NI = h->NI; a.edge_major = h->edge_major;
     a.zedge = st->zedge; a.mu = st->mu; a.copy = st->copy; a.xv = st->xv; a.zv = st->zv; a.yv = st->yv;
     a.counters = h->loop.d_counters.get(); a.cb = h->loop.d_cb.get();
@@ -446,16 +266,16 @@ static VertexLaunchDesc make_launch_desc(gcsadmm_handle h, const gcsadmm_state *
     return d;
 }
 
-// part: -1 the whole vertex step; 0 / 1 the boundary / interior wavefronts of the overlapped partitioned loop (handles whose generic
-// vertices are all on the wavefront program; the closed-form vertices ride with the boundary part)
-// fused_trace (gcsadmm_run on a handle that fuses, h->fuses()): the launch also runs the edge and control steps; the trace may be null
-static gcsadmm_status launch_vertex(gcsadmm_handle h, const gcsadmm_state *st, hipStream_t s, int part = -1, bool reorder = false,
-                                    bool fused = false, double *fused_trace = nullptr);
-template <class T> static EdgeArgs<T> make_edge_args(gcsadmm_handle h, const gcsadmm_state *st);
-static WgTailDesc make_wg_tail(gcsadmm_handle h, const gcsadmm_state *st, double *trace);
-
-static gcsadmm_status launch_vertex(gcsadmm_handle h, const gcsadmm_state *st, hipStream_t s, int part, bool reorder, bool fused, double *fused_trace)
+// what a vertex-step launch is asked for; the default is the whole step alone
+struct VertexLaunch {
+    int part = -1;            // 0 / 1: the boundary / interior wavefronts of the overlapped partitioned loop (handles whose generic vertices
+                              // are all on the wavefront program; the closed-form vertices ride with the boundary part)
+    bool reorder = false;     // (a part) followed by the slowest-first reorder of the part's wavefronts
+    const WgTailDesc *tail = nullptr;      // (gcsadmm_run on a handle that fuses, h->fuses()) the launch also runs the edge and control steps
+};
+static gcsadmm_status launch_vertex(gcsadmm_handle h, const gcsadmm_state *st, hipStream_t s, const VertexLaunch &req = {})
 {
+    const int part = req.part;
     const auto &g = h->g;
     const int n_waves = h->plan.n_waves();
     const gcsadmm_control_block *cb = h->loop.d_cb.get();
@@ -481,7 +301,7 @@ static gcsadmm_status launch_vertex(gcsadmm_handle h, const gcsadmm_state *st, h
         d.n_waves = cnt;
         if (part) d.n_special = 0;
         launch_waves(d);
-        if (reorder && g.d_wave_iters)      // slowest first inside the part, on the part's own stream (its next launch reads the order)
+        if (req.reorder && g.d_wave_iters)      // slowest first inside the part, on the part's own stream (its next launch reads the order)
             hipLaunchKernelGGL(reorder_kernel, dim3(1), dim3(REORDER_THREADS), 0, s, cnt, g.d_wave_iters.get(), o.d_split_order.get() + off, cb, o.d_split_ids.get() + off);
         HIPCHK(h, hipGetLastError());
         return GCSADMM_OK;
@@ -490,7 +310,7 @@ static gcsadmm_status launch_vertex(gcsadmm_handle h, const gcsadmm_state *st, h
     if (n_waves > 0) launch_waves(make_launch_desc(h, st));
     if (h->n_wg() > 0 || (!special_on_wave && h->n_special() > 0)) {
         WgLaunchDesc d = make_wg_desc(h, st, !special_on_wave);
-        if (fused) d.tail = make_wg_tail(h, st, fused_trace);
+        if (req.tail) d.tail = *req.tail;
         if (h->plan.wg_t512) gcsadmm_wg_launch_t512(d, s);
         else gcsadmm_wg_launch(d, s);
     }
@@ -523,47 +343,38 @@ static WgTailDesc make_wg_tail(gcsadmm_handle h, const gcsadmm_state *st, double
 {
     WgTailDesc t;
     t.enabled = 1;
-    const EdgeArgs<char> a = make_edge_args<char>(h, st);      // (untyped: the launch casts the three state pointers back)
-    t.edge = EdgeArgs<void>{a.E, a.NI, a.c, a.edge_inc_tail, a.edge_inc_head, a.inc_counted, a.edge_counted, a.copy, a.zedge, a.mu, a.partials};
+    t.edge = retype<void>(make_edge_args<char>(h, st));      // (untyped: the launch casts the three state pointers back)
     t.cb = h->loop.d_cb.get(); t.sums = h->loop.d_sums.get(); t.cp = control_params(h);
     t.counters = h->loop.d_counters.get(); t.trace = trace; t.ticket = h->loop.d_ticket.get();
     return t;
 }
 
-// with_control: the control step rides in the same launches (gcsadmm_run); trace may be null
-static gcsadmm_status launch_edge(gcsadmm_handle h, const gcsadmm_state *st, double *sums, hipStream_t s, bool with_control = false,
-                                  double *trace = nullptr, bool sums6 = false)
+// How an edge step ends (the MODE of edge_kernel): the partials of every workgroup and a finalize launch (the separate steps of the
+// ABI); with the control step in the same launch, run by the single workgroup or by the last one to finish (gcsadmm_run; the trace may
+// be null); the six sums of a partition, reduced by the last workgroup (the partitioned loop)
+enum class EdgeMode { Partials = 0, ControlOneGroup = 1, ControlLastGroup = 2, Sums6 = 3 };
+static EdgeMode edge_mode_with_control(const gcsadmm_handle_s *h) { return h->plan.edge_blocks == 1 ? EdgeMode::ControlOneGroup : EdgeMode::ControlLastGroup; }
+
+static gcsadmm_status launch_edge(gcsadmm_handle h, const gcsadmm_state *st, double *sums, hipStream_t s, EdgeMode mode, double *trace = nullptr)
 {
     const ControlParams cp = control_params(h);
     const int edge_blocks = h->plan.edge_blocks;
     with_state(h, [&](auto t) {
         using T = decltype(t);
         const EdgeArgs<T> a = make_edge_args<T>(h, st);
-        // one kernel instantiation per (state type, mode, words per copy)
-        auto go = [&](auto mode, int blocks) {
-            constexpr int M = decltype(mode)::value;
-#define GCS_EDGE_U(CC, UU) hipLaunchKernelGGL((edge_kernel<T, M, CC, UU>), dim3(blocks), dim3(EDGE_BLOCK), 0, s, a, h->loop.d_cb.get(), sums, cp, h->loop.d_counters.get(), trace, h->loop.d_ticket.get())
-#define GCS_EDGE(CC) do { if (h->plan.edge_unroll > 1) GCS_EDGE_U(CC, (edge_unroll<T, CC>())); else GCS_EDGE_U(CC, 1); } while (0)
-            switch (h->c) {      // c = 2n + 1
-            case 3: GCS_EDGE(3); break;
-            case 5: GCS_EDGE(5); break;
-            case 7: GCS_EDGE(7); break;
-            case 9: GCS_EDGE(9); break;
-            case 11: GCS_EDGE(11); break;
-            case 13: GCS_EDGE(13); break;
-            case 15: GCS_EDGE(15); break;
-            default: GCS_EDGE(17);          // n = 8 (gcsadmm_create admits n = 1 .. 8)
-            }
-#undef GCS_EDGE_U
-#undef GCS_EDGE
-        };
-        if (sums6) go(std::integral_constant<int, 3>(), edge_blocks);
-        else if (with_control && edge_blocks == 1) go(std::integral_constant<int, 1>(), 1);
-        else if (with_control) go(std::integral_constant<int, 2>(), edge_blocks);
-        else {
-            go(std::integral_constant<int, 0>(), edge_blocks);
-            hipLaunchKernelGGL(finalize_kernel, dim3(1), dim3(256), 0, s, a.partials, edge_blocks, sums, h->loop.d_cb.get());
-        }
+        // one kernel instantiation per (state type, mode, words per copy c = 2n + 1, edges per thread)
+        dispatch_dim<1, 2, 3, 4, 5, 6, 7, 8>(h->n, [&](auto N) {
+            dispatch_dim<0, 1, 2, 3>((int)mode, [&](auto M) {
+                constexpr int C = 2 * decltype(N)::value + 1;
+                auto go = [&](auto U) {
+                    hipLaunchKernelGGL((edge_kernel<T, decltype(M)::value, C, decltype(U)::value>), dim3(edge_blocks), dim3(EDGE_BLOCK), 0, s, a, h->loop.d_cb.get(), sums, cp,
+                                       h->loop.d_counters.get(), trace, h->loop.d_ticket.get());
+                };
+                if (h->plan.edge_unroll > 1) go(std::integral_constant<int, edge_unroll<T, C>()>());
+                else go(std::integral_constant<int, 1>());
+            });
+        });
+        if (mode == EdgeMode::Partials) hipLaunchKernelGGL(finalize_kernel, dim3(1), dim3(256), 0, s, a.partials, edge_blocks, sums, h->loop.d_cb.get());
     });
     HIPCHK(h, hipGetLastError());
     return GCSADMM_OK;
@@ -576,58 +387,35 @@ static bool state_ok(gcsadmm_handle h, const gcsadmm_state *st)
     return true;
 }
 
-// ---- halo of a vertex partition: host-side helpers (C++ linkage) ----
-// the checks of the halo lists, on the host alone: no allocation, no collective (gcsadmm_check_halo, and the head of attach_comm)
-static gcsadmm_status halo_validate(gcsadmm_handle h, int rank, int world, const gcsadmm_halo_desc *hd)
+// ---- halo of a vertex partition: host-side helpers (C++ linkage); what the lists are refused for, the layout of the message and the
+// split of the wavefronts are halo_plan.h's ----
+// the three halo calls of the ABI: a state that can run, and a halo to move
+static bool need_halo(gcsadmm_handle h, const gcsadmm_state *st)
 {
-    if (!hd || world < 1 || rank < 0 || rank >= world) { h->err = "bad communicator arguments"; return GCSADMM_ERR_BAD_ARG; }
-    const int P = hd->num_peers;
-    if (P < 0 || (P > 0 && (!hd->peer_rank || !hd->send_ptr || !hd->recv_ptr || !hd->send_cols || !hd->recv_cols))) { h->err = "null halo array"; return GCSADMM_ERR_BAD_ARG; }
-    const int n_send = P ? hd->send_ptr[P] : 0, n_recv = P ? hd->recv_ptr[P] : 0;
-    if (n_send != n_recv) { h->err = "halo lists: a partition sends and receives one column per cut edge and neighbour"; return GCSADMM_ERR_BAD_ARG; }
-    for (int p = 0; p < P; ++p) {
-        const int lo = hd->send_ptr[p], cnt = hd->send_ptr[p + 1] - lo;
-        if (cnt < 0 || hd->recv_ptr[p + 1] - hd->recv_ptr[p] != cnt || hd->recv_ptr[p] != lo) { h->err = "halo lists: send and receive counts per peer must agree"; return GCSADMM_ERR_BAD_ARG; }
-        if (hd->peer_rank[p] < 0 || hd->peer_rank[p] >= world || hd->peer_rank[p] == rank) { h->err = "halo lists: bad peer rank"; return GCSADMM_ERR_BAD_ARG; }
-    }
-    const std::vector<char> &col_owned = h->plan.col_owned;
-    for (int j = 0; j < n_send; ++j) {
-        if (hd->send_cols[j] < 0 || hd->send_cols[j] >= h->NI || hd->recv_cols[j] < 0 || hd->recv_cols[j] >= h->NI) { h->err = "halo lists: column out of range"; return GCSADMM_ERR_BAD_ARG; }
-        if (!col_owned[hd->send_cols[j]]) { h->err = "halo lists: send column is not an owned incidence"; return GCSADMM_ERR_BAD_ARG; }
-        if (col_owned[hd->recv_cols[j]]) { h->err = "halo lists: receive column is not a ghost column"; return GCSADMM_ERR_BAD_ARG; }
-    }
-    return GCSADMM_OK;
+    if (!state_ok(h, st)) return false;
+    if (!h->halo.attached()) { h->err = "no halo attached"; return false; }
+    return true;
 }
 
-// The split of the wavefronts for the overlapped loop: boundary = holds a vertex one of whose columns (send_cols) is sent to a neighbour.
-// Only for handles whose generic vertices all run the wavefront program (config 4's strips); mode 1 (tests) splits even without
-// neighbours -- the first quarter of the wavefronts plays the boundary -- so that the two launches, the second stream and the events can
-// be exercised on one GPU.  Leaves n_wave_b = 0 when there is nothing to split.
-static gcsadmm_status overlap_setup(gcsadmm_handle h, const std::vector<int> &send_cols)
+// gcsadmm_check_halo, and the head of gcsadmm_attach_comm: on the host alone
+static gcsadmm_status check_halo_of(gcsadmm_handle h, int rank, int world, const gcsadmm_halo_desc *hd)
 {
-    const CreatePlan &p = h->plan;
-    const int n_waves = p.n_waves(), n_send = (int)send_cols.size();
+    if (h->halo.attached()) { h->err = "a communicator is already attached"; return GCSADMM_ERR_BAD_ARG; }
+    return check_halo(h->plan.col_owned, h->NI, rank, world, hd, h->err);
+}
+
+// The overlapped loop's split (overlap_split, from the send list validated at attach), its second stream and its two events.  Leaves
+// n_wave_b = 0 when there is nothing to split.
+static gcsadmm_status overlap_setup(gcsadmm_handle h)
+{
     Overlap &o = h->overlap;
     o = {};
-    if (h->overlap_mode == 2 || n_waves < 2 || h->n_wg() > 0 || h->n_split() > 0) return GCSADMM_OK;
-    if (n_send == 0 && h->overlap_mode != 1) return GCSADMM_OK;
-    std::vector<char> vb((size_t)std::max(h->V, 1), 0);
-    for (int j = 0; j < n_send; ++j) {
-        const int v = p.col_vertex[send_cols[j]];
-        if (v >= 0) vb[v] = 1;
-    }
-    std::vector<int> ids_b, ids_i;
-    for (int w = 0; w < n_waves; ++w) {
-        bool b = (n_send == 0) && w < std::max(1, n_waves / 4);
-        for (int q = p.wave_slot_ptr[w]; q < p.wave_slot_ptr[w + 1] && !b; ++q) b = vb[p.wave_vtx[q]] != 0;
-        (b ? ids_b : ids_i).push_back(w);
-    }
-    if (ids_b.empty() || ids_i.empty()) return GCSADMM_OK;      // nothing to overlap with
-    o.n_wave_b = (int)ids_b.size();
-    ids_b.insert(ids_b.end(), ids_i.begin(), ids_i.end());
-    HIPCHK(h, o.d_split_ids.upload(ids_b.data(), ids_b.size()));
-    HIPCHK(h, o.d_split_order.upload(ids_b.data(), ids_b.size()));
-    if (!h->g.d_wave_iters) HIPCHK(h, h->g.d_wave_iters.upload(nullptr, (size_t)n_waves));
+    const OverlapSplit split = overlap_split(h->plan, h->V, h->halo.send_cols, h->overlap_mode, h->n_wg(), h->n_split());
+    if (split.n_wave_b == 0) return GCSADMM_OK;
+    o.n_wave_b = split.n_wave_b;
+    HIPCHK(h, o.d_split_ids.upload(split.ids.data(), split.ids.size()));
+    HIPCHK(h, o.d_split_order.upload(split.ids.data(), split.ids.size()));
+    if (!h->g.d_wave_iters) HIPCHK(h, h->g.d_wave_iters.upload(nullptr, (size_t)h->plan.n_waves()));
     HIPCHK(h, create_owned(o.comm_stream, hipStreamCreateWithFlags, hipStreamNonBlocking));
     HIPCHK(h, create_owned(o.ev_boundary, hipEventCreateWithFlags, hipEventDisableTiming));
     HIPCHK(h, create_owned(o.ev_halo, hipEventCreateWithFlags, hipEventDisableTiming));
@@ -636,25 +424,15 @@ static gcsadmm_status overlap_setup(gcsadmm_handle h, const std::vector<int> &se
 
 static gcsadmm_status halo_upload(gcsadmm_handle h, const gcsadmm_halo_desc *hd)
 {
-    const int P = hd->num_peers, c = h->c;
     Halo &H = h->halo;
-    H.peers.assign(hd->peer_rank, hd->peer_rank + P);
-    H.peer_cnt.resize(P); H.peer_off.resize(P);
-    H.n_send = P ? hd->send_ptr[P] : 0; H.n_recv = P ? hd->recv_ptr[P] : 0;
-    H.send_cols.assign(hd->send_cols, hd->send_cols + H.n_send);
-    std::vector<int> sbase(std::max(H.n_send, 1)), sstride(std::max(H.n_send, 1));
-    for (int p = 0; p < P; ++p) {
-        const int lo = hd->send_ptr[p], cnt = hd->send_ptr[p + 1] - lo;
-        H.peer_cnt[p] = cnt; H.peer_off[p] = lo;
-        for (int j = 0; j < cnt; ++j) { sbase[lo + j] = lo * c + j; sstride[lo + j] = cnt; }     // block of peer p: [c][cnt] at lo * c
-    }
-    const size_t esz = state_bytes(h);
+    static_cast<HaloPlan &>(H) = make_halo_plan(h->c, hd);
+    const size_t esz = state_bytes(h), c = (size_t)h->c;
     HIPCHK(h, H.d_send_cols.upload(hd->send_cols, (size_t)H.n_send));
     HIPCHK(h, H.d_recv_cols.upload(hd->recv_cols, (size_t)H.n_recv));
-    HIPCHK(h, H.d_send_base.upload(sbase.data(), (size_t)H.n_send));
-    HIPCHK(h, H.d_send_stride.upload(sstride.data(), (size_t)H.n_send));
-    HIPCHK(h, H.d_recv_base.upload(sbase.data(), (size_t)H.n_recv));        // same block layout on the receiving side
-    HIPCHK(h, H.d_recv_stride.upload(sstride.data(), (size_t)H.n_recv));
+    HIPCHK(h, H.d_send_base.upload(H.base.data(), (size_t)H.n_send));
+    HIPCHK(h, H.d_send_stride.upload(H.stride.data(), (size_t)H.n_send));
+    HIPCHK(h, H.d_recv_base.upload(H.base.data(), (size_t)H.n_recv));        // same block layout on the receiving side
+    HIPCHK(h, H.d_recv_stride.upload(H.stride.data(), (size_t)H.n_recv));
     HIPCHK(h, H.d_sendbuf.alloc(std::max<size_t>((size_t)H.n_send * c * esz, 16)));
     HIPCHK(h, H.d_recvbuf.alloc(std::max<size_t>((size_t)H.n_recv * c * esz, 16)));
     // [0..6): this partition's five norms + inner failures, written by the edge step; [6..12): their sum over the ranks.  (Out of
@@ -703,6 +481,18 @@ static gcsadmm_status halo_transfer(gcsadmm_handle h, hipStream_t s)
     return GCSADMM_OK;
 }
 
+// pack, grouped send / recv, unpack: one halo exchange on one stream
+static gcsadmm_status halo_exchange(gcsadmm_handle h, const gcsadmm_state *st, hipStream_t s)
+{
+    return with_state(h, [&](auto t) {
+        using T = decltype(t);
+        gcsadmm_status r;
+        if ((r = halo_pack<T>(h, st, s)) != GCSADMM_OK) return r;
+        if ((r = halo_transfer(h, s)) != GCSADMM_OK) return r;
+        return halo_unpack<T>(h, st, s);
+    });
+}
+
 // the timing entry points bracket their stages with events of the handle's pool: at least `count` of them
 static gcsadmm_status ensure_events(gcsadmm_handle h, size_t count)
 {
@@ -711,6 +501,18 @@ static gcsadmm_status ensure_events(gcsadmm_handle h, size_t count)
         HIPCHK(h, create_owned(e, hipEventCreateWithFlags, hipEventDefault));
         h->events.push_back(std::move(e));
     }
+    return GCSADMM_OK;
+}
+// ... `stride` per iteration; *ms: the time from event `from` to event `to` of an iteration, summed over the k iterations
+static gcsadmm_status elapsed_sum(gcsadmm_handle h, int stride, int k, int from, int to, float *ms)
+{
+    double acc = 0;
+    for (int i = 0; i < k; ++i) {
+        float t = 0;
+        HIPCHK(h, hipEventElapsedTime(&t, h->events[stride * i + from].get(), h->events[stride * i + to].get()));
+        acc += t;
+    }
+    *ms = (float)acc;
     return GCSADMM_OK;
 }
 
@@ -742,6 +544,12 @@ static void batches_forget(gcsadmm_handle h)
     }
 }
 
+static gcsadmm_status need_bound(gcsadmm_batch_s *b)
+{
+    if (!b->bound) b->err = "gcsadmm_batch_bind has not been called";
+    return bad_unless(b->bound);
+}
+
 // one vertex launch and one edge + control launch for the whole batch
 static gcsadmm_status launch_batch_iteration(gcsadmm_batch_s *b, hipStream_t s)
 {
@@ -751,277 +559,12 @@ static gcsadmm_status launch_batch_iteration(gcsadmm_batch_s *b, hipStream_t s)
     with_state_type(bp.dtype == GCSADMM_F64, [&](auto t) {
         using T = decltype(t);
         const auto *table = (const EdgeBatchEntry<T> *)b->d_edge_table.get();
-#define GCS_EDGE_BATCH(CC) hipLaunchKernelGGL((edge_batch_kernel<T, CC>), dim3(bp.edge_grid_x, bp.count), dim3(EDGE_BLOCK), 0, s, table)
-        switch (2 * bp.n + 1) {
-        case 3: GCS_EDGE_BATCH(3); break;
-        case 5: GCS_EDGE_BATCH(5); break;
-        case 7: GCS_EDGE_BATCH(7); break;
-        case 9: GCS_EDGE_BATCH(9); break;
-        case 11: GCS_EDGE_BATCH(11); break;
-        case 13: GCS_EDGE_BATCH(13); break;
-        case 15: GCS_EDGE_BATCH(15); break;
-        default: GCS_EDGE_BATCH(17);
-        }
-#undef GCS_EDGE_BATCH
+        dispatch_dim<1, 2, 3, 4, 5, 6, 7, 8>(bp.n, [&](auto N) {
+            hipLaunchKernelGGL((edge_batch_kernel<T, 2 * decltype(N)::value + 1>), dim3(bp.edge_grid_x, bp.count), dim3(EDGE_BLOCK), 0, s, table);
+        });
     });
     HIPCHK(b, hipGetLastError());
     return GCSADMM_OK;
-}
-
-extern "C" {
-
-const char *gcsadmm_last_error(gcsadmm_handle h) { return h ? h->err.c_str() : g_create_error.c_str(); }
-
-void gcsadmm_destroy(gcsadmm_handle h)
-{
-    if (!h) return;
-    DeviceGuard device_guard_(h->device);      // the owners release on the handle's device
-    batches_forget(h);
-    if (h->comm && rccl().ok()) (void)rccl().CommDestroy((ncclComm_t)h->comm);
-    delete h;
-}
-
-gcsadmm_status gcsadmm_create(const gcsadmm_graph_desc *g, gcsadmm_handle *out)
-{
-    if (out) *out = nullptr;
-    auto fail = [&](gcsadmm_status st, const std::string &msg) { g_create_error = msg; return st; };
-    std::string msg;
-    gcsadmm_status st;
-    if (!out) return fail(GCSADMM_ERR_BAD_ARG, "null descriptor or output pointer");
-    if ((st = check_graph_desc(g, msg)) != GCSADMM_OK) return fail(st, msg);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(GCSADMM_ERR_NO_DEVICE, "no HIP device");
-    if (g->device < 0 || g->device >= ndev) return fail(GCSADMM_ERR_BAD_ARG, "device ordinal out of range");
-    CreatePlan plan;
-    if ((st = make_create_plan(*g, plan, msg)) != GCSADMM_OK) return fail(st, msg);
-
-    const int V = g->num_vertices, E = g->num_edges, n = g->n, NIo = g->inc_ptr[V], MT = g->poly_ptr[V];
-    auto *h = new (std::nothrow) gcsadmm_handle_s;
-    if (!h) return fail(GCSADMM_ERR_HIP, "out of host memory");
-    h->n = n; h->V = V; h->E = E; h->NI = g->num_incidences; h->c = 2 * n + 1;
-    h->edge_major = g->edge_major_columns; h->src = g->src; h->dst = g->dst;
-    h->dtype = g->state_dtype; h->device = g->device;
-    h->plan = std::move(plan);
-    CreatePlan &p = h->plan;
-    DeviceGuard device_guard_(g->device);
-    auto bail = [&](hipError_t e, const char *what) {      // (under the guard: whatever has been filled is released with the handle)
-        g_create_error = std::string(what) + ": " + hipGetErrorString(e);
-        delete h;
-        return GCSADMM_ERR_HIP;
-    };
-    hipError_t e;
-    if ((e = device_guard_.err) != hipSuccess) return bail(e, "hipSetDevice");
-#define UP(group, dst, src, cnt) if ((e = h->group.dst.upload(src, (size_t)(cnt))) != hipSuccess) return bail(e, "upload " #dst)
-    UP(g, d_inc_ptr, g->inc_ptr, V + 1);
-    UP(g, d_deg_in, p.deg_in.data(), V);
-    UP(g, d_inc_edge, g->inc_edge, NIo);
-    UP(g, d_poly_ptr, g->poly_ptr, V + 1);
-    UP(g, d_edge_inc_tail, g->edge_inc_tail, E);
-    UP(g, d_edge_inc_head, g->edge_inc_head, E);
-    UP(g, d_wave_slot_ptr, p.wave_slot_ptr.data(), p.wave_slot_ptr.size());
-    UP(g, d_wave_vtx, p.wave_vtx.data(), p.wave_vtx.size());
-    UP(g, d_special_vtx, p.special_vtx.data(), p.special_vtx.size());
-    UP(g, d_special_kind, p.special_kind.data(), p.special_kind.size());
-    UP(g, d_wg_vtx, p.wg_vtx.data(), p.wg_vtx.size());
-    if (!p.split_vtx.empty()) {
-        UP(g, d_split_vtx, p.split_vtx.data(), p.split_vtx.size());
-        UP(g, d_split_off, p.split_off.data(), p.split_off.size());
-        UP(g, d_split_ws, nullptr, p.split_doubles);
-    }
-    UP(g, d_poly_A, g->poly_A, (size_t)MT * n);
-    UP(g, d_poly_bc, p.bc.data(), MT);
-    UP(g, d_center, g->center, (size_t)V * n);
-    if (g->inc_counted) UP(g, d_inc_counted, g->inc_counted, g->num_incidences);
-    if (g->edge_counted) UP(g, d_edge_counted, g->edge_counted, E);
-    UP(loop, d_cb, nullptr, 1);
-    UP(loop, d_counters, nullptr, 2);
-    UP(loop, d_partials, nullptr, (size_t)p.edge_blocks * 5);
-    UP(loop, d_sums, nullptr, 5);
-    UP(loop, d_ticket, nullptr, 1);
-    if (p.n_term > 0) {       // region terminals: workspace, an auxiliary stream and the fork / join events
-        UP(term, d_term_ws, nullptr, p.term_ws_doubles);
-        UP(term, d_term_rec, nullptr, p.term_rec_doubles);
-        if ((e = create_owned(h->term.term_stream, hipStreamCreateWithFlags, hipStreamNonBlocking)) != hipSuccess) return bail(e, "hipStreamCreate");
-        if ((e = create_owned(h->term.ev_term_fork, hipEventCreateWithFlags, hipEventDisableTiming)) != hipSuccess) return bail(e, "hipEventCreate");
-        if ((e = create_owned(h->term.ev_term_join, hipEventCreateWithFlags, hipEventDisableTiming)) != hipSuccess) return bail(e, "hipEventCreate");
-    }
-    UP(g, d_warm_ptr, p.warm_ptr.data(), V + 1);
-    UP(g, d_warm, nullptr, p.warm_ptr[V]);
-    // slowest-first dispatch: only where a launch needs more than one round of the chip (small graphs run all at once)
-    const int n_waves = p.n_waves(), n_wg = h->n_wg();
-    h->iota.resize(std::max(std::max(n_waves, n_wg), 1));
-    for (size_t i = 0; i < h->iota.size(); ++i) h->iota[i] = (int)i;
-    if (p.wave_reorder) { UP(g, d_wave_iters, nullptr, n_waves); UP(g, d_wave_order, h->iota.data(), n_waves); }
-    if (p.wg_reorder) { UP(g, d_wg_iters, nullptr, n_wg); UP(g, d_wg_order, h->iota.data(), n_wg); }
-    UP(prox, d_prox_vtx, p.prox_vtx.data(), p.prox_vtx.size());
-    UP(prox, d_prox_counters, nullptr, 2);
-#undef UP
-    // the plan's arrays that only fed an upload (the three the halo checks and the overlap split read stay: wave_slot_ptr, wave_vtx,
-    // col_owned / col_vertex)
-    auto release = [](auto &v) { v.clear(); v.shrink_to_fit(); };
-    release(p.bc); release(p.deg_in); release(p.warm_ptr); release(p.prox_vtx); release(p.special_vtx); release(p.special_kind);
-    release(p.wg_vtx); release(p.split_vtx); release(p.split_off);
-    if (p.lds_bytes > 48 * 1024) {
-        e = with_state(h, [&](auto t) { return set_lds_attr<2, decltype(t)>(p.all_m4, p.lds_bytes); });
-        if (e != hipSuccess) return bail(e, "hipFuncSetAttribute(MaxDynamicSharedMemorySize)");
-    }
-    if (p.wg_lds_bytes > 48 * 1024 && (e = p.wg_t512 ? gcsadmm_wg_set_lds_t512(h->n, h->dtype, p.wg_lds_bytes)
-                                                      : gcsadmm_wg_set_lds(h->n, h->dtype, p.wg_lds_bytes)) != hipSuccess)
-        return bail(e, "hipFuncSetAttribute(MaxDynamicSharedMemorySize, workgroup program)");
-    if (p.split_lds_bytes > 48 * 1024 && (e = gcsadmm_wg_set_split_lds(h->n, h->dtype, p.split_lds_bytes)) != hipSuccess)
-        return bail(e, "hipFuncSetAttribute(MaxDynamicSharedMemorySize, split workgroup program)");
-    *out = h;
-    return GCSADMM_OK;
-}
-
-gcsadmm_status gcsadmm_reset(gcsadmm_handle h, const gcsadmm_params *p, void *stream)
-{
-    if (!h || !p) return GCSADMM_ERR_BAD_ARG;
-    if (!(p->rho > 0) || p->max_it < 1 || !(p->ipm_tol > 0) || p->ipm_max_iter < 1) { h->err = "bad parameter"; return GCSADMM_ERR_BAD_ARG; }
-    h->params = *p; h->params_set = true; ++h->resets;
-    gcsadmm_control_block cb{};
-    cb.rho = p->rho; cb.mu_scale = 1.0; cb.it = 1; cb.status = GCSADMM_RUNNING;
-    USE_DEVICE(h);
-    hipStream_t s = (hipStream_t)stream;
-    HIPCHK(h, hipMemcpyAsync(h->loop.d_cb.get(), &cb, sizeof(cb), hipMemcpyHostToDevice, s));
-    HIPCHK(h, h->loop.d_counters.zero(s));
-    // a new run starts without warm-start records (runs from the same state are then identical, whatever ran before)
-    HIPCHK(h, h->g.d_warm.zero(s));
-    HIPCHK(h, h->term.d_term_rec.zero(s));
-    h->vertex_steps = 0;
-    const Overlap &o = h->overlap;
-    if (o.d_split_order) HIPCHK(h, hipMemcpyAsync(o.d_split_order.get(), o.d_split_ids.get(), sizeof(int) * o.d_split_order.size(), hipMemcpyDeviceToDevice, s));
-    for (const DevBuf<int> *order : {&h->g.d_wave_order, &h->g.d_wg_order})      // (h->iota outlives the copies)
-        if (*order) HIPCHK(h, hipMemcpyAsync(order->get(), h->iota.data(), sizeof(int) * order->size(), hipMemcpyHostToDevice, s));
-    HIPCHK(h, hipStreamSynchronize(s));   // cb is a stack object
-    return GCSADMM_OK;
-}
-
-gcsadmm_status gcsadmm_vertex_step(gcsadmm_handle h, const gcsadmm_state *st, void *stream)
-{
-    if (!state_ok(h, st)) return GCSADMM_ERR_BAD_ARG;
-    USE_DEVICE(h);
-    return launch_vertex(h, st, (hipStream_t)stream);
-}
-
-gcsadmm_status gcsadmm_edge_step(gcsadmm_handle h, const gcsadmm_state *st, double *sums_dev, void *stream)
-{
-    if (!state_ok(h, st) || !sums_dev) return GCSADMM_ERR_BAD_ARG;
-    USE_DEVICE(h);
-    return launch_edge(h, st, sums_dev, (hipStream_t)stream);
-}
-
-gcsadmm_status gcsadmm_control(gcsadmm_handle h, const double *sums_dev, double *trace_dev, void *stream)
-{
-    if (!h || !sums_dev || !h->params_set) return GCSADMM_ERR_BAD_ARG;
-    USE_DEVICE(h);
-    hipLaunchKernelGGL(control_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, h->loop.d_cb.get(), sums_dev, control_params(h), h->loop.d_counters.get(), trace_dev, false);
-    HIPCHK(h, hipGetLastError());
-    return GCSADMM_OK;
-}
-
-gcsadmm_status gcsadmm_run(gcsadmm_handle h, const gcsadmm_state *st, int32_t k, double *trace_dev, void *stream)
-{
-    if (!state_ok(h, st) || k < 0) return GCSADMM_ERR_BAD_ARG;
-    USE_DEVICE(h);      // (the edge launches below are issued from here, not through an entry point that guards for itself)
-    const bool fused = h->fuses();
-    for (int i = 0; i < k; ++i) {
-        gcsadmm_status s;
-        if (fused) {      // small graphs: the last vertex workgroup runs the edge and control steps, one launch per iteration
-            if ((s = launch_vertex(h, st, (hipStream_t)stream, -1, false, true, trace_dev)) != GCSADMM_OK) return s;
-            continue;
-        }
-        if ((s = gcsadmm_vertex_step(h, st, stream)) != GCSADMM_OK) return s;
-        // edge step and control step in two launches (one when all edges fit a single workgroup)
-        if ((s = launch_edge(h, st, h->loop.d_sums.get(), (hipStream_t)stream, true, trace_dev)) != GCSADMM_OK) return s;
-    }
-    return GCSADMM_OK;
-}
-
-// =================================================================================================
-// vertex partitions across GPUs (SURVEY.md section 8e): one handle per rank, RCCL over xGMI.
-// Per iteration, all on one stream with no host synchronisation:
-//   vertex step -> pack the cut edges' copies per neighbour -> grouped ncclSend / ncclRecv -> unpack into the ghost columns
-//   -> edge step on local + ghost columns -> ncclAllReduce(sum) of the five norms and the inner-failure count (6 doubles)
-//   -> control (every rank takes the same decision from the same numbers).
-// Both messages are latency-bound at every configuration of BASELINE.json (about 25 KB per boundary of the 100k lattice,
-// 48 bytes for the all-reduce).
-// =================================================================================================
-gcsadmm_status gcsadmm_comm_unique_id(void *id128)
-{
-    if (!id128) return GCSADMM_ERR_BAD_ARG;
-    if (!rccl().ok()) { g_create_error = rccl().err; return GCSADMM_ERR_HIP; }
-    static_assert(sizeof(ncclUniqueId) == 128, "ncclUniqueId is 128 bytes");
-    ncclUniqueId id;
-    if (rccl().GetUniqueId(&id) != ncclSuccess) { g_create_error = "ncclGetUniqueId failed"; return GCSADMM_ERR_HIP; }
-    std::memcpy(id128, &id, sizeof(id));
-    return GCSADMM_OK;
-}
-
-gcsadmm_status gcsadmm_check_halo(gcsadmm_handle h, int32_t rank, int32_t world, const gcsadmm_halo_desc *halo)
-{
-    if (!h) return GCSADMM_ERR_BAD_ARG;
-    if (h->halo.attached()) { h->err = "a communicator is already attached"; return GCSADMM_ERR_BAD_ARG; }
-    return halo_validate(h, rank, world, halo);
-}
-
-gcsadmm_status gcsadmm_attach_comm(gcsadmm_handle h, int32_t rank, int32_t world, const void *id128, const gcsadmm_halo_desc *halo)
-{
-    // everything that can fail on this rank alone comes first: a rank must not return an error while its peers wait in the collective
-    gcsadmm_status st = gcsadmm_check_halo(h, rank, world, halo);
-    if (st != GCSADMM_OK) return st;
-    if (id128 && !rccl().ok()) { h->err = rccl().err; return GCSADMM_ERR_HIP; }
-    USE_DEVICE(h);
-    h->rank = rank; h->world = world;
-    if ((st = halo_upload(h, halo)) != GCSADMM_OK) { h->halo = {}; return st; }
-    if (id128) {      // id128 == NULL: no communicator (the host moves the packed buffers itself; gcsadmm_run_partitioned needs one)
-        ncclUniqueId id;
-        std::memcpy(&id, id128, sizeof(id));
-        ncclComm_t comm = nullptr;
-        const ncclResult_t r = rccl().CommInitRank(&comm, world, id, rank);
-        if (r != ncclSuccess) {      // not attached: the handle can be attached again
-            h->err = std::string("ncclCommInitRank: ") + (rccl().GetErrorString ? rccl().GetErrorString(r) : "RCCL error");
-            h->halo = {};
-            return GCSADMM_ERR_HIP;
-        }
-        h->comm = comm;
-    }
-    return overlap_setup(h, h->halo.send_cols);
-}
-
-gcsadmm_status gcsadmm_halo_pack(gcsadmm_handle h, const gcsadmm_state *st, void *stream)
-{
-    if (!state_ok(h, st) || !h->halo.attached()) { if (h) h->err = "no halo attached"; return GCSADMM_ERR_BAD_ARG; }
-    USE_DEVICE(h);
-    return with_state(h, [&](auto t) { return halo_pack<decltype(t)>(h, st, (hipStream_t)stream); });
-}
-gcsadmm_status gcsadmm_halo_unpack(gcsadmm_handle h, const gcsadmm_state *st, void *stream)
-{
-    if (!state_ok(h, st) || !h->halo.attached()) { if (h) h->err = "no halo attached"; return GCSADMM_ERR_BAD_ARG; }
-    USE_DEVICE(h);
-    return with_state(h, [&](auto t) { return halo_unpack<decltype(t)>(h, st, (hipStream_t)stream); });
-}
-gcsadmm_status gcsadmm_halo_buffers(gcsadmm_handle h, void **send_buf, void **recv_buf, int64_t *num_elements)
-{
-    if (!h || !h->halo.attached()) { if (h) h->err = "no halo attached"; return GCSADMM_ERR_BAD_ARG; }
-    if (send_buf) *send_buf = h->halo.d_sendbuf.get();
-    if (recv_buf) *recv_buf = h->halo.d_recvbuf.get();
-    if (num_elements) *num_elements = (int64_t)h->c * h->halo.n_send;
-    return GCSADMM_OK;
-}
-
-gcsadmm_status gcsadmm_halo_exchange(gcsadmm_handle h, const gcsadmm_state *st, void *stream)
-{
-    if (!state_ok(h, st) || !h->halo.attached()) { if (h) h->err = "no halo attached"; return GCSADMM_ERR_BAD_ARG; }
-    USE_DEVICE(h);
-    hipStream_t s = (hipStream_t)stream;
-    return with_state(h, [&](auto t) {
-        using T = decltype(t);
-        gcsadmm_status r;
-        if ((r = halo_pack<T>(h, st, s)) != GCSADMM_OK) return r;
-        if ((r = halo_transfer(h, s)) != GCSADMM_OK) return r;
-        return halo_unpack<T>(h, st, s);
-    });
 }
 
 // The end of an iteration of the partitioned loop, on the caller's stream: the edge step (sums + failure count, one launch), the
@@ -1030,7 +573,7 @@ gcsadmm_status gcsadmm_halo_exchange(gcsadmm_handle h, const gcsadmm_state *st, 
 static gcsadmm_status partitioned_tail(gcsadmm_handle h, const gcsadmm_state *st, double *trace_dev, hipStream_t s, const Event *ev)
 {
     double *sums6 = h->halo.d_sums6.get();
-    gcsadmm_status r = launch_edge(h, st, sums6, s, false, nullptr, true);
+    gcsadmm_status r = launch_edge(h, st, sums6, s, EdgeMode::Sums6);
     if (r != GCSADMM_OK) return r;
     if (ev) HIPCHK(h, hipEventRecord(ev[0].get(), s));
     const double *reduced = sums6;
@@ -1045,6 +588,15 @@ static gcsadmm_status partitioned_tail(gcsadmm_handle h, const gcsadmm_state *st
     return GCSADMM_OK;
 }
 
+// =================================================================================================
+// vertex partitions across GPUs (SURVEY.md section 8e): one handle per rank, RCCL over xGMI.
+// Per iteration, all on one stream with no host synchronisation:
+//   vertex step -> pack the cut edges' copies per neighbour -> grouped ncclSend / ncclRecv -> unpack into the ghost columns
+//   -> edge step on local + ghost columns -> ncclAllReduce(sum) of the five norms and the inner-failure count (6 doubles)
+//   -> control (every rank takes the same decision from the same numbers).
+// Both messages are latency-bound at every configuration of BASELINE.json (about 25 KB per boundary of the 100k lattice,
+// 48 bytes for the all-reduce).
+// =================================================================================================
 // one loop for gcsadmm_run_partitioned and its event-bracketed twin: ev != nullptr records 6 events per iteration on the stream
 // (before / after the vertex step, after the halo exchange, after the edge step, after the all-reduce, after the control step)
 static gcsadmm_status run_partitioned_loop(gcsadmm_handle h, const gcsadmm_state *st, int k, double *trace_dev, hipStream_t s, const Event *ev)
@@ -1067,10 +619,10 @@ static gcsadmm_status run_partitioned_loop(gcsadmm_handle h, const gcsadmm_state
             const bool reorder = ++h->vertex_steps % REORDER_EVERY == 0;
             HIPCHK(h, hipEventRecord(o.ev_boundary.get(), s));
             HIPCHK(h, hipStreamWaitEvent(sc, o.ev_boundary.get(), 0));
-            if ((r = launch_vertex(h, st, sc, 0, reorder)) != GCSADMM_OK) return r;
-            if ((r = gcsadmm_halo_exchange(h, st, (void *)sc)) != GCSADMM_OK) return r;
+            if ((r = launch_vertex(h, st, sc, VertexLaunch{0, reorder})) != GCSADMM_OK) return r;
+            if ((r = halo_exchange(h, st, sc)) != GCSADMM_OK) return r;
             HIPCHK(h, hipEventRecord(o.ev_halo.get(), sc));
-            if ((r = launch_vertex(h, st, s, 1, reorder)) != GCSADMM_OK) return r;
+            if ((r = launch_vertex(h, st, s, VertexLaunch{1, reorder})) != GCSADMM_OK) return r;
             HIPCHK(h, hipStreamWaitEvent(s, o.ev_halo.get(), 0));
             if ((r = partitioned_tail(h, st, trace_dev, s, nullptr)) != GCSADMM_OK) return r;
         }
@@ -1081,45 +633,281 @@ static gcsadmm_status run_partitioned_loop(gcsadmm_handle h, const gcsadmm_state
     }
     for (int i = 0; i < k; ++i) {
         if (ev) HIPCHK(h, hipEventRecord(ev[6 * i + 0].get(), s));
-        if ((r = gcsadmm_vertex_step(h, st, (void *)s)) != GCSADMM_OK) return r;
+        if ((r = launch_vertex(h, st, s)) != GCSADMM_OK) return r;
         if (ev) HIPCHK(h, hipEventRecord(ev[6 * i + 1].get(), s));
-        if ((r = gcsadmm_halo_exchange(h, st, (void *)s)) != GCSADMM_OK) return r;
+        if ((r = halo_exchange(h, st, s)) != GCSADMM_OK) return r;
         if (ev) HIPCHK(h, hipEventRecord(ev[6 * i + 2].get(), s));
         if ((r = partitioned_tail(h, st, trace_dev, s, ev ? ev + 6 * i + 3 : nullptr)) != GCSADMM_OK) return r;
     }
     return GCSADMM_OK;
 }
+// what both entry points of that loop refuse
+static gcsadmm_status need_partitioned(gcsadmm_handle h, bool args_ok)
+{
+    if (!args_ok) return GCSADMM_ERR_BAD_ARG;
+    if (!h->halo.attached()) h->err = "gcsadmm_attach_comm has not been called";
+    return bad_unless(h->halo.attached());
+}
+
+// Every entry point that takes a handle or a batch is one handle_entry / batch_entry (the argument checks, then the work under the
+// object's device), and none calls another: the loops and the shared checks are the helpers above.  Plain -- they never reach the
+// device -- are the two last_error calls, the two queries, set_fused_tail, halo_buffers and check_halo.
+extern "C" {
+
+const char *gcsadmm_last_error(gcsadmm_handle h) { return h ? h->err.c_str() : g_create_error.c_str(); }
+
+void gcsadmm_destroy(gcsadmm_handle h)
+{
+    if (!h) return;
+    DeviceGuard device_guard_(h->device);      // the owners release on the handle's device
+    batches_forget(h);
+    if (h->comm && rccl().ok()) (void)rccl().CommDestroy((ncclComm_t)h->comm);
+    delete h;
+}
+
+gcsadmm_status gcsadmm_create(const gcsadmm_graph_desc *g, gcsadmm_handle *out)
+{
+    if (out) *out = nullptr;
+    return entry(g_create_error, [&]() -> gcsadmm_status {
+        auto fail = [&](gcsadmm_status st, const std::string &msg) { g_create_error = msg; return st; };
+        std::string msg;
+        gcsadmm_status st;
+        if (!out) return fail(GCSADMM_ERR_BAD_ARG, "null descriptor or output pointer");
+        if ((st = check_graph_desc(g, msg)) != GCSADMM_OK) return fail(st, msg);
+        int ndev = 0;
+        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(GCSADMM_ERR_NO_DEVICE, "no HIP device");
+        if (g->device < 0 || g->device >= ndev) return fail(GCSADMM_ERR_BAD_ARG, "device ordinal out of range");
+        CreatePlan plan;
+        if ((st = make_create_plan(*g, plan, msg)) != GCSADMM_OK) return fail(st, msg);
+
+        const int V = g->num_vertices, E = g->num_edges, n = g->n, NIo = g->inc_ptr[V], MT = g->poly_ptr[V];
+        DeviceGuard device_guard_(g->device);      // (declared before the handle: whatever has been filled is released under the guard)
+        auto h = std::make_unique<gcsadmm_handle_s>();
+        h->n = n; h->V = V; h->E = E; h->NI = g->num_incidences; h->c = 2 * n + 1;
+        h->edge_major = g->edge_major_columns; h->src = g->src; h->dst = g->dst;
+        h->dtype = g->state_dtype; h->device = g->device;
+        h->plan = std::move(plan);
+        CreatePlan &p = h->plan;
+        auto bail = [&](hipError_t e, const char *what) { return fail(GCSADMM_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e)); };
+        hipError_t e;
+        if ((e = device_guard_.err) != hipSuccess) return bail(e, "hipSetDevice");
+#define UP(group, dst, src, cnt) if ((e = h->group.dst.upload(src, (size_t)(cnt))) != hipSuccess) return bail(e, "upload " #dst)
+        UP(g, d_inc_ptr, g->inc_ptr, V + 1);
+        UP(g, d_deg_in, p.deg_in.data(), V);
+        UP(g, d_inc_edge, g->inc_edge, NIo);
+        UP(g, d_poly_ptr, g->poly_ptr, V + 1);
+        UP(g, d_edge_inc_tail, g->edge_inc_tail, E);
+        UP(g, d_edge_inc_head, g->edge_inc_head, E);
+        UP(g, d_wave_slot_ptr, p.wave_slot_ptr.data(), p.wave_slot_ptr.size());
+        UP(g, d_wave_vtx, p.wave_vtx.data(), p.wave_vtx.size());
+        UP(g, d_special_vtx, p.special_vtx.data(), p.special_vtx.size());
+        UP(g, d_special_kind, p.special_kind.data(), p.special_kind.size());
+        UP(g, d_wg_vtx, p.wg_vtx.data(), p.wg_vtx.size());
+        if (!p.split_vtx.empty()) {
+            UP(g, d_split_vtx, p.split_vtx.data(), p.split_vtx.size());
+            UP(g, d_split_off, p.split_off.data(), p.split_off.size());
+            UP(g, d_split_ws, nullptr, p.split_doubles);
+        }
+        UP(g, d_poly_A, g->poly_A, (size_t)MT * n);
+        UP(g, d_poly_bc, p.bc.data(), MT);
+        UP(g, d_center, g->center, (size_t)V * n);
+        if (g->inc_counted) UP(g, d_inc_counted, g->inc_counted, g->num_incidences);
+        if (g->edge_counted) UP(g, d_edge_counted, g->edge_counted, E);
+        UP(loop, d_cb, nullptr, 1);
+        UP(loop, d_counters, nullptr, 2);
+        UP(loop, d_partials, nullptr, (size_t)p.edge_blocks * 5);
+        UP(loop, d_sums, nullptr, 5);
+        UP(loop, d_ticket, nullptr, 1);
+        if (p.n_term > 0) {       // region terminals: workspace, an auxiliary stream and the fork / join events
+            UP(term, d_term_ws, nullptr, p.term_ws_doubles);
+            UP(term, d_term_rec, nullptr, p.term_rec_doubles);
+            if ((e = create_owned(h->term.term_stream, hipStreamCreateWithFlags, hipStreamNonBlocking)) != hipSuccess) return bail(e, "hipStreamCreate");
+            if ((e = create_owned(h->term.ev_term_fork, hipEventCreateWithFlags, hipEventDisableTiming)) != hipSuccess) return bail(e, "hipEventCreate");
+            if ((e = create_owned(h->term.ev_term_join, hipEventCreateWithFlags, hipEventDisableTiming)) != hipSuccess) return bail(e, "hipEventCreate");
+        }
+        UP(g, d_warm_ptr, p.warm_ptr.data(), V + 1);
+        UP(g, d_warm, nullptr, p.warm_ptr[V]);
+        // slowest-first dispatch: only where a launch needs more than one round of the chip (small graphs run all at once)
+        const int n_waves = p.n_waves(), n_wg = h->n_wg();
+        h->iota.resize(std::max(std::max(n_waves, n_wg), 1));
+        for (size_t i = 0; i < h->iota.size(); ++i) h->iota[i] = (int)i;
+        if (p.wave_reorder) { UP(g, d_wave_iters, nullptr, n_waves); UP(g, d_wave_order, h->iota.data(), n_waves); }
+        if (p.wg_reorder) { UP(g, d_wg_iters, nullptr, n_wg); UP(g, d_wg_order, h->iota.data(), n_wg); }
+        UP(prox, d_prox_vtx, p.prox_vtx.data(), p.prox_vtx.size());
+        UP(prox, d_prox_counters, nullptr, 2);
+#undef UP
+        // the plan's arrays that only fed an upload (the three the halo checks and the overlap split read stay: wave_slot_ptr, wave_vtx,
+        // col_owned / col_vertex)
+        auto release = [](auto &v) { v.clear(); v.shrink_to_fit(); };
+        release(p.bc); release(p.deg_in); release(p.warm_ptr); release(p.prox_vtx); release(p.special_vtx); release(p.special_kind);
+        release(p.wg_vtx); release(p.split_vtx); release(p.split_off);
+        if (p.lds_bytes > 48 * 1024) {
+            e = with_state(h.get(), [&](auto t) { return set_lds_attr<2, decltype(t)>(p.all_m4, p.lds_bytes); });
+            if (e != hipSuccess) return bail(e, "hipFuncSetAttribute(MaxDynamicSharedMemorySize)");
+        }
+        if (p.wg_lds_bytes > 48 * 1024 && (e = p.wg_t512 ? gcsadmm_wg_set_lds_t512(h->n, h->dtype, p.wg_lds_bytes)
+                                                          : gcsadmm_wg_set_lds(h->n, h->dtype, p.wg_lds_bytes)) != hipSuccess)
+            return bail(e, "hipFuncSetAttribute(MaxDynamicSharedMemorySize, workgroup program)");
+        if (p.split_lds_bytes > 48 * 1024 && (e = gcsadmm_wg_set_split_lds(h->n, h->dtype, p.split_lds_bytes)) != hipSuccess)
+            return bail(e, "hipFuncSetAttribute(MaxDynamicSharedMemorySize, split workgroup program)");
+        *out = h.release();
+        return GCSADMM_OK;
+    });
+}
+
+gcsadmm_status gcsadmm_reset(gcsadmm_handle h, const gcsadmm_params *p, void *stream)
+{
+    return handle_entry(h, [&] {
+        if (!p) return GCSADMM_ERR_BAD_ARG;
+        if (!(p->rho > 0) || p->max_it < 1 || !(p->ipm_tol > 0) || p->ipm_max_iter < 1) { h->err = "bad parameter"; return GCSADMM_ERR_BAD_ARG; }
+        h->params = *p; h->params_set = true; ++h->resets;
+        return GCSADMM_OK;
+    }, [&] {
+        gcsadmm_control_block cb{};
+        cb.rho = p->rho; cb.mu_scale = 1.0; cb.it = 1; cb.status = GCSADMM_RUNNING;
+        hipStream_t s = (hipStream_t)stream;
+        HIPCHK(h, hipMemcpyAsync(h->loop.d_cb.get(), &cb, sizeof(cb), hipMemcpyHostToDevice, s));
+        HIPCHK(h, h->loop.d_counters.zero(s));
+        // a new run starts without warm-start records (runs from the same state are then identical, whatever ran before)
+        HIPCHK(h, h->g.d_warm.zero(s));
+        HIPCHK(h, h->term.d_term_rec.zero(s));
+        h->vertex_steps = 0;
+        const Overlap &o = h->overlap;
+        if (o.d_split_order) HIPCHK(h, hipMemcpyAsync(o.d_split_order.get(), o.d_split_ids.get(), sizeof(int) * o.d_split_order.size(), hipMemcpyDeviceToDevice, s));
+        for (const DevBuf<int> *order : {&h->g.d_wave_order, &h->g.d_wg_order})      // (h->iota outlives the copies)
+            if (*order) HIPCHK(h, hipMemcpyAsync(order->get(), h->iota.data(), sizeof(int) * order->size(), hipMemcpyHostToDevice, s));
+        HIPCHK(h, hipStreamSynchronize(s));   // cb is a stack object
+        return GCSADMM_OK;
+    });
+}
+
+gcsadmm_status gcsadmm_vertex_step(gcsadmm_handle h, const gcsadmm_state *st, void *stream)
+{
+    return handle_entry(h, [&] { return bad_unless(state_ok(h, st)); }, [&] { return launch_vertex(h, st, (hipStream_t)stream); });
+}
+
+gcsadmm_status gcsadmm_edge_step(gcsadmm_handle h, const gcsadmm_state *st, double *sums_dev, void *stream)
+{
+    return handle_entry(h, [&] { return bad_unless(state_ok(h, st) && sums_dev); },
+                        [&] { return launch_edge(h, st, sums_dev, (hipStream_t)stream, EdgeMode::Partials); });
+}
+
+gcsadmm_status gcsadmm_control(gcsadmm_handle h, const double *sums_dev, double *trace_dev, void *stream)
+{
+    return handle_entry(h, [&] { return bad_unless(sums_dev && h->params_set); }, [&] {
+        hipLaunchKernelGGL(control_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, h->loop.d_cb.get(), sums_dev, control_params(h), h->loop.d_counters.get(), trace_dev, false);
+        HIPCHK(h, hipGetLastError());
+        return GCSADMM_OK;
+    });
+}
+
+gcsadmm_status gcsadmm_run(gcsadmm_handle h, const gcsadmm_state *st, int32_t k, double *trace_dev, void *stream)
+{
+    return handle_entry(h, [&] { return bad_unless(state_ok(h, st) && k >= 0); }, [&] {
+        hipStream_t s = (hipStream_t)stream;
+        gcsadmm_status r = GCSADMM_OK;
+        if (h->fuses()) {      // small graphs: the last vertex workgroup runs the edge and control steps, one launch per iteration
+            const WgTailDesc tail = make_wg_tail(h, st, trace_dev);
+            for (int i = 0; i < k && r == GCSADMM_OK; ++i) r = launch_vertex(h, st, s, VertexLaunch{-1, false, &tail});
+            return r;
+        }
+        const EdgeMode mode = edge_mode_with_control(h);      // edge step and control step in one launch
+        for (int i = 0; i < k && r == GCSADMM_OK; ++i)
+            if ((r = launch_vertex(h, st, s)) == GCSADMM_OK) r = launch_edge(h, st, h->loop.d_sums.get(), s, mode, trace_dev);
+        return r;
+    });
+}
+
+gcsadmm_status gcsadmm_comm_unique_id(void *id128)
+{
+    return entry(g_create_error, [&] {
+        if (!id128) return GCSADMM_ERR_BAD_ARG;
+        if (!rccl().ok()) { g_create_error = rccl().err; return GCSADMM_ERR_HIP; }
+        static_assert(sizeof(ncclUniqueId) == 128, "ncclUniqueId is 128 bytes");
+        ncclUniqueId id;
+        if (rccl().GetUniqueId(&id) != ncclSuccess) { g_create_error = "ncclGetUniqueId failed"; return GCSADMM_ERR_HIP; }
+        std::memcpy(id128, &id, sizeof(id));
+        return GCSADMM_OK;
+    });
+}
+
+gcsadmm_status gcsadmm_check_halo(gcsadmm_handle h, int32_t rank, int32_t world, const gcsadmm_halo_desc *halo)
+{
+    return h ? check_halo_of(h, rank, world, halo) : GCSADMM_ERR_BAD_ARG;
+}
+
+gcsadmm_status gcsadmm_attach_comm(gcsadmm_handle h, int32_t rank, int32_t world, const void *id128, const gcsadmm_halo_desc *halo)
+{
+    // everything that can fail on this rank alone comes first: a rank must not return an error while its peers wait in the collective
+    return handle_entry(h, [&] {
+        const gcsadmm_status st = check_halo_of(h, rank, world, halo);
+        if (st != GCSADMM_OK) return st;
+        if (id128 && !rccl().ok()) { h->err = rccl().err; return GCSADMM_ERR_HIP; }
+        return GCSADMM_OK;
+    }, [&] {
+        h->rank = rank; h->world = world;
+        const gcsadmm_status st = halo_upload(h, halo);
+        if (st != GCSADMM_OK) { h->halo = {}; return st; }
+        if (id128) {      // id128 == NULL: no communicator (the host moves the packed buffers itself; gcsadmm_run_partitioned needs one)
+            ncclUniqueId id;
+            std::memcpy(&id, id128, sizeof(id));
+            ncclComm_t comm = nullptr;
+            const ncclResult_t r = rccl().CommInitRank(&comm, world, id, rank);
+            if (r != ncclSuccess) {      // not attached: the handle can be attached again
+                h->err = std::string("ncclCommInitRank: ") + rccl().text(r);
+                h->halo = {};
+                return GCSADMM_ERR_HIP;
+            }
+            h->comm = comm;
+        }
+        return overlap_setup(h);
+    });
+}
+
+gcsadmm_status gcsadmm_halo_pack(gcsadmm_handle h, const gcsadmm_state *st, void *stream)
+{
+    return handle_entry(h, [&] { return bad_unless(need_halo(h, st)); },
+                        [&] { return with_state(h, [&](auto t) { return halo_pack<decltype(t)>(h, st, (hipStream_t)stream); }); });
+}
+gcsadmm_status gcsadmm_halo_unpack(gcsadmm_handle h, const gcsadmm_state *st, void *stream)
+{
+    return handle_entry(h, [&] { return bad_unless(need_halo(h, st)); },
+                        [&] { return with_state(h, [&](auto t) { return halo_unpack<decltype(t)>(h, st, (hipStream_t)stream); }); });
+}
+gcsadmm_status gcsadmm_halo_buffers(gcsadmm_handle h, void **send_buf, void **recv_buf, int64_t *num_elements)
+{
+    if (!h || !h->halo.attached()) { if (h) h->err = "no halo attached"; return GCSADMM_ERR_BAD_ARG; }
+    if (send_buf) *send_buf = h->halo.d_sendbuf.get();
+    if (recv_buf) *recv_buf = h->halo.d_recvbuf.get();
+    if (num_elements) *num_elements = (int64_t)h->c * h->halo.n_send;
+    return GCSADMM_OK;
+}
+
+gcsadmm_status gcsadmm_halo_exchange(gcsadmm_handle h, const gcsadmm_state *st, void *stream)
+{
+    return handle_entry(h, [&] { return bad_unless(need_halo(h, st)); }, [&] { return halo_exchange(h, st, (hipStream_t)stream); });
+}
 
 gcsadmm_status gcsadmm_run_partitioned(gcsadmm_handle h, const gcsadmm_state *st, int32_t k, double *trace_dev, void *stream)
 {
-    if (!state_ok(h, st) || k < 0) return GCSADMM_ERR_BAD_ARG;
-    if (!h->halo.attached()) { h->err = "gcsadmm_attach_comm has not been called"; return GCSADMM_ERR_BAD_ARG; }
-    USE_DEVICE(h);
-    return run_partitioned_loop(h, st, k, trace_dev, (hipStream_t)stream, nullptr);
+    return handle_entry(h, [&] { return need_partitioned(h, state_ok(h, st) && k >= 0); },
+                        [&] { return run_partitioned_loop(h, st, k, trace_dev, (hipStream_t)stream, nullptr); });
 }
 
 gcsadmm_status gcsadmm_run_partitioned_timed(gcsadmm_handle h, const gcsadmm_state *st, int32_t k, double *trace_dev, void *stream,
                                              float *vertex_ms, float *halo_ms, float *edge_ms, float *reduce_ms)
 {
-    if (!state_ok(h, st) || k < 0 || !vertex_ms || !halo_ms || !edge_ms || !reduce_ms) return GCSADMM_ERR_BAD_ARG;
-    if (!h->halo.attached()) { h->err = "gcsadmm_attach_comm has not been called"; return GCSADMM_ERR_BAD_ARG; }
-    USE_DEVICE(h);
-    hipStream_t s = (hipStream_t)stream;
-    gcsadmm_status r = ensure_events(h, (size_t)6 * k);
-    if (r != GCSADMM_OK) return r;
-    const std::vector<Event> &ev = h->events;
-    if ((r = run_partitioned_loop(h, st, k, trace_dev, s, ev.data())) != GCSADMM_OK) return r;
-    HIPCHK(h, hipStreamSynchronize(s));
-    double acc[4] = {0, 0, 0, 0};
-    for (int i = 0; i < k; ++i) {
-        float t = 0;
-        HIPCHK(h, hipEventElapsedTime(&t, ev[6 * i + 0].get(), ev[6 * i + 1].get())); acc[0] += t;
-        HIPCHK(h, hipEventElapsedTime(&t, ev[6 * i + 1].get(), ev[6 * i + 2].get())); acc[1] += t;
-        HIPCHK(h, hipEventElapsedTime(&t, ev[6 * i + 2].get(), ev[6 * i + 3].get())); acc[2] += t;
-        HIPCHK(h, hipEventElapsedTime(&t, ev[6 * i + 3].get(), ev[6 * i + 5].get())); acc[3] += t;
-    }
-    *vertex_ms = (float)acc[0]; *halo_ms = (float)acc[1]; *edge_ms = (float)acc[2]; *reduce_ms = (float)acc[3];
-    return GCSADMM_OK;
+    return handle_entry(h, [&] { return need_partitioned(h, state_ok(h, st) && k >= 0 && vertex_ms && halo_ms && edge_ms && reduce_ms); }, [&] {
+        hipStream_t s = (hipStream_t)stream;
+        gcsadmm_status r = ensure_events(h, (size_t)6 * k);
+        if (r == GCSADMM_OK) r = run_partitioned_loop(h, st, k, trace_dev, s, h->events.data());
+        if (r != GCSADMM_OK) return r;
+        HIPCHK(h, hipStreamSynchronize(s));
+        float *const out[4] = {vertex_ms, halo_ms, edge_ms, reduce_ms};
+        const int from[4] = {0, 1, 2, 3}, to[4] = {1, 2, 3, 5};
+        for (int q = 0; q < 4 && r == GCSADMM_OK; ++q) r = elapsed_sum(h, 6, k, from[q], to[q], out[q]);
+        return r;
+    });
 }
 
 int32_t gcsadmm_set_fused_tail(gcsadmm_handle h, int32_t mode)
@@ -1131,104 +919,104 @@ int32_t gcsadmm_set_fused_tail(gcsadmm_handle h, int32_t mode)
 
 gcsadmm_status gcsadmm_set_overlap(gcsadmm_handle h, int32_t mode, int32_t *boundary_units)
 {
-    if (!h || mode < 0 || mode > 2) return GCSADMM_ERR_BAD_ARG;
-    if (boundary_units) *boundary_units = 0;
-    if (!h->halo.attached()) { h->err = "gcsadmm_attach_comm has not been called"; return GCSADMM_ERR_BAD_ARG; }
-    USE_DEVICE(h);
-    h->overlap_mode = mode;
-    const gcsadmm_status r = overlap_setup(h, h->halo.send_cols);      // the split is derived from the send list validated at attach
-    if (boundary_units) *boundary_units = h->overlap.n_wave_b;
-    return r;
+    return handle_entry(h, [&] {
+        if (mode < 0 || mode > 2) return GCSADMM_ERR_BAD_ARG;
+        if (boundary_units) *boundary_units = 0;
+        return need_partitioned(h, true);
+    }, [&] {
+        h->overlap_mode = mode;
+        const gcsadmm_status r = overlap_setup(h);
+        if (boundary_units) *boundary_units = h->overlap.n_wave_b;
+        return r;
+    });
 }
 
 gcsadmm_status gcsadmm_comm_count(gcsadmm_handle h, int32_t *count)
 {
-    if (!h || !count) return GCSADMM_ERR_BAD_ARG;
-    *count = 0;
-    if (!h->comm) return GCSADMM_OK;        // no communicator attached (single handle, or a host-side transport)
-    if (!rccl().CommCount) { h->err = "librccl lacks ncclCommCount"; return GCSADMM_ERR_HIP; }
-    USE_DEVICE(h);
-    int n = 0;
-    NCCLCHK(h, rccl().CommCount((ncclComm_t)h->comm, &n));
-    *count = n;
-    return GCSADMM_OK;
+    return handle_entry(h, [&] {
+        if (!count) return GCSADMM_ERR_BAD_ARG;
+        *count = 0;        // (stays 0 without a communicator: a single handle, or a host-side transport)
+        if (h->comm && !rccl().CommCount) { h->err = "librccl lacks ncclCommCount"; return GCSADMM_ERR_HIP; }
+        return GCSADMM_OK;
+    }, [&] {
+        int n = 0;
+        if (h->comm) NCCLCHK(h, rccl().CommCount((ncclComm_t)h->comm, &n));
+        *count = n;
+        return GCSADMM_OK;
+    });
 }
 
 gcsadmm_status gcsadmm_vertex_prox(gcsadmm_handle h, const double *q_dev, const double *c_dev, double *xv_dev, double *zv_dev,
                                    double *yv_dev, double ipm_tol, int32_t ipm_max_iter, int32_t *failures_host, void *stream)
 {
-    if (!h || !q_dev || !c_dev || !xv_dev || !zv_dev || !yv_dev || !(ipm_tol > 0) || ipm_max_iter < 1) { if (h) h->err = "bad prox argument"; return GCSADMM_ERR_BAD_ARG; }
-    if (h->plan.prox_lds_bytes > 160 * 1024) { h->err = "facet count too large for LDS"; return GCSADMM_ERR_UNSUPPORTED; }
-    if (h->plan.n_term > 0) { h->err = "the prox kernel (v1 x-update) takes its terminals as points; this graph has a terminal that is a region"; return GCSADMM_ERR_UNSUPPORTED; }
-    USE_DEVICE(h);
-    hipStream_t s = (hipStream_t)stream;
-    const auto &g = h->g;
-    HIPCHK(h, h->prox.d_prox_counters.zero(s));
-    WgLaunchDesc d{};
-    d.n = h->n; d.dtype = GCSADMM_F64; d.n_vtx = (int)h->prox.d_prox_vtx.size(); d.lds_bytes = h->plan.prox_lds_bytes; d.vtx = h->prox.d_prox_vtx.get();
-    StepDesc &p = d.step;     // the ADMM state, the edge tolerance and the warm start stay unset: the PROX solve reads none of them
-    p.inc_ptr = g.d_inc_ptr.get(); p.deg_in = g.d_deg_in.get(); p.inc_edge = g.d_inc_edge.get(); p.poly_ptr = g.d_poly_ptr.get();
-    p.poly_A = g.d_poly_A.get(); p.poly_bc = g.d_poly_bc.get(); p.center = g.d_center.get();
-    p.xv = xv_dev; p.zv = zv_dev; p.yv = yv_dev; p.counters = h->prox.d_prox_counters.get(); p.ipm_tol = ipm_tol; p.ipm_max_iter = ipm_max_iter;
-    gcsadmm_wg_launch_prox(d, q_dev, c_dev, h->src, h->dst, s);
-    HIPCHK(h, hipGetLastError());
-    if (failures_host) {      // optional: synchronises the stream
-        int cnt[2] = {0, 0};
-        HIPCHK(h, hipMemcpyAsync(cnt, h->prox.d_prox_counters.get(), sizeof(cnt), hipMemcpyDeviceToHost, s));
-        HIPCHK(h, hipStreamSynchronize(s));
-        *failures_host = cnt[0];
-    }
-    return GCSADMM_OK;
+    return handle_entry(h, [&] {
+        if (!q_dev || !c_dev || !xv_dev || !zv_dev || !yv_dev || !(ipm_tol > 0) || ipm_max_iter < 1) { h->err = "bad prox argument"; return GCSADMM_ERR_BAD_ARG; }
+        if (h->plan.prox_lds_bytes > 160 * 1024) { h->err = "facet count too large for LDS"; return GCSADMM_ERR_UNSUPPORTED; }
+        if (h->plan.n_term > 0) { h->err = "the prox kernel (v1 x-update) takes its terminals as points; this graph has a terminal that is a region"; return GCSADMM_ERR_UNSUPPORTED; }
+        return GCSADMM_OK;
+    }, [&] {
+        hipStream_t s = (hipStream_t)stream;
+        HIPCHK(h, h->prox.d_prox_counters.zero(s));
+        WgLaunchDesc d{};
+        d.n = h->n; d.dtype = GCSADMM_F64; d.n_vtx = (int)h->prox.d_prox_vtx.size(); d.lds_bytes = h->plan.prox_lds_bytes; d.vtx = h->prox.d_prox_vtx.get();
+        StepDesc &p = d.step = make_step_graph(h);     // the ADMM state, the edge tolerance and the warm start stay unset: the PROX solve reads none of them
+        p.xv = xv_dev; p.zv = zv_dev; p.yv = yv_dev; p.counters = h->prox.d_prox_counters.get(); p.ipm_tol = ipm_tol; p.ipm_max_iter = ipm_max_iter;
+        gcsadmm_wg_launch_prox(d, q_dev, c_dev, h->src, h->dst, s);
+        HIPCHK(h, hipGetLastError());
+        if (failures_host) {      // optional: synchronises the stream
+            int cnt[2] = {0, 0};
+            HIPCHK(h, hipMemcpyAsync(cnt, h->prox.d_prox_counters.get(), sizeof(cnt), hipMemcpyDeviceToHost, s));
+            HIPCHK(h, hipStreamSynchronize(s));
+            *failures_host = cnt[0];
+        }
+        return GCSADMM_OK;
+    });
 }
 
 gcsadmm_status gcsadmm_run_timed(gcsadmm_handle h, const gcsadmm_state *st, int32_t k, double *trace_dev, void *stream,
                                  float *vertex_ms, int32_t *vertex_launches, float *edge_ms, int32_t *edge_launches)
 {
-    if (!state_ok(h, st) || k < 0 || !vertex_ms || !edge_ms || !vertex_launches || !edge_launches) return GCSADMM_ERR_BAD_ARG;
-    USE_DEVICE(h);
-    hipStream_t s = (hipStream_t)stream;
-    gcsadmm_status r = ensure_events(h, (size_t)4 * k);
-    if (r != GCSADMM_OK) return r;
-    const std::vector<Event> &ev = h->events;
-    for (int i = 0; i < k; ++i) {
-        HIPCHK(h, hipEventRecord(ev[4 * i + 0].get(), s));
-        if ((r = gcsadmm_vertex_step(h, st, stream)) != GCSADMM_OK) return r;
-        HIPCHK(h, hipEventRecord(ev[4 * i + 1].get(), s));
-        HIPCHK(h, hipEventRecord(ev[4 * i + 2].get(), s));
-        if ((r = launch_edge(h, st, h->loop.d_sums.get(), s, true, trace_dev)) != GCSADMM_OK) return r;
-        HIPCHK(h, hipEventRecord(ev[4 * i + 3].get(), s));
-    }
-    HIPCHK(h, hipStreamSynchronize(s));
-    double vm = 0, em = 0;
-    for (int i = 0; i < k; ++i) {
-        float t = 0;
-        HIPCHK(h, hipEventElapsedTime(&t, ev[4 * i + 0].get(), ev[4 * i + 1].get())); vm += t;
-        HIPCHK(h, hipEventElapsedTime(&t, ev[4 * i + 2].get(), ev[4 * i + 3].get())); em += t;
-    }
-    *vertex_ms = (float)vm; *edge_ms = (float)em; *vertex_launches = k; *edge_launches = k;
-    return GCSADMM_OK;
+    return handle_entry(h, [&] { return bad_unless(state_ok(h, st) && k >= 0 && vertex_ms && edge_ms && vertex_launches && edge_launches); }, [&] {
+        hipStream_t s = (hipStream_t)stream;
+        gcsadmm_status r = ensure_events(h, (size_t)4 * k);
+        if (r != GCSADMM_OK) return r;
+        const std::vector<Event> &ev = h->events;
+        const EdgeMode mode = edge_mode_with_control(h);
+        for (int i = 0; i < k; ++i) {
+            HIPCHK(h, hipEventRecord(ev[4 * i + 0].get(), s));
+            if ((r = launch_vertex(h, st, s)) != GCSADMM_OK) return r;
+            HIPCHK(h, hipEventRecord(ev[4 * i + 1].get(), s));
+            HIPCHK(h, hipEventRecord(ev[4 * i + 2].get(), s));
+            if ((r = launch_edge(h, st, h->loop.d_sums.get(), s, mode, trace_dev)) != GCSADMM_OK) return r;
+            HIPCHK(h, hipEventRecord(ev[4 * i + 3].get(), s));
+        }
+        HIPCHK(h, hipStreamSynchronize(s));
+        if ((r = elapsed_sum(h, 4, k, 0, 1, vertex_ms)) != GCSADMM_OK || (r = elapsed_sum(h, 4, k, 2, 3, edge_ms)) != GCSADMM_OK) return r;
+        *vertex_launches = k; *edge_launches = k;
+        return GCSADMM_OK;
+    });
 }
 
 gcsadmm_status gcsadmm_read_control(gcsadmm_handle h, gcsadmm_control_block *out, void *stream)
 {
-    if (!h || !out) return GCSADMM_ERR_BAD_ARG;
-    USE_DEVICE(h);
-    HIPCHK(h, hipMemcpyAsync(out, h->loop.d_cb.get(), sizeof(*out), hipMemcpyDeviceToHost, (hipStream_t)stream));
-    HIPCHK(h, hipStreamSynchronize((hipStream_t)stream));
-    return GCSADMM_OK;
+    return handle_entry(h, [&] { return bad_unless(out); }, [&] {
+        HIPCHK(h, hipMemcpyAsync(out, h->loop.d_cb.get(), sizeof(*out), hipMemcpyDeviceToHost, (hipStream_t)stream));
+        HIPCHK(h, hipStreamSynchronize((hipStream_t)stream));
+        return GCSADMM_OK;
+    });
 }
 
 gcsadmm_status gcsadmm_cost(gcsadmm_handle h, const gcsadmm_state *st, double eps_edge, double *cost_dev, void *stream)
 {
-    if (!h || !st || !st->zv || !st->zedge || !cost_dev) return GCSADMM_ERR_BAD_ARG;
-    USE_DEVICE(h);
-    with_state(h, [&](auto t) {
-        using T = decltype(t);
-        hipLaunchKernelGGL((cost_kernel<T>), dim3(1), dim3(256), 0, (hipStream_t)stream, h->V, h->E, h->n, st->zv,
-                           (const T *)st->zedge, h->g.d_edge_counted.get(), eps_edge, cost_dev);
+    return handle_entry(h, [&] { return bad_unless(st && st->zv && st->zedge && cost_dev); }, [&] {
+        with_state(h, [&](auto t) {
+            using T = decltype(t);
+            hipLaunchKernelGGL((cost_kernel<T>), dim3(1), dim3(256), 0, (hipStream_t)stream, h->V, h->E, h->n, st->zv,
+                               (const T *)st->zedge, h->g.d_edge_counted.get(), eps_edge, cost_dev);
+        });
+        HIPCHK(h, hipGetLastError());
+        return GCSADMM_OK;
     });
-    HIPCHK(h, hipGetLastError());
-    return GCSADMM_OK;
 }
 
 #ifdef GCS_PHASE_TIMING
@@ -1266,16 +1054,16 @@ gcsadmm_status gcsadmm_query_workspace(gcsadmm_handle h, int32_t *num_split_vert
 
 gcsadmm_status gcsadmm_unit_iterations(gcsadmm_handle h, int32_t *out, int32_t capacity, int32_t *count, void *stream)
 {
-    if (!h || !count) return GCSADMM_ERR_BAD_ARG;
-    USE_DEVICE(h);
-    const auto &g = h->g;
-    const int *src = g.d_wave_iters ? g.d_wave_iters.get() : g.d_wg_iters.get();
-    const int n = g.d_wave_iters ? h->plan.n_waves() : (g.d_wg_iters ? h->n_wg() : 0);
-    *count = n;
-    if (n == 0 || !out) return GCSADMM_OK;
-    HIPCHK(h, hipStreamSynchronize((hipStream_t)stream));
-    HIPCHK(h, hipMemcpy(out, src, sizeof(int) * (size_t)(n < capacity ? n : capacity), hipMemcpyDeviceToHost));
-    return GCSADMM_OK;
+    return handle_entry(h, [&] { return bad_unless(count); }, [&] {
+        const auto &g = h->g;
+        const int *src = g.d_wave_iters ? g.d_wave_iters.get() : g.d_wg_iters.get();
+        const int n = g.d_wave_iters ? h->plan.n_waves() : (g.d_wg_iters ? h->n_wg() : 0);
+        *count = n;
+        if (n == 0 || !out) return GCSADMM_OK;
+        HIPCHK(h, hipStreamSynchronize((hipStream_t)stream));
+        HIPCHK(h, hipMemcpy(out, src, sizeof(int) * (size_t)(n < capacity ? n : capacity), hipMemcpyDeviceToHost));
+        return GCSADMM_OK;
+    });
 }
 
 // =================================================================================================
@@ -1296,115 +1084,116 @@ void gcsadmm_batch_destroy(struct gcsadmm_batch_s *b)
 gcsadmm_status gcsadmm_batch_create(const gcsadmm_handle *members, int32_t count, struct gcsadmm_batch_s **out)
 {
     if (out) *out = nullptr;
-    auto fail = [&](gcsadmm_status st, const std::string &msg) { g_create_error = msg; return st; };
-    if (!out) return fail(GCSADMM_ERR_BAD_ARG, "null output pointer");
-    if (!members || count < 1) return fail(GCSADMM_ERR_BAD_ARG, "a batch needs at least one member");
-    auto b = std::unique_ptr<gcsadmm_batch_s>(new (std::nothrow) gcsadmm_batch_s);
-    if (!b) return fail(GCSADMM_ERR_HIP, "out of host memory");
-    b->members.assign(members, members + count);
-    std::string msg;
-    const gcsadmm_status st = batch_plan_of(b->members, b->plan, msg);
-    if (st != GCSADMM_OK) return fail(st, msg);
-    b->device = b->plan.device;
-    DeviceGuard device_guard_(b->device);
-    hipError_t e = device_guard_.err;
-    if (e == hipSuccess) e = b->d_vertex_table.alloc(gcsadmm_wg_batch_entry_bytes(b->plan.dtype) * (size_t)count);
-    if (e == hipSuccess) e = b->d_edge_table.alloc((b->plan.dtype == GCSADMM_F64 ? sizeof(EdgeBatchEntry<double>) : sizeof(EdgeBatchEntry<float>)) * (size_t)count);
-    if (e == hipSuccess) e = b->d_cbs.alloc((size_t)count);
-    if (e == hipSuccess) e = b->d_poll.upload(nullptr, 2 * (size_t)count);
-    if (e == hipSuccess && b->plan.vertex_lds_bytes > 48 * 1024) e = gcsadmm_wg_set_batch_lds(b->plan.n, b->plan.dtype, b->plan.vertex_lds_bytes);
-    if (e != hipSuccess) return fail(GCSADMM_ERR_HIP, std::string("gcsadmm_batch_create: ") + hipGetErrorString(e));      // (b is released under the guard)
-    b->poll_host.resize(2 * (size_t)count);
-    for (gcsadmm_handle h : b->members) h->batches.push_back(b.get());
-    *out = b.release();
-    return GCSADMM_OK;
+    return entry(g_create_error, [&]() -> gcsadmm_status {
+        auto fail = [&](gcsadmm_status st, const std::string &msg) { g_create_error = msg; return st; };
+        if (!out) return fail(GCSADMM_ERR_BAD_ARG, "null output pointer");
+        if (!members || count < 1) return fail(GCSADMM_ERR_BAD_ARG, "a batch needs at least one member");
+        auto b = std::make_unique<gcsadmm_batch_s>();
+        b->members.assign(members, members + count);
+        std::string msg;
+        const gcsadmm_status st = batch_plan_of(b->members, b->plan, msg);
+        if (st != GCSADMM_OK) return fail(st, msg);
+        const BatchPlan &plan = b->plan;
+        b->device = plan.device;
+        DeviceGuard device_guard_(b->device);
+        hipError_t e = device_guard_.err;
+        if (e == hipSuccess) e = b->d_vertex_table.alloc(gcsadmm_wg_batch_entry_bytes(plan.dtype) * (size_t)count);
+        if (e == hipSuccess) e = b->d_edge_table.alloc((plan.dtype == GCSADMM_F64 ? sizeof(EdgeBatchEntry<double>) : sizeof(EdgeBatchEntry<float>)) * (size_t)count);
+        if (e == hipSuccess) e = b->d_cbs.alloc((size_t)count);
+        if (e == hipSuccess) e = b->d_poll.upload(nullptr, 2 * (size_t)count);
+        if (e == hipSuccess && plan.vertex_lds_bytes > 48 * 1024) e = gcsadmm_wg_set_batch_lds(plan.n, plan.dtype, plan.vertex_lds_bytes);
+        if (e != hipSuccess) return fail(GCSADMM_ERR_HIP, std::string("gcsadmm_batch_create: ") + hipGetErrorString(e));
+        b->poll_host.resize(2 * (size_t)count);
+        for (gcsadmm_handle h : b->members) h->batches.reserve(h->batches.size() + 1);      // (a push that failed half way would leave members listing a batch that is gone)
+        for (gcsadmm_handle h : b->members) h->batches.push_back(b.get());
+        *out = b.release();
+        return GCSADMM_OK;
+    });
 }
 
 gcsadmm_status gcsadmm_batch_bind(struct gcsadmm_batch_s *b, const gcsadmm_state *states, double *const *traces_dev, void *stream)
 {
-    if (!b) return GCSADMM_ERR_BAD_ARG;
-    if (!states) { b->err = "null state array"; return GCSADMM_ERR_BAD_ARG; }
-    const int count = (int)b->members.size();
-    // the members may have changed since create (a communicator attached): the rules again, then what only a bind can check
-    BatchPlan bp;
-    gcsadmm_status st = batch_plan_of(b->members, bp, b->err);
-    if (st != GCSADMM_OK) return st;
-    for (int i = 0; i < count; ++i) {
-        gcsadmm_handle h = b->members[i];
-        const std::string who = "member " + std::to_string(i) + ": ";
-        if (!state_ok(h, &states[i])) { b->err = who + h->err; return GCSADMM_ERR_BAD_ARG; }
-        if (h->batch && h->batch != b) { b->err = who + "the handle is bound to another batch (destroy that batch, or bind it to other states, first)"; return GCSADMM_ERR_BAD_ARG; }
-    }
-    DeviceGuard device_guard_(b->device);
-    HIPCHK(b, device_guard_.err);
-    hipStream_t s = (hipStream_t)stream;
-    HIPCHK(b, hipStreamSynchronize(s));      // launches of an earlier bind may still read the tables
-    batch_unbind(b);
-    b->plan = bp;
-    const size_t vbytes = gcsadmm_wg_batch_entry_bytes(bp.dtype);
-    std::vector<char> vtab(vbytes * (size_t)count);
-    std::vector<const gcsadmm_control_block *> cbs((size_t)count);
-    b->resets.assign((size_t)count, 0u);
-    for (int i = 0; i < count; ++i) {
-        gcsadmm_handle h = b->members[i];
-        gcsadmm_wg_batch_fill(make_wg_desc(h, &states[i], true), vtab.data() + vbytes * (size_t)i);
-        cbs[i] = h->loop.d_cb.get();
-        b->resets[i] = h->resets;
-    }
-    HIPCHK(b, hipMemcpy(b->d_vertex_table.get(), vtab.data(), vtab.size(), hipMemcpyHostToDevice));
-    HIPCHK(b, hipMemcpy(b->d_cbs.get(), cbs.data(), sizeof(cbs[0]) * cbs.size(), hipMemcpyHostToDevice));
-    const gcsadmm_status est = with_state_type(bp.dtype == GCSADMM_F64, [&](auto t) -> gcsadmm_status {
-        using T = decltype(t);
-        std::vector<EdgeBatchEntry<T>> etab((size_t)count);
+    BatchPlan bp;      // (made by the checks, taken by the work)
+    return batch_entry(b, [&] {
+        if (!states) { b->err = "null state array"; return GCSADMM_ERR_BAD_ARG; }
+        // the members may have changed since create (a communicator attached): the rules again, then what only a bind can check
+        const gcsadmm_status st = batch_plan_of(b->members, bp, b->err);
+        if (st != GCSADMM_OK) return st;
+        for (int i = 0; i < (int)b->members.size(); ++i) {
+            gcsadmm_handle h = b->members[i];
+            const std::string who = "member " + std::to_string(i) + ": ";
+            if (!state_ok(h, &states[i])) { b->err = who + h->err; return GCSADMM_ERR_BAD_ARG; }
+            if (h->batch && h->batch != b) { b->err = who + "the handle is bound to another batch (destroy that batch, or bind it to other states, first)"; return GCSADMM_ERR_BAD_ARG; }
+        }
+        return GCSADMM_OK;
+    }, [&] {
+        const int count = (int)b->members.size();
+        HIPCHK(b, hipStreamSynchronize((hipStream_t)stream));      // launches of an earlier bind may still read the tables
+        batch_unbind(b);
+        b->plan = bp;
+        const size_t vbytes = gcsadmm_wg_batch_entry_bytes(bp.dtype);
+        std::vector<char> vtab(vbytes * (size_t)count);
+        std::vector<const gcsadmm_control_block *> cbs((size_t)count);
+        b->resets.assign((size_t)count, 0u);
         for (int i = 0; i < count; ++i) {
             gcsadmm_handle h = b->members[i];
-            etab[i] = EdgeBatchEntry<T>{make_edge_args<T>(h, &states[i]), h->loop.d_cb.get(), h->loop.d_sums.get(), control_params(h), h->loop.d_counters.get(),
-                                        traces_dev ? traces_dev[i] : nullptr, h->loop.d_ticket.get(), h->plan.edge_blocks};
+            gcsadmm_wg_batch_fill(make_wg_desc(h, &states[i], true), vtab.data() + vbytes * (size_t)i);
+            cbs[i] = h->loop.d_cb.get();
+            b->resets[i] = h->resets;
         }
-        HIPCHK(b, hipMemcpy(b->d_edge_table.get(), etab.data(), sizeof(etab[0]) * etab.size(), hipMemcpyHostToDevice));
+        HIPCHK(b, hipMemcpy(b->d_vertex_table.get(), vtab.data(), vtab.size(), hipMemcpyHostToDevice));
+        HIPCHK(b, hipMemcpy(b->d_cbs.get(), cbs.data(), sizeof(cbs[0]) * cbs.size(), hipMemcpyHostToDevice));
+        const gcsadmm_status est = with_state_type(bp.dtype == GCSADMM_F64, [&](auto t) -> gcsadmm_status {
+            using T = decltype(t);
+            std::vector<EdgeBatchEntry<T>> etab((size_t)count);
+            for (int i = 0; i < count; ++i) {
+                gcsadmm_handle h = b->members[i];
+                etab[i] = EdgeBatchEntry<T>{make_edge_args<T>(h, &states[i]), h->loop.d_cb.get(), h->loop.d_sums.get(), control_params(h), h->loop.d_counters.get(),
+                                            traces_dev ? traces_dev[i] : nullptr, h->loop.d_ticket.get(), h->plan.edge_blocks};
+            }
+            HIPCHK(b, hipMemcpy(b->d_edge_table.get(), etab.data(), sizeof(etab[0]) * etab.size(), hipMemcpyHostToDevice));
+            return GCSADMM_OK;
+        });
+        if (est != GCSADMM_OK) return est;
+        for (gcsadmm_handle h : b->members) h->batch = b;
+        b->bound = true;
         return GCSADMM_OK;
     });
-    if (est != GCSADMM_OK) return est;
-    for (gcsadmm_handle h : b->members) h->batch = b;
-    b->bound = true;
-    return GCSADMM_OK;
 }
 
 gcsadmm_status gcsadmm_batch_run(struct gcsadmm_batch_s *b, int32_t k, void *stream)
 {
-    if (!b || k < 0) return GCSADMM_ERR_BAD_ARG;
-    if (!b->bound) { b->err = "gcsadmm_batch_bind has not been called"; return GCSADMM_ERR_BAD_ARG; }
-    for (size_t i = 0; i < b->members.size(); ++i)      // (bound: every member is alive and bound to this batch)
-        if (b->members[i]->resets != b->resets[i]) {
-            b->err = "member " + std::to_string(i) + ": gcsadmm_reset was called after gcsadmm_batch_bind (bind again: the tables hold the parameters)";
-            return GCSADMM_ERR_BAD_ARG;
-        }
-    DeviceGuard device_guard_(b->device);
-    HIPCHK(b, device_guard_.err);
-    for (int i = 0; i < k; ++i) {
-        const gcsadmm_status st = launch_batch_iteration(b, (hipStream_t)stream);
-        if (st != GCSADMM_OK) return st;
-    }
-    return GCSADMM_OK;
+    return batch_entry(b, [&] {
+        if (k < 0) return GCSADMM_ERR_BAD_ARG;
+        if (need_bound(b) != GCSADMM_OK) return GCSADMM_ERR_BAD_ARG;
+        for (size_t i = 0; i < b->members.size(); ++i)      // (bound: every member is alive and bound to this batch)
+            if (b->members[i]->resets != b->resets[i]) {
+                b->err = "member " + std::to_string(i) + ": gcsadmm_reset was called after gcsadmm_batch_bind (bind again: the tables hold the parameters)";
+                return GCSADMM_ERR_BAD_ARG;
+            }
+        return GCSADMM_OK;
+    }, [&] {
+        gcsadmm_status st = GCSADMM_OK;
+        for (int i = 0; i < k && st == GCSADMM_OK; ++i) st = launch_batch_iteration(b, (hipStream_t)stream);
+        return st;
+    });
 }
 
 gcsadmm_status gcsadmm_batch_poll(struct gcsadmm_batch_s *b, int32_t *status, int32_t *it, void *stream)
 {
-    if (!b) return GCSADMM_ERR_BAD_ARG;
-    if (!b->bound) { b->err = "gcsadmm_batch_bind has not been called"; return GCSADMM_ERR_BAD_ARG; }
-    DeviceGuard device_guard_(b->device);
-    HIPCHK(b, device_guard_.err);
-    hipStream_t s = (hipStream_t)stream;
-    const int count = (int)b->members.size();
-    hipLaunchKernelGGL(batch_poll_kernel, dim3((count + 255) / 256), dim3(256), 0, s, b->d_cbs.get(), count, b->d_poll.get());
-    HIPCHK(b, hipGetLastError());
-    HIPCHK(b, hipMemcpyAsync(b->poll_host.data(), b->d_poll.get(), sizeof(int) * 2 * (size_t)count, hipMemcpyDeviceToHost, s));
-    HIPCHK(b, hipStreamSynchronize(s));
-    for (int i = 0; i < count; ++i) {
-        if (status) status[i] = b->poll_host[i];
-        if (it) it[i] = b->poll_host[count + i];
-    }
-    return GCSADMM_OK;
+    return batch_entry(b, [&] { return need_bound(b); }, [&] {
+        hipStream_t s = (hipStream_t)stream;
+        const int count = (int)b->members.size();
+        hipLaunchKernelGGL(batch_poll_kernel, dim3((count + 255) / 256), dim3(256), 0, s, b->d_cbs.get(), count, b->d_poll.get());
+        HIPCHK(b, hipGetLastError());
+        HIPCHK(b, hipMemcpyAsync(b->poll_host.data(), b->d_poll.get(), sizeof(int) * 2 * (size_t)count, hipMemcpyDeviceToHost, s));
+        HIPCHK(b, hipStreamSynchronize(s));
+        for (int i = 0; i < count; ++i) {
+            if (status) status[i] = b->poll_host[i];
+            if (it) it[i] = b->poll_host[count + i];
+        }
+        return GCSADMM_OK;
+    });
 }
 
 } // extern "C"

@@ -1,6 +1,6 @@
 // step_args.h -- the inputs every vertex-step program reads: the wavefront program (vertex_program.inc), the workgroup program
 // (vertex_wg.h), the closed-form vertices (special_vertex.h) and the region terminals (terminal_region.h).  Their argument
-// structs derive from StepArgs<T>; the host fills the untyped StepDesc once per launch (gcsadmm.hip make_step).
+// structs derive from StepArgs<T>; the host fills the untyped StepDesc once per launch (gcsadmm.hip make_step_graph / make_step).
 // Host-compilable (the emulations in tests/hostemu and tools/flopcount include it): no hip_runtime.h.
 #pragma once
 #include <type_traits>

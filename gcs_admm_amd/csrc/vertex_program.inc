@@ -1341,7 +1341,7 @@ struct ControlView {   // the fields of gcsadmm_control_block the kernels read
 // First lane of a vertex group (1 border lane + d block lanes: d_in incoming, then d - d_in outgoing) placed at
 // or after lane `cur` of a wavefront.  With `align` the group is moved up until neither side segment straddles
 // a 16-lane row, so that the segmented reductions can use DPP row shifts; -1: does not fit into this wavefront.
-// The host packers (gcsadmm.hip, tests/hostemu/emu.cpp) and phase_setup share this rule.
+// The host packers (create_plan.h, tests/hostemu/emu.cpp) and phase_setup share this rule.
 GCS_HD int group_base(int cur, int d, int d_in, int align)
 {
     const int d_out = d - d_in;
@@ -1360,7 +1360,7 @@ template <class T> struct VertexArgs : gcsadmm_k::StepArgs<T> {
     const int *wave_slot_ptr;   // [n_waves+1] into wave_vtx
     const int *wave_vtx;        // vertex ids, grouped per wave
     int MM;
-    // slowest-first dispatch (gcsadmm.hip reorder_kernel): workgroup b of the launch runs wavefront wave_order[b]; every wavefront
+    // slowest-first dispatch (loop_kernels.h reorder_kernel): workgroup b of the launch runs wavefront wave_order[b]; every wavefront
     // leaves the number of Newton iterations it ran in wave_iters (both may be null: identity order, nothing recorded)
     const int *wave_order = nullptr;
     int *wave_iters = nullptr;

@@ -267,7 +267,7 @@ template <class T> struct WgArgs : gcsadmm_k::StepArgs<T> {
     // no edge blocks; a separable quadratic 1/2 sum_k q_k (u_k - c_k)^2 on the border unknowns u = (x_v, z_v, y_v) instead of
     // the consensus penalty.  [V][4n+1] each, order x (2n), z (2n), y; nullptr = the ADMM vertex step of the v3 solver.
     const double *prox_q = nullptr, *prox_c = nullptr;
-    // slowest-first dispatch (gcsadmm.hip reorder_kernel): workgroup b of the launch solves vtx[order[b]] and leaves its Newton
+    // slowest-first dispatch (loop_kernels.h reorder_kernel): workgroup b of the launch solves vtx[order[b]] and leaves its Newton
     // iteration count in unit_iters[order[b]] (both may be null: the static heaviest-first order of vtx, nothing recorded)
     const int *order = nullptr;
     int *unit_iters = nullptr;

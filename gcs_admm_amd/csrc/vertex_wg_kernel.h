@@ -241,10 +241,7 @@ template <class T> gcs_wg::WgArgs<T> in_lds_args(const WgLaunchDesc &d)
 // the typed tail of an in-LDS launch (its last kernel argument)
 template <class T> WgTail<T> in_lds_tail(const WgTailDesc &d)
 {
-    const EdgeArgs<void> &e = d.edge;
-    return WgTail<T>{d.enabled,
-                     EdgeArgs<T>{e.E, e.NI, e.c, e.edge_inc_tail, e.edge_inc_head, e.inc_counted, e.edge_counted, (const T *)e.copy, (T *)e.zedge, (T *)e.mu, e.partials},
-                     d.cb, d.sums, d.cp, d.counters, d.trace, d.ticket};
+    return WgTail<T>{d.enabled, retype<T>(d.edge), d.cb, d.sums, d.cp, d.counters, d.trace, d.ticket};
 }
 
 template <int N> void launch(const WgLaunchDesc &d, hipStream_t s)

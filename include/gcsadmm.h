@@ -48,7 +48,7 @@ typedef enum gcsadmm_status {
                                        region without an edge on its live side, or source and target the same region */
     GCSADMM_ERR_HIP = 3,            /* a HIP runtime call failed */
     GCSADMM_ERR_NO_DEVICE = 4,
-    GCSADMM_ERR_NO_MEMORY = 5       /* a host allocation failed (gcsadmm_scene_*) */
+    GCSADMM_ERR_NO_MEMORY = 5       /* a host allocation failed ("out of host memory"); never an exception across the ABI */
 } gcsadmm_status;
 
 enum { GCSADMM_F64 = 0, GCSADMM_F32 = 1 };

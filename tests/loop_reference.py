@@ -5,7 +5,7 @@ stop test, trace record: admm_solver_v3.py:697-733) and the cost of the last ite
 repository's array layout: ``copy`` / ``mu`` are [c, NI], ``zedge`` is [c, E], c = 2n + 1 coupled words per copy, column
 ``tail[e]`` / ``head[e]`` of edge e.  No oracle, no torch: tests/test_loop_reference.py holds this file and the C oracle against
 each other on the CPU, tests/test_gpu_edge_control.py holds edge_kernel (every launch mode), finalize_kernel, control_body and
-cost_kernel of csrc/gcsadmm.hip to it.
+cost_kernel of csrc/loop_kernels.h to it.
 
 The bounds are derived, none is fitted to the code under test:
 

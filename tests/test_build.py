@@ -53,7 +53,7 @@ def _device_disassembly(tmp_path, obj_name):
 
 
 def test_edge_kernel_hands_its_partials_over_with_sc1(tmp_path):
-    """The last-workgroup hand-off of edge_kernel MODE 2 / 3 (csrc/gcsadmm.hip) is relaxed agent-scope atomics + `s_waitcnt
+    """The last-workgroup hand-off of edge_kernel MODE 2 / 3 (csrc/loop_kernels.h, in gcsadmm.o) is relaxed agent-scope atomics + `s_waitcnt
     vmcnt(0)` -- it relies on the partials being WRITE-THROUGH stores (sc1) that are drained before the ticket add, and on the last
     workgroup reading them with sc1 loads (visible across the XCDs' L2s).  That is a property of the generated code, so it is pinned
     here: in every MODE >= 2 instantiation, in program order: an sc1 store, a vmcnt(0) drain, the ticket's atomic add, sc1 loads."""
@@ -84,15 +84,17 @@ def test_edge_kernel_hands_its_partials_over_with_sc1(tmp_path):
 
 def test_every_launching_entry_point_selects_the_handles_device():
     """Entry points work on the handle's device whatever the caller's current device is (a process may hold handles on several
-    GPUs): every extern "C" function of csrc/gcsadmm.hip that touches the HIP runtime or launches a kernel does so under USE_DEVICE /
-    DeviceGuard, directly or by delegating at once to entry points that do."""
+    GPUs).  The structure holds that: every extern "C" function of csrc/gcsadmm.hip whose first parameter is a handle or a batch is one
+    `return handle_entry(h, args, body)` / `return batch_entry(b, args, body)` -- the shim runs `args` (argument checks, on the host), takes
+    the DeviceGuard and only then runs `body` -- unless it is on the named list of calls that never reach the device.  Neither those nor
+    an `args` lambda may spell any device work: the guard comes before the first device call, as the earlier form of this test held."""
     import os
     import re
     from gcs_admm_amd import build
     src = open(os.path.join(build.CSRC, "gcsadmm.hip")).read()
     ext = src[src.index('extern "C" {'):]
-    bodies = {}
-    for m in re.finditer(r"\n(?:gcsadmm_status|void|const char \*|int) ?(gcsadmm_[a-z_0-9]+)\(([^)]*)\)\s*\n\{", ext):
+    bodies, first_param = {}, {}
+    for m in re.finditer(r"\n(?:gcsadmm_status|void|const char \*|int|int32_t) ?(gcsadmm_[a-z_0-9]+)\(([^)]*)\)\s*\n?\s*\{", ext):
         start = m.end()
         depth, i = 1, start
         while depth:
@@ -100,43 +102,80 @@ def test_every_launching_entry_point_selects_the_handles_device():
             depth += (c == "{") - (c == "}")
             i += 1
         bodies[m.group(1)] = ext[start:i]
-    assert len(bodies) >= 20, sorted(bodies)
+        first_param[m.group(1)] = m.group(2).split(",")[0]
+    assert len(bodies) >= 30, sorted(bodies)
     # device work as this file spells it: the HIP runtime and kernel launches, the helpers that enqueue (launch_vertex, launch_edge, the
     # halo helpers, the partitioned loop), the owners that allocate (DevBuf upload / alloc / zero, create_owned, ensure_events,
     # overlap_setup) or release (delete h, a sub-struct of owners reset with `= {}`), RCCL, and the other objects' launch / attribute entries
     touches = re.compile(r"\bhip[A-Z]\w+\(|hipLaunchKernelGGL|\blaunch_vertex\(|\blaunch_edge\(|\bhalo_pack<|\bhalo_unpack<|\bhalo_transfer\(|\bhalo_upload\("
                          r"|\.(?:upload|alloc|zero)\(|\bcreate_owned\(|\bensure_events\(|\boverlap_setup\(|\bdelete h\b|h->(?:halo|overlap) = \{\}"
                          r"|\bset_lds_attr<|rccl\(\)\.(?!ok\b|err\b|GetErrorString\b)\w+\(|\brun_partitioned_loop\(|\bpartitioned_tail\(|gcsadmm_wg_launch|gcsadmm_wg_set")
-    guarded = re.compile(r"USE_DEVICE\(h\)|DeviceGuard device_guard_")
-    exempt = {"gcsadmm_comm_unique_id", "gcsadmm_debug_sub_cycles", "gcsadmm_debug_phase_cycles"}        # no handle: ncclGetUniqueId; symbols of the diagnostic build
-    # the pattern must not go blind: these entry points do device work, whatever helper spells it
+    plain = {"gcsadmm_" + n for n in ("last_error", "batch_last_error", "query", "query_workspace", "set_fused_tail", "halo_buffers", "check_halo")}
+    own_guard = {"gcsadmm_create", "gcsadmm_batch_create", "gcsadmm_destroy", "gcsadmm_batch_destroy"}      # no object yet / the owners release
+    no_object = {"gcsadmm_comm_unique_id", "gcsadmm_debug_sub_cycles", "gcsadmm_debug_phase_cycles"}        # ncclGetUniqueId; symbols of the diagnostic build
+    # the list must not go blind: these entry points do device work, whatever helper spells it
     must_touch = {"gcsadmm_" + n for n in ("create", "destroy", "reset", "vertex_step", "edge_step", "control", "run", "run_timed", "attach_comm",
                                            "halo_pack", "halo_unpack", "halo_exchange", "run_partitioned", "run_partitioned_timed", "set_overlap",
                                            "vertex_prox", "read_control", "cost", "unit_iterations")}
-    assert must_touch <= set(bodies), sorted(must_touch - set(bodies))
-    for name in must_touch:
-        assert touches.search(bodies[name]), f"{name}: no device work found -- the pattern no longer matches how this file spells it"
+    assert must_touch | plain <= set(bodies), sorted((must_touch | plain) - set(bodies))
+    assert not must_touch & plain
+    shimmed = set()
     for name, body in bodies.items():
-        if name in exempt or not touches.search(body):
+        if name in plain:
+            assert not touches.search(body), f"{name} is on the list of calls that never reach the device, and touches it"
+            assert not re.search(r"\b(?:handle|batch)_entry\(|DeviceGuard", body), name
             continue
-        g = guarded.search(body)
-        assert g, f"{name} touches the device without selecting the handle's device"
-        first = touches.search(body)
-        # the guard comes before the first device call (argument checks may precede it); hipGetDeviceCount in create is the one query allowed earlier
-        pre = body[:g.start()]
-        early = [t.group(0) for t in touches.finditer(pre) if t.group(0) not in ("hipGetDeviceCount(", "hipGetErrorString(")]
-        assert not early, (name, early)
+        if name in own_guard:
+            g = re.search(r"DeviceGuard device_guard_", body)
+            assert g, f"{name} touches the device without selecting the object's device"
+            early = [t.group(0) for t in touches.finditer(body[:g.start()]) if t.group(0) not in ("hipGetDeviceCount(", "hipGetErrorString(")]
+            assert not early, (name, early)         # hipGetDeviceCount in create is the one query allowed before the guard
+            continue
+        if name in no_object:
+            continue
+        kind = {"gcsadmm_handle": "handle", "struct gcsadmm_batch_s *": "batch"}[re.sub(r"\w+$", "", first_param[name]).strip()]
+        # one statement: `return <kind>_entry(obj, args, body)` whose closing parenthesis ends the body; before it at most declarations
+        # of locals that both lambdas see (`Type name;`, nothing evaluated)
+        m = re.fullmatch(rf"\s*(?:(?://[^\n]*|\w+ \w+;[^\n]*)\n\s*)*return {kind}_entry\((.*)\);\s*\}}", body, re.S)
+        assert m, f"{name} is not a single `return {kind}_entry(...)`"
+        depth, parts = 0, [""]
+        for ch in re.sub(r'"(?:[^"\\]|\\.)*"|//[^\n]*', "", m.group(1)):
+            depth += (ch in "([{") - (ch in ")]}")
+            assert depth >= 0, f"{name}: the {kind}_entry call ends before the body does"
+            if ch == "," and depth == 0:
+                parts.append("")
+            else:
+                parts[-1] += ch
+        assert depth == 0 and len(parts) == 3, (name, len(parts))
+        # `args`, the second argument, runs BEFORE the shim takes the guard: it checks arguments on the host and nothing else
+        early = [t.group(0) for t in touches.finditer(parts[1])]
+        assert not early, f"{name} touches the device before the guard is taken: {early}"
+        shimmed.add(name)
+    assert must_touch - own_guard <= shimmed
+    # the guard is taken by the shims, the creates and the destroys alone, and no entry point calls another
+    for m in re.finditer(r"\bDeviceGuard \w+\(", src):
+        # the last function head before it: relies on this file's layout -- a definition's head starts in column 0 on ONE line that
+        # holds its name and opening parenthesis and does not end in `;`; everything inside a function is indented
+        heads = re.findall(r"\n(?![ /#{}])[^\n(]*?(\w+)\([^\n]*[^;\n]\n", src[:m.start()])
+        assert heads[-1] in own_guard | {"guarded_entry"}, f"a DeviceGuard in {heads[-1]}"
+    for shim in ("handle_entry", "batch_entry"):
+        assert re.search(rf"gcsadmm_status {shim}\([^)]*\) \{{ return guarded_entry\(", src), shim
+    code = re.sub(r"//[^\n]*", "", src)
+    calls = set(re.findall(r"\b(gcsadmm_[a-z_0-9]+)\(", code[code.index('extern "C" {'):])) & set(bodies)
+    defs = [n for n in calls if len(re.findall(rf"\b{n}\(", code)) > 1]
+    assert not defs, f"entry points called from inside gcsadmm.hip: {defs}"
 
 
 def test_device_resources_are_released_by_their_owners_alone():
     """Ownership rule of the host code of the handle and of the scene (csrc/gcsadmm.hip, csrc/polytope_lp.hip with the headers split from
-    it, and csrc/hip_owners.h, which has the owners): a device allocation, a stream and an event each belong to an owning type (DevBuf, Stream, Event) whose
+    them, and csrc/hip_owners.h, which has the owners): a device allocation, a stream and an event each belong to an owning type (DevBuf, Stream, Event) whose
     destructor releases it, so hipFree, hipStreamDestroy and hipEventDestroy are each written exactly once -- in the owners' releasing
     functor -- and hipMalloc only inside DevBuf.  A buffer added to the handle or the scene as a raw pointer and freed by hand fails here."""
     import os
     import re
     from gcs_admm_amd import build
-    src = "".join(open(os.path.join(build.CSRC, f)).read() for f in ("hip_owners.h", "gcsadmm.hip", "polytope_lp.hip", "scene_kernels.h", "scene_stage.h"))
+    src = "".join(open(os.path.join(build.CSRC, f)).read() for f in ("hip_owners.h", "gcsadmm.hip", "loop_kernels.h", "rccl_api.h", "halo_plan.h", "polytope_lp.hip", "scene_kernels.h",
+                                                                         "scene_stage.h"))
     for call in ("hipFree(", "hipStreamDestroy(", "hipEventDestroy("):
         assert src.count(call) == 1, (call, src.count(call))
     m = re.search(r"\nstruct HipRelease \{\n.*?\n\};\n", src, re.S)

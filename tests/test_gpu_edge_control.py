@@ -1,5 +1,5 @@
 """The non-vertex half of the ADMM iteration on the device -- edge_kernel in every launch mode, finalize_kernel, control_body,
-cost_kernel (csrc/gcsadmm.hip) -- against the plain numpy restatement of tests/loop_reference.py, to the bounds derived there:
+cost_kernel (csrc/loop_kernels.h, launched by csrc/gcsadmm.hip) -- against the plain numpy restatement of tests/loop_reference.py, to the bounds derived there:
 zedge bitwise, mu bitwise (a stated per-word bound when mu_scale is not a power of two), the five sums within (N + 8) 2^-53
 relative, the control block's decisions exact and its residuals within 4 ulp, the cost within its rounding bound.
 

@@ -265,7 +265,7 @@ def test_what_the_mu_bound_says_of_a_contracted_dual_update(fault_bench):
     stated, so it asks for a dual update whose product is rounded on its own whenever mu_scale is not a power of two; two ulp are
     outside on any reading.  (On the MI355X the contracted form, which the compiler chooses if left alone, put 4-5 % of the f64 words
     of a standard-normal state outside the bound, and left 2e-17 in an f32 word whose two terms cancel exactly; edge_kernel therefore
-    forms the product with contraction off, csrc/gcsadmm.hip scaled_plus.)"""
+    forms the product with contraction off, csrc/edge_step.h scaled_plus.)"""
     if not lr.LONGDOUBLE_OK:
         pytest.skip("models the fma in extended precision")
     g, copy, z_old, mu_old, p = fault_bench

@@ -83,7 +83,7 @@ def test_two_rank_gloo_matches_single_partition(tmp_path, name):
 
 
 def _halo_worker(rank, world, port, out):
-    """the message layout of the C ABI's halo exchange (gcsadmm_halo_desc, csrc/gcsadmm.hip halo_pack_kernel /
+    """the message layout of the C ABI's halo exchange (gcsadmm_halo_desc, csrc/halo_plan.h make_halo_plan, csrc/loop_kernels.h halo_pack_kernel /
     halo_unpack_kernel: per peer one block [c][columns of that peer], peers in ascending rank order), emulated with numpy
     over a real gloo group: after pack -> send/recv -> unpack every ghost column holds the remote owner's copy."""
     sys.path.insert(0, HERE); sys.path.insert(0, os.path.dirname(HERE))
