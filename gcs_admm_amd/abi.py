@@ -120,6 +120,9 @@ PROTOTYPES = {
     "gcsadmm_scene_build_region_graph": ([_p] * 3, _i),
     "gcsadmm_scene_read_region_graph": ([_p] * 5, _i),
     "gcsadmm_scene_query_graphs": ([_p, _i, _p, _p, _p, _i] + [_p] * 8, _i),
+    # the informed region set of every query of a batch (csrc/informed_core.h)
+    "gcsadmm_scene_region_paths": ([_p, _i, _p, _p, _p, _i] + [_p] * 4, _i),
+    "gcsadmm_scene_informed_regions": ([_p, _i, _p, _p, _d, _p, _p], _i),
     # the candidate paths of the rounding step, drawn on the device (gcs_admm_amd/walks.py)
     "gcsadmm_walks_create": ([_i] + [_p] * 7 + [_i, _p], _i),
     "gcsadmm_walks_destroy": ([_p], None),

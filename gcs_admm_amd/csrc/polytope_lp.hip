@@ -24,7 +24,8 @@
 // The resident regions also serve the step after the loop (path_restrict_kernel: path_restrict_core.h, on the offsets and sizes
 // restrict_plan.h decides), the queries on a decided scene (locate_kernel: point_locate_core.h), its edits (gcsadmm_scene_add_regions,
 // gcsadmm_scene_remove_regions: scene_edit_core.h) and the query graphs of a batch (gcsadmm_scene_build_region_graph,
-// gcsadmm_scene_query_graphs: query_graph_core.h).
+// gcsadmm_scene_query_graphs: query_graph_core.h) and the informed region set of every query (gcsadmm_scene_region_paths,
+// gcsadmm_scene_informed_regions: informed_core.h).
 //
 // This file is the host side of one translation unit: scene_kernels.h has the __global__ wrappers around the *_core.h headers,
 // scene_stage.h which results a scene holds, which of them each call needs and which it ends (the table is there), hip_owners.h
@@ -94,6 +95,7 @@ struct SceneHits {                                     // the hit list of the la
 struct SceneGraph {                                    // region graph of the decided pairs (HAVE_GRAPH; query_graph_core.h): rows [P + 1],
     DevBuf<long long> row_ptr;
     DevBuf<int> tail, head, rev;                       //   edges by (tail, head) and the id of each one's opposite edge
+    DevBuf<double> w;                                  //   distance between the centres of every edge (region_paths: made on first use)
     long long edges = 0;
 };
 struct LocateScratch {                                 // locate_points, kept and grown from call to call: the points [num_points][n],
@@ -107,6 +109,15 @@ struct QueryScratch {                                  // query_graphs, kept and
     DevBuf<unsigned char> st;
     DevBuf<int> edge_tail, edge_head, inc_ptr, inc_edge, inc_out, edge_inc_tail, edge_inc_head;      //   one chunk of results
 };
+struct InformedScratch {                               // region_paths and informed_regions, kept and grown from call to call:
+    DevBuf<double> points, bound;                      //   the caller's arrays,
+    DevBuf<long long> term_ptr;
+    DevBuf<int> term_region;
+    DevBuf<double> d;                                  //   distances of one chunk of queries [chunk][P],
+    DevBuf<int> path_region, path_len, status;         //   the results
+    DevBuf<double> cost;
+    DevBuf<unsigned char> keep;
+};
 // A gcsadmm_scene holds one from create to destroy (read: gcsadmm_scene_read_pairs); a batch call (gcsadmm_polytope_*) holds one on
 // its stack, with the buffers of its stage.
 struct gcsadmm_scene_s {
@@ -118,6 +129,7 @@ struct gcsadmm_scene_s {
     SceneGraph graph;
     LocateScratch lq;                                  // (locate_points)
     QueryScratch qg;                                   // (query_graphs)
+    InformedScratch inf;                               // (region_paths, informed_regions)
 };
 
 namespace {
@@ -1006,6 +1018,85 @@ int gcsadmm_scene_query_graphs(gcsadmm_scene s, int B, const int64_t *term_ptr, 
             LPCHK(to_host(edge_inc_tail + at, a.out.edge_inc_tail, E)); LPCHK(to_host(edge_inc_head + at, a.out.edge_inc_head, E));
         }
         LPCHK(hipStreamSynchronize(nullptr));
+        return GCSADMM_OK;
+    });
+}
+
+// ---- the informed region set of every query of a batch (informed_core.h); like restrict_paths outside the table of scene_stage.h ----
+int gcsadmm_scene_region_paths(gcsadmm_scene s, int num_queries, const double *points, const int64_t *term_ptr, const int *term_region,
+                               int max_len, int *path_region, int *path_len, double *path_cost, int *status)
+{
+    return scene_entry(s, [&]() -> int {
+        for (const NeedRule &rule : {NEED_FRESH_GRAPH, NEED_CENTERS})
+            if (!has(s->have, rule.flags)) { g_err = rule.refusal; return GCSADMM_ERR_BAD_ARG; }
+        const SceneRegions &r = s->reg;
+        SceneGraph &rg = s->graph;
+        InformedScratch &q = s->inf;
+        const int B = num_queries, P = r.P, n = r.n;
+        LPRUN(informed_check_paths(P, n, B, points, (const long long *)term_ptr, term_region, max_len, g_err));
+        if (B == 0) return GCSADMM_OK;
+        if (!path_region || !path_len || !path_cost || !status) { g_err = "null output array"; return GCSADMM_ERR_BAD_ARG; }
+        if ((long long)B * max_len > (long long)INT32_MAX) { g_err = "num_queries * max_len above 2^31 - 1"; return GCSADMM_ERR_UNSUPPORTED; }
+        if (!rg.w) {      // once per region graph
+            LPCHK(rg.w.alloc((size_t)rg.edges));
+            if (rg.edges > 0)
+                hipLaunchKernelGGL(region_weight_kernel, dim3(blocks_of((long)rg.edges)), dim3(TB), 0, 0, r.cen.get(), n, rg.tail.get(), rg.head.get(), rg.edges, rg.w.get());
+            LPCHK(hipGetLastError());
+        }
+        const size_t coords = 2 * (size_t)B * n, hits = (size_t)term_ptr[2 * (size_t)B], cells = (size_t)B * max_len;
+        const int chunk = informed_chunk(P);
+        LPCHK(q.points.reserve(coords)); LPCHK(q.term_ptr.reserve(2 * (size_t)B + 1)); LPCHK(q.term_region.reserve(hits));
+        LPCHK(q.d.reserve((size_t)std::min(chunk, B) * P));
+        LPCHK(q.path_region.reserve(cells)); LPCHK(q.path_len.reserve((size_t)B)); LPCHK(q.status.reserve((size_t)B)); LPCHK(q.cost.reserve((size_t)B));
+        LPCHK(to_device(q.points.get(), points, coords));
+        LPCHK(to_device(q.term_ptr.get(), (const long long *)term_ptr, 2 * (size_t)B + 1));
+        if (hits > 0) LPCHK(to_device(q.term_region.get(), term_region, hits));      // (no hit at all: term_region may be null; the buffer is there)
+        LPCHK(hipMemset(q.path_region.get(), 0xff, sizeof(int) * cells));      // entries beyond a path's length: -1
+        PathArgs a{};
+        a.g = PathGraph{P, n, rg.row_ptr.get(), rg.head.get(), rg.w.get(), r.cen.get()};
+        a.points = q.points.get(); a.term_ptr = q.term_ptr.get(); a.term_region = q.term_region.get();
+        a.B = B; a.max_len = max_len; a.d = q.d.get();
+        a.path_region = q.path_region.get(); a.path_len = q.path_len.get(); a.status = q.status.get(); a.path_cost = q.cost.get();
+        for (int first = 0; first < B; first += chunk) {      // (a chunk's launch follows the one before on the stream: d is theirs in turn)
+            a.first = first;
+            hipLaunchKernelGGL(region_path_kernel, dim3((unsigned)std::min(chunk, B - first)), dim3(PATH_THREADS), 0, 0, a);
+            LPCHK(hipGetLastError());
+        }
+        LPCHK(to_host(path_region, q.path_region.get(), cells)); LPCHK(to_host(path_len, q.path_len.get(), (size_t)B));
+        LPCHK(to_host(path_cost, q.cost.get(), (size_t)B)); LPCHK(to_host(status, q.status.get(), (size_t)B));
+        LPCHK(hipStreamSynchronize(nullptr));
+        return GCSADMM_OK;
+    });
+}
+
+int gcsadmm_scene_informed_regions(gcsadmm_scene s, int num_queries, const double *points, const double *bound, double pad,
+                                   unsigned char *keep, int64_t *num_kept)
+{
+    return scene_entry(s, [&]() -> int {
+        if (!has(s->have, NEED_BOXES.flags)) { g_err = NEED_BOXES.refusal; return GCSADMM_ERR_BAD_ARG; }
+        const SceneRegions &r = s->reg;
+        InformedScratch &q = s->inf;
+        const int B = num_queries, P = r.P, n = r.n;
+        LPRUN(informed_check_keep(n, B, points, bound, pad, g_err));
+        if (B == 0) return GCSADMM_OK;
+        if (!keep) { g_err = "null output array"; return GCSADMM_ERR_BAD_ARG; }
+        const size_t coords = 2 * (size_t)B * n, cells = (size_t)B * P;
+        LPCHK(q.points.reserve(coords)); LPCHK(q.bound.reserve((size_t)B)); LPCHK(q.keep.reserve(cells));
+        LPCHK(to_device(q.points.get(), points, coords)); LPCHK(to_device(q.bound.get(), bound, (size_t)B));
+        KeepArgs a{P, n, B, 0, r.lo.get(), r.hi.get(), q.points.get(), q.bound.get(), pad, q.keep.get()};
+        for (int first = 0; first < B && P > 0; first += QUERY_CHUNK_MAX) {      // grid.y
+            a.first = first;
+            hipLaunchKernelGGL(informed_keep_kernel, dim3(blocks_of(P), (unsigned)std::min(QUERY_CHUNK_MAX, B - first)), dim3(TB), 0, 0, a);
+            LPCHK(hipGetLastError());
+        }
+        LPCHK(to_host(keep, q.keep.get(), cells));
+        LPCHK(hipStreamSynchronize(nullptr));
+        if (num_kept)
+            for (int i = 0; i < B; ++i) {
+                int64_t kept = 0;
+                for (int p = 0; p < P; ++p) kept += keep[(size_t)i * P + p];
+                num_kept[i] = kept;
+            }
         return GCSADMM_OK;
     });
 }

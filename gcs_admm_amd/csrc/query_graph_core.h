@@ -250,6 +250,26 @@ inline int query_chunk(int P, long long region_edges, int asked)
     const long long chunk = asked > 0 ? asked : std::max(fit, 1LL);
     return (int)std::min<long long>(chunk, QUERY_CHUNK_MAX);
 }
+// The hit lists of B > 0 queries (term_ptr not null): 2 B segments from 0 on, each strictly ascending within [0, P).
+inline int query_check_terms(int P, int B, const long long *term_ptr, const int *term_region, std::string &err)
+{
+    if (B > INT32_MAX / 2) { err = "more than 2^30 queries"; return QUERY_UNSUPPORTED; }
+    const long long points = 2LL * B;
+    if (term_ptr[0] != 0) { err = "term_ptr[0] != 0"; return QUERY_BAD_ARG; }
+    for (long long p = 0; p < points; ++p)
+        if (term_ptr[p + 1] < term_ptr[p]) { err = "term_ptr is not non-decreasing"; return QUERY_BAD_ARG; }
+    if (term_ptr[points] > (long long)INT32_MAX) { err = "more than 2^31 - 1 hits"; return QUERY_UNSUPPORTED; }
+    if (term_ptr[points] > 0 && !term_region) { err = "null term_region"; return QUERY_BAD_ARG; }
+    for (long long p = 0; p < points; ++p)
+        for (long long j = term_ptr[p]; j < term_ptr[p + 1]; ++j) {
+            const int r = term_region[j];
+            if (r < 0 || r >= P) { err = "hit list of point " + std::to_string(p) + ": region index out of range"; return QUERY_BAD_ARG; }
+            if (j > term_ptr[p] && term_region[j - 1] >= r) {
+                err = "hit list of point " + std::to_string(p) + " is not strictly ascending"; return QUERY_BAD_ARG;
+            }
+        }
+    return QUERY_OK;
+}
 // Everything the kernel will index with, checked before any launch.  *max_items: the most work items of one query.
 inline int query_check(int P, long long region_edges, const QueryBatch &q, int chunk_queries, std::string &err, long long *max_items)
 {
@@ -257,21 +277,7 @@ inline int query_check(int P, long long region_edges, const QueryBatch &q, int c
     if (q.B < 0 || chunk_queries < 0) { err = "negative number of queries or chunk_queries"; return QUERY_BAD_ARG; }
     if (q.B == 0) return QUERY_OK;
     if (!q.term_ptr || !q.st || !q.edge_off) { err = "null term_ptr, st_adjacent or edge_off"; return QUERY_BAD_ARG; }
-    if (q.B > INT32_MAX / 2) { err = "more than 2^30 queries"; return QUERY_UNSUPPORTED; }
-    const long long points = 2LL * q.B;
-    if (q.term_ptr[0] != 0) { err = "term_ptr[0] != 0"; return QUERY_BAD_ARG; }
-    for (long long p = 0; p < points; ++p)
-        if (q.term_ptr[p + 1] < q.term_ptr[p]) { err = "term_ptr is not non-decreasing"; return QUERY_BAD_ARG; }
-    if (q.term_ptr[points] > (long long)INT32_MAX) { err = "more than 2^31 - 1 hits"; return QUERY_UNSUPPORTED; }
-    if (q.term_ptr[points] > 0 && !q.term_region) { err = "null term_region"; return QUERY_BAD_ARG; }
-    for (long long p = 0; p < points; ++p)
-        for (long long j = q.term_ptr[p]; j < q.term_ptr[p + 1]; ++j) {
-            const int r = q.term_region[j];
-            if (r < 0 || r >= P) { err = "hit list of point " + std::to_string(p) + ": region index out of range"; return QUERY_BAD_ARG; }
-            if (j > q.term_ptr[p] && q.term_region[j - 1] >= r) {
-                err = "hit list of point " + std::to_string(p) + " is not strictly ascending"; return QUERY_BAD_ARG;
-            }
-        }
+    if (const int rc = query_check_terms(P, q.B, q.term_ptr, q.term_region, err)) return rc;
     if (q.edge_off[0] < 0) { err = "edge_off starts below 0"; return QUERY_BAD_ARG; }
     for (int i = 0; i < q.B; ++i) {
         if (q.st[i] > 1) { err = "st_adjacent of query " + std::to_string(i) + " is neither 0 nor 1"; return QUERY_BAD_ARG; }

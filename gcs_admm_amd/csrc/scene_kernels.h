@@ -8,6 +8,7 @@
 #include "point_locate_core.h"
 #include "scene_edit_core.h"
 #include "query_graph_core.h"
+#include "informed_core.h"
 #include "path_restrict_core.h"
 #include "restrict_plan.h"
 
@@ -330,6 +331,73 @@ __global__ __launch_bounds__(256) void query_graph_kernel(QueryGraphArgs a)
     const long long x = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (x >= a.items) return;
     query_item(a.g, query_terms(a.q, i), query_arrays(a.out, a.q, a.g.P, a.first, i), x);
+}
+
+// ---- the informed region set of a query (informed_core.h) ----
+__global__ void region_weight_kernel(const double *centers, int n, const int *tail, const int *head, long long E, double *w)
+{
+    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p < E) w[p] = informed_weight(centers, n, tail, head, p);
+}
+
+struct PathArgs {
+    PathGraph g;
+    const double *points;           // [2 B][n]: the starts, then the goals
+    const long long *term_ptr;      // [2 B + 1]
+    const int *term_region;
+    int B, first, max_len;          // blockIdx.x counts queries from `first`
+    double *d;                      // [queries of the chunk][P]
+    int *path_region, *path_len, *status;      // [B][max_len], [B], [B]
+    double *path_cost;              // [B]
+};
+// One workgroup per query.  Lane t owns the vertices t, t + 256, ...: it alone writes their entries of d, by plain stores, from what
+// it reads of its rows' neighbours, in place.  A round ends at a barrier that first waits for the wavefront's global accesses
+// (RestrictExec::sync has the form), so the next round reads what this one wrote; `changed` carries whether any lane lowered a value
+// across it -- three flags in turn, so that the one of round r + 2 is cleared between barriers r and r + 1, when nobody reads or sets
+// it.  A round that changes nothing has read final values only: the fixed point, whatever order the lanes ran in.  At most P rounds.
+__global__ __launch_bounds__(PATH_THREADS) void region_path_kernel(PathArgs a)
+{
+    __shared__ int changed[3];
+    const int i = a.first + (int)blockIdx.x, t = (int)threadIdx.x, P = a.g.P, n = a.g.n;
+    if (i >= a.B) return;
+    PathQuery q;
+    q.s = a.points + (size_t)i * n; q.g = a.points + (size_t)(a.B + i) * n;
+    q.rs = a.term_region + a.term_ptr[i]; q.a = (int)(a.term_ptr[i + 1] - a.term_ptr[i]);
+    q.rt = a.term_region + a.term_ptr[a.B + i]; q.b = (int)(a.term_ptr[a.B + i + 1] - a.term_ptr[a.B + i]);
+    double *d = a.d + (size_t)blockIdx.x * P;
+    auto sync = [] {
+        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+        __syncthreads();
+    };
+    for (int v = t; v < P; v += PATH_THREADS) d[v] = informed_init(a.g, q, v);
+    if (t < 3) changed[t] = 0;
+    sync();
+    for (int round = 0; round < P; ++round) {
+        bool fell = false;
+        for (int v = t; v < P; v += PATH_THREADS) fell |= informed_relax(a.g, d, v);
+        if (fell) changed[round % 3] = 1;
+        sync();
+        if (!changed[round % 3]) break;      // (the same in every lane)
+        if (t == 0) changed[(round + 2) % 3] = 0;
+    }
+    if (t == 0)
+        a.status[i] = informed_backtrack(a.g, q, d, a.max_len, a.path_region + (size_t)i * a.max_len, a.path_len + i, a.path_cost + i);
+}
+
+struct KeepArgs {
+    int P, n, B, first;             // blockIdx.y counts queries from `first`
+    const double *lo, *hi;          // [P][n]
+    const double *points, *bound;   // [2 B][n], [B]
+    double pad;
+    unsigned char *keep;            // [B][P]
+};
+// one thread per (query, region)
+__global__ __launch_bounds__(256) void informed_keep_kernel(KeepArgs a)
+{
+    const int i = a.first + (int)blockIdx.y, r = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (r >= a.P) return;
+    const double lb = informed_lower_bound(a.points + (size_t)i * a.n, a.points + (size_t)(a.B + i) * a.n, a.lo + (size_t)r * a.n, a.hi + (size_t)r * a.n, a.n, a.pad);
+    a.keep[(size_t)i * a.P + r] = informed_keep(lb, a.bound[i]) ? 1 : 0;
 }
 
 } // namespace gcsadmm_lp

@@ -17,8 +17,9 @@
 //   read_centers      centers        read_boxes   boxes        read_pairs   pairs        read_decisions   pairs, decided
 //   read_hits         hits           read_graph   graph        query_graphs graph (its own text)            (reads change nothing)
 //
-// "decided" is pairs and overlaps together.  gcsadmm_scene_restrict_paths needs the regions alone and is not in the table; an edit
-// of no regions returns before its finish.
+// "decided" is pairs and overlaps together.  gcsadmm_scene_restrict_paths needs the regions alone and is not in the table; nor are
+// gcsadmm_scene_region_paths (NEED_FRESH_GRAPH, NEED_CENTERS) and gcsadmm_scene_informed_regions (NEED_BOXES), which read and change
+// nothing.  An edit of no regions returns before its finish.
 #pragma once
 
 namespace gcsadmm_stage {

@@ -6,7 +6,9 @@ lists the regions under every start and goal point; only hits in the band of abo
 all of them in one call.  The query graphs are the region graph plus the terminals' edges, in the order and with the arrays a
 from-scratch ``graph_from_sets_device`` on ``{'s', 't', regions}`` gives; ``solve`` takes them through ``BatchSolver`` and
 ``rounding_many``.  By default the graphs are assembled on the host (a sort over all edges per query); ``assemble="device"`` takes them
-from one kernel call on the scene's own region graph (csrc/query_graph_core.h), the same arrays.  The scene is not frozen: ``add_regions`` and ``remove_regions`` edit it in place, and only the LPs of what is new run.  There is no CPU fallback: the LPs and the locate call run on the device (tests inject stand-ins).
+from one kernel call on the scene's own region graph (csrc/query_graph_core.h), the same arrays.  ``prune="informed"`` runs every query on
+its informed region set alone (``informed``, csrc/informed_core.h): the regions within the length of a feasible path of both terminals,
+which loses no optimal path.  The scene is not frozen: ``add_regions`` and ``remove_regions`` edit it in place, and only the LPs of what is new run.  There is no CPU fallback: the LPs and the locate call run on the device (tests inject stand-ins).
 """
 from __future__ import annotations
 
@@ -48,7 +50,8 @@ class SceneQueries:
             raise
         self.centers = np.ascontiguousarray(self.centers, float)
         self.last = {}      # counts of the last regions_at call: hits, undecided, redone_on_host
-        # assemble="device" alone: is the scene's region graph that of _pairs?  The regions' stacked polytope CSR (rows int64, A, b)
+        # assemble="device" and informed: is the scene's region graph that of _pairs?  assemble="device" alone: the regions' stacked
+        # polytope CSR (rows int64, A, b)
         self._graph_resident, self._stacked = False, None
 
     def close(self):
@@ -174,24 +177,116 @@ class SceneQueries:
         counts = np.bincount(np.repeat(np.arange(Q), np.diff(hit_ptr))[keep], minlength=Q)
         return np.split(hit_region[keep].astype(np.int32), np.cumsum(counts)[:-1]) if Q else []
 
+    def _region_graph_on_device(self):
+        """the scene's region graph is that of ``_pairs``: built on first use and after an edit, with the host's decisions in it when an
+        LP left a pair undecided"""
+        if not self._graph_resident:
+            undecided = np.any(np.asarray(self._pairs["status"]) < 0)
+            self.scene.build_region_graph(self._pairs["flags"] if undecided else None)
+            self._graph_resident = True
+
+    @staticmethod
+    def _term_lists(regs):
+        term_ptr = np.zeros(len(regs) + 1, np.int64)
+        term_ptr[1:] = np.cumsum([len(r) for r in regs])
+        return term_ptr, (np.concatenate(regs) if regs else np.zeros(0, np.int32))
+
+    def _located(self, starts, goals, eps, tol):
+        """(S [B, n], G [B, n], the region lists of ``regions_at`` for the starts, then the goals); a point in no region raises"""
+        S = np.ascontiguousarray(starts, float).reshape(-1, self.n)
+        G = np.ascontiguousarray(goals, float).reshape(-1, self.n)
+        if len(S) != len(G):
+            raise ValueError("one goal for every start")
+        B = len(S)
+        regs = self.regions_at(np.vstack([S, G]), eps, tol)
+        for i in range(B):
+            for which, r in (("start", regs[i]), ("goal", regs[B + i])):
+                if len(r) == 0:
+                    raise ValueError(f"query {i}: the {which} lies in no region")
+        return S, G, regs
+
+    def informed(self, starts, goals, eps: float = 1e-6, tol: float = 1e-9, restrict=None):
+        """The informed region set of every query (csrc/informed_core.h): the regions an optimal path can touch lie in the ellipsoid with
+        foci start and goal whose major axis is the length of any feasible path.  Per query a dict: ``path`` (int32 region indices of a
+        shortest path on the region graph under the distances between centres, one ``region_paths`` call for all queries; empty when
+        there is none), ``bound`` (the cost of the convex restriction along ``('s', *path, 't')``, all of them in one ``restrict`` call on
+        the terminal boxes and the distinct path regions; ``inf`` without a path or when the restriction is infeasible or failed),
+        ``keep`` (bool [P], one ``informed_regions`` call: the regions whose padded box is within the bound of both terminals; all of
+        them for an ``inf`` bound) and ``restriction`` (the points of the bound's path by vertex key, or None).  The terminals are boxes
+        of half-width ``eps`` around the points the kernel measures from, so the kernel's bound is ``bound + 4 eps sqrt(n)``, and the
+        regions under the two points are kept whatever it says: both only widen the set.
+
+        ``restrict``: ``(As, bs, n, paths) -> [(cost, xs)]`` as ``solver`` in ``rounding`` (default: ``solve_path_restrictions_device``).
+        The boxes are moved out by ``scene.SWEEP_PAD``.  The region graph is built on the scene on first use and after an edit."""
+        S, G, regs = self._located(starts, goals, eps, tol)
+        return self._informed(S, G, regs, eps, restrict)
+
+    def _informed(self, S, G, regs, eps, restrict=None):
+        from .rounding import solve_path_restrictions_device
+        B = len(S)
+        if B == 0:
+            return []
+        restrict = restrict or (lambda As, bs, n, paths: solve_path_restrictions_device(As, bs, n, paths, self.device))
+        self._region_graph_on_device()
+        points = np.vstack([S, G])
+        paths, _, status = self.scene.region_paths(points, *self._term_lists(regs))
+        As, bs, jobs, owner = {}, {}, [], []
+        for i in range(B):
+            if status[i] != 0:
+                continue
+            for key, p in ((('s', i), S[i]), (('t', i), G[i])):
+                As[key], bs[key] = convert_pt_to_polytope(p, eps)
+            for r in paths[i]:
+                As[('r', int(r))], bs[('r', int(r))] = self.polys[r]
+            jobs.append([('s', i)] + [('r', int(r)) for r in paths[i]] + [('t', i)])
+            owner.append(i)
+        bound, points_of = np.full(B, np.inf), [None] * B
+        if jobs:
+            name = lambda k: k[0] if k[0] in ('s', 't') else self.keys[k[1]]
+            for i, (cost, xs) in zip(owner, restrict(As, bs, self.n, jobs)):
+                if xs is not None and np.isfinite(cost):
+                    bound[i], points_of[i] = float(cost), {name(k): x for k, x in xs.items()}
+        keep = self.scene.informed_regions(points, bound + 4.0 * eps * np.sqrt(self.n))
+        keep = np.array(keep, dtype=bool, copy=True)
+        for i in range(B):
+            keep[i, regs[i]] = True
+            keep[i, regs[B + i]] = True
+        return [dict(path=np.asarray(paths[i], np.int32), bound=float(bound[i]), keep=keep[i], restriction=points_of[i]) for i in range(B)]
+
+    def _host_graph(self, s, g, rs, rt, eps, keep=None):
+        """the graph of one query from one ``lexsort`` over all edges and ``graph._finish_graph``: on all regions, or (``keep``: bool [P]) on
+        the induced subgraph of the kept ones, renumbered in scene order"""
+        tail_r, head_r, keys, polys, centers = self.edge_tail, self.edge_head, self.keys, self.polys, self.centers
+        if keep is not None:
+            idx = np.nonzero(keep)[0]
+            new = np.cumsum(keep) - 1
+            both = keep[tail_r] & keep[head_r]
+            tail_r, head_r = new[tail_r[both]], new[head_r[both]]
+            keys, polys, centers = [keys[r] for r in idx], [polys[r] for r in idx], centers[idx]
+            rs, rt = new[rs], new[rt]
+        rs, rt = rs.astype(np.int64) + 2, rt.astype(np.int64) + 2
+        (lo_s, hi_s), (lo_t, hi_t) = (s - eps, s + eps), (g - eps, g + eps)      # the bounds graph._as_box reads off convert_pt_to_polytope(p, eps)
+        st = np.array([0], np.int64) if np.all(np.maximum(lo_s, lo_t) <= np.minimum(hi_s, hi_t) + 1e-9) else np.zeros(0, np.int64)
+        zs, zt = np.zeros(len(rs), np.int64), np.ones(len(rt), np.int64)
+        tail = np.concatenate([tail_r.astype(np.int64) + 2, zs, rs, zt, rt, st, st + 1])
+        head = np.concatenate([head_r.astype(np.int64) + 2, rs, zs, rt, zt, st + 1, st])
+        o = np.lexsort((head, tail))
+        polys = [convert_pt_to_polytope(s, eps), convert_pt_to_polytope(g, eps)] + polys
+        return _finish_graph(self.n, ['s', 't'] + keys, tail[o], head[o], polys, np.vstack([s, g, centers]), 0, 1)
+
     def _assemble_on_device(self, S, G, regs, eps):
         """the graphs of ``graphs`` from ONE ``query_graphs`` call: the scene's region graph (built on first use and after an edit, with
         the host's decisions in it when an LP left a pair undecided) merged with every query's terminal edges by a kernel, the arrays
         taken as they come; the polytope CSR is the regions' stacked one behind the two point boxes"""
         B = len(S)
-        if not self._graph_resident:
-            undecided = np.any(np.asarray(self._pairs["status"]) < 0)
-            self.scene.build_region_graph(self._pairs["flags"] if undecided else None)
-            self._graph_resident = True
+        self._region_graph_on_device()
         if self._stacked is None:
             rows = np.zeros(len(self.polys) + 1, np.int64)
             rows[1:] = np.cumsum([len(b) for _, b in self.polys])
             self._stacked = (rows, np.ascontiguousarray(np.vstack([A for A, _ in self.polys]).reshape(-1, self.n)) if self.polys else np.zeros((0, self.n)),
                              np.ascontiguousarray(np.hstack([b for _, b in self.polys])) if self.polys else np.zeros(0))
         rows, A_all, b_all = self._stacked
-        term_ptr = np.zeros(2 * B + 1, np.int64)
-        term_ptr[1:] = np.cumsum([len(r) for r in regs])
-        term_region = np.concatenate(regs) if regs else np.zeros(0, np.int32)
+        term_ptr, term_region = self._term_lists(regs)
         st = np.array([np.all(np.maximum(S[i] - eps, G[i] - eps) <= np.minimum(S[i] + eps, G[i] + eps) + 1e-9) for i in range(B)], np.uint8)
         arrays = self.scene.query_graphs(term_ptr, term_region, st)
         keys = ['s', 't'] + self.keys
@@ -207,7 +302,7 @@ class SceneQueries:
                                 interior=np.concatenate([S[i][None], G[i][None], self.centers]), src=0, dst=1))
         return out
 
-    def graphs(self, starts, goals, eps: float = 1e-6, tol: float = 1e-9, assemble: str = "host"):
+    def graphs(self, starts, goals, eps: float = 1e-6, tol: float = 1e-9, assemble: str = "host", prune=None, restrict=None):
         """One ``GcsGraph`` per query ``(starts[i], goals[i])``, keys ``['s', 't', *region keys]``: what ``graph_from_sets`` makes of the
         sets ``{'s': box of the start, 't': box of the goal, regions}`` -- the region edges shifted by two, both directions of every
         terminal-region hit, and both directions of s-t when the two boxes meet (the interval rule of ``graph.polytopes_overlap``), in
@@ -216,43 +311,38 @@ class SceneQueries:
 
         ``assemble``: ``"host"`` (the default: one ``lexsort`` over all edges and ``graph._finish_graph`` per query) or ``"device"`` (the
         region graph is built once on the scene, where the pair list lives, and ONE kernel call writes the index arrays of all queries
-        -- csrc/query_graph_core.h --; every field of every graph is the host path's, dtype, shape and bytes)."""
+        -- csrc/query_graph_core.h --; every field of every graph is the host path's, dtype, shape and bytes).
+
+        ``prune``: ``None`` (the default: every region) or ``"informed"``: the graph of query i is the host path's on the induced
+        subgraph of its informed region set (``informed``; ``restrict`` as there), the regions renumbered in scene order, keys ``['s',
+        't', *kept keys]``.  No optimal path is lost.  Not with ``assemble="device"``."""
+        return self._graphs(starts, goals, eps, tol, assemble, prune, restrict)[0]
+
+    def _graphs(self, starts, goals, eps, tol, assemble, prune, restrict):
+        """(the graphs of ``graphs``, the records of ``informed`` or None)"""
         if assemble not in ("host", "device"):
             raise ValueError(f"assemble must be 'host' or 'device', not {assemble!r}")
-        S = np.ascontiguousarray(starts, float).reshape(-1, self.n)
-        G = np.ascontiguousarray(goals, float).reshape(-1, self.n)
-        if len(S) != len(G):
-            raise ValueError("one goal for every start")
+        if prune not in (None, "informed"):
+            raise ValueError(f"prune must be None or 'informed', not {prune!r}")
+        if prune is not None and assemble == "device":
+            raise ValueError("prune needs assemble='host': the device assembles the graphs of the whole scene")
+        S, G, regs = self._located(starts, goals, eps, tol)
         B = len(S)
-        regs = self.regions_at(np.vstack([S, G]), eps, tol)
-        for i in range(B):
-            for which, r in (("start", regs[i]), ("goal", regs[B + i])):
-                if len(r) == 0:
-                    raise ValueError(f"query {i}: the {which} lies in no region")
         if assemble == "device":
-            return self._assemble_on_device(S, G, regs, eps)
-        box = lambda p: (p - eps, p + eps)      # the bounds graph._as_box reads off convert_pt_to_polytope(p, eps)
-        keys = ['s', 't'] + self.keys
-        out = []
-        for i in range(B):
-            rs, rt = regs[i].astype(np.int64) + 2, regs[B + i].astype(np.int64) + 2
-            (lo_s, hi_s), (lo_t, hi_t) = box(S[i]), box(G[i])
-            st = np.array([0], np.int64) if np.all(np.maximum(lo_s, lo_t) <= np.minimum(hi_s, hi_t) + 1e-9) else np.zeros(0, np.int64)
-            zs, zt = np.zeros(len(rs), np.int64), np.ones(len(rt), np.int64)
-            tail = np.concatenate([self.edge_tail.astype(np.int64) + 2, zs, rs, zt, rt, st, st + 1])
-            head = np.concatenate([self.edge_head.astype(np.int64) + 2, rs, zs, rt, zt, st + 1, st])
-            o = np.lexsort((head, tail))
-            polys = [convert_pt_to_polytope(S[i], eps), convert_pt_to_polytope(G[i], eps)] + self.polys
-            out.append(_finish_graph(self.n, keys, tail[o], head[o], polys, np.vstack([S[i], G[i], self.centers]), 0, 1))
-        return out
+            return self._assemble_on_device(S, G, regs, eps), None
+        info = self._informed(S, G, regs, eps, restrict) if prune else None
+        return [self._host_graph(S[i], G[i], regs[i], regs[B + i], eps, info[i]["keep"] if prune else None) for i in range(B)], info
 
     def solve(self, starts, goals, state_dtype: str = "f64", N: int = 5, M: int = 20, seeds=None, params=None, return_state: bool = False,
-              walk: str = "host", assemble: str = "host", **common):
+              walk: str = "host", assemble: str = "host", prune=None, restrict=None, **common):
         """Every query to its stop test in one ``BatchSolver`` (``params``: one dict per query, ``common``: parameters of all, as
         ``BatchSolver.solve``), then rounded by ``rounding_many`` (``N``, ``M``: as ``rounding``; ``seeds``: one per query, default 0).
         ``walk``: ``"host"`` (the default: the walks of ``rounding``, on a host copy of every query's activations) or ``"device"``
         (``rounding_members``: the walks of all queries drawn on the device while the activations are still there, by the rule of
         ``walks.walk_reference`` -- other draws than the host's for the same seed).  ``assemble``: as ``graphs`` (the same graphs either way).
+        ``prune``, ``restrict``: as ``graphs``; with ``prune="informed"`` every query runs on its informed region set alone, each record
+        gains ``informed_bound`` and ``kept_regions``, and the bound's path is one more candidate of the rounding step, so that
+        ``rounded_cost <= informed_bound`` whenever the bound is finite.
         Returns one record per query: that of ``DeviceSolver.solve`` plus ``rounded_cost``, ``x_v_rounded``, ``y_v_rounded`` and
         ``graph``; with ``return_state`` also ``trace`` and ``state``, host copies of the member's trace and of its six state arrays (the
         batch and its members are closed on return)."""
@@ -261,10 +351,12 @@ class SceneQueries:
         from .rounding import rounding_many, rounding_members, rounding_problem
         if walk not in ("host", "device"):
             raise ValueError(f"walk must be 'host' or 'device', not {walk!r}")
-        graphs = self.graphs(starts, goals, assemble=assemble)
+        graphs, info = self._graphs(starts, goals, 1e-6, 1e-9, assemble, prune, restrict)
         seeds = [0] * len(graphs) if seeds is None else list(seeds)
         if len(seeds) != len(graphs):
             raise ValueError("one seed per query")
+        # the bound's path with its restriction: one more candidate of the rounding step
+        extra = info and [[(r["bound"], list(r["restriction"]), r["restriction"])] if r["restriction"] is not None else [] for r in info]
         batch = BatchSolver(graphs, state_dtype, device=self.device)
 
         def close():
@@ -282,13 +374,15 @@ class SceneQueries:
             members_open.callback(close)
             records = batch.solve(params=params, **common)
             if walk == "device":         # the walks read the activations where the members hold them
-                rounded = rounding_members(batch.members, graphs, N=N, M=M, seeds=seeds, device=self.device)
+                rounded = rounding_members(batch.members, graphs, N=N, M=M, seeds=seeds, device=self.device, extra=extra)
                 keep(records)
             else:                        # the host walks read a copy of them; the batch is closed before the rounding
                 problems = [rounding_problem(m, *sets_of_graph(g), seed=s) for m, g, s in zip(batch.members, graphs, seeds)]
                 keep(records)
                 members_open.close()
-                rounded = rounding_many(problems, N=N, M=M, device=self.device)
-        for rec, (cost, x_v, y_v) in zip(records, rounded):
+                rounded = rounding_many(problems, N=N, M=M, device=self.device, extra=extra)
+        for i, (rec, (cost, x_v, y_v)) in enumerate(zip(records, rounded)):
+            if info is not None:
+                rec.update(informed_bound=info[i]["bound"], kept_regions=int(info[i]["keep"].sum()))
             rec.update(rounded_cost=cost, x_v_rounded=x_v, y_v_rounded=y_v)
         return records

@@ -234,12 +234,14 @@ def _rounded(cands, V, n):
     return cost, {v: xs.get(v, np.zeros(2 * n)) for v in V}, {v: (1 if v in xs else 0) for v in V}
 
 
-def rounding_many(problems, N=5, M=20, device=0, solver=None):
+def rounding_many(problems, N=5, M=20, device=0, solver=None, extra=None):
     """``rounding(..., restriction="device")`` for many problems at once (the members of a ``BatchSolver``, for instance):
     ``problems`` is a list of dicts with the arguments of ``rounding`` (``y_e_sol, V, E, I_v_out, As, bs, n`` and optionally
     ``seed``), all of one dimension n.  The candidates of every problem are solved in ONE call per round, on one scene over the
     concatenated regions.  Returns the list of ``(cost, x_v_rounded, y_v_rounded)``, each exactly what ``rounding`` returns for
-    that problem alone.  ``solver``: as in ``rounding``, on the concatenated regions (keys ``(problem index, region key)``)."""
+    that problem alone.  ``solver``: as in ``rounding``, on the concatenated regions (keys ``(problem index, region key)``).
+    ``extra``: per problem a list of candidates ``(cost, path, xs)`` that are solved already (``xs`` by vertex key, as ``solver``
+    returns them); they join the problem's candidates under the result rule, beside the N paths of the walks."""
     if not problems:
         return []
     n = problems[0]["n"]
@@ -248,7 +250,7 @@ def rounding_many(problems, N=5, M=20, device=0, solver=None):
     As = {(i, v): pr["As"][v] for i, pr in enumerate(problems) for v in pr["As"]}
     bs = {(i, v): pr["bs"][v] for i, pr in enumerate(problems) for v in pr["As"]}
     cands = [_Candidates(_host_walks(pr["y_e_sol"], pr["I_v_out"], M, pr.get("seed", 0)), N) for pr in problems]
-    return _round_batch(cands, [pr["V"] for pr in problems], As, bs, n, device, solver)
+    return _round_batch(cands, [pr["V"] for pr in problems], As, bs, n, device, solver, extra)
 
 
 @contextlib.contextmanager
@@ -262,15 +264,16 @@ def _scene_solver(As, bs, device, solver=None):
         yield lambda As_, bs_, n_, paths: solve_path_restrictions_device(As_, bs_, n_, paths, device, scene)
 
 
-def _round_batch(cands, Vs, As, bs, n, device, solver):
+def _round_batch(cands, Vs, As, bs, n, device, solver, extra=None):
     """the rounds of many problems on their concatenated regions ``As``, ``bs`` (keys ``(problem index, region key)``: the solver gets
-    paths of such keys, the candidates get their points back by region key), and every problem's result"""
+    paths of such keys, the candidates get their points back by region key), and every problem's result; ``extra``: as ``rounding_many``"""
     with _scene_solver(As, bs, device, solver) as run:
         def solve(jobs):
             results = run(As, bs, n, [[(i, v) for v in pth] for i, pth in jobs])
             return [(cost, None if xs is None else {k[1]: x for k, x in xs.items()}) for cost, xs in results]
         _solve_rounds(cands, solve)
-    return [_rounded(c.cands, V, n) for c, V in zip(cands, Vs)]
+    extra = extra or [[]] * len(cands)
+    return [_rounded(c.cands + list(more), V, n) for c, V, more in zip(cands, Vs, extra)]
 
 
 def device_sampler(device=0):
@@ -283,7 +286,7 @@ def device_sampler(device=0):
     return sample
 
 
-def rounding_members(members, graphs, N=5, M=20, seeds=None, device=0, sampler=None, solver=None):
+def rounding_members(members, graphs, N=5, M=20, seeds=None, device=0, sampler=None, solver=None, extra=None):
     """The rounding step for the members of a batch with the walks drawn on the device: ``members[i]`` is the solver that has just run
     ``graphs[i]`` (its activations are read on the device; nothing per edge comes to the host), all of one dimension n.
     ``sampler(members, graphs, seeds, count) -> [(paths, status)]`` per member, paths as arrays of vertex indices (default:
@@ -291,7 +294,7 @@ def rounding_members(members, graphs, N=5, M=20, seeds=None, device=0, sampler=N
     1 .. M in order, without dead ends, overruns and duplicates, at most N feasible or pending at any time, as in ``rounding``; the
     restrictions go through ``solver`` (as in ``rounding_many``: default ``solve_path_restrictions_device`` on one scene over the
     concatenated regions), one call per round for all members.  Returns ``(cost, x_v_rounded, y_v_rounded)`` per member, in the
-    shape of ``rounding``; a member without a successful walk gives ``(inf, None, None)``.
+    shape of ``rounding``; a member without a successful walk gives ``(inf, None, None)``.  ``extra``: as ``rounding_many``.
 
     The walks follow the rule of ``walks.walk_reference``, not the host generator's draws: for one seed the candidates differ from
     those of ``rounding``.  An activation below 2^-40 counts as absent (the host walk: 1e-15)."""
@@ -312,7 +315,7 @@ def rounding_members(members, graphs, N=5, M=20, seeds=None, device=0, sampler=N
     for i, g in enumerate(graphs):      # per vertex: views into the graph's polytope CSR
         A_i, b_i = sets_of_graph(g)
         As.update(((i, v), A) for v, A in A_i.items()); bs.update(((i, v), b) for v, b in b_i.items())
-    return _round_batch(cands, [g.keys for g in graphs], As, bs, n, device, solver)
+    return _round_batch(cands, [g.keys for g in graphs], As, bs, n, device, solver, extra)
 
 
 def rounding(y_e_sol, V, E, I_v_out, As, bs, n, N=5, M=20, seed=0, restriction="host", solver=None, device=0):

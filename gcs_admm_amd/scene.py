@@ -316,6 +316,49 @@ class DeviceScene:
                                  lambda *arrays: self._call("gcsadmm_scene_query_graphs", *arrays), chunk_queries)
 
 
+    def region_paths(self, points, term_ptr, term_region, max_len=None):
+        """One candidate path per query: a shortest path on the resident region graph under the distances between centres
+        (``gcsadmm_scene_region_paths``; csrc/informed_core.h has the rule; after ``build_region_graph``).  ``points`` [2 B, n]: the
+        starts, then the goals; ``term_ptr``, ``term_region``: as ``query_graphs``.  ``max_len``: the most regions of a path (default P).
+        Returns ``(paths, cost, status)``: int32 arrays of region indices from the start side to the goal side, the length of the
+        polyline through their centres, and 0 found / 1 none (empty path, cost inf) / 2 longer than ``max_len`` (empty path, its cost) /
+        -1 not read back."""
+        return region_path_views(self.n, self.P, points, term_ptr, term_region, max_len, lambda *arrays: self._call("gcsadmm_scene_region_paths", *arrays))
+
+    def informed_regions(self, points, bound, pad: float = SWEEP_PAD):
+        """bool [B, P]: ``keep[i, r]`` iff ``dist(s_i, box_r) + dist(g_i, box_r) <= bound[i] (1 + 1e-9)`` on the resident boxes, every
+        side moved out by ``pad`` (``gcsadmm_scene_informed_regions``).  ``points`` [2 B, n]: the starts, then the goals; ``bound`` [B]:
+        the length of a feasible path of each query, or ``inf`` (keeps every region)."""
+        return informed_keep_array(self.n, self.P, points, bound, pad, lambda *arrays: self._call("gcsadmm_scene_informed_regions", *arrays))
+
+
+def region_path_views(n, P, points, term_ptr, term_region, max_len, call):
+    """the arrays of ``gcsadmm_scene_region_paths`` around ``call(num_queries, points, term_ptr, term_region, max_len, *four outputs)``
+    (addresses), the paths cut to their lengths"""
+    pts = np.ascontiguousarray(points, float).reshape(-1, n)
+    ptr = np.ascontiguousarray(term_ptr, np.int64).ravel()
+    reg = np.ascontiguousarray(term_region, np.int32).ravel()
+    B = pts.shape[0] // 2
+    if pts.shape[0] != 2 * B or len(ptr) != 2 * B + 1:
+        raise ValueError("points needs 2 B rows and term_ptr 2 B + 1 entries: the starts, then the goals")
+    max_len = max(int(P), 1) if max_len is None else int(max_len)
+    path = np.full((B, max(max_len, 0)), -1, np.int32); length = np.zeros(B, np.int32); cost = np.full(B, np.inf); status = np.full(B, 1, np.int32)
+    call(B, pts.ctypes.data, ptr.ctypes.data, reg.ctypes.data, max_len, path.ctypes.data, length.ctypes.data, cost.ctypes.data, status.ctypes.data)
+    return [path[i, :length[i]] if status[i] == 0 else path[i, :0] for i in range(B)], cost, status
+
+
+def informed_keep_array(n, P, points, bound, pad, call):
+    """the arrays of ``gcsadmm_scene_informed_regions`` around ``call(num_queries, points, bound, pad, keep, num_kept)`` (addresses)"""
+    pts = np.ascontiguousarray(points, float).reshape(-1, n)
+    bnd = np.ascontiguousarray(bound, float).ravel()
+    B = len(bnd)
+    if pts.shape[0] != 2 * B:
+        raise ValueError("points needs 2 B rows: the starts, then the goals")
+    keep = np.zeros((B, P), np.uint8)
+    call(B, pts.ctypes.data, bnd.ctypes.data, float(pad), keep.ctypes.data, None)
+    return keep != 0
+
+
 def query_graph_views(P, region_edges, term_ptr, term_region, st_adjacent, call, chunk_queries=0):
     """the flat arrays of ``gcsadmm_scene_query_graphs`` around ``call(num_queries, term_ptr, term_region, st_adjacent, chunk_queries,
     edge_off, *seven outputs)`` (addresses), cut into one tuple of views per query"""

@@ -488,6 +488,33 @@ int gcsadmm_scene_query_graphs(gcsadmm_scene s, int num_queries, const int64_t *
                                const unsigned char *st_adjacent, int chunk_queries, const int64_t *edge_off, int *edge_tail, int *edge_head,
                                int *inc_ptr, int *inc_edge, int *inc_out, int *edge_inc_tail, int *edge_inc_head);
 
+/* The informed region set of every query of a batch (csrc/informed_core.h has the rule): the regions an optimal path of query (s, g)
+ * can touch lie in the ellipsoid with foci s and g whose major axis is the length of any feasible path.  points[2 num_queries][n]: the
+ * starts, then the goals (finite); term_ptr and term_region: exactly those of gcsadmm_scene_query_graphs.
+ *
+ * region_paths finds one candidate path per query: a shortest path on the resident region graph, an edge weighing the distance
+ * between the resident centres of its two regions, from a region r under the start (at distance |s - c_r|) to the region r under the
+ * goal that minimises distance + |c_r - g| (the smallest r among equals).  One 256-lane workgroup per query relaxes every vertex from
+ * its row in rounds, in place, until a round changes nothing; the result does not depend on the order of the lanes.  Device workspace:
+ * 8 P bytes per query of a launch, kept within 256 MiB (or one query).  path_region[num_queries][max_len] receives the path from the
+ * start side to the goal side (-1 beyond its length), path_len its length, path_cost the length of the polyline s, centres, g.
+ * status: 0 found; 1 no region under the start reaches one under the goal (length 0, cost inf); 2 the path has more than max_len
+ * regions (length and cost are reported, no region is); -1 the path could not be read back (regions with identical centres in a
+ * cycle).  Needs the region graph (not one from before an edit) and the centres.
+ *
+ * informed_regions applies a bound: keep[i][r] = 1 iff dist(s_i, box_r) + dist(g_i, box_r) <= bound[i] (1 + 1e-9) on the resident
+ * boxes, every side moved out by pad, a side opened to infinity never counting.  For a bound that is the length of a feasible path no
+ * region of an optimal path is dropped; bound = inf keeps every region.  keep[num_queries][P]; num_kept[num_queries] (or NULL): the
+ * count per query.  Needs the boxes.
+ *
+ * GCSADMM_ERR_BAD_ARG: a missing result, negative num_queries, max_len < 1, a point that is not finite, a hit list that is not
+ * strictly ascending or leaves [0, P), a NaN pad, a NaN or negative bound, a null array.  num_queries = 0 does nothing.  A refused call
+ * writes no output and changes nothing resident. */
+int gcsadmm_scene_region_paths(gcsadmm_scene s, int num_queries, const double *points, const int64_t *term_ptr, const int *term_region,
+                               int max_len, int *path_region, int *path_len, double *path_cost, int *status);
+int gcsadmm_scene_informed_regions(gcsadmm_scene s, int num_queries, const double *points, const double *bound, double pad,
+                                   unsigned char *keep, int64_t *num_kept);
+
 /* ---- the candidate paths of the rounding step, drawn on the device (gcs_admm_amd/walks.py; csrc/path_walk_core.h has the rule) ----
  * After the loop, rounding draws s-t walks on the relaxed edge activations y_e.  walk_kernel draws them where the solver left y: one
  * 64-lane workgroup per (walk, problem), the visited set a bitmap in LDS, the draws from a counter-based generator (splitmix64 on
