@@ -36,11 +36,13 @@ extern "C" void EMU_CAT(EMU_NAME, _set_warm)(double *warm, const long long *warm
 static int *g_iters = nullptr;
 extern "C" void EMU_CAT(EMU_NAME, _set_iters)(int *iters) { g_iters = iters; }
 
-extern "C" int EMU_NAME(int n, int V, int E, int NI, const int *inc_ptr, const int *inc_edge, const int *inc_out,
-                               const int *poly_ptr, const double *poly_A, const double *poly_b, const double *center,
-                               int src, int dst, const double *zedge, const double *mu, double rho, double mu_scale,
-                               double eps_edge, double ipm_tol, int ipm_max_iter, double *copy, double *xv, double *zv,
-                               double *yv, int *counters, int *is_generic)
+// T: the state type of zedge, mu and copy (the handle's dtype on the device); everything else is double either way
+template <class T>
+static int emu_run(int n, int V, int E, int NI, const int *inc_ptr, const int *inc_edge, const int *inc_out,
+                   const int *poly_ptr, const double *poly_A, const double *poly_b, const double *center,
+                   int src, int dst, const T *zedge, const T *mu, double rho, double mu_scale,
+                   double eps_edge, double ipm_tol, int ipm_max_iter, T *copy, double *xv, double *zv,
+                   double *yv, int *counters, int *is_generic)
 {
     if (n != 2 && n != 3 && n != 6) return 1;
     std::vector<int> deg_in(V, 0);
@@ -71,9 +73,9 @@ extern "C" int EMU_NAME(int n, int V, int E, int NI, const int *inc_ptr, const i
     }
     if ((int)wave_vtx.size() > wave_slot_ptr.back()) wave_slot_ptr.push_back((int)wave_vtx.size());
     const int n_waves = (int)wave_slot_ptr.size() - 1;
-    VertexArgs<double> a;
+    VertexArgs<T> a;
     a.n_waves = n_waves; a.wave_slot_ptr = wave_slot_ptr.data(); a.wave_vtx = wave_vtx.data(); a.align_rows = align_rows; a.MM = MM;
-    gcsadmm_k::StepArgs<double> &s = a;     // the inputs every vertex-step program shares (step_args.h)
+    gcsadmm_k::StepArgs<T> &s = a;     // the inputs every vertex-step program shares (step_args.h)
     s.inc_ptr = inc_ptr; s.deg_in = deg_in.data(); s.inc_edge = inc_edge; s.poly_ptr = poly_ptr;
     s.poly_A = poly_A; s.poly_bc = bc.data(); s.center = center; s.E = E; s.NI = NI;
     s.zedge = zedge; s.mu = mu; s.copy = copy; s.xv = xv; s.zv = zv; s.yv = yv; s.counters = counters;
@@ -86,8 +88,8 @@ extern "C" int EMU_NAME(int n, int V, int E, int NI, const int *inc_ptr, const i
             WaveShared S;
             wave_shared_init(S, smem.data(), n, MM, STORE_DL);
             ex->solve_iters.clear();
-            if (STORE_DL) run_vertex_program<NN, double, 1>(*ex, w, a, S, rho, mu_scale);
-            else run_vertex_program<NN, double, 0>(*ex, w, a, S, rho, mu_scale);
+            if (STORE_DL) run_vertex_program<NN, T, 1>(*ex, w, a, S, rho, mu_scale);
+            else run_vertex_program<NN, T, 0>(*ex, w, a, S, rho, mu_scale);
             if (g_iters && (int)ex->solve_iters.size() == wave_slot_ptr[w + 1] - wave_slot_ptr[w])
                 for (int k = 0; k < (int)ex->solve_iters.size(); ++k) g_iters[wave_vtx[wave_slot_ptr[w] + k]] = ex->solve_iters[k];
             else if (g_iters)
@@ -100,3 +102,17 @@ extern "C" int EMU_NAME(int n, int V, int E, int NI, const int *inc_ptr, const i
     else run_all(new CpuExec<6>(), std::integral_constant<int, 6>());
     return 0;
 }
+
+#define EMU_STEP_ARGS(T)                                                                                                        \
+    int n, int V, int E, int NI, const int *inc_ptr, const int *inc_edge, const int *inc_out, const int *poly_ptr,              \
+    const double *poly_A, const double *poly_b, const double *center, int src, int dst, const T *zedge, const T *mu,            \
+    double rho, double mu_scale, double eps_edge, double ipm_tol, int ipm_max_iter, T *copy, double *xv, double *zv,            \
+    double *yv, int *counters, int *is_generic
+#define EMU_STEP_PASS                                                                                                           \
+    n, V, E, NI, inc_ptr, inc_edge, inc_out, poly_ptr, poly_A, poly_b, center, src, dst, zedge, mu, rho, mu_scale, eps_edge,    \
+    ipm_tol, ipm_max_iter, copy, xv, zv, yv, counters, is_generic
+extern "C" int EMU_NAME(EMU_STEP_ARGS(double)) { return emu_run<double>(EMU_STEP_PASS); }
+// f32 state: float zedge / mu in, a float copy out (the program's float instantiation: the S10k configuration of the device)
+extern "C" int EMU_CAT(EMU_NAME, _f32)(EMU_STEP_ARGS(float)) { return emu_run<float>(EMU_STEP_PASS); }
+#undef EMU_STEP_ARGS
+#undef EMU_STEP_PASS

@@ -11,12 +11,14 @@
 
 #ifdef GCS_WG_REVERSE
 #define EMU_FN wg_emu_vertex_step_rev
+#define EMU_FN_F32 wg_emu_vertex_step_f32_rev
 #define EMU_BOX wg_emu_set_box_rev
 #define EMU_LDS wg_emu_lds_doubles_rev
 #define EMU_WARM wg_emu_set_warm_rev
 #else
 #define EMU_WARM wg_emu_set_warm
 #define EMU_FN wg_emu_vertex_step
+#define EMU_FN_F32 wg_emu_vertex_step_f32
 #define EMU_BOX wg_emu_set_box
 #define EMU_LDS wg_emu_lds_doubles
 #endif
@@ -25,15 +27,15 @@ static bool g_emu_box = false;      // set per call: run the BOX instantiation (
 static double *g_emu_warm = nullptr;                // warm-start records of the following steps (warm_start.h); null = cold solves
 static const long long *g_emu_warm_ptr = nullptr;
 
-template <int N>
-static void run_all(const gcs_wg::WgArgs<double> &a, double rho, double mu_scale, int lds, int *status, int *iters)
+template <int N, class T>
+static void run_all(const gcs_wg::WgArgs<T> &a, double rho, double mu_scale, int lds, int *status, int *iters)
 {
     std::vector<double> smem(lds);
     for (int w = 0; w < a.n_vtx; ++w) {
         std::fill(smem.begin(), smem.end(), 0.0 / 0.0);
         int st = -9, it = 0;
-        if (g_emu_box && (N == 3 || N == 6)) gcs_wg::wg_solve_vertex<N, double, (N == 3 || N == 6)>(a, a.vtx[w], rho, mu_scale, smem.data(), st, it);
-        else gcs_wg::wg_solve_vertex<N, double, false>(a, a.vtx[w], rho, mu_scale, smem.data(), st, it);
+        if (g_emu_box && (N == 3 || N == 6)) gcs_wg::wg_solve_vertex<N, T, (N == 3 || N == 6)>(a, a.vtx[w], rho, mu_scale, smem.data(), st, it);
+        else gcs_wg::wg_solve_vertex<N, T, false>(a, a.vtx[w], rho, mu_scale, smem.data(), st, it);
         status[a.vtx[w]] = st; iters[a.vtx[w]] = it;
         a.counters[0] += st != 0; a.counters[1] += it;
     }
@@ -48,12 +50,14 @@ extern "C" long long wg_emu_warm_doubles(int n, int m, int d) { return gcs_ws::w
 // 1: the following steps run the BOX instantiation of the program (every polytope must be a canonical box: canonical_box.h)
 extern "C" void EMU_BOX(int on) { g_emu_box = on != 0; }
 
-// one vertex step over the generic vertices of a graph; special vertices (s, t, no-flow) are left untouched
-extern "C" int EMU_FN(int n, int V, int E, int NI, const int *inc_ptr, const int *inc_edge, const int *inc_out,
-                      const int *poly_ptr, const double *poly_A, const double *poly_b, const double *center,
-                      int src, int dst, const double *zedge, const double *mu, double rho, double mu_scale,
-                      double eps_edge, double ipm_tol, int ipm_max_iter, double *copy, double *xv, double *zv,
-                      double *yv, int *counters, int *is_generic, int *status, int *iters)
+// one vertex step over the generic vertices of a graph; special vertices (s, t, no-flow) are left untouched.  T: the state type of
+// zedge, mu and copy (the handle's dtype on the device); everything else is double either way
+template <class T>
+static int emu_step(int n, int V, int E, int NI, const int *inc_ptr, const int *inc_edge, const int *inc_out,
+                    const int *poly_ptr, const double *poly_A, const double *poly_b, const double *center,
+                    int src, int dst, const T *zedge, const T *mu, double rho, double mu_scale,
+                    double eps_edge, double ipm_tol, int ipm_max_iter, T *copy, double *xv, double *zv,
+                    double *yv, int *counters, int *is_generic, int *status, int *iters)
 {
     if (n < 1 || n > gcs_wg::WG_MAX_N) return 1;
     std::vector<int> deg_in(V, 0), vtx;
@@ -75,16 +79,30 @@ extern "C" int EMU_FN(int n, int V, int E, int NI, const int *inc_ptr, const int
             for (int k = 0; k < n; ++k) s -= poly_A[(size_t)j * n + k] * center[(size_t)v * n + k];
             bc[j] = s;
         }
-    gcs_wg::WgArgs<double> a;
+    gcs_wg::WgArgs<T> a;
     a.n_vtx = (int)vtx.size(); a.vtx = vtx.data();
-    gcsadmm_k::StepArgs<double> &s = a;     // the inputs every vertex-step program shares (step_args.h)
+    gcsadmm_k::StepArgs<T> &s = a;     // the inputs every vertex-step program shares (step_args.h)
     s.inc_ptr = inc_ptr; s.deg_in = deg_in.data(); s.inc_edge = inc_edge; s.poly_ptr = poly_ptr;
     s.poly_A = poly_A; s.poly_bc = bc.data(); s.center = center; s.E = E; s.NI = NI;
     s.zedge = zedge; s.mu = mu; s.copy = copy; s.xv = xv; s.zv = zv; s.yv = yv; s.counters = counters;
     s.eps_edge = eps_edge; s.ipm_tol = ipm_tol; s.ipm_max_iter = ipm_max_iter; s.warm = g_emu_warm; s.warm_ptr = g_emu_warm_ptr;
-    const bool ran = gcsadmm_k::dispatch_dim<1, 2, 3, 4, 5, 6, 7, 8>(n, [&](auto nn) { run_all<decltype(nn)::value>(a, rho, mu_scale, lds, status, iters); });
+    const bool ran = gcsadmm_k::dispatch_dim<1, 2, 3, 4, 5, 6, 7, 8>(n, [&](auto nn) { run_all<decltype(nn)::value, T>(a, rho, mu_scale, lds, status, iters); });
     return ran ? 0 : 1;
 }
+
+#define EMU_STEP_ARGS(T)                                                                                                        \
+    int n, int V, int E, int NI, const int *inc_ptr, const int *inc_edge, const int *inc_out, const int *poly_ptr,              \
+    const double *poly_A, const double *poly_b, const double *center, int src, int dst, const T *zedge, const T *mu,            \
+    double rho, double mu_scale, double eps_edge, double ipm_tol, int ipm_max_iter, T *copy, double *xv, double *zv,            \
+    double *yv, int *counters, int *is_generic, int *status, int *iters
+#define EMU_STEP_PASS                                                                                                           \
+    n, V, E, NI, inc_ptr, inc_edge, inc_out, poly_ptr, poly_A, poly_b, center, src, dst, zedge, mu, rho, mu_scale, eps_edge,    \
+    ipm_tol, ipm_max_iter, copy, xv, zv, yv, counters, is_generic, status, iters
+extern "C" int EMU_FN(EMU_STEP_ARGS(double)) { return emu_step<double>(EMU_STEP_PASS); }
+// f32 state: float zedge / mu in, a float copy out (the program's float instantiation: what an f32 handle runs on the device)
+extern "C" int EMU_FN_F32(EMU_STEP_ARGS(float)) { return emu_step<float>(EMU_STEP_PASS); }
+#undef EMU_STEP_ARGS
+#undef EMU_STEP_PASS
 
 #ifdef GCS_WG_REVERSE
 #define EMU_PROX wg_emu_vertex_prox_rev
@@ -119,6 +137,6 @@ extern "C" int EMU_PROX(int n, int V, const int *poly_ptr, const double *poly_A,
     s.inc_ptr = zero.data(); s.deg_in = zero.data(); s.inc_edge = zero.data(); s.poly_ptr = poly_ptr;
     s.poly_A = poly_A; s.poly_bc = bc.data(); s.center = center;
     s.xv = xv; s.zv = zv; s.yv = yv; s.counters = counters; s.ipm_tol = ipm_tol; s.ipm_max_iter = ipm_max_iter;
-    const bool ran = gcsadmm_k::dispatch_dim<2, 3, 6>(n, [&](auto nn) { run_all<decltype(nn)::value>(a, 1.0, 1.0, lds, status, iters); });
+    const bool ran = gcsadmm_k::dispatch_dim<2, 3, 6>(n, [&](auto nn) { run_all<decltype(nn)::value, double>(a, 1.0, 1.0, lds, status, iters); });
     return ran ? 0 : 1;
 }

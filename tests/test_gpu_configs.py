@@ -16,6 +16,7 @@ import pytest
 
 from gcs_admm_amd.cases import load_fixture
 from gcs_admm_amd.graph import lattice_boxes
+from scaled_cases import region_row as _region_row, region_scene as _region_scene
 from solve_agreement import Agreement, NewtonParity, device_newton, f32_round, generic_mask, oracle_step
 
 pytestmark = pytest.mark.gpu
@@ -219,31 +220,6 @@ def test_inner_failure_keeps_previous_copy(torch_gpu):
         kept = [v for v in generic
                 if d.copy[:, int(g.inc_ptr[v]):int(g.inc_ptr[v + 1])].abs().max().item() == 0.0 and d.yv[v].item() == 0.0]
         assert len(kept) >= cb.inner_failures - 0 and len(kept) >= len(generic) - 4, (len(kept), len(generic), cb.inner_failures)
-
-
-def _region_row():
-    """three boxes in a row, the outer two are the terminals: s = [0,1] x [0,1], t = [2,3] x [0,1], between them [0.8,2.2] x [0,1].
-    Shortest path: leave s and enter t at the faces x = 1 and x = 2 -> length 1 (with point terminals at the box centres: 2)"""
-    from gcs_admm_amd.graph import graph_from_sets
-    A = np.vstack([np.eye(2), -np.eye(2)])
-    box = lambda x0, x1, y0, y1: (A, np.array([x1, y1, -x0, -y0], float))
-    As, bs = {}, {}
-    As['s'], bs['s'] = box(0, 1, 0, 1); As['t'], bs['t'] = box(2, 3, 0, 1); As[0], bs[0] = box(0.8, 2.2, 0, 1)
-    return graph_from_sets(As, bs, 2)
-
-
-def _region_scene(seed, half=0.35):
-    """a 4 x 4 polygon scene (tools/scale_demo.py) whose terminals are boxes of half-width `half` about the points they were"""
-    import os, sys
-    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
-    from scale_demo import polygon_scene
-    from gcs_admm_amd.graph import graph_from_sets
-    As, bs = polygon_scene(4, seed=seed, m=3 + seed % 4)
-    A = np.vstack([np.eye(2), -np.eye(2)])
-    for key in ('s', 't'):
-        pt = 0.5 * (bs[key][:2] - bs[key][2:])
-        As[key], bs[key] = A, np.hstack([pt + half, -pt + half])
-    return graph_from_sets(As, bs, 2)
 
 
 @pytest.mark.parametrize("program,columns,dtype", [("workgroup", "incidence", "f64"), ("wavefront", "edge", "f64"), ("workgroup", "edge", "f32")])

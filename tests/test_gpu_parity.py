@@ -24,6 +24,14 @@ Stated tolerances (f64):
     step's total within one of the oracle's (measured: equal in every step of every case); warm, the run's total within 0.5 % + 24
     iterations (measured: within 0.50 % = 24 iterations on benchmark4 with the workgroup program -- the wavefront host build is off
     by the same 24 --, within 0.6 % = 13 iterations on the random scenes); no inner failure on either side.
+  * the same two contracts away from rho = 1, mu_scale = 1 and f64 state (tests/test_gpu_scaled_steps.py; the tests of this module
+    run there almost only, where consensus_target's scaling, the rho of the warm-start rule and the (T) stores are the identity):
+    22 steps under the penalty schedule of tests/scaled_cases.py (rho = 1, 3, 9, 4.5, 2.25, mu_scale 1 / 3 or 3 on the step of a
+    change, produced by the handle's own control step and asserted bit for bit), where the steps after a change of rho are judged
+    as cold steps on top; and f32 state under the "nearest" rule (a word counts beyond HALF an f32 spacing, so a truncating store
+    fails it).  Same thresholds, checked on the host builds (tests/solve_agreement.py lists every case).  Measured on the MI355X:
+    f64 0.909 - 0.970 within 1e-9, 0.966 - 1.0 within 1e-7, worst 4.5e-5; f32 0.945 - 1.0, 0.973 - 1.0, worst 1.4e-4; warm totals
+    within 2 iterations of the oracle's, after-change steps equal to it in every case; closed-form columns within 1e-12.
   * whole runs: stop iteration identical; residual traces within |a-b| <= 2e-4 + 1e-3|b|; cost 2e-4 rel.
 """
 from gcs_admm_amd import IPM_TOL
