@@ -142,26 +142,36 @@ def check(status, message):
         raise GcsAdmmError(message())
 
 
-_libs = {}
+_lib = None        # the one library of this process
 
 
-def load_library(path: str | None = None) -> C.CDLL:
-    """dlopen the in-tree HIP library (or the build at ``path``) and declare every prototype on it; fail loudly if it has not been built."""
-    path = path or LIB_PATH
-    if path not in _libs:
-        if not os.path.exists(path):
-            raise RuntimeError(f"{path} is missing: run `python -m gcs_admm_amd.build` (hipcc, gfx950). "
+def select_library(path: str) -> None:
+    """Make ``path`` (a build.variant(..) of the library) the one every handle of this process runs.  The only way to change LIB_PATH:
+    a process that has already loaded another library is refused, so no run mixes two."""
+    global LIB_PATH
+    path = os.path.abspath(path)
+    if _lib is not None and _lib._name != path:
+        raise RuntimeError(f"{_lib._name} is already loaded: select {path} before the first handle is made")
+    LIB_PATH = path
+
+
+def load_library() -> C.CDLL:
+    """dlopen the library at LIB_PATH and declare every prototype on it; fail loudly if it has not been built."""
+    global _lib
+    if _lib is None:
+        if not os.path.exists(LIB_PATH):
+            raise RuntimeError(f"{LIB_PATH} is missing: run `python -m gcs_admm_amd.build` (hipcc, gfx950). "
                                "There is no CPU fallback.")
         # PyTorch-ROCm ships its own HIP runtime (same SONAME as /opt/rocm's): it must be the one already
         # loaded when libgcsadmm.so resolves libamdhip64, or the process ends up with two runtimes and
         # the tensors' device pointers mean nothing to the library.
         import torch  # noqa: F401
-        lib = C.CDLL(path)
+        lib = C.CDLL(LIB_PATH)
         for name, (argtypes, restype) in PROTOTYPES.items():
             f = getattr(lib, name)
             f.argtypes, f.restype = argtypes, restype
-        _libs[path] = lib
-    return _libs[path]
+        _lib = lib
+    return _lib
 
 
 def graph_desc(g, *, state_dtype, device, num_incidences=None, inc_counted=None, edge_counted=None, nx_global=0.0,

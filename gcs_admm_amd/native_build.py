@@ -85,21 +85,30 @@ def _compile(cmd, obj, root, remarks, verbose):
     return deps
 
 
-def build_library(out, units, flags=(), compiler="g++", link_flags=None, root=ROOT, objdir=None, remarks=None, force=False, verbose=False):
-    """Build the shared library ``out`` and return its path.  units: (source, extra flags) or (source, extra flags, object path);
-    each is compiled with ``flags`` + its extra flags, all stale ones concurrently, then linked with ``link_flags`` (default: ``flags``
-    and -shared).  remarks: a suffix; the compiler's stderr of each unit is kept at <object><suffix> (hipcc's resource remarks).
-    A failed compile raises BuildError with the compiler's message and leaves no stamp."""
-    out, root = os.path.abspath(str(out)), os.path.abspath(str(root))
-    objdir = str(objdir) if objdir else os.path.join(root, "build", "obj")
-    jobs = []        # (command, object)
+def version(compiler="g++") -> str:
+    """what ``compiler --version`` prints (bits are a property of compiler plus source: tools/wg_bits_record.py)"""
+    return subprocess.check_output([compiler, "--version"], text=True)
+
+
+def command_lines(out, units, flags, compiler, link_flags, root, objdir):
+    """([(compile command, object)], link command) of build_library"""
+    jobs = []
     for src, extra, *obj in units:
         base = [compiler, *flags, *extra]
         src = os.path.abspath(str(src))
         key = hashlib.sha256(_rel("\0".join(base + [src]), root).encode()).hexdigest()[:16]
         obj = obj[0] if obj else os.path.join(objdir, f"{os.path.splitext(os.path.basename(src))[0]}-{key}.o")
         jobs.append((base + ["-MMD", "-MF", obj + ".d", "-c", src, "-o", obj], obj))
-    link = [compiler, *(link_flags if link_flags is not None else [*flags, "-shared"]), *(o for _, o in jobs), "-o", out]
+    return jobs, [compiler, *(link_flags if link_flags is not None else [*flags, "-shared"]), *(o for _, o in jobs), "-o", out]
+
+
+def build_library(out, units, flags=(), compiler="g++", link_flags=None, root=ROOT, objdir=None, remarks=None, force=False, verbose=False):
+    """Build the shared library ``out`` and return its path.  units: (source, extra flags) or (source, extra flags, object path);
+    each is compiled with ``flags`` + its extra flags, all stale ones concurrently, then linked with ``link_flags`` (default: ``flags``
+    and -shared).  remarks: a suffix; the compiler's stderr of each unit is kept at <object><suffix> (hipcc's resource remarks).
+    A failed compile raises BuildError with the compiler's message and leaves no stamp."""
+    out, root = os.path.abspath(str(out)), os.path.abspath(str(root))
+    jobs, link = command_lines(out, units, flags, compiler, link_flags, root, str(objdir) if objdir else os.path.join(root, "build", "obj"))
     cmds = [c for c, _ in jobs] + [link]
     if not force and _fresh(out, cmds, root) is not None:
         return out

@@ -15,14 +15,12 @@ from typing import Optional
 import numpy as np
 
 from . import abi
-from .abi import (CONVERGED, DIVERGED, EXPORTS, F32, F64, LIB_PATH, MAX_IT, RUNNING, STATUS_NAME,  # noqa: F401  (re-exported)
+from .abi import (CONVERGED, DIVERGED, EXPORTS, F32, F64, MAX_IT, RUNNING, STATUS_NAME,  # noqa: F401  (re-exported)
                   ControlBlock, GcsAdmmError, GraphDesc, HaloDesc, Params, State)
 from .graph import GcsGraph
 
 
-def load_library() -> C.CDLL:
-    """abi.load_library at this module's LIB_PATH (diagnostic tools point it at a variant build before they make a solver)"""
-    return abi.load_library(LIB_PATH)
+load_library = abi.load_library
 
 
 def halo_arrays(send_idx, recv_idx):

@@ -15,7 +15,7 @@ import os
 import numpy as np
 
 import sweep_cases as S
-from gcs_admm_amd.native_build import build_library
+from hostemu_lib import emu_library
 from gcs_admm_amd.scene import SWEEP_PAD, candidate_pairs, edge_arrays, informed_keep_array, region_path_views
 
 ROOT = S.ROOT
@@ -330,9 +330,7 @@ def declare(lib):
 
 def load_informed_emu():
     """tests/hostemu/informed_emu.cpp against csrc/informed_core.h, rebuilt when a source changes"""
-    out = build_library(os.path.join(ROOT, "tests", "hostemu", "libinformedemu.so"), [(EMU_SRC, [])],
-                        flags=["-O1", "-std=c++17", "-fPIC", "-I" + S.CSRC])
-    return declare(C.CDLL(out))
+    return declare(emu_library("informedemu"))
 
 
 _emu = []

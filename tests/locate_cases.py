@@ -13,15 +13,11 @@ completeness, which any correct rule of that shape meets."""
 from __future__ import annotations
 
 import ctypes as C
-import os
 
 import numpy as np
 
-from gcs_admm_amd.native_build import build_library
+from hostemu_lib import emu_library
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "gcs_admm_amd", "csrc")
-EMU_SRC = os.path.join(ROOT, "tests", "hostemu", "locate_emu.cpp")
 
 OUT, IN, UNDECIDED = 0, 1, 2
 EPS, TOL = 1e-6, 1e-9
@@ -185,8 +181,7 @@ def check_crafted(hits, names, polys, pts, expect):
 def load_locate_emu():
     """tests/hostemu/locate_emu.cpp against csrc/point_locate_core.h, rebuilt when a source changes.  -ffp-contract=off:
     only the written fma calls fuse, as in the kernel"""
-    out = build_library(os.path.join(ROOT, "tests", "hostemu", "liblocateemu.so"), [(EMU_SRC, [])], flags=["-O1", "-std=c++17", "-ffp-contract=off", "-fPIC", "-I" + CSRC])
-    lib = C.CDLL(out)
+    lib = emu_library("locateemu")
     lib.locate_emu_hits.restype = C.c_longlong
     lib.locate_emu_hits.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_double,
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong]

@@ -23,11 +23,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 from gcs_admm_amd.graph import convert_pt_to_polytope   # noqa: E402
-from gcs_admm_amd.native_build import build_library     # noqa: E402
+from hostemu_lib import emu_library     # noqa: E402
 from gcs_admm_amd.scene import SWEEP_PAD                 # noqa: E402
 from oracle import polytope_oracle as PO                 # noqa: E402
 
-CSRC = os.path.join(ROOT, "gcs_admm_amd", "csrc")
 EMU_SRC = os.path.join(ROOT, "tests", "hostemu", "lp_emu.cpp")
 
 TOL = 1e-9                          # the pipeline's overlap tolerance (build_graph_device)
@@ -242,8 +241,7 @@ def reference(name, n):
 # ------------------------------------------------------------------------------------------- the host build
 def load_lp_emu():
     """tests/hostemu/lp_emu.cpp against csrc/polytope_lp_core.h, rebuilt when a source changes"""
-    out = build_library(os.path.join(ROOT, "tests", "hostemu", "liblpemu.so"), [(EMU_SRC, [])], flags=["-O1", "-std=c++17", "-fPIC", "-I" + CSRC])
-    return C.CDLL(out)
+    return emu_library("lpemu")
 
 
 class HostLP:

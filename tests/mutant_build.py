@@ -6,6 +6,7 @@ import shutil
 from concurrent.futures import ThreadPoolExecutor
 
 from gcs_admm_amd.native_build import build_library
+from hostemu_lib import BASE
 
 CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gcs_admm_amd", "csrc")
 
@@ -25,7 +26,7 @@ def build_mutants(base, header, mutants, source, flags=(), more=()):
         with open(os.path.join(csrc, header), "w") as f:
             f.write(text)
         try:
-            return build_library(os.path.join(base, name, "libmutant.so"), [(source, []), *more], flags=["-O1", "-std=c++17", "-fPIC", "-I" + csrc, *flags],
+            return build_library(os.path.join(base, name, "libmutant.so"), [(source, []), *more], flags=[*BASE, "-I" + csrc, *flags],
                                  objdir=os.path.join(base, name))
         except RuntimeError as e:
             raise AssertionError(f"build of mutant {name} failed") from e

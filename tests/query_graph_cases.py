@@ -14,7 +14,7 @@ import numpy as np
 
 import sweep_cases as S
 from gcs_admm_amd.graph import _finish_graph
-from gcs_admm_amd.native_build import build_library
+from hostemu_lib import emu_library
 from gcs_admm_amd.scene import candidate_pairs, edge_arrays, query_graph_views
 
 ROOT = S.ROOT
@@ -170,9 +170,7 @@ def declare(lib):
 
 def load_query_graph_emu():
     """tests/hostemu/query_graph_emu.cpp against csrc/query_graph_core.h, rebuilt when a source changes"""
-    out = build_library(os.path.join(ROOT, "tests", "hostemu", "libquerygraphemu.so"), [(EMU_SRC, [])],
-                        flags=["-O1", "-std=c++17", "-fPIC", "-I" + S.CSRC])
-    return declare(C.CDLL(out))
+    return declare(emu_library("querygraphemu"))
 
 
 _emu = []

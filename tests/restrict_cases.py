@@ -28,14 +28,13 @@ import os
 import numpy as np
 
 from gcs_admm_amd.graph import chebyshev_center, convert_pt_to_polytope
-from gcs_admm_amd.native_build import build_library
+from hostemu_lib import emu_library
 from gcs_admm_amd.rounding import solve_path_restriction
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(ROOT, "gcs_admm_amd", "csrc")
 SRC = os.path.join(HERE, "hostemu", "restrict_emu.cpp")
-LIB = os.path.join(HERE, "hostemu", "librestrictemu.so")
 TOL, MAX_ITER = 1e-10, 100
 OK, BAD_ARG, UNSUPPORTED = 0, 1, 2
 RECORDS = {"benchmark1": 3.236065, "benchmark2": 7.413745, "benchmark3": 60.177021, "benchmark4": 32.627198}
@@ -445,17 +444,13 @@ def split_points(n, pp, flat):
 
 
 # ---- the host emulation ----
-def build_lib(out=LIB):
-    return build_library(out, [(SRC, [])], flags=["-std=c++17", "-fPIC", "-O2", "-I" + CSRC, "-I" + os.path.join(ROOT, "include")])
-
-
 _lib = None
 
 
 def emu():
     global _lib
     if _lib is None:
-        _lib = C.CDLL(build_lib())
+        _lib = emu_library("restrictemu")
         _lib.restrict_emu_error.restype = C.c_char_p
         _lib.restrict_emu_ws_doubles.restype = C.c_longlong
         _lib.restrict_emu_ws_doubles.argtypes = [C.c_int, C.c_longlong, C.c_longlong]

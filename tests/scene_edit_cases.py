@@ -5,16 +5,13 @@ element, with the flag and status of every pair that was there before the edit."
 from __future__ import annotations
 
 import ctypes as C
-import os
 
 import numpy as np
 
 import sweep_cases as S
-from gcs_admm_amd.native_build import build_library
+from hostemu_lib import emu_library
 from gcs_admm_amd.scene import candidate_pairs
 
-ROOT = S.ROOT
-EMU_SRC = os.path.join(ROOT, "tests", "hostemu", "scene_edit_emu.cpp")
 
 DIMS = (1, 2, 8)
 RESIDENT = (0, 1, 63, 64, 65, 200)
@@ -48,8 +45,7 @@ def tags(T):
 # ------------------------------------------------------------------------------------------- the host build
 def load_edit_emu():
     """tests/hostemu/scene_edit_emu.cpp against csrc/scene_edit_core.h, rebuilt when a source changes"""
-    out = build_library(os.path.join(ROOT, "tests", "hostemu", "libsceneeditemu.so"), [(EMU_SRC, [])], flags=["-O1", "-std=c++17", "-fPIC", "-I" + S.CSRC])
-    lib = C.CDLL(out)
+    lib = emu_library("sceneeditemu")
     p, i, ll, d = C.c_void_p, C.c_int, C.c_longlong, C.c_double
     lib.edit_emu_add.restype = ll
     lib.edit_emu_add.argtypes = [i, i, i, p, p, d, ll, p, p, p, p, p, p, p, p, ll, p]

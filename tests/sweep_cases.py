@@ -13,11 +13,9 @@ import os
 
 import numpy as np
 
-from gcs_admm_amd.native_build import build_library
+from hostemu_lib import emu_library
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "gcs_admm_amd", "csrc")
-EMU_SRC = os.path.join(ROOT, "tests", "hostemu", "sweep_emu.cpp")
 
 DIMS = (1, 2, 3, 8)
 SIZES = (1, 2, 65, 130, 1000)       # one box, one pair, one wavefront of boxes and one more, two and a tail, windows of several strides
@@ -87,8 +85,7 @@ def brute_force(lo, hi, pad):
 # ------------------------------------------------------------------------------------------- the host build
 def load_sweep_emu():
     """tests/hostemu/sweep_emu.cpp against csrc/box_sweep_core.h, rebuilt when a source changes"""
-    out = build_library(os.path.join(ROOT, "tests", "hostemu", "libsweepemu.so"), [(EMU_SRC, [])], flags=["-O1", "-std=c++17", "-fPIC", "-I" + CSRC])
-    lib = C.CDLL(out)
+    lib = emu_library("sweepemu")
     lib.sweep_emu_pairs.restype = C.c_longlong
     lib.sweep_emu_pairs.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_longlong]
     lib.sweep_emu_scan.restype = C.c_int

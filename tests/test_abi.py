@@ -154,13 +154,47 @@ def test_graph_desc_builder(columns):
         assert d0.inc_counted is None and d0.edge_counted is None and d0.vertex_program == 0 and d0.state_dtype == abi.F64
 
 
-def test_abi_imports_without_library(tmp_path):
-    """gcs_admm_amd.abi imports without the library and without torch; a missing library is an error only when it is loaded"""
+def _run(code):
     import subprocess
     import sys
-    code = ("import sys; sys.path.insert(0, %r); from gcs_admm_amd import abi; assert 'torch' not in sys.modules and not abi._libs\n"
-            "try: abi.load_library(%r)\nexcept RuntimeError as e: assert 'is missing' in str(e)\nelse: raise SystemExit(1)" % (ROOT, str(tmp_path / "none.so")))
-    subprocess.check_call([sys.executable, "-c", code])
+    subprocess.check_call([sys.executable, "-c", "import sys; sys.path.insert(0, %r)\n" % ROOT + code])
+
+
+def test_abi_imports_without_library(tmp_path):
+    """gcs_admm_amd.abi imports without the library and without torch; a missing library is an error only when it is loaded, and
+    after select_library both loaders (solver.load_library is abi's) name the selected path"""
+    _run("from gcs_admm_amd import abi; assert 'torch' not in sys.modules and abi._lib is None\n"
+         "abi.select_library(%r)\n"
+         "from gcs_admm_amd import solver\n"
+         "for load in (abi.load_library, solver.load_library):\n"
+         "    try: load()\n"
+         "    except RuntimeError as e: assert 'is missing' in str(e) and %r in str(e), e\n"
+         "    else: raise SystemExit(1)" % (str(tmp_path / "none.so"), str(tmp_path / "none.so")))
+
+
+def test_a_second_library_is_refused(tmp_path):
+    """one library per process: after a load, select_library takes the loaded path again and refuses every other (a stand-in for the
+    loaded library: the rule needs neither the build nor a GPU)"""
+    _run("import ctypes\nfrom gcs_admm_amd import abi\n"
+         "abi._lib = ctypes.CDLL(None); abi._lib._name = abi.LIB_PATH\n"
+         "abi.select_library(abi.LIB_PATH)\n"
+         "try: abi.select_library(%r)\n"
+         "except RuntimeError as e: assert 'already loaded' in str(e) and abi.LIB_PATH in str(e), e\n"
+         "else: raise SystemExit(1)\n"
+         "assert abi.LIB_PATH.endswith('libgcsadmm.so')" % str(tmp_path / "other.so"))
+
+
+def test_lib_path_is_read_in_abi_alone():
+    """the package and the tools reach the library's path through abi.select_library / abi.load_library only"""
+    seen = 0
+    for top in ("gcs_admm_amd", "tools"):
+        for d, _, files in os.walk(os.path.join(ROOT, top)):
+            for f in files:
+                if f.endswith(".py") and os.path.join(top, f) != os.path.join("gcs_admm_amd", "abi.py"):
+                    seen += 1
+                    text = open(os.path.join(d, f)).read()
+                    assert "LIB_PATH" not in text and "GCSADMM_PROBE_LIB" not in text and "GCSADMM_TIMING_LIB" not in text, os.path.join(d, f)
+    assert seen > 40
 
 
 def test_struct_layouts_match_header(tmp_path):

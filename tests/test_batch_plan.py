@@ -4,7 +4,6 @@ against the maxima of its members' own plans (those come from the create-plan sh
 refusal with its message, and the registers and scratch of the two batch kernels from the compiler's resource remarks.  What the GPU
 computes with a batch is checked by test_gpu_batch.py."""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
@@ -12,23 +11,17 @@ import pytest
 import test_create_plan as cp
 from gcs_admm_amd.cases import load_fixture
 from gcs_admm_amd.graph import lattice_boxes
+from hostemu_lib import emu_library
 from test_gpu_configs import _region_star
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "hostemu", "batch_plan_emu.cpp")
-LIB = os.path.join(HERE, "hostemu", "libbatchplanemu.so")
 OK, BAD_ARG, UNSUPPORTED = cp.OK, cp.BAD_ARG, cp.UNSUPPORTED
 WG256 = dict(vertex_program=3)       # what solver.DeviceSolver(program="workgroup256") asks for: the program a batch member runs
 MAX_SPECIAL_DEG = 256                # step_args.h
 
 
-def build_lib(out=LIB):
-    return cp.build_shim(out, SRC)
-
-
 @pytest.fixture(scope="module")
 def lib():
-    lib = C.CDLL(build_lib())
+    lib = emu_library("batchplanemu")
     lib.batch_emu_error.restype = C.c_char_p
     lib.batch_emu_get.restype = lib.batch_emu_member.restype = C.c_double
     return lib

@@ -4,37 +4,24 @@ The descriptor is the one solver.DeviceSolver hands to gcsadmm_create.  Pinned h
 rules, the wavefront packing, the schedule knobs of include/gcsadmm.h, the region-terminal layout, and the refusals with their
 messages.  What the GPU runs with these plans is checked by test_gpu_parity.py / test_gpu_configs.py."""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
 
 from conftest import BENCHMARKS, star_case
-from gcs_admm_amd.build import T512
 from gcs_admm_amd.cases import load_fixture
 from gcs_admm_amd.graph import convert_pt_to_polytope, graph_from_sets, lattice_boxes
 from gcs_admm_amd.abi import graph_desc
-from gcs_admm_amd.native_build import build_library
+from hostemu_lib import emu_path
 from test_gpu_configs import _region_row, _region_star
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-CSRC = os.path.join(ROOT, "gcs_admm_amd", "csrc")
-SRC, SIZES = os.path.join(HERE, "hostemu", "plan_emu.cpp"), os.path.join(HERE, "hostemu", "wg_sizes.cpp")
-LIB = os.path.join(HERE, "hostemu", "libplanemu.so")
 OK, BAD_ARG, UNSUPPORTED = 0, 1, 2          # gcsadmm_status
 KB = 1024
 
 
-def build_shim(out, src, flags=("-O1",), extra=()):
-    """a plan shim: wg_sizes.cpp at 256 and at 512 threads (build.T512, as vertex_wg.hip is built), linked with ``src`` (compiled with
-    ``extra`` on top).  Every shim built with the same flags links the same two sizing objects: they are compiled once."""
-    cxx = ["-std=c++17", "-fPIC", "-I" + CSRC, "-I" + os.path.join(ROOT, "include")] + list(flags)
-    return build_library(out, [(SIZES, []), (SIZES, T512), (src, list(extra))], flags=cxx)
-
-
-def build_lib(out=LIB, flags=("-O1",)):
-    return build_shim(out, SRC, flags)
+def build_lib(out=None, flags=()):
+    """the plan shim of hostemu_lib.py; ``out`` and ``flags`` are for builds beside it (tools/sanitize_cpu.sh)"""
+    return emu_path("planemu", out, flags)
 
 
 def load(path):

@@ -3,7 +3,6 @@ checked without a GPU, the way test_create_plan.py reaches make_create_plan (tes
 in one edge workgroup, every generic vertex on the in-LDS workgroup program, no region terminal, a whole (unpartitioned) handle -- case
 by case, and the LDS request of the launch that carries the tail."""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
@@ -11,15 +10,13 @@ import pytest
 from fused_tail_cases import EDGE_BLOCK, largest_fused_lattice, path3, smallest_unfused_lattice
 from gcs_admm_amd.cases import load_fixture
 from gcs_admm_amd.graph import lattice_boxes
-from test_create_plan import HERE, build_shim, descriptor
-
-SRC = os.path.join(HERE, "hostemu", "fused_plan_emu.cpp")
-LIB = os.path.join(HERE, "hostemu", "libfusedplanemu.so")
+from hostemu_lib import emu_library
+from test_create_plan import descriptor
 
 
 @pytest.fixture(scope="module")
 def lib():
-    lib = C.CDLL(build_shim(LIB, SRC))
+    lib = emu_library("fusedplanemu")
     lib.fused_plan_error.restype = C.c_char_p
     return lib
 

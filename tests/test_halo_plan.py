@@ -5,22 +5,18 @@ numpy rule of test_partition.py::test_halo_message_layout_over_gloo as well), an
 boundary.  The last three tests build the header with one seeded error each and require these checks to fail.  What the GPU does with
 these plans is checked by test_gpu_configs.py (halo pack / unpack, overlapped against serial, the strips)."""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
 
+import hostemu_lib as H
 import test_create_plan as cp
 from gcs_admm_amd.abi import HaloDesc
-from gcs_admm_amd.build import T512
 from gcs_admm_amd.graph import lattice_boxes
 from gcs_admm_amd.partition import build_partition, strip_owner
 from gcs_admm_amd.solver import halo_arrays
 from mutant_build import build_mutants
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "hostemu", "halo_plan_emu.cpp")
-LIB = os.path.join(HERE, "hostemu", "libhaloplanemu.so")
 OK, BAD_ARG = cp.OK, cp.BAD_ARG
 WAVES = dict(vertex_program=1)       # every generic vertex on the wavefront program, as test_create_plan.py forces it
 
@@ -32,7 +28,7 @@ def prepare(lib):
 
 @pytest.fixture(scope="module")
 def lib():
-    return prepare(C.CDLL(cp.build_shim(LIB, SRC)))
+    return prepare(H.emu_library("haloplanemu"))
 
 
 def i32(a):
@@ -270,8 +266,8 @@ MUTANTS = {
 
 @pytest.fixture(scope="module")
 def builds(tmp_path_factory):
-    libs = build_mutants(tmp_path_factory.mktemp("halo_mutants"), "halo_plan.h", MUTANTS, SRC, flags=["-I" + os.path.join(cp.ROOT, "include")],
-                         more=[(cp.SIZES, []), (cp.SIZES, T512)])
+    *sizes, (source, _) = H.sources(H.LIBRARIES["haloplanemu"][0])
+    libs = build_mutants(tmp_path_factory.mktemp("halo_mutants"), "halo_plan.h", MUTANTS, source, flags=[H.INCLUDE], more=sizes)
     return {k: prepare(v) for k, v in libs.items()}
 
 

@@ -9,27 +9,18 @@ implementations that differ in operation order agree to ~1e-8 typically and to t
 the worst case."""
 from gcs_admm_amd import IPM_TOL
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
 
 from gcs_admm_amd.cases import load_fixture
-from gcs_admm_amd.native_build import build_library
+from hostemu_lib import emu_library
 from solve_agreement import Agreement, NewtonParity, oracle_step
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-
-
-def build_emu():
-    return build_library(os.path.join(HERE, "hostemu", "libemu.so"), [(os.path.join(HERE, "hostemu", "emu.cpp"), [])],
-                         flags=["-O1", "-std=c++17", "-fPIC", "-I" + os.path.join(ROOT, "gcs_admm_amd", "csrc")])
 
 
 @pytest.fixture(scope="module")
 def emu():
-    return C.CDLL(build_emu())
+    return emu_library("emu")
 
 
 def _p(a):

@@ -3,7 +3,6 @@ the handle's device-memory workspace on the GPU) compiled for the host (tests/ho
 equals the in-LDS form bit for bit (same layout, same arithmetic, same order) for n = 1, 2, 3, 6, 8, generic rows and BOX, with the
 tasks of every region in ascending and in descending order; on hubs too large for LDS it matches the CPU oracle, warm and cold."""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
@@ -11,22 +10,13 @@ import pytest
 from gcs_admm_amd import IPM_TOL
 from gcs_admm_amd.cases import load_fixture
 from gcs_admm_amd.graph import lattice_boxes
-from gcs_admm_amd.native_build import build_library
+from hostemu_lib import emu_library
 from solve_agreement import Agreement, NewtonParity, oracle_step
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-CSRC = os.path.join(ROOT, "gcs_admm_amd", "csrc")
 
 
 @pytest.fixture(scope="module")
 def libs():
-    src = os.path.join(HERE, "hostemu", "wg_split_emu.cpp")
-    out = {}
-    for rev, name, flags in ((False, "libwgsplitemu.so", []), (True, "libwgsplitemu_rev.so", ["-DGCS_WG_REVERSE"])):
-        lib = C.CDLL(build_library(os.path.join(HERE, "hostemu", name), [(src, flags)], flags=["-O1", "-std=c++17", "-fPIC", "-I" + CSRC]))
-        out[rev] = getattr(lib, "wg_split_emu_vertex_step_rev" if rev else "wg_split_emu_vertex_step")
-    return out
+    return {False: emu_library("wgsplitemu").wg_split_emu_vertex_step, True: emu_library("wgsplitemu_rev").wg_split_emu_vertex_step_rev}
 
 
 def _p(a):

@@ -6,31 +6,20 @@ order-dependent operations are the floating-point sums of the workgroup reductio
 (the emulation poisons it with NaN).  The GPU parity tests proper are test_gpu_parity.py / test_gpu_configs.py."""
 from gcs_admm_amd import IPM_TOL
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
 
 from gcs_admm_amd.cases import load_fixture
 from gcs_admm_amd.graph import lattice_boxes
-from gcs_admm_amd.native_build import build_library
+from hostemu_lib import emu_library
 from solve_agreement import Agreement, NewtonParity, oracle_step
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-CSRC = os.path.join(ROOT, "gcs_admm_amd", "csrc")
-
-
-def build_libs():
-    """[ascending, descending task order] (rebuilt when the program changes)"""
-    return [build_library(os.path.join(HERE, "hostemu", name), [(os.path.join(HERE, "hostemu", "wg_emu.cpp"), flags)],
-                          flags=["-O1", "-std=c++17", "-fPIC", "-I" + CSRC])
-            for name, flags in (("libwgemu.so", []), ("libwgemu_rev.so", ["-DGCS_WG_REVERSE"]))]
 
 
 @pytest.fixture(scope="module")
 def libs():
-    return [C.CDLL(so) for so in build_libs()]
+    """[ascending, descending task order] (rebuilt when the program changes)"""
+    return [emu_library("wgemu"), emu_library("wgemu_rev")]
 
 
 def _p(a):

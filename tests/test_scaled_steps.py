@@ -21,8 +21,9 @@ from gcs_admm_amd import IPM_TOL
 from mutant_build import build_mutants
 from scaled_cases import Judgement, graph, pattern
 from solve_agreement import f32_round, generic_mask, oracle_step
-from test_hostemu import WarmRecords as WaveRecords, build_emu
-from test_hostemu_wg import WarmRecords as WgRecords, build_libs
+from hostemu_lib import emu_library
+from test_hostemu import WarmRecords as WaveRecords
+from test_hostemu_wg import WarmRecords as WgRecords
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -33,20 +34,17 @@ def _p(a):
 
 @pytest.fixture(scope="module")
 def wave():
-    return C.CDLL(build_emu())
+    return emu_library("emu")
 
 
 @pytest.fixture(scope="module")
 def wg():
-    return C.CDLL(build_libs()[0])
+    return emu_library("wgemu")
 
 
 @pytest.fixture(scope="module")
 def term():
-    from gcs_admm_amd.native_build import build_library
-    csrc = os.path.join(os.path.dirname(HERE), "gcs_admm_amd", "csrc")
-    return C.CDLL(build_library(os.path.join(HERE, "hostemu", "libtermemu.so"), [(os.path.join(HERE, "hostemu", "term_emu.cpp"), [])],
-                                flags=["-O1", "-std=c++17", "-fPIC", "-I" + csrc]))
+    return emu_library("termemu")
 
 
 def _state_args(g, zedge, mu, rho, mu_scale, f32):

@@ -6,14 +6,11 @@ No GPU."""
 from __future__ import annotations
 
 import ctypes as C
-import os
 
 import pytest
 
-from gcs_admm_amd.native_build import build_library
+from hostemu_lib import emu_library
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-CSRC = os.path.join(os.path.dirname(HERE), "gcs_admm_amd", "csrc")
 
 CENTERS, BOXES, PAIRS, OVERLAPS, HITS, GRAPH = 1, 2, 4, 8, 16, 32
 ALL = 63
@@ -51,9 +48,7 @@ CALLS = [pytest.param(i, id=row[0].split(":")[0].replace(" ", "_") + f"_{i}") fo
 
 @pytest.fixture(scope="module")
 def emu():
-    out = build_library(os.path.join(HERE, "hostemu", "libscenestageemu.so"), [(os.path.join(HERE, "hostemu", "scene_stage_emu.cpp"), [])],
-                        flags=["-O1", "-std=c++17", "-fPIC", "-I" + CSRC])
-    lib = C.CDLL(out)
+    lib = emu_library("scenestageemu")
     lib.stage_emu_calls.restype = C.c_int
     lib.stage_emu_need.restype = C.c_char_p
     lib.stage_emu_need.argtypes = [C.c_uint, C.c_int]

@@ -167,12 +167,8 @@ def test_a_point_terminal_is_the_limit_of_a_small_region():
 # ---- the HIP library's solve (gcs_admm_amd/csrc/terminal_region.h) compiled for the host, against the oracle ----
 @pytest.fixture(scope="module")
 def term_emu():
-    import os
-    from gcs_admm_amd.native_build import build_library
-    here = os.path.dirname(os.path.abspath(__file__))
-    csrc = os.path.join(os.path.dirname(here), "gcs_admm_amd", "csrc")
-    return C.CDLL(build_library(os.path.join(here, "hostemu", "libtermemu.so"), [(os.path.join(here, "hostemu", "term_emu.cpp"), [])],
-                                flags=["-O1", "-std=c++17", "-fPIC", "-I" + csrc]))
+    from hostemu_lib import emu_library
+    return emu_library("termemu")
 
 
 def emu_terminal(lib, n, A, b, cen, d, d_in, is_src, T, rho, tol=IPM_TOL, warm=None):

@@ -2,7 +2,6 @@
 of the workgroup program (edge blocks in a device-memory workspace), the workspace layout, the refusals.  The shim is plan_emu.cpp with
 the split fields added (tests/hostemu/plan_ws_emu.cpp); descriptors and plans are read as in test_create_plan.py."""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
@@ -10,19 +9,17 @@ import pytest
 from conftest import BENCHMARKS, star_case
 from gcs_admm_amd.cases import load_fixture
 from gcs_admm_amd.graph import graph_from_sets, lattice_boxes
-from test_create_plan import BAD_ARG, KB, OK, UNSUPPORTED, build_shim, descriptor, make, _p
+from hostemu_lib import emu_library
+from test_create_plan import BAD_ARG, KB, OK, UNSUPPORTED, descriptor, make, _p
 from test_gpu_vertex_workspace import hub_case
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "hostemu", "plan_ws_emu.cpp")
-LIB = os.path.join(HERE, "hostemu", "libplanwsemu.so")
 OLD_MSG = "a vertex sub-problem (degree x facets) does not fit the 160 KB of LDS of a CU"
 POLY_MSG = "a vertex's border system and polytope do not fit the 160 KB of LDS of a CU"
 
 
 @pytest.fixture(scope="module")
 def lib():
-    lib = C.CDLL(build_shim(LIB, SRC, extra=["-I" + os.path.join(HERE, "hostemu")]))
+    lib = emu_library("planwsemu")
     lib.plan_emu_error.restype = C.c_char_p
     lib.plan_emu_get.restype = C.c_double
     lib.plan_emu_vec.restype = C.c_longlong

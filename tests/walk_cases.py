@@ -2,17 +2,13 @@
 reach every branch of the rule, the four benchmarks under the oracle's activations, the host build of the kernel, and the mirror's
 answers computed once per (case, dtype, seed, walk)."""
 import ctypes as C
-import os
 from types import SimpleNamespace
 
 import numpy as np
 
 from gcs_admm_amd import walks as W
-from gcs_admm_amd.native_build import build_library
+from hostemu_lib import emu_library
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-CSRC = os.path.join(ROOT, "gcs_admm_amd", "csrc")
 SEEDS = (0, 7, 2 ** 63 + 5)
 WALKS = 21                                   # walks 0 .. 20: what rounding draws with M = 20
 DTYPES = (np.float64, np.float32)
@@ -116,9 +112,7 @@ _lib = []
 
 def emu():
     if not _lib:
-        out = build_library(os.path.join(HERE, "hostemu", "libwalkemu.so"), [(os.path.join(HERE, "hostemu", "walk_emu.cpp"), [])],
-                            flags=["-O1", "-std=c++17", "-fPIC", "-I" + CSRC])
-        lib = C.CDLL(out)
+        lib = emu_library("walkemu")
         lib.walk_emu_sample.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 4 + [C.c_int] * 3 + [C.c_uint64] + [C.c_int] * 3 + [C.c_void_p] * 3
         for f, args in ((lib.walk_emu_weight, [C.c_double]), (lib.walk_emu_mix, [C.c_uint64, C.c_uint32, C.c_uint32]), (lib.walk_emu_mulhi, [C.c_uint64] * 2)):
             f.argtypes, f.restype = args, C.c_uint64

@@ -1,7 +1,7 @@
 #!/bin/bash
 # copies the summaries tools/profile_round.sh left under gpurun_out/r04p into profiles/r04 (tracked): every file with the version tag
 # given as $1, and the HBM counter summaries also without a tag (bench.py reads profiles/r04/<workload>_hbm_counters.json for
-# roofline.traffic)
+# roofline.traffic).  Copies files only: it starts nothing on the GPU, and ends at the first copy that fails.
 set -e
 tag=${1:?version tag, e.g. v2}
 S=gpurun_out/r04p; D=profiles/r04

@@ -1,7 +1,7 @@
 """Host replay of steps of tools/fuzz_soak.py: the oracle's (warm) vertex step, a cold tight solve of the same sub-problems as the truth, and the
 host builds of both device programs (tests/hostemu), per step: worst entry of each against the truth.  No GPU.
 python3 tools/fuzz_replay.py seed [seed ...]"""
-import ctypes as C, os, sys
+import os, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tools")); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -10,9 +10,9 @@ from gcs_admm_amd.graph import graph_from_sets
 from oracle.oracle import Oracle
 from scale_demo import polygon_scene
 import test_hostemu as TW, test_hostemu_wg as TG
+from hostemu_lib import emu_library
 
-emu = C.CDLL(TW.build_emu())
-wg = C.CDLL(TG.build_libs()[0])
+emu, wg = emu_library("emu"), emu_library("wgemu")
 for seed in map(int, sys.argv[1:]):
     rng = np.random.default_rng(100 + seed)
     As, bs = polygon_scene(5 + seed % 3, seed=seed, m=3 + seed % 5)

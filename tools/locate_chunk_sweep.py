@@ -1,11 +1,11 @@
 """What LOCATE_CHUNK (regions per workgroup of locate_kernel, csrc/point_locate_core.h) is measured against: the time of one
 ``DeviceScene.locate`` call for builds of the library with other chunk sizes, on the scenes of tools/query_bench.py.
 
-  python tools/locate_chunk_sweep.py --build [--chunks 64 256 1024]     # compile the variants (hipcc, no GPU needed)
+  python tools/locate_chunk_sweep.py --build [--chunks 64 256 1024]     # compile the variants (no GPU needed)
   python tools/locate_chunk_sweep.py [--chunks 64 256 1024]             # time them: one fresh process per variant, two rounds, alternated
 
-A variant is csrc/polytope_lp.hip compiled with -DGCS_LOCATE_CHUNK=<c> and linked with the other objects of the in-tree build into
-gcs_admm_amd/libgcsadmm_chunk<c>.so.  Median of 51 calls after 5 warm-up calls, host clock (the call ends in a copy from the device).
+A variant is ``build.variant("locate_chunk", n=<c>)``: csrc/polytope_lp.hip compiled with -DGCS_LOCATE_CHUNK=<c> and linked with the
+other objects of the in-tree build into gcs_admm_amd/libgcsadmm_chunk<c>.so.  Median of 51 calls after 5 warm-up calls, host clock (the call ends in a copy from the device).
 One JSON line per (variant, round, scene, Q).
 """
 import argparse, json, os, subprocess, sys, time
@@ -14,25 +14,10 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 
-def variant_path(chunk):
-    from gcs_admm_amd import build
-    return os.path.join(build.HERE, f"libgcsadmm_chunk{chunk}.so")
-
-
-def build_variant(chunk):
-    from gcs_admm_amd import build
-    build.build()
-    flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I" + os.path.join(build.ROOT, "include"), "-I" + build.CSRC]
-    obj = os.path.join(build.HERE, f"polytope_lp_chunk{chunk}.o")
-    subprocess.check_call([build.hipcc()] + flags + [f"-DGCS_LOCATE_CHUNK={chunk}", "-c", build.LP, "-o", obj])
-    objs = [obj if name == "polytope_lp.o" else os.path.join(build.HERE, name) for _, name, _ in build.UNITS]
-    subprocess.check_call([build.hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC"] + objs + ["-o", variant_path(chunk)])
-
-
 def child(chunk, rnd):
     import numpy as np
-    from gcs_admm_amd import abi
-    abi.LIB_PATH = variant_path(chunk)               # before the first load: every scene of this process runs the variant
+    from gcs_admm_amd import abi, build
+    abi.select_library(build.variant("locate_chunk", n=chunk))               # before the first load: every scene of this process runs the variant
     from bench_overlap import scene_polys
     from gcs_admm_amd.scene import DeviceScene
     for n, P in ((2, 1000), (2, 20000), (6, 1000)):
@@ -61,12 +46,10 @@ def main():
     if args.child:
         return child(*args.child)
     if args.build:
+        from gcs_admm_amd import build
         for c in args.chunks:
-            build_variant(c)
+            print(build.variant("locate_chunk", n=c))
         return
-    missing = [c for c in args.chunks if not os.path.exists(variant_path(c))]
-    if missing:
-        raise SystemExit(f"variants {missing} are not built: run with --build first")
     for rnd in range(2):
         for c in args.chunks:
             subprocess.check_call([sys.executable, os.path.abspath(__file__), "--child", str(c), str(rnd)], timeout=120)

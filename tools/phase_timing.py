@@ -1,15 +1,17 @@
-"""Diagnostic: share of wave cycles per barrier-separated phase of the vertex kernel (needs the\n-DGCS_PHASE_TIMING build: hipcc ... -DGCS_PHASE_TIMING -o gcs_admm_amd/libgcsadmm_timing.so).  Read its SHARES, not its length."""
+"""Diagnostic: share of wave cycles per barrier-separated phase of the vertex kernel, from the -DGCS_PHASE_TIMING build
+(python -m gcs_admm_amd.build --variant phase).  Read its SHARES, not its length.
+usage: python tools/phase_timing.py [s10k] [benchmark4]      (default: both)"""
 import sys, os, ctypes as C, numpy as np
-sys.path.insert(0, os.getcwd())
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
-from gcs_admm_amd import solver
-solver.LIB_PATH = os.path.join(os.getcwd(), "gcs_admm_amd", "libgcsadmm_timing.so")
+from gcs_admm_amd import abi, build, solver
+abi.select_library(build.variant("phase"))
 from gcs_admm_amd.graph import lattice_boxes
 from gcs_admm_amd.cases import load_fixture
 names = ["setup", "targets", "dT:reduce", "decide", "start point",
          "passA+blockfactor+3 chunk reductions", "border_factor+affine", "passB+reduce", "border_sigma", "corr_rhs+reduce",
          "border_corr_solve", "passD+reduce", "border_alpha", "update(passE)"]
-for wl in ("s10k", "benchmark4"):
+for wl in sys.argv[1:] or ("s10k", "benchmark4"):
     g = lattice_boxes(100, 100, seed=0) if wl == "s10k" else load_fixture("benchmark4")[1]
     d = solver.DeviceSolver(g, "f32" if wl == "s10k" else "f64", device=0, program="wavefront", columns="edge" if wl == "s10k" else "incidence")
     d.reset(max_it=1000, eps_abs=0.0, eps_rel=0.0)
@@ -22,6 +24,7 @@ for wl in ("s10k", "benchmark4"):
     d.lib.gcsadmm_debug_phase_cycles(out); cyc = np.array(list(out), dtype=np.float64) - before
     tot = cyc.sum()
     print(wl, "total wave-cycles (s_memtime ticks) over 20 steps: %.3e" % tot)
+    print("  inner failures of the stamped kernels (they use scratch, profiles/diagnostic_builds): %d" % d.read_control().inner_failures)
     for i, n in enumerate(names):
         print("  %-28s %6.2f %%" % (n, 100 * cyc[i] / tot))
     sub = (C.c_ulonglong * 16)()

@@ -11,30 +11,15 @@ side, host clocks around calls that end in a copy from the device; min and max a
 What EDIT_CHUNK (targets per workgroup of cross_kernel, csrc/scene_edit_core.h) is measured against: the ``DeviceScene.add_regions``
 call for builds of the library with other chunk sizes, on the same scenes.
 
-  python tools/scene_edit_bench.py --build [--chunks 64 256 1024]      # compile the variants (hipcc, no GPU needed)
+  python tools/scene_edit_bench.py --build [--chunks 64 256 1024]      # compile the variants (no GPU needed)
   python tools/scene_edit_bench.py --sweep [--chunks 64 256 1024]      # time them: one fresh process per variant, two rounds, alternated
 
-A variant is csrc/polytope_lp.hip compiled with -DGCS_EDIT_CHUNK=<c> and linked with the other objects of the in-tree build into
-gcs_admm_amd/libgcsadmm_editchunk<c>.so.  One JSON line per measurement.
+A variant is ``build.variant("edit_chunk", n=<c>)``: csrc/polytope_lp.hip compiled with -DGCS_EDIT_CHUNK=<c> and linked with the other
+objects of the in-tree build into gcs_admm_amd/libgcsadmm_editchunk<c>.so.  One JSON line per measurement.
 """
 import argparse, json, os, subprocess, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-
-
-def variant_path(chunk):
-    from gcs_admm_amd import build
-    return os.path.join(build.HERE, f"libgcsadmm_editchunk{chunk}.so")
-
-
-def build_variant(chunk):
-    from gcs_admm_amd import build
-    build.build()
-    flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I" + os.path.join(build.ROOT, "include"), "-I" + build.CSRC]
-    obj = os.path.join(build.HERE, f"polytope_lp_editchunk{chunk}.o")
-    subprocess.check_call([build.hipcc()] + flags + [f"-DGCS_EDIT_CHUNK={chunk}", "-c", build.LP, "-o", obj])
-    objs = [obj if name == "polytope_lp.o" else os.path.join(build.HERE, name) for _, name, _ in build.UNITS]
-    subprocess.check_call([build.hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC"] + objs + ["-o", variant_path(chunk)])
 
 
 def lattice(spec):
@@ -107,8 +92,8 @@ def measure(spec, adds, warm=2, reps=11, rebuilds=5):
 
 def child(chunk, rnd, lattices, adds):
     import torch  # noqa: F401
-    from gcs_admm_amd import abi
-    abi.LIB_PATH = variant_path(chunk)               # before the first load: every scene of this process runs the variant
+    from gcs_admm_amd import abi, build
+    abi.select_library(build.variant("edit_chunk", n=chunk))               # before the first load: every scene of this process runs the variant
     for spec in lattices:
         polys = lattice(spec)
         for K in adds:
@@ -129,13 +114,11 @@ def main():
     if args.child:
         return child(*args.child, args.lattices, args.adds)
     if args.build:
+        from gcs_admm_amd import build
         for c in args.chunks:
-            build_variant(c)
+            print(build.variant("edit_chunk", n=c))
         return
     if args.sweep:
-        missing = [c for c in args.chunks if not os.path.exists(variant_path(c))]
-        if missing:
-            raise SystemExit(f"variants {missing} are not built: run with --build first")
         for rnd in range(2):
             for c in args.chunks:
                 subprocess.check_call([sys.executable, os.path.abspath(__file__), "--child", str(c), str(rnd), "--lattices", *args.lattices,

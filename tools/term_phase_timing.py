@@ -5,8 +5,8 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tools"))
 import torch
-from gcs_admm_amd import solver
-solver.LIB_PATH = os.path.join(ROOT, "gcs_admm_amd", "libgcsadmm_timing.so")
+from gcs_admm_amd import abi, build, solver
+abi.select_library(build.variant("timing"))
 from scale_demo import polygon_scene
 from gcs_admm_amd.graph import graph_from_sets
 NAMES = {0: "slacks + reduction", 1: "stop test + cone scaling (thread 0)", 2: "block Hessians", 3: "Cholesky", 4: "X, S", 5: "right-hand sides", 6: "X' rhs, H^-1 rhs",

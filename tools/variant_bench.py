@@ -3,8 +3,8 @@
 import os, sys, json
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from gcs_admm_amd import solver
-solver.LIB_PATH = os.path.abspath(sys.argv[1])
+from gcs_admm_amd import abi, solver
+abi.select_library(sys.argv[1])
 import bench
 wl = sys.argv[2]; steps = int(sys.argv[3]) if len(sys.argv) > 3 else 20
 small = wl in ("benchmark1", "benchmark2", "benchmark3")

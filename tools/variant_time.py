@@ -1,6 +1,6 @@
-"""Diagnostic: vertex-kernel time of library variants (e.g. builds with -DGCS_DUP=k, which execute one part of the
-border factorisation twice; the time added is that part's cost in place).
-usage: python tools/variant_time.py lib1.so [lib2.so ...]   (one subprocess per library)"""
+"""Diagnostic: vertex-kernel time of library variants (e.g. ``python -m gcs_admm_amd.build --variant dup k=1``: builds with -DGCS_DUP=k
+execute one part of the border factorisation twice; the time added is that part's cost in place).
+usage: python tools/variant_time.py lib1.so [lib2.so ...]   (one subprocess per library; --all: every libgcsadmm_dup*.so built)"""
 import sys, os, subprocess, json
 if len(sys.argv) > 2 or (len(sys.argv) == 2 and sys.argv[1] == "--all"):
     libs = sys.argv[1:] if sys.argv[1] != "--all" else sorted(p for p in os.listdir("gcs_admm_amd") if p.startswith("libgcsadmm_dup"))
@@ -10,8 +10,8 @@ if len(sys.argv) > 2 or (len(sys.argv) == 2 and sys.argv[1] == "--all"):
     sys.exit(0)
 sys.path.insert(0, os.getcwd())
 import torch
-from gcs_admm_amd import solver
-solver.LIB_PATH = os.path.abspath(sys.argv[1])
+from gcs_admm_amd import abi, solver
+abi.select_library(sys.argv[1])
 from gcs_admm_amd.graph import lattice_boxes
 from gcs_admm_amd.cases import load_fixture
 out = {}

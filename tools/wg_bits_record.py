@@ -8,7 +8,6 @@ A change that touches no floating-point operation of the program (address arithm
 the fixture byte for byte; the file carries the compiler's version, since bits are a property of compiler plus source."""
 import argparse
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -30,8 +29,7 @@ def case_id(c):
 
 def compiler_version():
     from gcs_admm_amd import build
-    text = subprocess.check_output([build.hipcc(), "--version"], text=True)
-    return "\n".join(line for line in text.splitlines() if "version" in line)
+    return "\n".join(line for line in build.compiler_version().splitlines() if "version" in line)
 
 
 def graph_of(spec):
@@ -63,8 +61,8 @@ def main():
     ap.add_argument("--lib", help="a build of the library other than the in-tree one")
     args = ap.parse_args()
     if args.lib:
-        from gcs_admm_amd import solver
-        solver.LIB_PATH = os.path.abspath(args.lib)
+        from gcs_admm_amd import abi
+        abi.select_library(args.lib)
     data = {"compiler": np.array(compiler_version())}
     for c in CASES:
         for name, arr in run_case(c).items():

@@ -1,17 +1,19 @@
 """A/B yardstick for the workgroup vertex program: whole-solve s_memtime ticks per workgroup (mean over launches) from a
 -DGCS_WG_BLOCKTIME build (two s_memtime reads per solve: far less intrusive than the region stamps).
-usage: python tools/wg_blocktime.py <lib.so> [<lib2.so> ...]      (development tool; builds: tools/build_variant.sh)"""
-import ctypes as C, os, sys
+usage: python tools/wg_blocktime.py [--workloads benchmark4 lat2 lat6] [<lib.so> ...]
+Default library: ``build.variant("blocktime")``, the ticks in the 512-thread object -- the one graphs of at most one workgroup per CU such
+as benchmark4 and the two lattices run; ``threads=256`` puts them into the other.  One fresh process per (workload, library)."""
+import argparse, ctypes as C, os, subprocess, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import torch
-from gcs_admm_amd import solver
+from gcs_admm_amd import abi, build, solver
 from gcs_admm_amd.cases import load_fixture
 from gcs_admm_amd.graph import lattice_boxes
 
 def run(lib, wl):
-    solver.LIB_PATH = os.path.abspath(lib); solver._lib = None
+    abi.select_library(lib)
     if wl == "benchmark4": g, dt = load_fixture("benchmark4")[1], "f64"
     elif wl == "lat6": g, dt = lattice_boxes(16, 16, n=6, seed=0), "f32"
     elif wl == "lat2": g, dt = lattice_boxes(16, 16, seed=0), "f32"
@@ -28,11 +30,17 @@ def run(lib, wl):
     print(f"{os.path.basename(lib):28s} {wl:10s} ticks/solve: max {t1.max():8.0f} mean {t1.mean():8.0f}   per Newton iteration: mean {np.mean(t1 / i1):7.0f}   "
           f"{steps / el:7.1f} it/s", flush=True)
     if os.environ.get("WG_BLOCKTIME_TOP"):
-        vt = d.wg_vertices() if hasattr(d, "wg_vertices") else None
         for b in np.argsort(-t1)[:int(os.environ["WG_BLOCKTIME_TOP"])]:
             print(f"    workgroup {b:2d}: {t1[b]:8.0f} ticks, {i1[b]:5.2f} Newton iterations, {t1[b] / i1[b]:7.0f} ticks each", flush=True)
 
-libs = sys.argv[1:]
-for wl in (os.environ.get("WG_BLOCKTIME_WL", "benchmark4,lat2,lat6").split(",")):
-    for lib in libs:
-        run(lib, wl)
+ap = argparse.ArgumentParser()
+ap.add_argument("libs", nargs="*")
+ap.add_argument("--workloads", nargs="*", default=["benchmark4", "lat2", "lat6"])
+ap.add_argument("--child", action="store_true")
+args = ap.parse_args()
+if args.child:
+    run(args.libs[0], args.workloads[0])
+else:
+    for wl in args.workloads:
+        for lib in args.libs or [build.variant("blocktime")]:
+            subprocess.check_call([sys.executable, os.path.abspath(__file__), "--child", "--workloads", wl, "--", lib], timeout=300)

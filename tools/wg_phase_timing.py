@@ -5,8 +5,8 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import torch
-from gcs_admm_amd import solver
-solver.LIB_PATH = os.path.abspath(os.environ.get("GCSADMM_TIMING_LIB", os.path.join(ROOT, "gcs_admm_amd", "libgcsadmm_timing.so")))
+from gcs_admm_amd import abi, build, solver
+abi.select_library(build.variant("timing"))
 from gcs_admm_amd.cases import load_fixture
 from gcs_admm_amd.graph import lattice_boxes
 
