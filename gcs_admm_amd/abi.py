@@ -123,6 +123,9 @@ PROTOTYPES = {
     # the informed region set of every query of a batch (csrc/informed_core.h)
     "gcsadmm_scene_region_paths": ([_p, _i, _p, _p, _p, _i] + [_p] * 4, _i),
     "gcsadmm_scene_informed_regions": ([_p, _i, _p, _p, _d, _p, _p], _i),
+    # the query graphs of a batch on each query's kept regions (csrc/induced_graph_core.h)
+    "gcsadmm_scene_induced_sizes": ([_p, _i] + [_p] * 6, _i),
+    "gcsadmm_scene_induced_query_graphs": ([_p, _i, _p, _p, _p, _p, _i] + [_p] * 9, _i),
     # the candidate paths of the rounding step, drawn on the device (gcs_admm_amd/walks.py)
     "gcsadmm_walks_create": ([_i] + [_p] * 7 + [_i, _p], _i),
     "gcsadmm_walks_destroy": ([_p], None),

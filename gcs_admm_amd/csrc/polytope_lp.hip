@@ -25,7 +25,8 @@
 // restrict_plan.h decides), the queries on a decided scene (locate_kernel: point_locate_core.h), its edits (gcsadmm_scene_add_regions,
 // gcsadmm_scene_remove_regions: scene_edit_core.h) and the query graphs of a batch (gcsadmm_scene_build_region_graph,
 // gcsadmm_scene_query_graphs: query_graph_core.h) and the informed region set of every query (gcsadmm_scene_region_paths,
-// gcsadmm_scene_informed_regions: informed_core.h).
+// gcsadmm_scene_informed_regions: informed_core.h), and the query graphs on those sets alone (gcsadmm_scene_induced_sizes,
+// gcsadmm_scene_induced_query_graphs: induced_graph_core.h).
 //
 // This file is the host side of one translation unit: scene_kernels.h has the __global__ wrappers around the *_core.h headers,
 // scene_stage.h which results a scene holds, which of them each call needs and which it ends (the table is there), hip_owners.h
@@ -118,6 +119,19 @@ struct InformedScratch {                               // region_paths and infor
     DevBuf<double> cost;
     DevBuf<unsigned char> keep;
 };
+struct InducedScratch {                                // induced_sizes and induced_query_graphs, kept and grown from call to call:
+    DevBuf<long long> term_ptr, vertex_off, edge_off;  //   the caller's arrays (keep: the flags of one chunk) and the renumbered
+    DevBuf<int> term_region, term_new;                 //   hit lists,
+    DevBuf<unsigned char> st, keep;
+    DevBuf<InducedQuery> table;                        //   of one chunk: the table of its slabs,
+    DevBuf<int> sizes, newidx, kept, deg;              //   the counts and the arrays of the count kernel [chunk][P],
+    DevBuf<long long> row_ptr;                         //   the induced graphs with their ranks, one query behind the other
+    DevBuf<int> full_ptr, rank, tail, head, rev;       //   (the seven result arrays are QueryScratch's)
+    InducedWorkspace workspace() const
+    {
+        return InducedWorkspace{keep.get(), newidx.get(), kept.get(), deg.get(), row_ptr.get(), full_ptr.get(), rank.get(), tail.get(), head.get(), rev.get()};
+    }
+};
 // A gcsadmm_scene holds one from create to destroy (read: gcsadmm_scene_read_pairs); a batch call (gcsadmm_polytope_*) holds one on
 // its stack, with the buffers of its stage.
 struct gcsadmm_scene_s {
@@ -130,6 +144,7 @@ struct gcsadmm_scene_s {
     LocateScratch lq;                                  // (locate_points)
     QueryScratch qg;                                   // (query_graphs)
     InformedScratch inf;                               // (region_paths, informed_regions)
+    InducedScratch ig;                                 // (induced_sizes, induced_query_graphs)
 };
 
 namespace {
@@ -369,6 +384,91 @@ int read_boxes(const SceneRegions &r, double *lo, double *hi, int *status)
 int read_decisions(const ScenePairs &pr, unsigned char *overlap, int *status)
 {
     LPCHK(to_host(overlap, pr.flag)); LPCHK(to_host(status, pr.st_o));
+    return GCSADMM_OK;
+}
+
+// ---- the induced query graphs of a batch (induced_graph_core.h): what the two entry points share ----
+InducedArgs induced_args(const gcsadmm_scene_s &s, int B, int first)
+{
+    const SceneGraph &rg = s.graph;
+    const InducedScratch &w = s.ig;
+    InducedArgs a{};
+    a.g = RegionGraph{s.reg.P, rg.edges, rg.row_ptr.get(), rg.tail.get(), rg.head.get(), rg.rev.get()};
+    a.table = w.table.get();
+    a.q = QueryBatch{B, w.term_ptr.get(), w.term_region.get(), w.st.get(), w.edge_off.get()};
+    a.term_new = w.term_new.get(); a.first = first; a.sizes = w.sizes.get();
+    return a;
+}
+// the count kernel on the queries first .. first + count: their flags up, the table of the slabs of fixed size, the counts back
+int induced_count(gcsadmm_scene_s &s, const InducedBatch &host, int first, int count, int *sizes)
+{
+    InducedScratch &w = s.ig;
+    const size_t cells = (size_t)count * s.reg.P;
+    LPCHK(w.keep.reserve(cells)); LPCHK(w.newidx.reserve(cells)); LPCHK(w.kept.reserve(cells)); LPCHK(w.deg.reserve(cells));
+    LPCHK(w.table.reserve((size_t)count)); LPCHK(w.sizes.reserve((size_t)INDUCED_SIZES * count));
+    LPCHK(to_device(w.keep.get(), host.keep + (size_t)first * s.reg.P, cells));
+    std::vector<InducedQuery> table((size_t)count);
+    induced_table(w.workspace(), s.reg.P, count, nullptr, table.data());
+    LPCHK(to_device(w.table.get(), table.data(), table.size()));
+    hipLaunchKernelGGL(induced_count_kernel, dim3((unsigned)count), dim3(INDUCED_TILE), 0, 0, induced_args(s, host.B, first));
+    LPCHK(hipGetLastError());
+    LPCHK(to_host(sizes, w.sizes.get(), (size_t)INDUCED_SIZES * count));
+    return GCSADMM_OK;
+}
+// The checks that need no count, the hit lists to the device, then the counts of every query [B][INDUCED_SIZES], chunk by chunk (the
+// arrays of the count kernel are those of the last chunk afterwards).
+int induced_counts(gcsadmm_scene_s &s, const InducedBatch &host, int chunk_queries, int &chunk, std::vector<int> &sizes)
+{
+    static_assert(QUERY_BAD_ARG == GCSADMM_ERR_BAD_ARG && QUERY_UNSUPPORTED == GCSADMM_ERR_UNSUPPORTED && QUERY_OK == GCSADMM_OK, "induced_check returns the ABI's codes");
+    if (!has(s.have, NEED_FRESH_GRAPH.flags)) { g_err = NEED_FRESH_GRAPH.refusal; return GCSADMM_ERR_BAD_ARG; }
+    LPRUN(induced_check(s.reg.P, host, chunk_queries, g_err));
+    if (host.B == 0) return GCSADMM_OK;
+    InducedScratch &w = s.ig;
+    const size_t B = (size_t)host.B, hits = (size_t)host.term_ptr[2 * B];
+    LPCHK(w.term_ptr.reserve(2 * B + 1)); LPCHK(w.term_region.reserve(hits)); LPCHK(w.term_new.reserve(hits)); LPCHK(w.st.reserve(B));
+    LPCHK(to_device(w.term_ptr.get(), host.term_ptr, 2 * B + 1));
+    LPCHK(to_device(w.term_region.get(), host.term_region, hits));
+    LPCHK(to_device(w.st.get(), host.st, B));
+    sizes.resize(INDUCED_SIZES * B);
+    chunk = induced_chunk(s.reg.P, s.graph.edges, chunk_queries);
+    for (int first = 0; first < host.B; first += chunk)
+        LPRUN(induced_count(s, host, first, std::min(chunk, host.B - first), sizes.data() + (size_t)INDUCED_SIZES * first));
+    return GCSADMM_OK;
+}
+// The build and the query kernel on a counted chunk whose count arrays are resident, and its results to the caller's arrays.
+int induced_write(gcsadmm_scene_s &s, const InducedBatch &host, int first, int count, const int *sizes, const long long *vertex_off,
+                  const long long *edge_off, const QueryArrays &out)
+{
+    InducedScratch &w = s.ig;
+    QueryScratch &qg = s.qg;
+    const InducedTotals n = induced_totals(sizes, count);
+    LPCHK(w.row_ptr.reserve(n.kept + (size_t)count)); LPCHK(w.full_ptr.reserve(n.kept)); LPCHK(w.rank.reserve(n.ranks));
+    LPCHK(w.tail.reserve(n.edges)); LPCHK(w.head.reserve(n.edges)); LPCHK(w.rev.reserve(n.edges));
+    std::vector<InducedQuery> table((size_t)count);
+    induced_table(w.workspace(), s.reg.P, count, sizes, table.data());
+    LPCHK(to_device(w.table.get(), table.data(), table.size()));
+    hipLaunchKernelGGL(induced_build_kernel, dim3((unsigned)count), dim3(INDUCED_TILE), 0, 0, induced_args(s, host.B, first));
+    LPCHK(hipGetLastError());
+    const size_t at = (size_t)edge_off[first], E = (size_t)(edge_off[first + count] - edge_off[first]);
+    const size_t v_at = (size_t)vertex_off[first], V = (size_t)(vertex_off[first + count] - vertex_off[first]);
+    LPCHK(qg.edge_tail.reserve(E)); LPCHK(qg.edge_head.reserve(E)); LPCHK(qg.inc_ptr.reserve(V));
+    LPCHK(qg.inc_edge.reserve(2 * E)); LPCHK(qg.inc_out.reserve(2 * E)); LPCHK(qg.edge_inc_tail.reserve(E)); LPCHK(qg.edge_inc_head.reserve(E));
+    InducedGraphArgs a{};
+    a.table = w.table.get();
+    a.q = QueryBatch{host.B, w.term_ptr.get(), w.term_new.get(), w.st.get(), w.edge_off.get()};
+    a.vertex_off = w.vertex_off.get();
+    a.out = QueryArrays{qg.edge_tail.get(), qg.edge_head.get(), qg.inc_ptr.get(), qg.inc_edge.get(), qg.inc_out.get(), qg.edge_inc_tail.get(),
+                        qg.edge_inc_head.get()};
+    a.first = first;
+    long long max_items = 0;
+    for (int y = 0; y < count; ++y)
+        max_items = std::max(max_items, query_items(induced_region_graph(table[(size_t)y]), induced_hits(QueryBatch{host.B, host.term_ptr}, first + y), 0));
+    hipLaunchKernelGGL(induced_graph_kernel, dim3((unsigned)((max_items + 255) / 256), (unsigned)count), dim3(256), 0, 0, a);
+    LPCHK(hipGetLastError());
+    LPCHK(to_host(out.edge_tail + at, a.out.edge_tail, E)); LPCHK(to_host(out.edge_head + at, a.out.edge_head, E));
+    LPCHK(to_host(out.inc_ptr + v_at, a.out.inc_ptr, V));
+    LPCHK(to_host(out.inc_edge + 2 * at, a.out.inc_edge, 2 * E)); LPCHK(to_host(out.inc_out + 2 * at, a.out.inc_out, 2 * E));
+    LPCHK(to_host(out.edge_inc_tail + at, a.out.edge_inc_tail, E)); LPCHK(to_host(out.edge_inc_head + at, a.out.edge_inc_head, E));
     return GCSADMM_OK;
 }
 
@@ -1097,6 +1197,57 @@ int gcsadmm_scene_informed_regions(gcsadmm_scene s, int num_queries, const doubl
                 for (int p = 0; p < P; ++p) kept += keep[(size_t)i * P + p];
                 num_kept[i] = kept;
             }
+        return GCSADMM_OK;
+    });
+}
+
+// ---- the query graphs of a batch on each query's kept regions (induced_graph_core.h); like region_paths outside the table of scene_stage.h ----
+int gcsadmm_scene_induced_sizes(gcsadmm_scene s, int num_queries, const unsigned char *keep, const int64_t *term_ptr, const int *term_region,
+                                const unsigned char *st_adjacent, int *num_kept, int64_t *num_edges)
+{
+    return scene_entry(s, [&]() -> int {
+        const InducedBatch host{num_queries, keep, (const long long *)term_ptr, term_region, st_adjacent};
+        if (num_queries > 0 && (!num_kept || !num_edges)) { g_err = "null output array"; return GCSADMM_ERR_BAD_ARG; }
+        std::vector<int> sizes;
+        int chunk = 0;
+        LPRUN(induced_counts(*s, host, 0, chunk, sizes));
+        const QueryBatch b{host.B, host.term_ptr, host.term_region, host.st, nullptr};
+        for (int i = 0; i < num_queries; ++i) {
+            const QueryTerms t = query_terms(b, i);
+            num_kept[i] = sizes[(size_t)INDUCED_SIZES * i];
+            num_edges[i] = query_edges(sizes[(size_t)INDUCED_SIZES * i + 1], t.a, t.b, t.c);
+        }
+        return GCSADMM_OK;
+    });
+}
+
+int gcsadmm_scene_induced_query_graphs(gcsadmm_scene s, int num_queries, const unsigned char *keep, const int64_t *term_ptr, const int *term_region,
+                                       const unsigned char *st_adjacent, int chunk_queries, const int64_t *vertex_off, const int64_t *edge_off,
+                                       int *edge_tail, int *edge_head, int *inc_ptr, int *inc_edge, int *inc_out, int *edge_inc_tail, int *edge_inc_head)
+{
+    return scene_entry(s, [&]() -> int {
+        const InducedBatch host{num_queries, keep, (const long long *)term_ptr, term_region, st_adjacent};
+        const int B = num_queries;
+        if (B > 0 && (!vertex_off || !edge_off || !edge_tail || !edge_head || !inc_ptr || !inc_edge || !inc_out || !edge_inc_tail || !edge_inc_head)) {
+            g_err = "null vertex_off, edge_off or output array"; return GCSADMM_ERR_BAD_ARG;
+        }
+        std::vector<int> sizes, again;
+        int chunk = 0;
+        LPRUN(induced_counts(*s, host, chunk_queries, chunk, sizes));
+        if (B == 0) return GCSADMM_OK;
+        const long long *v_off = (const long long *)vertex_off, *e_off = (const long long *)edge_off;
+        LPRUN(induced_check_offsets(host, sizes.data(), v_off, e_off, g_err));      // nothing of the caller's is written before this
+        InducedScratch &w = s->ig;
+        LPCHK(w.vertex_off.reserve((size_t)B + 1)); LPCHK(w.edge_off.reserve((size_t)B + 1));
+        LPCHK(to_device(w.vertex_off.get(), v_off, (size_t)B + 1)); LPCHK(to_device(w.edge_off.get(), e_off, (size_t)B + 1));
+        const QueryArrays out{edge_tail, edge_head, inc_ptr, inc_edge, inc_out, edge_inc_tail, edge_inc_head};
+        again.resize((size_t)INDUCED_SIZES * std::min(chunk, B));
+        for (int first = 0; first < B; first += chunk) {
+            const int count = std::min(chunk, B - first);
+            if (chunk < B) LPRUN(induced_count(*s, host, first, count, again.data()));      // (several chunks: the count arrays are the last one's)
+            LPRUN(induced_write(*s, host, first, count, sizes.data() + (size_t)INDUCED_SIZES * first, v_off, e_off, out));
+        }
+        LPCHK(hipStreamSynchronize(nullptr));
         return GCSADMM_OK;
     });
 }

@@ -8,6 +8,7 @@
 #include "point_locate_core.h"
 #include "scene_edit_core.h"
 #include "query_graph_core.h"
+#include "induced_graph_core.h"
 #include "informed_core.h"
 #include "path_restrict_core.h"
 #include "restrict_plan.h"
@@ -331,6 +332,78 @@ __global__ __launch_bounds__(256) void query_graph_kernel(QueryGraphArgs a)
     const long long x = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (x >= a.items) return;
     query_item(a.g, query_terms(a.q, i), query_arrays(a.out, a.q, a.g.P, a.first, i), x);
+}
+
+// ---- the query graphs of a batch on each query's kept regions (induced_graph_core.h) ----
+struct InducedArgs {
+    RegionGraph g;                  // the scene's
+    const InducedQuery *table;      // [queries of the chunk]: blockIdx.x (count, build) or blockIdx.y (query) indexes it
+    QueryBatch q;                   // device copies of the caller's arrays, scene indices in term_region
+    int *term_new;                  // the hit lists renumbered, laid out as term_region
+    int first;                      // the chunk's first query
+    int *sizes;                     // [queries of the chunk][INDUCED_SIZES]
+};
+// One workgroup per query: the flags in tiles of 256, each lane the region of its place in the tile.
+__global__ __launch_bounds__(INDUCED_TILE) void induced_count_kernel(InducedArgs a)
+{
+    __shared__ int part[INDUCED_TILE / INDUCED_WAVE];
+    const InducedQuery q = a.table[blockIdx.x];
+    const int P = a.g.P, t = (int)threadIdx.x;
+    TileCarry below;
+    InducedCount sum{0, 0};
+    for (int base = 0; base < P; base += INDUCED_TILE) {      // (the same trips in every lane: the scan has barriers)
+        const int r = base + t, flag = induced_flag(q, P, r);
+        int total;
+        const int within = induced_tile_scan(flag, part, total);
+        if (r < P) induced_number(a.g, q, r, flag, below.at(within), sum);
+        below.next(total);
+    }
+    int edges, ranks;
+    induced_tile_scan(sum.edges, part, edges);
+    induced_tile_scan(sum.ranks, part, ranks);
+    if (t == 0) {
+        int *z = a.sizes + (size_t)INDUCED_SIZES * blockIdx.x;
+        z[0] = below.sum; z[1] = edges; z[2] = ranks;
+    }
+}
+// One workgroup per query: the kept rows in tiles of 256, each lane the row of its place in the tile; then, behind a barrier that
+// first waits for the wavefront's stores (region_path_kernel has the form), the reverse edges from the ranks the other lanes wrote.
+__global__ __launch_bounds__(INDUCED_TILE) void induced_build_kernel(InducedArgs a)
+{
+    __shared__ int part[INDUCED_TILE / INDUCED_WAVE];
+    const InducedQuery q = a.table[blockIdx.x];
+    const int i = a.first + (int)blockIdx.x, t = (int)threadIdx.x, kept = q.kept_count;
+    TileCarry first, ranks;
+    for (int base = 0; base < kept; base += INDUCED_TILE) {
+        const int j = base + t;
+        int edges, full;
+        const int e_within = induced_tile_scan(j < kept ? q.deg[j] : 0, part, edges);
+        const int f_within = induced_tile_scan(j < kept ? induced_full_degree(a.g, q, j) : 0, part, full);
+        if (j < kept) induced_row(a.g, q, j, first.at(e_within), ranks.at(f_within));
+        first.next(edges); ranks.next(full);
+    }
+    if (t == 0) q.row_ptr[kept] = first.sum;
+    for (int k = t, hits = induced_hits(a.q, i); k < hits; k += INDUCED_TILE) induced_term(a.q, i, q.newidx, a.term_new, k);
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    __syncthreads();
+    for (int j = t; j < kept; j += INDUCED_TILE) induced_reverse(a.g, q, j);
+}
+struct InducedGraphArgs {
+    const InducedQuery *table;      // [queries of the chunk]
+    QueryBatch q;                   // device copies; term_region holds the renumbered lists
+    const long long *vertex_off;    // [B + 1]
+    QueryArrays out;                // the chunk's buffers: they begin with query `first`
+    int first;
+};
+// query_graph_kernel with the region graph and the item count of each query from the table (the grid covers the most items of one)
+__global__ __launch_bounds__(256) void induced_graph_kernel(InducedGraphArgs a)
+{
+    const int i = a.first + (int)blockIdx.y;
+    const long long x = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const RegionGraph g = induced_region_graph(a.table[blockIdx.y]);
+    const QueryTerms t = query_terms(a.q, i);
+    if (x >= query_items(g, t.a, t.b)) return;
+    query_item(g, t, induced_arrays(a.out, a.q, a.vertex_off, a.first, i), x);
 }
 
 // ---- the informed region set of a query (informed_core.h) ----

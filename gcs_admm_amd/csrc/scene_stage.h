@@ -18,8 +18,8 @@
 //   read_hits         hits           read_graph   graph        query_graphs graph (its own text)            (reads change nothing)
 //
 // "decided" is pairs and overlaps together.  gcsadmm_scene_restrict_paths needs the regions alone and is not in the table; nor are
-// gcsadmm_scene_region_paths (NEED_FRESH_GRAPH, NEED_CENTERS) and gcsadmm_scene_informed_regions (NEED_BOXES), which read and change
-// nothing.  An edit of no regions returns before its finish.
+// gcsadmm_scene_region_paths (NEED_FRESH_GRAPH, NEED_CENTERS), gcsadmm_scene_informed_regions (NEED_BOXES) and
+// gcsadmm_scene_induced_sizes / _induced_query_graphs (NEED_FRESH_GRAPH), which read and change nothing.  An edit of no regions returns before its finish.
 #pragma once
 
 namespace gcsadmm_stage {

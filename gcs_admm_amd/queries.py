@@ -8,7 +8,8 @@ from-scratch ``graph_from_sets_device`` on ``{'s', 't', regions}`` gives; ``solv
 ``rounding_many``.  By default the graphs are assembled on the host (a sort over all edges per query); ``assemble="device"`` takes them
 from one kernel call on the scene's own region graph (csrc/query_graph_core.h), the same arrays.  ``prune="informed"`` runs every query on
 its informed region set alone (``informed``, csrc/informed_core.h): the regions within the length of a feasible path of both terminals,
-which loses no optimal path.  The scene is not frozen: ``add_regions`` and ``remove_regions`` edit it in place, and only the LPs of what is new run.  There is no CPU fallback: the LPs and the locate call run on the device (tests inject stand-ins).
+which loses no optimal path; ``assemble="induced"`` builds those pruned graphs on the device too (csrc/induced_graph_core.h), in work
+proportional to the kept set.  The scene is not frozen: ``add_regions`` and ``remove_regions`` edit it in place, and only the LPs of what is new run.  There is no CPU fallback: the LPs and the locate call run on the device (tests inject stand-ins).
 """
 from __future__ import annotations
 
@@ -50,7 +51,7 @@ class SceneQueries:
             raise
         self.centers = np.ascontiguousarray(self.centers, float)
         self.last = {}      # counts of the last regions_at call: hits, undecided, redone_on_host
-        # assemble="device" and informed: is the scene's region graph that of _pairs?  assemble="device" alone: the regions' stacked
+        # assemble="device" / "induced" and informed: is the scene's region graph that of _pairs?  The two assemblies: the regions' stacked
         # polytope CSR (rows int64, A, b)
         self._graph_resident, self._stacked = False, None
 
@@ -274,31 +275,69 @@ class SceneQueries:
         polys = [convert_pt_to_polytope(s, eps), convert_pt_to_polytope(g, eps)] + polys
         return _finish_graph(self.n, ['s', 't'] + keys, tail[o], head[o], polys, np.vstack([s, g, centers]), 0, 1)
 
+    def _stack(self):
+        """the regions' stacked polytope CSR (rows int64, A, b): made on first use, kept across edits"""
+        if self._stacked is None:
+            rows = np.zeros(len(self.polys) + 1, np.int64)
+            rows[1:] = np.cumsum([len(b) for _, b in self.polys])
+            self._stacked = (rows, np.ascontiguousarray(np.vstack([A for A, _ in self.polys]).reshape(-1, self.n)) if self.polys else np.zeros((0, self.n)),
+                             np.ascontiguousarray(np.hstack([b for _, b in self.polys])) if self.polys else np.zeros(0))
+        return self._stacked
+
+    @staticmethod
+    def _adjacent(S, G, eps):
+        """uint8 [B]: do the boxes of start and goal meet (the interval rule of ``_host_graph``)"""
+        return np.array([np.all(np.maximum(S[i] - eps, G[i] - eps) <= np.minimum(S[i] + eps, G[i] + eps) + 1e-9) for i in range(len(S))], np.uint8)
+
+    def _point_rows(self, s, g, eps):
+        """the polytope rows of the two point boxes of a query: (A [4 n, n], b [4 n])"""
+        (A_s, b_s), (A_t, b_t) = convert_pt_to_polytope(s, eps), convert_pt_to_polytope(g, eps)
+        return (np.concatenate([np.asarray(A_s, float).reshape(-1, self.n), np.asarray(A_t, float).reshape(-1, self.n)]),
+                np.concatenate([np.asarray(b_s, float).ravel(), np.asarray(b_t, float).ravel()]))
+
+    def _assemble_induced(self, S, G, regs, eps, info):
+        """the pruned graphs of ``graphs`` from ONE ``induced_query_graphs`` call on the keep flags of ``_informed``: the induced subgraph
+        of every query's kept set is built on the device from the rows of its kept regions (csrc/induced_graph_core.h), the arrays taken
+        as they come; per query the host reads the P flags, and gathers the kept regions' rows of the stacked polytope CSR"""
+        B = len(S)
+        self._region_graph_on_device()
+        rows, A_all, b_all = self._stack()
+        term_ptr, term_region = self._term_lists(regs)
+        keep = np.array([r["keep"] for r in info], np.uint8).reshape(B, len(self.keys))
+        arrays = self.scene.induced_query_graphs(keep, term_ptr, term_region, self._adjacent(S, G, eps))
+        out = []
+        for i in range(B):
+            idx = np.nonzero(keep[i])[0]
+            counts = rows[idx + 1] - rows[idx]
+            ends = np.cumsum(counts)
+            take = np.repeat(rows[idx] - (ends - counts), counts) + np.arange(int(ends[-1]) if len(ends) else 0)      # the kept regions' rows
+            A_pts, b_pts = self._point_rows(S[i], G[i], eps)
+            tail, head, inc_ptr, inc_edge, inc_out, inc_tail, inc_head = arrays[i]
+            out.append(GcsGraph(n=self.n, keys=['s', 't'] + [self.keys[r] for r in idx], edge_tail=tail, edge_head=head, inc_ptr=inc_ptr,
+                                inc_edge=inc_edge, inc_out=inc_out, edge_inc_tail=inc_tail, edge_inc_head=inc_head,
+                                poly_ptr=np.concatenate([[0, 2 * self.n, 4 * self.n], ends + 4 * self.n]).astype(np.int32),
+                                poly_A=np.concatenate([A_pts, A_all[take]]), poly_b=np.concatenate([b_pts, b_all[take]]),
+                                interior=np.concatenate([S[i][None], G[i][None], self.centers[idx]]), src=0, dst=1))
+        return out
+
     def _assemble_on_device(self, S, G, regs, eps):
         """the graphs of ``graphs`` from ONE ``query_graphs`` call: the scene's region graph (built on first use and after an edit, with
         the host's decisions in it when an LP left a pair undecided) merged with every query's terminal edges by a kernel, the arrays
         taken as they come; the polytope CSR is the regions' stacked one behind the two point boxes"""
         B = len(S)
         self._region_graph_on_device()
-        if self._stacked is None:
-            rows = np.zeros(len(self.polys) + 1, np.int64)
-            rows[1:] = np.cumsum([len(b) for _, b in self.polys])
-            self._stacked = (rows, np.ascontiguousarray(np.vstack([A for A, _ in self.polys]).reshape(-1, self.n)) if self.polys else np.zeros((0, self.n)),
-                             np.ascontiguousarray(np.hstack([b for _, b in self.polys])) if self.polys else np.zeros(0))
-        rows, A_all, b_all = self._stacked
+        rows, A_all, b_all = self._stack()
         term_ptr, term_region = self._term_lists(regs)
-        st = np.array([np.all(np.maximum(S[i] - eps, G[i] - eps) <= np.minimum(S[i] + eps, G[i] + eps) + 1e-9) for i in range(B)], np.uint8)
-        arrays = self.scene.query_graphs(term_ptr, term_region, st)
+        arrays = self.scene.query_graphs(term_ptr, term_region, self._adjacent(S, G, eps))
         keys = ['s', 't'] + self.keys
         poly_ptr = np.concatenate([[0, 2 * self.n, 4 * self.n], rows[1:] + 4 * self.n]).astype(np.int32)
         out = []
         for i in range(B):
-            (A_s, b_s), (A_t, b_t) = convert_pt_to_polytope(S[i], eps), convert_pt_to_polytope(G[i], eps)
+            A_pts, b_pts = self._point_rows(S[i], G[i], eps)
             tail, head, inc_ptr, inc_edge, inc_out, inc_tail, inc_head = arrays[i]
             out.append(GcsGraph(n=self.n, keys=list(keys), edge_tail=tail, edge_head=head, inc_ptr=inc_ptr, inc_edge=inc_edge, inc_out=inc_out,
                                 edge_inc_tail=inc_tail, edge_inc_head=inc_head, poly_ptr=poly_ptr.copy(),
-                                poly_A=np.concatenate([np.asarray(A_s, float).reshape(-1, self.n), np.asarray(A_t, float).reshape(-1, self.n), A_all]),
-                                poly_b=np.concatenate([np.asarray(b_s, float).ravel(), np.asarray(b_t, float).ravel(), b_all]),
+                                poly_A=np.concatenate([A_pts, A_all]), poly_b=np.concatenate([b_pts, b_all]),
                                 interior=np.concatenate([S[i][None], G[i][None], self.centers]), src=0, dst=1))
         return out
 
@@ -315,22 +354,29 @@ class SceneQueries:
 
         ``prune``: ``None`` (the default: every region) or ``"informed"``: the graph of query i is the host path's on the induced
         subgraph of its informed region set (``informed``; ``restrict`` as there), the regions renumbered in scene order, keys ``['s',
-        't', *kept keys]``.  No optimal path is lost.  Not with ``assemble="device"``."""
+        't', *kept keys]``.  No optimal path is lost.  Not with ``assemble="device"``, which is the assembly of the WHOLE scene; the pruned
+        one is ``assemble="induced"`` (only with ``prune``): one ``induced_query_graphs`` call builds the induced subgraph of every query's
+        kept set on the device, from the rows of its kept regions alone -- csrc/induced_graph_core.h --, where ``"host"`` masks and
+        renumbers the whole region edge list per query; every field of every graph is the host path's."""
         return self._graphs(starts, goals, eps, tol, assemble, prune, restrict)[0]
 
     def _graphs(self, starts, goals, eps, tol, assemble, prune, restrict):
         """(the graphs of ``graphs``, the records of ``informed`` or None)"""
-        if assemble not in ("host", "device"):
-            raise ValueError(f"assemble must be 'host' or 'device', not {assemble!r}")
+        if assemble not in ("host", "device", "induced"):
+            raise ValueError(f"assemble must be 'host' or 'device', or 'induced' with prune, not {assemble!r}")
         if prune not in (None, "informed"):
             raise ValueError(f"prune must be None or 'informed', not {prune!r}")
         if prune is not None and assemble == "device":
-            raise ValueError("prune needs assemble='host': the device assembles the graphs of the whole scene")
+            raise ValueError("prune needs assemble='host' or 'induced': 'device' assembles the graphs of the whole scene")
+        if prune is None and assemble == "induced":
+            raise ValueError("assemble='induced' needs prune")
         S, G, regs = self._located(starts, goals, eps, tol)
         B = len(S)
         if assemble == "device":
             return self._assemble_on_device(S, G, regs, eps), None
         info = self._informed(S, G, regs, eps, restrict) if prune else None
+        if assemble == "induced":
+            return (self._assemble_induced(S, G, regs, eps, info) if B else []), info
         return [self._host_graph(S[i], G[i], regs[i], regs[B + i], eps, info[i]["keep"] if prune else None) for i in range(B)], info
 
     def solve(self, starts, goals, state_dtype: str = "f64", N: int = 5, M: int = 20, seeds=None, params=None, return_state: bool = False,
@@ -339,7 +385,7 @@ class SceneQueries:
         ``BatchSolver.solve``), then rounded by ``rounding_many`` (``N``, ``M``: as ``rounding``; ``seeds``: one per query, default 0).
         ``walk``: ``"host"`` (the default: the walks of ``rounding``, on a host copy of every query's activations) or ``"device"``
         (``rounding_members``: the walks of all queries drawn on the device while the activations are still there, by the rule of
-        ``walks.walk_reference`` -- other draws than the host's for the same seed).  ``assemble``: as ``graphs`` (the same graphs either way).
+        ``walks.walk_reference`` -- other draws than the host's for the same seed).  ``assemble``: as ``graphs`` (the same graphs whichever way; ``"induced"`` only with ``prune``).
         ``prune``, ``restrict``: as ``graphs``; with ``prune="informed"`` every query runs on its informed region set alone, each record
         gains ``informed_bound`` and ``kept_regions``, and the bound's path is one more candidate of the rounding step, so that
         ``rounded_cost <= informed_bound`` whenever the bound is finite.

@@ -331,6 +331,21 @@ class DeviceScene:
         the length of a feasible path of each query, or ``inf`` (keeps every region)."""
         return informed_keep_array(self.n, self.P, points, bound, pad, lambda *arrays: self._call("gcsadmm_scene_informed_regions", *arrays))
 
+    def induced_sizes(self, keep, term_ptr, term_region, st_adjacent):
+        """``(num_kept int32 [B], num_edges int64 [B])`` of the graphs ``induced_query_graphs`` would write (``gcsadmm_scene_induced_sizes``:
+        the counts alone)"""
+        return induced_size_arrays(self.P, keep, term_ptr, term_region, st_adjacent, lambda *arrays: self._call("gcsadmm_scene_induced_sizes", *arrays))[4:]
+
+    def induced_query_graphs(self, keep, term_ptr, term_region, st_adjacent, chunk_queries: int = 0):
+        """The index arrays of the query graphs of a batch, each on its own kept regions (``gcsadmm_scene_induced_sizes``, then
+        ``gcsadmm_scene_induced_query_graphs``; csrc/induced_graph_core.h has the rule; after ``build_region_graph``).  ``keep`` [B, P]:
+        non-zero keeps region r for query i (every hit region must be kept); the other arguments as ``query_graphs``, in scene indices.
+        Returns one tuple of seven int32 views per query, as ``query_graphs``: vertex 0 the start, 1 the goal, j + 2 the j-th kept region
+        in scene order; ``inc_ptr`` has ``kept + 3`` entries."""
+        return induced_query_graph_views(self.P, keep, term_ptr, term_region, st_adjacent,
+                                         lambda *arrays: self._call("gcsadmm_scene_induced_sizes", *arrays),
+                                         lambda *arrays: self._call("gcsadmm_scene_induced_query_graphs", *arrays), chunk_queries)
+
 
 def region_path_views(n, P, points, term_ptr, term_region, max_len, call):
     """the arrays of ``gcsadmm_scene_region_paths`` around ``call(num_queries, points, term_ptr, term_region, max_len, *four outputs)``
@@ -382,6 +397,46 @@ def query_graph_views(P, region_edges, term_ptr, term_region, st_adjacent, call,
         e0, e1 = int(edge_off[i]), int(edge_off[i + 1])
         cut = (slice(e0, e1), slice(e0, e1), slice(i * (P + 3), (i + 1) * (P + 3)), slice(2 * e0, 2 * e1), slice(2 * e0, 2 * e1), slice(e0, e1),
                slice(e0, e1))
+        out.append(tuple(a[c] for a, c in zip(flat, cut)))
+    return out
+
+
+def induced_size_arrays(P, keep, term_ptr, term_region, st_adjacent, sizes_call):
+    """the arrays of ``gcsadmm_scene_induced_sizes`` around ``sizes_call(num_queries, keep, term_ptr, term_region, st_adjacent, num_kept,
+    num_edges)`` (addresses): the four inputs as the call takes them, then ``num_kept`` int32 [B] and ``num_edges`` int64 [B]"""
+    ptr = np.ascontiguousarray(term_ptr, np.int64).ravel()
+    reg = np.ascontiguousarray(term_region, np.int32).ravel()
+    st = np.ascontiguousarray(st_adjacent, np.uint8).ravel()
+    B = len(st)
+    if len(ptr) != 2 * B + 1:
+        raise ValueError("term_ptr needs 2 B + 1 entries: the starts, then the goals")
+    flags = np.ascontiguousarray(np.asarray(keep).reshape(B, P), np.uint8)      # (bool or uint8: any non-zero byte keeps)
+    num_kept = np.zeros(B, np.int32); num_edges = np.zeros(B, np.int64)
+    sizes_call(B, flags.ctypes.data, ptr.ctypes.data, reg.ctypes.data, st.ctypes.data, num_kept.ctypes.data, num_edges.ctypes.data)
+    return flags, ptr, reg, st, num_kept, num_edges
+
+
+def induced_query_graph_views(P, keep, term_ptr, term_region, st_adjacent, sizes_call, graphs_call, chunk_queries=0):
+    """the flat arrays of ``gcsadmm_scene_induced_query_graphs`` around ``sizes_call(num_queries, keep, term_ptr, term_region,
+    st_adjacent, num_kept, num_edges)`` and ``graphs_call(num_queries, keep, term_ptr, term_region, st_adjacent, chunk_queries,
+    vertex_off, edge_off, *seven outputs)`` (addresses): the sizes first, then arrays laid out by them, cut into one tuple of views per
+    query (its ``inc_ptr`` has ``num_kept + 3`` entries)"""
+    flags, ptr, reg, st, num_kept, num_edges = induced_size_arrays(P, keep, term_ptr, term_region, st_adjacent, sizes_call)
+    B = len(st)
+    vertex_off = np.zeros(B + 1, np.int64); edge_off = np.zeros(B + 1, np.int64)
+    vertex_off[1:] = np.cumsum(num_kept.astype(np.int64) + 3); edge_off[1:] = np.cumsum(num_edges)
+    E, V = int(edge_off[-1]), int(vertex_off[-1])
+    edge = [np.empty(E, np.int32) for _ in range(4)]            # edge_tail, edge_head, edge_inc_tail, edge_inc_head
+    inc = [np.empty(2 * E, np.int32) for _ in range(2)]         # inc_edge, inc_out
+    inc_ptr = np.empty(V, np.int32)
+    flat = (edge[0], edge[1], inc_ptr, inc[0], inc[1], edge[2], edge[3])
+    graphs_call(B, flags.ctypes.data, ptr.ctypes.data, reg.ctypes.data, st.ctypes.data, int(chunk_queries), vertex_off.ctypes.data,
+                edge_off.ctypes.data, *(a.ctypes.data for a in flat))
+    out = []
+    for i in range(B):
+        e0, e1 = int(edge_off[i]), int(edge_off[i + 1])
+        cut = (slice(e0, e1), slice(e0, e1), slice(int(vertex_off[i]), int(vertex_off[i + 1])), slice(2 * e0, 2 * e1), slice(2 * e0, 2 * e1),
+               slice(e0, e1), slice(e0, e1))
         out.append(tuple(a[c] for a, c in zip(flat, cut)))
     return out
 

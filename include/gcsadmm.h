@@ -515,6 +515,40 @@ int gcsadmm_scene_region_paths(gcsadmm_scene s, int num_queries, const double *p
 int gcsadmm_scene_informed_regions(gcsadmm_scene s, int num_queries, const double *points, const double *bound, double pad,
                                    unsigned char *keep, int64_t *num_kept);
 
+/* The query graphs of a batch, each on its own kept regions, assembled on the device (csrc/induced_graph_core.h has the contract): what
+ * gcs_admm_amd.queries.SceneQueries.graphs(prune="informed") builds on the host by masking and renumbering the whole edge list per
+ * query.  keep[num_queries][P]: any non-zero byte keeps region r for query i; the kept regions are renumbered in scene order (new[r] =
+ * number of kept regions below r), P'_i of them.  term_ptr, term_region and st_adjacent: exactly those of gcsadmm_scene_query_graphs,
+ * in scene indices; every hit region of a query must be kept.  The graph of query i is that of gcsadmm_scene_query_graphs on the
+ * induced region graph of its kept set (E'_R,i directed edges, both ends kept) with the hit lists renumbered: vertex 0 the start, 1
+ * the goal, new[r] + 2 kept region r.
+ *
+ * One 256-lane workgroup per query: an exclusive scan of its P flags in tiles of 256 (shuffles inside a wavefront, one LDS stage
+ * across the four, a carry from tile to tile), the kept heads of every kept row counted from that row, a scan over the P'_i kept rows,
+ * then every entry written once by a plain store; the reverse edge of an edge comes from the rank of every edge of a kept row among
+ * its row's kept heads.  Per query the device reads the P flags and the rows of the kept regions: no pass over all E_R edges, no
+ * atomics.  The seven arrays are then written by the closed forms of gcsadmm_scene_query_graphs, unchanged.
+ *
+ * induced_sizes runs the counts alone: num_kept[i] = P'_i, num_edges[i] = E'_R,i + 2 (a + b) + 2 st_adjacent[i], the sizes the caller
+ * lays its arrays out by.  induced_query_graphs repeats the counts and writes the graphs: vertex_off[num_queries + 1] must step by
+ * exactly P'_i + 3 and edge_off[num_queries + 1] by num_edges[i]; query i's inc_ptr (P'_i + 3 entries) begins at vertex_off[i], its
+ * edge arrays at edge_off[i], its incidence arrays (inc_edge, inc_out) at 2 edge_off[i].  One set of launches serves chunk_queries
+ * queries (0: the library chooses: at most 65 535, and as many queries with every region kept as keep workspace and results within
+ * 256 MiB, or one).  The result does not depend on chunk_queries.
+ *
+ * Both calls need the region graph (not one from before an edit).  Decided on the host before any launch: everything
+ * gcsadmm_scene_query_graphs refuses in the hit lists, a st_adjacent other than 0 or 1, negative num_queries or chunk_queries, a null
+ * array, a hit region whose flag is 0 (the text names the query): GCSADMM_ERR_BAD_ARG; more than 2^31 - 1 hits or 2^30 queries:
+ * GCSADMM_ERR_UNSUPPORTED.  Offsets that do not step by the counts: GCSADMM_ERR_BAD_ARG, after the counts (which write to the
+ * library's workspace alone) and before anything else.  A refused call writes no output and changes nothing resident.  num_queries =
+ * 0 does nothing. */
+int gcsadmm_scene_induced_sizes(gcsadmm_scene s, int num_queries, const unsigned char *keep, const int64_t *term_ptr, const int *term_region,
+                                const unsigned char *st_adjacent, int *num_kept, int64_t *num_edges);
+int gcsadmm_scene_induced_query_graphs(gcsadmm_scene s, int num_queries, const unsigned char *keep, const int64_t *term_ptr, const int *term_region,
+                                       const unsigned char *st_adjacent, int chunk_queries, const int64_t *vertex_off, const int64_t *edge_off,
+                                       int *edge_tail, int *edge_head, int *inc_ptr, int *inc_edge, int *inc_out, int *edge_inc_tail,
+                                       int *edge_inc_head);
+
 /* ---- the candidate paths of the rounding step, drawn on the device (gcs_admm_amd/walks.py; csrc/path_walk_core.h has the rule) ----
  * After the loop, rounding draws s-t walks on the relaxed edge activations y_e.  walk_kernel draws them where the solver left y: one
  * 64-lane workgroup per (walk, problem), the visited set a bitmap in LDS, the draws from a counter-based generator (splitmix64 on

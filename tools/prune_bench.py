@@ -9,11 +9,16 @@ goal a few cells from the start) and ``corner`` (first cell to last cell) --
   * with ``--solve``: seconds of ``SceneQueries.solve`` with and without ``prune="informed"``, alternated in one process on the same
     queries after a warm-up of both, with both rounded costs per query.  "Without" is the code path of a solve that knows no pruning;
     where the batch refuses a side (a member of 512 vertices or more), the refusal is recorded and the other side timed alone.
+  * with ``--assemble``: seconds of the assembly of the pruned graphs alone, on the keep flags ``informed`` returned: the host's
+    (``_host_graph(keep)``: a mask over all region edges, a ``lexsort`` and ``graph._finish_graph`` per query) against the device's
+    (``assemble="induced"``: one ``induced_query_graphs`` call, csrc/induced_graph_core.h, and the gather of the kept polytope rows),
+    alternated in one process on the same queries after a warm-up of both, and the ``induced_sizes`` call alone; the graphs of the two
+    must be equal byte for byte, or the run stops.
 
 Medians of ``--repeats`` (default 5) with the spread; every time is a host clock around calls that end in a copy from the device.  One
 JSON line per (lattice, class).
 
-  python tools/prune_bench.py [--lattices 25x40 100x200] [--queries 4] [--solve 25x40] [--max-it N] [--repeats 5]
+  python tools/prune_bench.py [--lattices 25x40 100x200] [--queries 4] [--solve 25x40] [--assemble] [--max-it N] [--repeats 5]
 """
 import argparse, json, os, sys, time
 import numpy as np
@@ -66,7 +71,36 @@ def host_search(sq, row_ptr, head, w, S, regs):
     return clock() - t0, out
 
 
-def measure(nx, ny, B, repeats, solve, common):
+GRAPH_FIELDS = ("edge_tail", "edge_head", "inc_ptr", "inc_edge", "inc_out", "edge_inc_tail", "edge_inc_head", "poly_ptr", "poly_A", "poly_b", "interior")
+
+
+def time_assembly(sq, S, G, regs, info, repeats, eps=1e-6):
+    """the fields of a line for ``--assemble``: host-pruned against induced assembly of the same graphs, alternated"""
+    B = len(S)
+    sides = {"host": lambda: [sq._host_graph(S[i], G[i], regs[i], regs[B + i], eps, info[i]["keep"]) for i in range(B)],
+             "induced": lambda: sq._assemble_induced(S, G, regs, eps, info)}
+    first = {k: f() for k, f in sides.items()}                         # warm-up of both
+    for g, h in zip(first["host"], first["induced"]):
+        if g.keys != h.keys or any(getattr(g, f).dtype != getattr(h, f).dtype or getattr(g, f).tobytes() != getattr(h, f).tobytes() for f in GRAPH_FIELDS):
+            raise SystemExit("the induced assembly differs from the host-pruned graphs")
+    keep = np.array([r["keep"] for r in info], np.uint8)
+    term = sq._term_lists(regs)
+    st = sq._adjacent(S, G, eps)
+    t = {k: [] for k in sides}
+    t_sizes = []
+    for _ in range(repeats):
+        for k, f in sides.items():
+            t0 = clock(); f(); t[k].append(clock() - t0)
+        t0 = clock(); sq.scene.induced_sizes(keep, *term, st); t_sizes.append(clock() - t0)
+    out = {"graph_vertices": [int(g.num_vertices) for g in first["host"]], "graph_edges": [int(len(g.edge_tail)) for g in first["host"]],
+           "graphs_equal": True, "induced_sizes_s": float(np.median(t_sizes)), "induced_sizes_s_spread": spread(t_sizes)}
+    for k in sides:
+        out[f"assemble_{k}_s"] = float(np.median(t[k])); out[f"assemble_{k}_s_spread"] = spread(t[k])
+    out["host_over_induced"] = out["assemble_host_s"] / out["assemble_induced_s"]
+    return out
+
+
+def measure(nx, ny, B, repeats, solve, common, assemble=False):
     As, bs = lattice_sets(nx, ny)
     P = nx * ny
     rng = np.random.default_rng(P)
@@ -99,6 +133,8 @@ def measure(nx, ny, B, repeats, solve, common):
                     "informed_regions_s": float(np.median(t_keep)), "informed_regions_s_spread": spread(t_keep),
                     "informed_s": float(np.median(t_all)), "informed_s_spread": spread(t_all),
                     "scipy_dijkstra_s": float(np.median(t_host)), "scipy_dijkstra_s_spread": spread(t_host), "costs_equal_scipy": True}
+            if assemble:
+                line.update(time_assembly(sq, S, G, regs, info, repeats))
             if solve:
                 sides = {"whole": {}, "pruned": dict(prune="informed")}
                 for k, kw in list(sides.items()):                      # warm-up of both; a side the batch refuses is recorded, not timed
@@ -125,13 +161,14 @@ def main():
     ap.add_argument("--lattices", nargs="*", default=["25x40", "100x200"])
     ap.add_argument("--queries", type=int, default=4)
     ap.add_argument("--solve", nargs="*", default=[], help="the lattices on which solve is timed with and without prune")
+    ap.add_argument("--assemble", action="store_true", help="time the host-pruned against the induced assembly of the pruned graphs")
     ap.add_argument("--max-it", type=int, default=None, help="max_it of every member of a timed solve (default: the solver's)")
     ap.add_argument("--repeats", type=int, default=5)
     args = ap.parse_args()
     common = {} if args.max_it is None else dict(max_it=args.max_it)
     for name in args.lattices:
         nx, ny = (int(x) for x in name.split("x"))
-        measure(nx, ny, args.queries, args.repeats, name in args.solve, common)
+        measure(nx, ny, args.queries, args.repeats, name in args.solve, common, args.assemble)
 
 
 if __name__ == "__main__":
