@@ -13,6 +13,7 @@ LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libgcsadmm.
 
 F64, F32 = 0, 1
 RUNNING, CONVERGED, MAX_IT, DIVERGED = -1, 0, 1, 2
+BATCH_LARGE = 1        # GCSADMM_BATCH_LARGE (gcsadmm_batch_create_ex)
 STATUS_NAME = {RUNNING: "running", CONVERGED: "converged", MAX_IT: "max_it", DIVERGED: "diverged"}
 
 
@@ -76,6 +77,8 @@ PROTOTYPES = {
     "gcsadmm_run_timed": (_run_timed, _i),
     # batches of handles (gcs_admm_amd/batch.py)
     "gcsadmm_batch_create": ([_p, _i, _p], _i),
+    "gcsadmm_batch_create_ex": ([_p, _i, _i, _p], _i),
+    "gcsadmm_batch_query": ([_p] * 4, _i),
     "gcsadmm_batch_destroy": ([_p], None),
     "gcsadmm_batch_last_error": ([_p], C.c_char_p),
     "gcsadmm_batch_bind": ([_p] * 4, _i),

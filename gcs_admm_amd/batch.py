@@ -4,6 +4,10 @@ A small graph leaves most of an MI355X idle, and its vertex step is bound by dep
 (many start / goal queries, many scenes) gain from occupancy: ``BatchSolver`` holds one ordinary ``DeviceSolver`` per graph and
 advances all of them with one vertex launch and one edge + control launch per iteration.  Every member keeps its own state, control
 block and trace, stops on its own, and computes bit for bit what the same solver computes when it is driven alone.
+
+``large=True`` (GCSADMM_BATCH_LARGE of include/gcsadmm.h) also takes the graphs a plain batch refuses: members on the wavefront program,
+whose launch fills a fraction of the chip's 1 024 wavefront slots once it packs several vertices per wavefront, and members of 512 or
+more workgroup-program vertices.  ``member_programs`` is the rule that chooses each member's program.
 """
 from __future__ import annotations
 
@@ -14,33 +18,72 @@ from . import abi
 from .abi import RUNNING, State
 from .solver import DeviceSolver
 
+WAVE_SLOTS_ON_CHIP = 1024      # one wavefront of the wavefront program per SIMD: gcsadmm_create's own crossover between the two programs
+WAVE_MAX_SLOTS = 7             # vertices a wavefront may take (gcs::MAX_SLOTS, csrc/vertex_program.inc)
+WAVE_MAX_DEGREE = 63           # a vertex and its incident edges fill at most one wavefront
+
+
+def generic_degrees(g):
+    """degrees of the generic vertices of ``g``: those with an interior-point solve (not a terminal, edges in and out)"""
+    import numpy as np
+    deg = np.diff(np.asarray(g.inc_ptr)).astype(np.int64)
+    out = np.add.reduceat(np.append(np.asarray(g.inc_out, dtype=np.int64), 0), np.asarray(g.inc_ptr[:-1], dtype=np.int64)) * (deg > 0)
+    keep = (out > 0) & (deg - out > 0)
+    keep[[v for v in (g.src, g.dst) if 0 <= v < len(keep)]] = False
+    return deg[keep]
+
+
+def member_programs(graphs, large: bool = False):
+    """The ``DeviceSolver`` knobs of every member of a batch over ``graphs``, one dict each.
+
+    Plain batch: ``program="workgroup256"`` for all.  ``large``: at n = 2, when the generic vertices of the WHOLE batch exceed 1 024,
+    the members whose generic vertices all have degree <= 63 run ``program="wavefront"`` with ``wave_slots = min(7, ceil(total generic
+    / 1024))``; every other member stays on ``"workgroup256"``.  1 024 is gcsadmm_create's crossover between the two programs (one
+    round of the workgroup program at four workgroups per CU; the wavefront program's slots on the chip) and the slot count its packing
+    rule, both applied to the batch as a whole instead of to one graph: the launches of a batch hold all members at once."""
+    plain = [dict(program="workgroup256") for _ in graphs]
+    if not large or not graphs or any(g.n != 2 for g in graphs):
+        return plain
+    degrees = [generic_degrees(g) for g in graphs]
+    total = int(sum(len(d) for d in degrees))
+    if total <= WAVE_SLOTS_ON_CHIP:
+        return plain
+    slots = min(WAVE_MAX_SLOTS, -(-total // WAVE_SLOTS_ON_CHIP))
+    return [dict(program="wavefront", wave_slots=slots) if len(d) and d.max() <= WAVE_MAX_DEGREE else k for d, k in zip(degrees, plain)]
+
 
 class BatchSolver:
     """``graphs``: GcsGraph instances of one space dimension, small enough for the workgroup program (fewer than 512 generic vertices
-    each).  ``members[i]`` is the ``DeviceSolver(graphs[i], program="workgroup256")`` of graph i: its state tensors, ``cost()``,
-    ``read_control()`` and rounding work per member as they do for a solver of its own."""
+    each) unless ``large``.  ``members[i]`` is the ``DeviceSolver(graphs[i], **member_programs(graphs, large)[i])`` of graph i
+    (``program="workgroup256"`` in a plain batch): its state tensors, ``cost()``, ``read_control()`` and rounding work per member as
+    they do for a solver of its own."""
 
-    def __init__(self, graphs, state_dtype: str = "f64", device=None):
-        self.members = [DeviceSolver(g, state_dtype, device=device, program="workgroup256") for g in graphs]
+    def __init__(self, graphs, state_dtype: str = "f64", device=None, large: bool = False):
+        graphs = list(graphs)
+        self.members = [DeviceSolver(g, state_dtype, device=device, **knobs) for g, knobs in zip(graphs, member_programs(graphs, large))]
         self.b = None
-        self._init(self.members)
+        self._init(self.members, large)
 
     @classmethod
-    def of(cls, members):
-        """a batch over existing solvers (they stay the caller's and must outlive the batch)"""
+    def of(cls, members, large: bool = False):
+        """a batch over existing solvers (they stay the caller's and must outlive the batch); ``large``: created with
+        GCSADMM_BATCH_LARGE, so the solvers may run the wavefront program or hold 512 and more workgroup-program vertices"""
         self = cls.__new__(cls)
         self.members, self.b = list(members), None
-        self._init(self.members)
+        self._init(self.members, large)
         return self
 
-    def _init(self, members):
+    def _init(self, members, large=False):
         import torch
         self.torch, self.lib = torch, abi.load_library()
         self.device = members[0].device if members else torch.device("cuda", torch.cuda.current_device())
         handles = (C.c_void_p * max(len(members), 1))(*[m.h.value for m in members])
         b = C.c_void_p()
-        self._call("gcsadmm_batch_create", handles, len(members), C.byref(b), batch=False)
-        self.b = b
+        if large:
+            self._call("gcsadmm_batch_create_ex", handles, len(members), abi.BATCH_LARGE, C.byref(b), batch=False)
+        else:
+            self._call("gcsadmm_batch_create", handles, len(members), C.byref(b), batch=False)
+        self.large, self.b = bool(large), b
 
     # ------------------------------------------------------------------
     def _call(self, name, *args, batch=True):
@@ -68,6 +111,12 @@ class BatchSolver:
 
     def __len__(self):
         return len(self.members)
+
+    def launches(self):
+        """(members in the workgroup launch, wave launches, members over all wave launches) of one iteration (gcsadmm_batch_query)"""
+        out = [C.c_int32() for _ in range(3)]
+        self._call("gcsadmm_batch_query", *[C.byref(o) for o in out])
+        return tuple(o.value for o in out)
 
     # ------------------------------------------------------------------
     def bind(self):

@@ -5,6 +5,8 @@
 // A batch is a set of ordinary handles.  Its two kernels (vertex_wg_batch_kernel, edge_batch_kernel) pick the member by blockIdx.y and
 // run the device functions of the solo kernels on that member's own arguments, so a member is eligible exactly when ONE launch of ONE
 // instantiation of the in-LDS workgroup program does its whole vertex step, and one launch of the edge kernel its edge step.
+// GCSADMM_BATCH_LARGE adds a third kernel, vertex_wave_batch_kernel, for members with vertices on the wavefront program: one launch per
+// group of members that run the same instantiation of it (WaveGroup below), beside the workgroup launch of those that have one.
 #pragma once
 #include <algorithm>
 #include <string>
@@ -25,6 +27,13 @@ struct BatchMember {
     int has_comm;               // a communicator / halo is attached (gcsadmm_attach_comm)
 };
 
+// one launch of vertex_wave_batch_kernel (GCSADMM_BATCH_LARGE): the members whose wavefront vertices run one instantiation
+struct WaveGroup {
+    int all_m4 = 0, align_rows = 0, store_dl = 0;      // the plan's three choices that select the instantiation (vertex_kernel.h)
+    int grid_x = 0, lds_bytes = 0;                      // grid (grid_x, members.size()), 64 threads; dynamic LDS of the largest member
+    std::vector<int> members;                           // indices into the batch, ascending
+};
+
 struct BatchPlan {
     int count = 0, n = 0, dtype = 0, device = 0, box = 0;
     // vertex launch: grid (vertex_grid_x, count), 256 threads, vertex_lds_bytes of dynamic LDS; member m uses the first vertex_grid[m] columns
@@ -32,16 +41,27 @@ struct BatchPlan {
     // edge launch: grid (edge_grid_x, count), EDGE_BLOCK threads; member m uses the first edge_blocks[m] columns
     int edge_grid_x = 0;
     std::vector<int> vertex_grid, edge_blocks;
+    // GCSADMM_BATCH_LARGE: the workgroup launch has a row for each of wg_members only (without the flag: every member, in order), and
+    // the wavefront vertices run one launch per group; wave_grid[m]: wavefronts + closed-form workgroups of member m, 0: none
+    unsigned flags = 0;
+    std::vector<int> wg_members, wave_grid;
+    std::vector<WaveGroup> wave_groups;
 };
 
-// the eligibility rules, in the order they are checked, and the launch geometry; `err` names the member and the reason
-inline gcsadmm_status make_batch_plan(const BatchMember *m, int count, BatchPlan &bp, std::string &err)
+// the eligibility rules, in the order they are checked, and the launch geometry; `err` names the member and the reason.
+// flags = 0: one launch of the in-LDS workgroup program at 256 threads is every member's whole vertex step.  GCSADMM_BATCH_LARGE: a
+// member may also have vertices on the wavefront program (n = 2) -- they run vertex_wave_batch_kernel, one launch per group of members
+// that share (all_m4, align_rows, store_dl), and carry the member's closed-form vertices as launch_vertex does for a solo handle --
+// and any number of workgroup-program vertices: a batch does no slowest-first reorder (that changes scheduling, never results).
+inline gcsadmm_status make_batch_plan(const BatchMember *m, int count, BatchPlan &bp, std::string &err, unsigned flags = 0)
 {
+    const bool large = (flags & GCSADMM_BATCH_LARGE) != 0;
     auto fail = [&](gcsadmm_status st, int i, const char *why) {
         err = i < 0 ? std::string(why) : "member " + std::to_string(i) + ": " + why;
         return st;
     };
     bp = BatchPlan();
+    if (flags & ~(unsigned)GCSADMM_BATCH_LARGE) return fail(GCSADMM_ERR_BAD_ARG, -1, "unknown batch flag");
     if (!m || count < 1) return fail(GCSADMM_ERR_BAD_ARG, -1, "a batch needs at least one member");
     if (count > BATCH_MAX_MEMBERS) return fail(GCSADMM_ERR_UNSUPPORTED, -1, "a batch holds at most 65535 members");
     for (int i = 0; i < count; ++i) {
@@ -49,6 +69,8 @@ inline gcsadmm_status make_batch_plan(const BatchMember *m, int count, BatchPlan
         for (int j = 0; j < i; ++j)
             if (m[j].id == m[i].id) return fail(GCSADMM_ERR_BAD_ARG, i, "the handle appears twice in the batch");
     }
+    int first_wg = 0;      // (large) the first member with workgroup-program vertices: its BOX choice is the launch's
+    while (large && first_wg < count - 1 && m[first_wg].n_wg == 0) ++first_wg;
     for (int i = 0; i < count; ++i) {
         const CreatePlan &p = *m[i].plan;
         // one kernel instantiation serves the launch
@@ -56,24 +78,42 @@ inline gcsadmm_status make_batch_plan(const BatchMember *m, int count, BatchPlan
         if (m[i].n != m[0].n) return fail(GCSADMM_ERR_UNSUPPORTED, i, "members must share the space dimension n");
         if (m[i].dtype != m[0].dtype) return fail(GCSADMM_ERR_UNSUPPORTED, i, "members must share the state_dtype");
         // one launch of the in-LDS workgroup program at 256 threads is the member's whole vertex step
-        if (p.n_waves() > 0) return fail(GCSADMM_ERR_UNSUPPORTED, i, "vertices on the wavefront program (create the handle with vertex_program = 3)");
+        if (!large && p.n_waves() > 0) return fail(GCSADMM_ERR_UNSUPPORTED, i, "vertices on the wavefront program (create the handle with vertex_program = 3)");
         if (p.wg_t512) return fail(GCSADMM_ERR_UNSUPPORTED, i, "the workgroup program runs with 512 threads (create the handle with vertex_program = 3)");
         if (m[i].n_split > 0) return fail(GCSADMM_ERR_UNSUPPORTED, i, "vertices in the split form of the workgroup program (vertex_workspace)");
         if (p.n_term > 0) return fail(GCSADMM_ERR_UNSUPPORTED, i, "a terminal that is a region");
-        if (p.wg_reorder || m[i].n_wg >= REORDER_MIN_UNITS) return fail(GCSADMM_ERR_UNSUPPORTED, i, "512 or more workgroup-program vertices (slowest-first dispatch)");
+        if (!large && (p.wg_reorder || m[i].n_wg >= REORDER_MIN_UNITS)) return fail(GCSADMM_ERR_UNSUPPORTED, i, "512 or more workgroup-program vertices (slowest-first dispatch)");
         if (p.edge_unroll != 1) return fail(GCSADMM_ERR_UNSUPPORTED, i, "the edge step runs unrolled (a graph this large gains nothing from a batch)");
         if (m[i].has_comm) return fail(GCSADMM_ERR_UNSUPPORTED, i, "a communicator is attached (partitioned handles run their own loop)");
-        if (p.wg_box != m[0].plan->wg_box) return fail(GCSADMM_ERR_UNSUPPORTED, i, "members must share the BOX choice of the workgroup program (plan.wg_box)");
+        // (large: among the members that have workgroup-program vertices; the closed-form workgroups are the same in both instantiations)
+        if ((!large || m[i].n_wg > 0) && p.wg_box != m[first_wg].plan->wg_box)
+            return fail(GCSADMM_ERR_UNSUPPORTED, i, "members must share the BOX choice of the workgroup program (plan.wg_box)");
     }
-    bp.count = count; bp.n = m[0].n; bp.dtype = m[0].dtype; bp.device = m[0].device; bp.box = m[0].plan->wg_box;
+    bp.count = count; bp.n = m[0].n; bp.dtype = m[0].dtype; bp.device = m[0].device; bp.box = m[first_wg].plan->wg_box; bp.flags = flags;
     for (int i = 0; i < count; ++i) {
         const CreatePlan &p = *m[i].plan;
-        const int grid = m[i].n_wg + (m[i].n_special + 255) / 256;
+        // the closed-form vertices ride on the wave launch of a member that has one (launch_vertex's special_on_wave), else here
+        const bool special_on_wave = large && p.n_waves() > 0;
+        const int grid = m[i].n_wg + (special_on_wave ? 0 : (m[i].n_special + 255) / 256);
         bp.vertex_grid.push_back(grid);
         bp.edge_blocks.push_back(p.edge_blocks);
-        bp.vertex_grid_x = std::max(bp.vertex_grid_x, grid);
-        bp.vertex_lds_bytes = std::max(bp.vertex_lds_bytes, std::max(p.wg_lds_bytes, 4 * MAX_SPECIAL_DEG * 8));
         bp.edge_grid_x = std::max(bp.edge_grid_x, p.edge_blocks);
+        bp.wave_grid.push_back(special_on_wave ? p.n_waves() + (m[i].n_special + 63) / 64 : 0);
+        if (!large || grid > 0) {
+            bp.wg_members.push_back(i);
+            bp.vertex_grid_x = std::max(bp.vertex_grid_x, grid);
+            bp.vertex_lds_bytes = std::max(bp.vertex_lds_bytes, std::max(p.wg_lds_bytes, 4 * MAX_SPECIAL_DEG * 8));
+        }
+        if (!special_on_wave) continue;
+        auto g = std::find_if(bp.wave_groups.begin(), bp.wave_groups.end(),
+                              [&](const WaveGroup &w) { return w.all_m4 == p.all_m4 && w.align_rows == p.align_rows && w.store_dl == p.store_dl; });
+        if (g == bp.wave_groups.end()) {
+            bp.wave_groups.push_back(WaveGroup{p.all_m4, p.align_rows, p.store_dl});
+            g = bp.wave_groups.end() - 1;
+        }
+        g->members.push_back(i);
+        g->grid_x = std::max(g->grid_x, bp.wave_grid.back());
+        g->lds_bytes = std::max(g->lds_bytes, std::max(p.lds_bytes, 4 * MAX_SPECIAL_DEG * 8));
     }
     return GCSADMM_OK;
 }

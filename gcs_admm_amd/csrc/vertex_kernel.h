@@ -149,16 +149,17 @@ struct ProgBox {       // every polytope an axis-aligned box in canonical facet 
     }
 };
 
+// what one workgroup (one wavefront) of a vertex-step launch does once it knows its arguments: workgroup bx runs wavefront bx of the
+// program (or wave_order[bx]), the trailing workgroups take the closed-form vertices.  One body for the kernel that gets its arguments
+// in the kernarg segment (vertex_kernel) and the one that reads them from a table (vertex_wave_batch_kernel,
+// vertex_wave_batch_kernel.h): the same instructions on the same numbers.
 // SDL = 1: the LDS allocation has room for the final dual directions of the facet rows (lds_doubles(.., 1)); the
 // update pass applies them instead of recomputing the rows.  Chosen by the host when it does not cost occupancy.
 template <class PROG, int N, class T, int RMODE, int SDL>
-__global__ __launch_bounds__(WAVE) void vertex_kernel(typename PROG::template Args<T> a, SpecialArgs sp, const gcsadmm_control_block *cb)
+__device__ __forceinline__ void vertex_wave_body(const typename PROG::template Args<T> &a, const SpecialArgs &sp, double rho, double mu_scale, int bx, double *smem)
 {
-    extern __shared__ __attribute__((aligned(16))) double smem[];
-    if (cb->status != GCSADMM_RUNNING) return;
-    const double rho = cb->rho, mu_scale = cb->mu_scale;
-    if ((int)blockIdx.x >= a.n_waves) {   // trailing workgroups: the special vertices, one per lane (saves a ~4 us launch per iteration)
-        const int i = ((int)blockIdx.x - a.n_waves) * WAVE + (int)threadIdx.x;
+    if (bx >= a.n_waves) {   // trailing workgroups: the special vertices, one per lane (saves a ~4 us launch per iteration)
+        const int i = (bx - a.n_waves) * WAVE + (int)threadIdx.x;
         if (i < sp.count) {
             double *vals = smem + (sp.kind[i] == 2 ? 2 * MAX_SPECIAL_DEG : 0);   // source and target: own work arrays in LDS
             special_body<N, T>(a, sp, i, rho, mu_scale, vals, vals + MAX_SPECIAL_DEG);
@@ -178,11 +179,19 @@ __global__ __launch_bounds__(WAVE) void vertex_kernel(typename PROG::template Ar
     GpuExec<LaneT, RMODE> ex{L, (int)threadIdx.x};
 #endif
     // (the launch ends when its slowest wavefront does: those that ran longest last time are dispatched first)
-    PROG::template run<N, T, SDL>(ex, a.wave_order ? a.wave_order[blockIdx.x] : (int)blockIdx.x, a, S, rho, mu_scale);
+    PROG::template run<N, T, SDL>(ex, a.wave_order ? a.wave_order[bx] : bx, a, S, rho, mu_scale);
 #ifdef GCS_PHASE_TIMING
     __syncthreads();
     if (threadIdx.x < 64) atomicAdd(&g_phase_cycles[threadIdx.x], acc[threadIdx.x]);
 #endif
+}
+
+template <class PROG, int N, class T, int RMODE, int SDL>
+__global__ __launch_bounds__(WAVE) void vertex_kernel(typename PROG::template Args<T> a, SpecialArgs sp, const gcsadmm_control_block *cb)
+{
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    if (cb->status != GCSADMM_RUNNING) return;
+    vertex_wave_body<PROG, N, T, RMODE, SDL>(a, sp, cb->rho, cb->mu_scale, (int)blockIdx.x, smem);
 }
 
 // The instantiations of the kernel, listed once: N = 2 (the tuned dimension) has PROG x RMODE x SDL -- dense packing + wave shifts, and

@@ -380,7 +380,7 @@ class SceneQueries:
         return [self._host_graph(S[i], G[i], regs[i], regs[B + i], eps, info[i]["keep"] if prune else None) for i in range(B)], info
 
     def solve(self, starts, goals, state_dtype: str = "f64", N: int = 5, M: int = 20, seeds=None, params=None, return_state: bool = False,
-              walk: str = "host", assemble: str = "host", prune=None, restrict=None, **common):
+              walk: str = "host", assemble: str = "host", prune=None, restrict=None, large: bool = False, **common):
         """Every query to its stop test in one ``BatchSolver`` (``params``: one dict per query, ``common``: parameters of all, as
         ``BatchSolver.solve``), then rounded by ``rounding_many`` (``N``, ``M``: as ``rounding``; ``seeds``: one per query, default 0).
         ``walk``: ``"host"`` (the default: the walks of ``rounding``, on a host copy of every query's activations) or ``"device"``
@@ -388,7 +388,8 @@ class SceneQueries:
         ``walks.walk_reference`` -- other draws than the host's for the same seed).  ``assemble``: as ``graphs`` (the same graphs whichever way; ``"induced"`` only with ``prune``).
         ``prune``, ``restrict``: as ``graphs``; with ``prune="informed"`` every query runs on its informed region set alone, each record
         gains ``informed_bound`` and ``kept_regions``, and the bound's path is one more candidate of the rounding step, so that
-        ``rounded_cost <= informed_bound`` whenever the bound is finite.
+        ``rounded_cost <= informed_bound`` whenever the bound is finite.  ``large``: as ``BatchSolver`` -- query graphs a plain batch
+        refuses (unpruned queries on a scene of a thousand regions) run as wavefront members; small ones take the path they always took.
         Returns one record per query: that of ``DeviceSolver.solve`` plus ``rounded_cost``, ``x_v_rounded``, ``y_v_rounded`` and
         ``graph``; with ``return_state`` also ``trace`` and ``state``, host copies of the member's trace and of its six state arrays (the
         batch and its members are closed on return)."""
@@ -403,7 +404,7 @@ class SceneQueries:
             raise ValueError("one seed per query")
         # the bound's path with its restriction: one more candidate of the rounding step
         extra = info and [[(r["bound"], list(r["restriction"]), r["restriction"])] if r["restriction"] is not None else [] for r in info]
-        batch = BatchSolver(graphs, state_dtype, device=self.device)
+        batch = BatchSolver(graphs, state_dtype, device=self.device, large=large)
 
         def close():
             batch.close()

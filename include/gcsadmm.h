@@ -231,10 +231,24 @@ gcsadmm_status gcsadmm_run_timed(gcsadmm_handle h, const gcsadmm_state *st, int3
  * no terminal that is a region, fewer than 512 workgroup-program vertices, an edge step that runs one edge per thread (always the case
  * below 131 072 edges), no communicator attached.  Members may differ in graph, sizes, LDS bytes, column numbering, ownership masks and every
  * field of gcsadmm_params.  Every member keeps its own copy of its graph's polytope data, also where members share a scene.
+ *
+ * GCSADMM_BATCH_LARGE (gcsadmm_batch_create_ex) lifts two of these rules.  A member may have vertices on the WAVEFRONT program (n = 2,
+ * vertex_program = 0 or 1): that program takes a whole SIMD per wavefront, 1 024 on the chip, and a member packed at several vertices
+ * per wavefront (wave_slots) fills a fraction of them, so several members share a launch.  The members are grouped by the three plan
+ * choices that select a kernel instantiation (box or generic rows, aligned or dense groups, stored dual directions or not) and every
+ * group is one launch of vertex_wave_batch_kernel per iteration, which also carries the closed-form vertices of its members.  And a
+ * member may have any number of workgroup-program vertices, or both kinds: a batch does no slowest-first reorder, which changes the
+ * order of dispatch and never a result.  Per iteration: the workgroup launch over the members that have something in it, one wave
+ * launch per group, the edge + control launch.  Everything else above holds, the bit-for-bit statement included.
  */
 typedef struct gcsadmm_batch_s gcsadmm_batch_s;
+enum { GCSADMM_BATCH_LARGE = 1 };
 
 gcsadmm_status gcsadmm_batch_create(const gcsadmm_handle *members, int32_t count, struct gcsadmm_batch_s **out);
+/* gcsadmm_batch_create is this call with flags 0; a bit other than GCSADMM_BATCH_LARGE is GCSADMM_ERR_BAD_ARG */
+gcsadmm_status gcsadmm_batch_create_ex(const gcsadmm_handle *members, int32_t count, int32_t flags, struct gcsadmm_batch_s **out);
+/* the launches of an iteration (any pointer may be NULL): members in the workgroup launch, wave launches, members over all wave launches */
+gcsadmm_status gcsadmm_batch_query(struct gcsadmm_batch_s *b, int32_t *wg_members, int32_t *wave_groups, int32_t *wave_members);
 void gcsadmm_batch_destroy(struct gcsadmm_batch_s *b);
 const char *gcsadmm_batch_last_error(struct gcsadmm_batch_s *b);   /* b may be NULL: error of the calling thread's last failed create */
 
@@ -245,7 +259,8 @@ const char *gcsadmm_batch_last_error(struct gcsadmm_batch_s *b);   /* b may be N
 gcsadmm_status gcsadmm_batch_bind(struct gcsadmm_batch_s *b, const gcsadmm_state *states, double *const *traces_dev, void *stream);
 
 /* Enqueue up to k iterations of every member that is still RUNNING, with no host synchronisation: per iteration ONE vertex launch and
- * ONE edge + control launch for the whole batch.  A member whose stop test has fired is left exactly as it stopped. */
+ * ONE edge + control launch for the whole batch (GCSADMM_BATCH_LARGE: the vertex step is the workgroup launch, if any member has
+ * something in it, and one wave launch per group).  A member whose stop test has fired is left exactly as it stopped. */
 gcsadmm_status gcsadmm_batch_run(struct gcsadmm_batch_s *b, int32_t k, void *stream);
 
 /* status[count] and it[count] of the members' control blocks in one copy (either may be NULL; synchronises `stream`). */
