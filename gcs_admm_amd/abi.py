@@ -14,6 +14,7 @@ LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libgcsadmm.
 F64, F32 = 0, 1
 RUNNING, CONVERGED, MAX_IT, DIVERGED = -1, 0, 1, 2
 BATCH_LARGE = 1        # GCSADMM_BATCH_LARGE (gcsadmm_batch_create_ex)
+BATCH_TERMINALS = 4    # GCSADMM_BATCH_TERMINALS (bit 1 stays undefined)
 STATUS_NAME = {RUNNING: "running", CONVERGED: "converged", MAX_IT: "max_it", DIVERGED: "diverged"}
 
 
@@ -79,6 +80,7 @@ PROTOTYPES = {
     "gcsadmm_batch_create": ([_p, _i, _p], _i),
     "gcsadmm_batch_create_ex": ([_p, _i, _i, _p], _i),
     "gcsadmm_batch_query": ([_p] * 4, _i),
+    "gcsadmm_batch_query_terminals": ([_p] * 3, _i),
     "gcsadmm_batch_destroy": ([_p], None),
     "gcsadmm_batch_last_error": ([_p], C.c_char_p),
     "gcsadmm_batch_bind": ([_p] * 4, _i),
@@ -114,6 +116,7 @@ PROTOTYPES = {
     "gcsadmm_scene_restrict_paths": ([_p, _i, _p, _p, _p, _d, _i, _p, _p, _p, _p], _i),
     # the regions under query points on a resident scene (gcs_admm_amd/queries.py)
     "gcsadmm_scene_locate_points": ([_p, _i, _p, _d, _d, _p], _i),
+    "gcsadmm_scene_locate_boxes": ([_p, _i, _p, _p, _d, _p], _i),
     "gcsadmm_scene_read_hits": ([_p] * 4, _i),
     # edits of a decided scene
     "gcsadmm_scene_add_regions": ([_p, _i, _p, _p, _p, _d, _d] + [_p] * 6, _i),

@@ -8,6 +8,10 @@ block and trace, stops on its own, and computes bit for bit what the same solver
 ``large=True`` (GCSADMM_BATCH_LARGE of include/gcsadmm.h) also takes the graphs a plain batch refuses: members on the wavefront program,
 whose launch fills a fraction of the chip's 1 024 wavefront slots once it packs several vertices per wavefront, and members of 512 or
 more workgroup-program vertices.  ``member_programs`` is the rule that chooses each member's program.
+
+``region_terminals=True`` (GCSADMM_BATCH_TERMINALS) takes members whose start or goal is a set with an extent: their terminals are
+solved in one launch per group of terminals (thread count, home of the work arrays) beside the vertex launches.  It is opt-in and may
+be combined with ``large``.
 """
 from __future__ import annotations
 
@@ -58,32 +62,34 @@ class BatchSolver:
     (``program="workgroup256"`` in a plain batch): its state tensors, ``cost()``, ``read_control()`` and rounding work per member as
     they do for a solver of its own."""
 
-    def __init__(self, graphs, state_dtype: str = "f64", device=None, large: bool = False):
+    def __init__(self, graphs, state_dtype: str = "f64", device=None, large: bool = False, region_terminals: bool = False):
         graphs = list(graphs)
         self.members = [DeviceSolver(g, state_dtype, device=device, **knobs) for g, knobs in zip(graphs, member_programs(graphs, large))]
         self.b = None
-        self._init(self.members, large)
+        self._init(self.members, large, region_terminals)
 
     @classmethod
-    def of(cls, members, large: bool = False):
+    def of(cls, members, large: bool = False, region_terminals: bool = False):
         """a batch over existing solvers (they stay the caller's and must outlive the batch); ``large``: created with
-        GCSADMM_BATCH_LARGE, so the solvers may run the wavefront program or hold 512 and more workgroup-program vertices"""
+        GCSADMM_BATCH_LARGE, so the solvers may run the wavefront program or hold 512 and more workgroup-program vertices;
+        ``region_terminals``: created with GCSADMM_BATCH_TERMINALS, so the solvers may have a terminal that is a region"""
         self = cls.__new__(cls)
         self.members, self.b = list(members), None
-        self._init(self.members, large)
+        self._init(self.members, large, region_terminals)
         return self
 
-    def _init(self, members, large=False):
+    def _init(self, members, large=False, region_terminals=False):
         import torch
         self.torch, self.lib = torch, abi.load_library()
         self.device = members[0].device if members else torch.device("cuda", torch.cuda.current_device())
         handles = (C.c_void_p * max(len(members), 1))(*[m.h.value for m in members])
         b = C.c_void_p()
-        if large:
-            self._call("gcsadmm_batch_create_ex", handles, len(members), abi.BATCH_LARGE, C.byref(b), batch=False)
+        flags = (abi.BATCH_LARGE if large else 0) | (abi.BATCH_TERMINALS if region_terminals else 0)
+        if flags:
+            self._call("gcsadmm_batch_create_ex", handles, len(members), flags, C.byref(b), batch=False)
         else:
             self._call("gcsadmm_batch_create", handles, len(members), C.byref(b), batch=False)
-        self.large, self.b = bool(large), b
+        self.large, self.region_terminals, self.b = bool(large), bool(region_terminals), b
 
     # ------------------------------------------------------------------
     def _call(self, name, *args, batch=True):
@@ -116,6 +122,13 @@ class BatchSolver:
         """(members in the workgroup launch, wave launches, members over all wave launches) of one iteration (gcsadmm_batch_query)"""
         out = [C.c_int32() for _ in range(3)]
         self._call("gcsadmm_batch_query", *[C.byref(o) for o in out])
+        return tuple(o.value for o in out)
+
+    def terminal_launches(self):
+        """(terminal launches, region terminals over all of them) of one iteration (gcsadmm_batch_query_terminals): (0, 0) unless
+        the batch was made with ``region_terminals`` and a member has such a terminal"""
+        out = [C.c_int32() for _ in range(2)]
+        self._call("gcsadmm_batch_query_terminals", *[C.byref(o) for o in out])
         return tuple(o.value for o in out)
 
     # ------------------------------------------------------------------

@@ -7,6 +7,8 @@
 // instantiation of the in-LDS workgroup program does its whole vertex step, and one launch of the edge kernel its edge step.
 // GCSADMM_BATCH_LARGE adds a third kernel, vertex_wave_batch_kernel, for members with vertices on the wavefront program: one launch per
 // group of members that run the same instantiation of it (WaveGroup below), beside the workgroup launch of those that have one.
+// GCSADMM_BATCH_TERMINALS adds terminal_region_batch_kernel for members with a terminal that is a region: one launch per group of
+// terminals that run with the same thread count and keep their work arrays in the same place (TermGroup below).
 #pragma once
 #include <algorithm>
 #include <string>
@@ -34,6 +36,15 @@ struct WaveGroup {
     std::vector<int> members;                           // indices into the batch, ascending
 };
 
+// one launch of terminal_region_batch_kernel (GCSADMM_BATCH_TERMINALS): the terminals -- not the members: a member may have two -- whose
+// solves run with one thread count and one home of the work arrays.  The reductions of the solve depend on the thread count and the
+// home is a template parameter of the kernel, so these two are what a terminal's solo launch and its batch launch must share.
+struct TermGroup {
+    int threads = 0, in_lds = 0;                        // 64 or 256 (plan.term_threads); plan.term_lds_doubles > 0
+    int lds_doubles = 0;                                // dynamic LDS of the launch: the largest term_lds_doubles of the group's members
+    std::vector<int> member, term;                      // entry k: terminal term[k] of member member[k]; by member, then by terminal
+};
+
 struct BatchPlan {
     int count = 0, n = 0, dtype = 0, device = 0, box = 0;
     // vertex launch: grid (vertex_grid_x, count), 256 threads, vertex_lds_bytes of dynamic LDS; member m uses the first vertex_grid[m] columns
@@ -46,6 +57,8 @@ struct BatchPlan {
     unsigned flags = 0;
     std::vector<int> wg_members, wave_grid;
     std::vector<WaveGroup> wave_groups;
+    // GCSADMM_BATCH_TERMINALS: the region terminals of all members, one launch per group, grid = entries of the group; at most four groups
+    std::vector<TermGroup> term_groups;
 };
 
 // the eligibility rules, in the order they are checked, and the launch geometry; `err` names the member and the reason.
@@ -53,6 +66,8 @@ struct BatchPlan {
 // member may also have vertices on the wavefront program (n = 2) -- they run vertex_wave_batch_kernel, one launch per group of members
 // that share (all_m4, align_rows, store_dl), and carry the member's closed-form vertices as launch_vertex does for a solo handle --
 // and any number of workgroup-program vertices: a batch does no slowest-first reorder (that changes scheduling, never results).
+// GCSADMM_BATCH_TERMINALS: a member may have terminals that are regions; they are listed in term_groups by (term_threads,
+// term_lds_doubles > 0) of the member's create plan.  Without it the verdicts, the texts and the plan are what they were before the flag.
 inline gcsadmm_status make_batch_plan(const BatchMember *m, int count, BatchPlan &bp, std::string &err, unsigned flags = 0)
 {
     const bool large = (flags & GCSADMM_BATCH_LARGE) != 0;
@@ -61,7 +76,8 @@ inline gcsadmm_status make_batch_plan(const BatchMember *m, int count, BatchPlan
         return st;
     };
     bp = BatchPlan();
-    if (flags & ~(unsigned)GCSADMM_BATCH_LARGE) return fail(GCSADMM_ERR_BAD_ARG, -1, "unknown batch flag");
+    const bool terminals = (flags & GCSADMM_BATCH_TERMINALS) != 0;
+    if (flags & ~(unsigned)(GCSADMM_BATCH_LARGE | GCSADMM_BATCH_TERMINALS)) return fail(GCSADMM_ERR_BAD_ARG, -1, "unknown batch flag");
     if (!m || count < 1) return fail(GCSADMM_ERR_BAD_ARG, -1, "a batch needs at least one member");
     if (count > BATCH_MAX_MEMBERS) return fail(GCSADMM_ERR_UNSUPPORTED, -1, "a batch holds at most 65535 members");
     for (int i = 0; i < count; ++i) {
@@ -81,7 +97,7 @@ inline gcsadmm_status make_batch_plan(const BatchMember *m, int count, BatchPlan
         if (!large && p.n_waves() > 0) return fail(GCSADMM_ERR_UNSUPPORTED, i, "vertices on the wavefront program (create the handle with vertex_program = 3)");
         if (p.wg_t512) return fail(GCSADMM_ERR_UNSUPPORTED, i, "the workgroup program runs with 512 threads (create the handle with vertex_program = 3)");
         if (m[i].n_split > 0) return fail(GCSADMM_ERR_UNSUPPORTED, i, "vertices in the split form of the workgroup program (vertex_workspace)");
-        if (p.n_term > 0) return fail(GCSADMM_ERR_UNSUPPORTED, i, "a terminal that is a region");
+        if (!terminals && p.n_term > 0) return fail(GCSADMM_ERR_UNSUPPORTED, i, "a terminal that is a region");
         if (!large && (p.wg_reorder || m[i].n_wg >= REORDER_MIN_UNITS)) return fail(GCSADMM_ERR_UNSUPPORTED, i, "512 or more workgroup-program vertices (slowest-first dispatch)");
         if (p.edge_unroll != 1) return fail(GCSADMM_ERR_UNSUPPORTED, i, "the edge step runs unrolled (a graph this large gains nothing from a batch)");
         if (m[i].has_comm) return fail(GCSADMM_ERR_UNSUPPORTED, i, "a communicator is attached (partitioned handles run their own loop)");
@@ -103,6 +119,17 @@ inline gcsadmm_status make_batch_plan(const BatchMember *m, int count, BatchPlan
             bp.wg_members.push_back(i);
             bp.vertex_grid_x = std::max(bp.vertex_grid_x, grid);
             bp.vertex_lds_bytes = std::max(bp.vertex_lds_bytes, std::max(p.wg_lds_bytes, 4 * MAX_SPECIAL_DEG * 8));
+        }
+        for (int ti = 0; ti < p.n_term; ++ti) {
+            const int in_lds = p.term_lds_doubles > 0;
+            auto g = std::find_if(bp.term_groups.begin(), bp.term_groups.end(),
+                                  [&](const TermGroup &t) { return t.threads == p.term_threads && t.in_lds == in_lds; });
+            if (g == bp.term_groups.end()) {
+                bp.term_groups.push_back(TermGroup{p.term_threads, in_lds});
+                g = bp.term_groups.end() - 1;
+            }
+            g->member.push_back(i); g->term.push_back(ti);
+            g->lds_doubles = std::max(g->lds_doubles, p.term_lds_doubles);
         }
         if (!special_on_wave) continue;
         auto g = std::find_if(bp.wave_groups.begin(), bp.wave_groups.end(),

@@ -20,6 +20,8 @@
 //                        with its own arguments and control state, one vertex launch and one edge + control launch per iteration
 //   vertex_wave_batch_kernel<PROG,2,T,RMODE,SDL> (vertex_wave_batch_kernel.h)   the same for vertex_kernel, in batches made with
 //                        GCSADMM_BATCH_LARGE: one launch per group of members that run the same instantiation
+//   terminal_region_batch_kernel<N,T,LDSWS> (terminal_region.hip)   the same for terminal_region_kernel, in batches made with
+//                        GCSADMM_BATCH_TERMINALS: one launch per group of terminals, on the batch's auxiliary stream
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -153,11 +155,16 @@ struct gcsadmm_batch_s {
     std::vector<unsigned> resets;       // members' reset counts at bind
     BatchPlan plan;
     bool bound = false;
-    unsigned flags = 0;                 // GCSADMM_BATCH_LARGE or 0 (gcsadmm_batch_create_ex)
+    unsigned flags = 0;                 // GCSADMM_BATCH_LARGE | GCSADMM_BATCH_TERMINALS or 0 (gcsadmm_batch_create_ex)
     DevBuf<char> d_vertex_table, d_edge_table;      // [plan.wg_members.size()] WgBatchEntry<T> (vertex_wg_launch.h) / [count] EdgeBatchEntry<T>
     DevBuf<char> d_wave_table;                      // the groups' tables back to back, each [members of the group] WaveBatchEntry<PROG, T> (vertex_wave_batch_kernel.h)
     DevBuf<const gcsadmm_control_block *> d_cbs;    // [count] the members' control blocks (batch_poll_kernel)
     DevBuf<int> d_poll;                             // [2 count] status, it
+    // GCSADMM_BATCH_TERMINALS: the groups' tables back to back, each [terminals of the group] TermBatchEntry<T> (terminal_launch.h); the
+    // batch's own auxiliary stream for their launches beside the vertex launches, as Terminals has for a solo handle
+    DevBuf<char> d_term_table;
+    Stream term_stream;
+    Event ev_term_fork, ev_term_join;
     std::vector<int> poll_host;
 };
 
@@ -543,6 +550,17 @@ template <class F> static void each_wave_launch(const gcsadmm_batch_s *b, F &&f)
     }
 }
 
+// the terminal launches of a batch, one per group of its plan, the tables laid out as the wave launches' are
+template <class F> static void each_term_launch(const gcsadmm_batch_s *b, F &&f)
+{
+    const BatchPlan &bp = b->plan;
+    size_t off = 0;
+    for (const TermGroup &g : bp.term_groups) {
+        f(gcsadmm_k::TermBatchLaunch{bp.n, bp.dtype, b->d_term_table.get() + off, (int)g.member.size(), g.threads, g.in_lds ? g.lds_doubles : 0});
+        off += gcsadmm_terminal_batch_entry_bytes(bp.dtype) * g.member.size();
+    }
+}
+
 // the members are released from the batch: it cannot run until it is bound again
 static void batch_unbind(gcsadmm_batch_s *b)
 {
@@ -565,7 +583,7 @@ static gcsadmm_status batch_make(const gcsadmm_handle *members, int count, unsig
 {
     auto fail = [&](gcsadmm_status st, const std::string &msg) { g_create_error = msg; return st; };
     if (!out) return fail(GCSADMM_ERR_BAD_ARG, "null output pointer");
-    if (flags & ~(unsigned)GCSADMM_BATCH_LARGE) return fail(GCSADMM_ERR_BAD_ARG, "unknown batch flag");
+    if (flags & ~(unsigned)(GCSADMM_BATCH_LARGE | GCSADMM_BATCH_TERMINALS)) return fail(GCSADMM_ERR_BAD_ARG, "unknown batch flag");
     if (!members || count < 1) return fail(GCSADMM_ERR_BAD_ARG, "a batch needs at least one member");
     b = std::make_unique<gcsadmm_batch_s>();
     b->members.assign(members, members + count);
@@ -583,12 +601,17 @@ static gcsadmm_status batch_finish(std::unique_ptr<gcsadmm_batch_s> &b, hipError
 {
     const BatchPlan &plan = b->plan;
     const size_t count = (size_t)plan.count;
-    size_t wave_entries = 0;
+    size_t wave_entries = 0, term_entries = 0;
     for (const WaveGroup &g : plan.wave_groups) wave_entries += g.members.size();
+    for (const TermGroup &g : plan.term_groups) term_entries += g.member.size();
     hipError_t e = guard;
     if (e == hipSuccess) e = b->d_vertex_table.alloc(gcsadmm_wg_batch_entry_bytes(plan.dtype) * std::max<size_t>(plan.wg_members.size(), 1));
     if (e == hipSuccess) e = b->d_edge_table.alloc((plan.dtype == GCSADMM_F64 ? sizeof(EdgeBatchEntry<double>) : sizeof(EdgeBatchEntry<float>)) * count);
     if (e == hipSuccess && wave_entries > 0) e = b->d_wave_table.alloc(wave_batch_entry_bytes(plan.dtype) * wave_entries);
+    if (e == hipSuccess && term_entries > 0) e = b->d_term_table.alloc(gcsadmm_terminal_batch_entry_bytes(plan.dtype) * term_entries);
+    if (e == hipSuccess && term_entries > 0) e = create_owned(b->term_stream, hipStreamCreateWithFlags, hipStreamNonBlocking);
+    if (e == hipSuccess && term_entries > 0) e = create_owned(b->ev_term_fork, hipEventCreateWithFlags, hipEventDisableTiming);
+    if (e == hipSuccess && term_entries > 0) e = create_owned(b->ev_term_join, hipEventCreateWithFlags, hipEventDisableTiming);
     if (e == hipSuccess) e = b->d_cbs.alloc(count);
     if (e == hipSuccess) e = b->d_poll.upload(nullptr, 2 * count);
     if (e == hipSuccess && plan.vertex_lds_bytes > 48 * 1024) e = gcsadmm_wg_set_batch_lds(plan.n, plan.dtype, plan.vertex_lds_bytes);
@@ -613,13 +636,23 @@ static gcsadmm_status need_bound(gcsadmm_batch_s *b)
 }
 
 // one vertex launch of the workgroup program over the members that have something in it, one of the wavefront program per group
-// (GCSADMM_BATCH_LARGE alone has any) and one edge + control launch for the whole batch
+// (GCSADMM_BATCH_LARGE alone has any) and one edge + control launch for the whole batch.  GCSADMM_BATCH_TERMINALS: the terminal launches,
+// one per group, run on the batch's auxiliary stream beside the vertex launches -- forked before them, joined before the edge step, as
+// launch_vertex does for a solo handle; no member's own terminal stream is used
 static gcsadmm_status launch_batch_iteration(gcsadmm_batch_s *b, hipStream_t s)
 {
     const BatchPlan &bp = b->plan;
+    const bool with_term = !bp.term_groups.empty();
+    if (with_term) {
+        HIPCHK(b, hipEventRecord(b->ev_term_fork.get(), s));
+        HIPCHK(b, hipStreamWaitEvent(b->term_stream.get(), b->ev_term_fork.get(), 0));
+        each_term_launch(b, [&](const gcsadmm_k::TermBatchLaunch &t) { gcsadmm_terminal_launch_batch(t, b->term_stream.get()); });
+        HIPCHK(b, hipEventRecord(b->ev_term_join.get(), b->term_stream.get()));
+    }
     if (bp.vertex_grid_x > 0)
         gcsadmm_wg_launch_batch(WgBatchLaunch{bp.n, bp.dtype, bp.box, b->d_vertex_table.get(), (unsigned)bp.vertex_grid_x, (unsigned)bp.wg_members.size(), bp.vertex_lds_bytes}, s);
     each_wave_launch(b, [&](const WaveBatchLaunch &w) { wave_batch_launch(w, s); });
+    if (with_term) HIPCHK(b, hipStreamWaitEvent(s, b->ev_term_join.get(), 0));
     with_state_type(bp.dtype == GCSADMM_F64, [&](auto t) {
         using T = decltype(t);
         const auto *table = (const EdgeBatchEntry<T> *)b->d_edge_table.get();
@@ -1187,6 +1220,18 @@ gcsadmm_status gcsadmm_batch_query(struct gcsadmm_batch_s *b, int32_t *wg_member
     });
 }
 
+gcsadmm_status gcsadmm_batch_query_terminals(struct gcsadmm_batch_s *b, int32_t *term_groups, int32_t *terminals)
+{
+    return batch_entry(b, [&] { return GCSADMM_OK; }, [&] {      // (host only: the plan's counts)
+        const BatchPlan &bp = b->plan;
+        int32_t total = 0;
+        for (const TermGroup &g : bp.term_groups) total += (int32_t)g.member.size();
+        if (term_groups) *term_groups = (int32_t)bp.term_groups.size();
+        if (terminals) *terminals = total;
+        return GCSADMM_OK;
+    });
+}
+
 gcsadmm_status gcsadmm_batch_bind(struct gcsadmm_batch_s *b, const gcsadmm_state *states, double *const *traces_dev, void *stream)
 {
     BatchPlan bp;      // (made by the checks, taken by the work)
@@ -1230,6 +1275,15 @@ gcsadmm_status gcsadmm_batch_bind(struct gcsadmm_batch_s *b, const gcsadmm_state
                 wave_batch_fill(make_launch_desc(b->members[i], &states[i]), bp.dtype, wtab.data() + wtab.size() - wbytes);
             }
         if (!wtab.empty()) HIPCHK(b, hipMemcpy(b->d_wave_table.get(), wtab.data(), wtab.size(), hipMemcpyHostToDevice));
+        // the terminals' entries: the member's solo launch as its parameters at this bind make it (cold_start: no warm-start records)
+        const size_t tbytes = gcsadmm_terminal_batch_entry_bytes(bp.dtype);
+        std::vector<char> ttab;
+        for (const TermGroup &g : bp.term_groups)
+            for (size_t k = 0; k < g.member.size(); ++k) {
+                ttab.resize(ttab.size() + tbytes);
+                gcsadmm_terminal_batch_fill(make_term_desc(b->members[g.member[k]], &states[g.member[k]]), g.term[k], ttab.data() + ttab.size() - tbytes);
+            }
+        if (!ttab.empty()) HIPCHK(b, hipMemcpy(b->d_term_table.get(), ttab.data(), ttab.size(), hipMemcpyHostToDevice));
         HIPCHK(b, hipMemcpy(b->d_cbs.get(), cbs.data(), sizeof(cbs[0]) * cbs.size(), hipMemcpyHostToDevice));
         const gcsadmm_status est = with_state_type(bp.dtype == GCSADMM_F64, [&](auto t) -> gcsadmm_status {
             using T = decltype(t);

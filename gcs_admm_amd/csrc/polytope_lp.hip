@@ -99,7 +99,7 @@ struct SceneGraph {                                    // region graph of the de
     DevBuf<double> w;                                  //   distance between the centres of every edge (region_paths: made on first use)
     long long edges = 0;
 };
-struct LocateScratch {                                 // locate_points, kept and grown from call to call: the points [num_points][n],
+struct LocateScratch {                                 // locate_points / locate_boxes, kept and grown from call to call: the points [num_points][n] (boxes: [num_boxes][2 n]),
     DevBuf<double> points;
     DevBuf<int> count;                                 //   counts and
     DevBuf<long long> offset;                          //   offsets per (point, chunk)
@@ -312,6 +312,20 @@ template <int N> int launch_locate(const LocateArgs &args, long long num_points,
         const dim3 grid((unsigned)a.chunks, (unsigned)std::min(SLAB, num_points - q0));
         if (fill) hipLaunchKernelGGL((locate_kernel<N, true>), grid, dim3(LOCATE_WAVE), 0, 0, a);
         else hipLaunchKernelGGL((locate_kernel<N, false>), grid, dim3(LOCATE_WAVE), 0, 0, a);
+        LPCHK(hipGetLastError());
+    }
+    return GCSADMM_OK;
+}
+
+template <int N> int launch_locate_boxes(const LocateBoxArgs &args, long long num_boxes, bool fill)
+{
+    constexpr long long SLAB = 65535;      // grid.y
+    for (long long q0 = 0; q0 < num_boxes; q0 += SLAB) {
+        LocateBoxArgs a = args;
+        a.first_box = (int)q0;
+        const dim3 grid((unsigned)a.chunks, (unsigned)std::min(SLAB, num_boxes - q0));
+        if (fill) hipLaunchKernelGGL((locate_box_kernel<N, true>), grid, dim3(LOCATE_WAVE), 0, 0, a);
+        else hipLaunchKernelGGL((locate_box_kernel<N, false>), grid, dim3(LOCATE_WAVE), 0, 0, a);
         LPCHK(hipGetLastError());
     }
     return GCSADMM_OK;
@@ -749,6 +763,57 @@ int gcsadmm_scene_locate_points(gcsadmm_scene s, int num_points, const double *p
             a.offset = lq.offset.get(); a.limit = total;
             a.hit_region = s->hits.region.get(); a.hit_class = s->hits.cls.get();
             LPRUN(for_dim(r.n, [&](auto N) { return launch_locate<decltype(N)::value>(a, Q, true); }));
+        }
+        LPCHK(hipStreamSynchronize(nullptr));
+        s->hits.ptr.swap(hit_ptr);
+        stage_finish(s->have, CALL_LOCATE_POINTS);
+        if (num_hits) *num_hits = total;
+        return GCSADMM_OK;
+    });
+}
+
+// locate_points for boxes: the same resident hit list (the stage rule of locate_points), from locate_box_kernel
+int gcsadmm_scene_locate_boxes(gcsadmm_scene s, int num_boxes, const double *lo, const double *hi, double tol, int64_t *num_hits)
+{
+    return scene_entry(s, [&]() -> int {
+        const SceneRegions &r = s->reg;
+        LocateScratch &lq = s->lq;
+        if (num_boxes < 0 || (num_boxes > 0 && (!lo || !hi))) { g_err = "negative number of boxes or null bounds"; return GCSADMM_ERR_BAD_ARG; }
+        if (!(tol >= 0.0) || std::isinf(tol)) { g_err = "tol must be finite and non-negative"; return GCSADMM_ERR_BAD_ARG; }
+        const size_t n = (size_t)r.n, coords = (size_t)num_boxes * n;
+        for (size_t i = 0; i < coords; ++i) {
+            if (!std::isfinite(lo[i]) || !std::isfinite(hi[i])) { g_err = "box with a NaN or an inf bound"; return GCSADMM_ERR_BAD_ARG; }
+            if (lo[i] > hi[i]) { g_err = "box with lo > hi"; return GCSADMM_ERR_BAD_ARG; }
+        }
+        stage_start(s->have, CALL_LOCATE_POINTS);
+        const long long Q = num_boxes, chunks = locate_chunks(r.P);
+        const size_t cells = (size_t)(Q * chunks);
+        std::vector<int> count(cells);
+        std::vector<long long> offset(cells);
+        std::vector<int64_t> hit_ptr((size_t)Q + 1, 0);
+        std::vector<double> boxes(2 * coords);
+        for (size_t q = 0; q < (size_t)Q; ++q) locate_box_prepare(r.n, lo + q * n, hi + q * n, tol, boxes.data() + q * 2 * n);
+        LocateBoxArgs a{};
+        a.R = LocateRegions{r.P, r.ptr.get(), r.A.get(), r.b.get()};
+        a.chunks = chunks;
+        long long total = 0;
+        if (cells > 0) {
+            LPCHK(lq.points.reserve(2 * coords)); LPCHK(lq.count.reserve(cells));
+            LPCHK(to_device(lq.points.get(), boxes.data(), 2 * coords));
+            a.boxes = lq.points.get(); a.count = lq.count.get();
+            LPRUN(for_dim(r.n, [&](auto N) { return launch_locate_boxes<decltype(N)::value>(a, Q, false); }));
+            LPCHK(to_host(count.data(), lq.count.get(), cells));
+            if (!locate_scan(count.data(), Q, chunks, offset.data(), hit_ptr.data())) {      // before the list is allocated
+                g_err = "more than 2^31 - 1 hits"; return GCSADMM_ERR_UNSUPPORTED;
+            }
+            total = hit_ptr[(size_t)Q];
+        }
+        if (total > 0) {
+            LPCHK(s->hits.region.reserve((size_t)total)); LPCHK(s->hits.cls.reserve((size_t)total)); LPCHK(lq.offset.reserve(cells));
+            LPCHK(to_device(lq.offset.get(), offset.data(), cells));
+            a.offset = lq.offset.get(); a.limit = total;
+            a.hit_region = s->hits.region.get(); a.hit_class = s->hits.cls.get();
+            LPRUN(for_dim(r.n, [&](auto N) { return launch_locate_boxes<decltype(N)::value>(a, Q, true); }));
         }
         LPCHK(hipStreamSynchronize(nullptr));
         s->hits.ptr.swap(hit_ptr);

@@ -6,6 +6,7 @@
 #include "polytope_lp_core.h"
 #include "box_sweep_core.h"
 #include "point_locate_core.h"
+#include "box_locate_core.h"
 #include "scene_edit_core.h"
 #include "query_graph_core.h"
 #include "induced_graph_core.h"
@@ -214,6 +215,48 @@ __global__ __launch_bounds__(LOCATE_WAVE) void locate_kernel(LocateArgs a)
     for (int stride = 0; stride < LOCATE_CHUNK / LOCATE_WAVE; ++stride) {
         const int region = locate_region(a.R.P, chunk, stride, lane);
         const int cls = locate_lane<N>(a.R, region, p, a.margin);
+        const unsigned long long mask = __ballot(cls != LOCATE_OUT);
+        if (FILL) {
+            locate_store(a.hit_region, a.hit_class, pos, a.limit, mask, lane, region, cls);
+            pos += locate_hits(mask);
+        } else {
+            total += locate_hits(mask);
+        }
+    }
+    if (!FILL && lane == 0) a.count[cell] = total;
+}
+
+// ---- the regions that query boxes meet (box_locate_core.h) ----
+struct LocateBoxArgs {
+    LocateRegions R;
+    const double *boxes;       // [num_boxes][2 N]: the centre, then the half-widths + 2 tol (locate_box_prepare)
+    int first_box;             // blockIdx.y counts from here (one launch takes at most 65 535 boxes)
+    long long chunks, limit;   // chunks of the P regions; length of the list
+    int *count;                // [num_boxes][chunks]
+    const long long *offset;   // [num_boxes][chunks]
+    int *hit_region;
+    unsigned char *hit_class;
+};
+
+// locate_kernel's shape with a box in the place of the point: one 64-lane workgroup per (chunk of regions, box), one region per lane,
+// a count pass (FILL = false) and a fill pass that runs the same tests again and writes the hits from offset[box][chunk] on
+template <int N, bool FILL>
+__global__ __launch_bounds__(LOCATE_WAVE) void locate_box_kernel(LocateBoxArgs a)
+{
+    const long long chunk = blockIdx.x, q = (long long)a.first_box + blockIdx.y;
+    const int lane = threadIdx.x;
+    double c[N], hw[N];
+#pragma unroll
+    for (int k = 0; k < N; ++k) {      // the same addresses in every lane
+        c[k] = a.boxes[(size_t)q * 2 * N + k];
+        hw[k] = a.boxes[(size_t)q * 2 * N + N + k];
+    }
+    const size_t cell = (size_t)(q * a.chunks + chunk);
+    long long pos = FILL ? a.offset[cell] : 0;
+    int total = 0;
+    for (int stride = 0; stride < LOCATE_CHUNK / LOCATE_WAVE; ++stride) {
+        const int region = locate_region(a.R.P, chunk, stride, lane);
+        const int cls = locate_box_lane<N>(a.R, region, c, hw);
         const unsigned long long mask = __ballot(cls != LOCATE_OUT);
         if (FILL) {
             locate_store(a.hit_region, a.hit_class, pos, a.limit, mask, lane, region, cls);

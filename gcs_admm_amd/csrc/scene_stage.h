@@ -10,7 +10,7 @@
 //   set_boxes         -                                 boxes, pairs, overlaps   -               boxes
 //   candidate_pairs   boxes                             pairs, overlaps, graph   -               pairs
 //   overlaps          pairs, centers                    overlaps, graph          -               overlaps
-//   locate_points     -                                 hits                     -               hits
+//   locate_points     -                                 hits                     -               hits          (and locate_boxes: the same list)
 //   add_regions       centers, boxes, pairs, decided    -                        hits, graph     -
 //   remove_regions    -                                 -                        hits, graph     -
 //   build_graph       decided                           -                        -               graph

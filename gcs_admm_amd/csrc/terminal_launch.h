@@ -25,7 +25,29 @@ struct TermLaunchDesc {
     int lds_doubles;                // > 0: the work arrays of every terminal fit this much dynamic LDS and live there; 0: in ws
 };
 
+// entry of the table of terminal_region_batch_kernel: what the solo kernel of the terminal's handle gets as arguments, and which of
+// the handle's terminals the workgroup solves
+template <class T> struct TermBatchEntry {
+    StepArgs<T> a;
+    TermBlock t;
+    const gcsadmm_control_block *cb;
+    int ti;
+};
+
+// one terminal launch of a batch: `table` is a device array of `count` entries laid out by gcsadmm_terminal_batch_fill, one per
+// terminal of the group; every terminal of the group runs with `threads` threads and keeps its work arrays in LDS or not as the group does
+struct TermBatchLaunch {
+    int n, dtype;
+    const void *table;
+    int count, threads;
+    int lds_doubles;                // the largest of the group's members; 0: the group's terminals work in their handles' ws
+};
+
 }  // namespace gcsadmm_k
 
 // (work-array and record sizes, gcsadmm_terminal_ws_doubles / gcsadmm_terminal_record_doubles: create_plan.h, which is host-only)
 void gcsadmm_terminal_launch(const gcsadmm_k::TermLaunchDesc &d, hipStream_t s);
+// the batch form: bytes of a table entry for that state type; the entry of terminal `ti` of the handle whose solo launch is `d`; the launch
+size_t gcsadmm_terminal_batch_entry_bytes(int dtype);
+void gcsadmm_terminal_batch_fill(const gcsadmm_k::TermLaunchDesc &d, int ti, void *entry_host);
+void gcsadmm_terminal_launch_batch(const gcsadmm_k::TermBatchLaunch &b, hipStream_t s);

@@ -1,5 +1,6 @@
 // terminal_region.hip -- x-update of terminals that are regions (terminal_region.h): one workgroup of 64 or 256 threads per terminal, launched on
-// the handle's auxiliary stream beside the vertex-step launch (gcsadmm.hip launch_vertex).  Own object: the vertex kernels are not touched.
+// the handle's auxiliary stream beside the vertex-step launch (gcsadmm.hip launch_vertex), or, for the members of a batch, one launch per
+// group of terminals on the batch's (launch_batch_iteration).  Own object: the vertex kernels are not touched.
 #include <hip/hip_runtime.h>
 
 #include "gcsadmm.h"
@@ -52,15 +53,18 @@ struct TermExec {
     }
 };
 
+// The solve of terminal `ti` of the handle that (a, t, cb) describe, by the calling workgroup: the body of both kernels below, so that a
+// terminal solved in a batch launch is the same instructions on the same arguments as in its handle's own launch.  A handle that has
+// stopped leaves before any barrier or LDS use.  TB is TermBlock as the kernel holds it: a kernel argument, or a table entry in the
+// constant address space -- `ti` indexes its arrays, and an index the compiler cannot resolve into a private copy would cost scratch.
+// The LDS objects are the calling kernel's own, so that each kernel lays out its LDS as if the other did not exist.
 // LDSWS: the work arrays live in dynamic LDS (its own instantiation, so that the compiler addresses them as LDS rather than through flat pointers)
-template <int N, class T, bool LDSWS>
-__global__ __launch_bounds__(TERM_THREADS) void terminal_region_kernel(StepArgs<T> a, TermBlock t, const gcsadmm_control_block *cb)
+template <int N, class T, bool LDSWS, class TB>
+__device__ __forceinline__ void terminal_region_body(const StepArgs<T> &a, TB &t, const gcsadmm_control_block *cb, const int ti,
+                                                     gcs_term::TermShared<N> &sh, double *red, double *term_lds)
 {
-    extern __shared__ __attribute__((aligned(16))) double term_lds[];
     if (cb->status != GCSADMM_RUNNING) return;
-    __shared__ gcs_term::TermShared<N> sh;
-    __shared__ double red[12];
-    const int ti = (int)blockIdx.x, v = t.vtx[ti];
+    const int v = t.vtx[ti];
     gcs_term::TermProblem<T> P;
     const int p0 = a.poly_ptr[v], lo = a.inc_ptr[v];
     P.m = a.poly_ptr[v + 1] - p0; P.d = a.inc_ptr[v + 1] - lo; P.d_in = a.deg_in[v]; P.is_src = t.is_src[ti];
@@ -82,11 +86,47 @@ __global__ __launch_bounds__(TERM_THREADS) void terminal_region_kernel(StepArgs<
     }
 }
 
+// one handle: workgroup blockIdx.x solves its terminal blockIdx.x
+template <int N, class T, bool LDSWS>
+__global__ __launch_bounds__(TERM_THREADS) void terminal_region_kernel(StepArgs<T> a, TermBlock t, const gcsadmm_control_block *cb)
+{
+    extern __shared__ __attribute__((aligned(16))) double term_lds[];
+    __shared__ gcs_term::TermShared<N> sh;
+    __shared__ double red[12];
+    terminal_region_body<N, T, LDSWS, const TermBlock>(a, t, cb, (int)blockIdx.x, sh, red, term_lds);
+}
+
+// BATCH form (gcsadmm_batch_run on a batch made with GCSADMM_BATCH_TERMINALS): workgroup blockIdx.x solves entry blockIdx.x of the
+// table, one entry per TERMINAL of the launch's group -- the kernarg of the solo launch of that terminal's handle and the terminal's
+// index in it.  The table is written by the host before the launch and by nobody during it: it is read through the constant address
+// space, as kernel arguments are (vertex_wave_batch_kernel.h).  The index is uniform over the workgroup, so the entry comes in through
+// scalar loads.  The launch's thread count and LDSWS are those of every member of the group (batch_plan.h groups by them).
+template <int N, class T, bool LDSWS>
+__global__ __launch_bounds__(TERM_THREADS) void terminal_region_batch_kernel(const TermBatchEntry<T> *__restrict__ table)
+{
+    extern __shared__ __attribute__((aligned(16))) double term_lds[];
+    __shared__ gcs_term::TermShared<N> sh;
+    __shared__ double red[12];
+    using Entry = const __attribute__((address_space(4))) TermBatchEntry<T>;
+    __builtin_assume_dereferenceable(table + blockIdx.x, sizeof(Entry));
+    Entry &e = *((Entry *)table + blockIdx.x);
+    const StepArgs<T> a = *(const StepArgs<T> *)&e.a;
+    terminal_region_body<N, T, LDSWS, const __attribute__((address_space(4))) TermBlock>(a, e.t, e.cb, e.ti, sh, red, term_lds);
+}
+
 template <int N, class T> static void launch_n(const TermLaunchDesc &d, hipStream_t s)
 {
     const size_t lds = (size_t)d.lds_doubles * sizeof(double);
     if (lds) hipLaunchKernelGGL((terminal_region_kernel<N, T, true>), dim3(d.count), dim3(d.threads), lds, s, d.step.typed<T>(), d.t, d.step.cb);
     else hipLaunchKernelGGL((terminal_region_kernel<N, T, false>), dim3(d.count), dim3(d.threads), 0, s, d.step.typed<T>(), d.t, d.step.cb);
+}
+
+template <int N, class T> static void launch_batch_n(const TermBatchLaunch &b, hipStream_t s)
+{
+    const size_t lds = (size_t)b.lds_doubles * sizeof(double);
+    const auto *table = (const TermBatchEntry<T> *)b.table;
+    if (lds) hipLaunchKernelGGL((terminal_region_batch_kernel<N, T, true>), dim3(b.count), dim3(b.threads), lds, s, table);
+    else hipLaunchKernelGGL((terminal_region_batch_kernel<N, T, false>), dim3(b.count), dim3(b.threads), 0, s, table);
 }
 
 }  // namespace gcsadmm_k
@@ -111,5 +151,28 @@ void gcsadmm_terminal_launch(const gcsadmm_k::TermLaunchDesc &d, hipStream_t s)
         constexpr int N = decltype(n)::value;
         if (d.dtype == GCSADMM_F64) launch_n<N, double>(d, s);
         else launch_n<N, float>(d, s);
+    });
+}
+
+size_t gcsadmm_terminal_batch_entry_bytes(int dtype)
+{
+    return dtype == GCSADMM_F64 ? sizeof(gcsadmm_k::TermBatchEntry<double>) : sizeof(gcsadmm_k::TermBatchEntry<float>);
+}
+
+void gcsadmm_terminal_batch_fill(const gcsadmm_k::TermLaunchDesc &d, int ti, void *entry_host)
+{
+    using namespace gcsadmm_k;
+    if (d.dtype == GCSADMM_F64) *(TermBatchEntry<double> *)entry_host = TermBatchEntry<double>{d.step.typed<double>(), d.t, d.step.cb, ti};
+    else *(TermBatchEntry<float> *)entry_host = TermBatchEntry<float>{d.step.typed<float>(), d.t, d.step.cb, ti};
+}
+
+void gcsadmm_terminal_launch_batch(const gcsadmm_k::TermBatchLaunch &b, hipStream_t s)
+{
+    using namespace gcsadmm_k;
+    if (b.count <= 0) return;
+    dispatch_dim<1, 2, 3, 4, 5, 6, 7, 8>(b.n, [&](auto n) {
+        constexpr int N = decltype(n)::value;
+        if (b.dtype == GCSADMM_F64) launch_batch_n<N, double>(b, s);
+        else launch_batch_n<N, float>(b, s);
     });
 }

@@ -157,8 +157,30 @@ class SceneQueries:
         if self.scene is None:
             raise RuntimeError("the scene is closed")
         pts = np.ascontiguousarray(points, float).reshape(-1, self.n)
+        return self._decide(self.scene.locate(pts, eps, tol), pts, lambda q: convert_pt_to_polytope(pts[q], eps), tol)
+
+    def regions_meeting(self, lo, hi, tol: float = 1e-9):
+        """``regions_at`` for boxes: the regions that meet each box ``[lo[q], hi[q]]`` ([Q, n] each), one ascending int32 array of region
+        indices per box.  One ``locate_boxes`` call (csrc/box_locate_core.h) for all boxes; its UNDECIDED hits -- for a box as wide as a
+        region, every region that reaches into it without holding its centre -- go through ONE call of the pair LPs, the box as the
+        polytope ``[I; -I] x <= [hi; -lo]`` first in every pair, its LP started at the box's centre; an LP that reports status < 0 is
+        decided by ``graph.polytopes_overlap``.  ``last`` is filled as ``regions_at`` fills it."""
+        if self.scene is None:
+            raise RuntimeError("the scene is closed")
+        lo = np.ascontiguousarray(lo, float).reshape(-1, self.n); hi = np.ascontiguousarray(hi, float).reshape(-1, self.n)
+        if lo.shape != hi.shape:
+            raise ValueError("lo and hi must have one shape")
+        return self._decide(self.scene.locate_boxes(lo, hi, tol), 0.5 * (lo + hi), lambda q: self._box_polytope(lo[q], hi[q]), tol)
+
+    def _box_polytope(self, lo, hi):
+        """the box as ``graph_from_sets`` is given it: ``[I; -I] x <= [hi; -lo]``"""
+        return np.vstack([np.eye(self.n), -np.eye(self.n)]), np.hstack([np.asarray(hi, float), -np.asarray(lo, float)])
+
+    def _decide(self, hits, pts, term_poly, tol):
+        """the region lists of a hit list: the IN hits and those UNDECIDED hits that one call of the pair LPs (terminal ``term_poly(q)``
+        first, started at ``pts[q]``) or, after a status < 0, ``graph.polytopes_overlap`` finds to overlap"""
+        hit_ptr, hit_region, hit_class = hits
         Q = pts.shape[0]
-        hit_ptr, hit_region, hit_class = self.scene.locate(pts, eps, tol)
         keep = hit_class == IN
         und = np.nonzero(hit_class == UNDECIDED)[0]
         redone = 0
@@ -166,7 +188,7 @@ class SceneQueries:
             point_of = np.repeat(np.arange(Q), np.diff(hit_ptr))[und]
             qs, pa = np.unique(point_of, return_inverse=True)
             rs, pb = np.unique(hit_region[und], return_inverse=True)
-            polys = [convert_pt_to_polytope(pts[q], eps) for q in qs] + [self.polys[r] for r in rs]
+            polys = [term_poly(q) for q in qs] + [self.polys[r] for r in rs]
             start = np.vstack([pts[qs], self.centers[rs]])
             flags, status = self._pair_lp(polys, pa.astype(np.int32), (len(qs) + pb).astype(np.int32), tol, start)
             flags = np.array(flags, copy=True)
@@ -192,19 +214,46 @@ class SceneQueries:
         term_ptr[1:] = np.cumsum([len(r) for r in regs])
         return term_ptr, (np.concatenate(regs) if regs else np.zeros(0, np.int32))
 
-    def _located(self, starts, goals, eps, tol):
-        """(S [B, n], G [B, n], the region lists of ``regions_at`` for the starts, then the goals); a point in no region raises"""
-        S = np.ascontiguousarray(starts, float).reshape(-1, self.n)
-        G = np.ascontiguousarray(goals, float).reshape(-1, self.n)
+    MIN_HALF_WIDTH = 1e-5      # of a box terminal: above it gcsadmm_create takes the terminal for a region, and the box has an interior
+
+    def _box_terminals(self, boxes, which):
+        """(lo [B, n], hi [B, n]) of ``start_boxes`` / ``goal_boxes``; a box thinner than a region may be is refused"""
+        lo, hi = boxes
+        lo = np.ascontiguousarray(lo, float).reshape(-1, self.n); hi = np.ascontiguousarray(hi, float).reshape(-1, self.n)
+        if lo.shape != hi.shape:
+            raise ValueError(f"{which}_boxes: lo and hi must have one shape")
+        if lo.size and not np.all(0.5 * (hi - lo) > self.MIN_HALF_WIDTH):
+            raise ValueError(f"{which}_boxes: every half-width must exceed {self.MIN_HALF_WIDTH:g}: give a point as a point ({which}s)")
+        return lo, hi
+
+    def _located(self, starts, goals, eps, tol, start_boxes=None, goal_boxes=None):
+        """(S [B, n], G [B, n], the region lists of ``regions_at`` / ``regions_meeting`` for the starts, then the goals, (lo, hi) of the
+        start boxes or None, (lo, hi) of the goal boxes or None); S, G: the points, or the centres of the boxes.  A terminal that meets
+        no region raises"""
+        for which, pts, boxes in (("start", starts, start_boxes), ("goal", goals, goal_boxes)):
+            if (pts is None) == (boxes is None):
+                raise ValueError(f"give exactly one of {which}s and {which}_boxes")
+        sb = self._box_terminals(start_boxes, "start") if start_boxes is not None else None
+        gb = self._box_terminals(goal_boxes, "goal") if goal_boxes is not None else None
+        S = np.ascontiguousarray(starts, float).reshape(-1, self.n) if sb is None else 0.5 * (sb[0] + sb[1])
+        G = np.ascontiguousarray(goals, float).reshape(-1, self.n) if gb is None else 0.5 * (gb[0] + gb[1])
         if len(S) != len(G):
             raise ValueError("one goal for every start")
         B = len(S)
-        regs = self.regions_at(np.vstack([S, G]), eps, tol)
+        if sb is None and gb is None:
+            regs = self.regions_at(np.vstack([S, G]), eps, tol)
+        elif sb is not None and gb is not None:
+            regs = self.regions_meeting(np.vstack([sb[0], gb[0]]), np.vstack([sb[1], gb[1]]), tol)
+        else:      # a point on one side, a box on the other: one locate call each; `last` adds the two up
+            first = self.regions_at(S, eps, tol) if sb is None else self.regions_meeting(*sb, tol)
+            counts = dict(self.last)
+            regs = first + (self.regions_at(G, eps, tol) if gb is None else self.regions_meeting(*gb, tol))
+            self.last = {k: v + counts[k] for k, v in self.last.items()}
         for i in range(B):
             for which, r in (("start", regs[i]), ("goal", regs[B + i])):
                 if len(r) == 0:
                     raise ValueError(f"query {i}: the {which} lies in no region")
-        return S, G, regs
+        return S, G, regs, sb, gb
 
     def informed(self, starts, goals, eps: float = 1e-6, tol: float = 1e-9, restrict=None):
         """The informed region set of every query (csrc/informed_core.h): the regions an optimal path can touch lie in the ellipsoid with
@@ -219,7 +268,7 @@ class SceneQueries:
 
         ``restrict``: ``(As, bs, n, paths) -> [(cost, xs)]`` as ``solver`` in ``rounding`` (default: ``solve_path_restrictions_device``).
         The boxes are moved out by ``scene.SWEEP_PAD``.  The region graph is built on the scene on first use and after an edit."""
-        S, G, regs = self._located(starts, goals, eps, tol)
+        S, G, regs, _, _ = self._located(starts, goals, eps, tol)
         return self._informed(S, G, regs, eps, restrict)
 
     def _informed(self, S, G, regs, eps, restrict=None):
@@ -254,9 +303,10 @@ class SceneQueries:
             keep[i, regs[B + i]] = True
         return [dict(path=np.asarray(paths[i], np.int32), bound=float(bound[i]), keep=keep[i], restriction=points_of[i]) for i in range(B)]
 
-    def _host_graph(self, s, g, rs, rt, eps, keep=None):
+    def _host_graph(self, s, g, rs, rt, eps, keep=None, sbox=None, gbox=None):
         """the graph of one query from one ``lexsort`` over all edges and ``graph._finish_graph``: on all regions, or (``keep``: bool [P]) on
-        the induced subgraph of the kept ones, renumbered in scene order"""
+        the induced subgraph of the kept ones, renumbered in scene order.  ``sbox``, ``gbox``: (lo, hi) of a terminal that is a box (s, g
+        are then its centre)"""
         tail_r, head_r, keys, polys, centers = self.edge_tail, self.edge_head, self.keys, self.polys, self.centers
         if keep is not None:
             idx = np.nonzero(keep)[0]
@@ -266,13 +316,15 @@ class SceneQueries:
             keys, polys, centers = [keys[r] for r in idx], [polys[r] for r in idx], centers[idx]
             rs, rt = new[rs], new[rt]
         rs, rt = rs.astype(np.int64) + 2, rt.astype(np.int64) + 2
-        (lo_s, hi_s), (lo_t, hi_t) = (s - eps, s + eps), (g - eps, g + eps)      # the bounds graph._as_box reads off convert_pt_to_polytope(p, eps)
+        # the bounds graph._as_box reads off convert_pt_to_polytope(p, eps), or off the box itself
+        (lo_s, hi_s), (lo_t, hi_t) = sbox or (s - eps, s + eps), gbox or (g - eps, g + eps)
         st = np.array([0], np.int64) if np.all(np.maximum(lo_s, lo_t) <= np.minimum(hi_s, hi_t) + 1e-9) else np.zeros(0, np.int64)
         zs, zt = np.zeros(len(rs), np.int64), np.ones(len(rt), np.int64)
         tail = np.concatenate([tail_r.astype(np.int64) + 2, zs, rs, zt, rt, st, st + 1])
         head = np.concatenate([head_r.astype(np.int64) + 2, rs, zs, rt, zt, st + 1, st])
         o = np.lexsort((head, tail))
-        polys = [convert_pt_to_polytope(s, eps), convert_pt_to_polytope(g, eps)] + polys
+        polys = [self._box_polytope(*sbox) if sbox else convert_pt_to_polytope(s, eps),
+                 self._box_polytope(*gbox) if gbox else convert_pt_to_polytope(g, eps)] + polys
         return _finish_graph(self.n, ['s', 't'] + keys, tail[o], head[o], polys, np.vstack([s, g, centers]), 0, 1)
 
     def _stack(self):
@@ -285,13 +337,21 @@ class SceneQueries:
         return self._stacked
 
     @staticmethod
-    def _adjacent(S, G, eps):
-        """uint8 [B]: do the boxes of start and goal meet (the interval rule of ``_host_graph``)"""
-        return np.array([np.all(np.maximum(S[i] - eps, G[i] - eps) <= np.minimum(S[i] + eps, G[i] + eps) + 1e-9) for i in range(len(S))], np.uint8)
+    def _box_of(boxes, i):
+        """(lo, hi) of terminal i of ``boxes`` = (lo [B, n], hi [B, n]), or None for a side given as points"""
+        return None if boxes is None else (boxes[0][i], boxes[1][i])
 
-    def _point_rows(self, s, g, eps):
-        """the polytope rows of the two point boxes of a query: (A [4 n, n], b [4 n])"""
-        (A_s, b_s), (A_t, b_t) = convert_pt_to_polytope(s, eps), convert_pt_to_polytope(g, eps)
+    @staticmethod
+    def _adjacent(S, G, eps, sb=None, gb=None):
+        """uint8 [B]: do the boxes of start and goal meet (the interval rule of ``_host_graph``)"""
+        lo_s, hi_s = (S - eps, S + eps) if sb is None else sb
+        lo_t, hi_t = (G - eps, G + eps) if gb is None else gb
+        return np.array([np.all(np.maximum(lo_s[i], lo_t[i]) <= np.minimum(hi_s[i], hi_t[i]) + 1e-9) for i in range(len(S))], np.uint8)
+
+    def _point_rows(self, s, g, eps, sbox=None, gbox=None):
+        """the polytope rows of the two terminals of a query, point boxes or (``sbox``, ``gbox``) boxes: (A [4 n, n], b [4 n])"""
+        A_s, b_s = self._box_polytope(*sbox) if sbox else convert_pt_to_polytope(s, eps)
+        A_t, b_t = self._box_polytope(*gbox) if gbox else convert_pt_to_polytope(g, eps)
         return (np.concatenate([np.asarray(A_s, float).reshape(-1, self.n), np.asarray(A_t, float).reshape(-1, self.n)]),
                 np.concatenate([np.asarray(b_s, float).ravel(), np.asarray(b_t, float).ravel()]))
 
@@ -320,7 +380,7 @@ class SceneQueries:
                                 interior=np.concatenate([S[i][None], G[i][None], self.centers[idx]]), src=0, dst=1))
         return out
 
-    def _assemble_on_device(self, S, G, regs, eps):
+    def _assemble_on_device(self, S, G, regs, eps, sb=None, gb=None):
         """the graphs of ``graphs`` from ONE ``query_graphs`` call: the scene's region graph (built on first use and after an edit, with
         the host's decisions in it when an LP left a pair undecided) merged with every query's terminal edges by a kernel, the arrays
         taken as they come; the polytope CSR is the regions' stacked one behind the two point boxes"""
@@ -328,12 +388,12 @@ class SceneQueries:
         self._region_graph_on_device()
         rows, A_all, b_all = self._stack()
         term_ptr, term_region = self._term_lists(regs)
-        arrays = self.scene.query_graphs(term_ptr, term_region, self._adjacent(S, G, eps))
+        arrays = self.scene.query_graphs(term_ptr, term_region, self._adjacent(S, G, eps, sb, gb))
         keys = ['s', 't'] + self.keys
         poly_ptr = np.concatenate([[0, 2 * self.n, 4 * self.n], rows[1:] + 4 * self.n]).astype(np.int32)
         out = []
         for i in range(B):
-            A_pts, b_pts = self._point_rows(S[i], G[i], eps)
+            A_pts, b_pts = self._point_rows(S[i], G[i], eps, self._box_of(sb, i), self._box_of(gb, i))
             tail, head, inc_ptr, inc_edge, inc_out, inc_tail, inc_head = arrays[i]
             out.append(GcsGraph(n=self.n, keys=list(keys), edge_tail=tail, edge_head=head, inc_ptr=inc_ptr, inc_edge=inc_edge, inc_out=inc_out,
                                 edge_inc_tail=inc_tail, edge_inc_head=inc_head, poly_ptr=poly_ptr.copy(),
@@ -341,12 +401,21 @@ class SceneQueries:
                                 interior=np.concatenate([S[i][None], G[i][None], self.centers]), src=0, dst=1))
         return out
 
-    def graphs(self, starts, goals, eps: float = 1e-6, tol: float = 1e-9, assemble: str = "host", prune=None, restrict=None):
+    def graphs(self, starts=None, goals=None, eps: float = 1e-6, tol: float = 1e-9, assemble: str = "host", prune=None, restrict=None,
+               start_boxes=None, goal_boxes=None):
         """One ``GcsGraph`` per query ``(starts[i], goals[i])``, keys ``['s', 't', *region keys]``: what ``graph_from_sets`` makes of the
         sets ``{'s': box of the start, 't': box of the goal, regions}`` -- the region edges shifted by two, both directions of every
         terminal-region hit, and both directions of s-t when the two boxes meet (the interval rule of ``graph.polytopes_overlap``), in
         double-loop order.  ``interior`` is the point itself for a terminal and the scene's centre for a region.  A start or goal whose
         box meets no region raises ValueError.
+
+        ``start_boxes``, ``goal_boxes``: ``(lo [B, n], hi [B, n])``, a start or goal SET in the place of the point -- exactly one of
+        ``starts`` / ``start_boxes`` is given, and likewise for the goals; a point start with a box goal is the common case.  Every
+        half-width of a box must exceed 1e-5 (the box is then a region for ``gcsadmm_create`` and has an interior; a point is given as
+        a point).  The terminal's polytope is ``[I; -I] x <= [hi; -lo]``, its ``interior`` the box's centre, its edges those of
+        ``regions_meeting``, and s-t is decided by the interval rule on the two boxes: the graph is what ``graph_from_sets`` makes of
+        ``{'s': box, 't': box, regions}``, field for field.  Such a graph has a terminal that is a region: ``solve`` runs it in a
+        batch made with ``region_terminals``.  Not with ``prune``: the ellipsoid bound of csrc/informed_core.h is measured from points.
 
         ``assemble``: ``"host"`` (the default: one ``lexsort`` over all edges and ``graph._finish_graph`` per query) or ``"device"`` (the
         region graph is built once on the scene, where the pair list lives, and ONE kernel call writes the index arrays of all queries
@@ -358,9 +427,9 @@ class SceneQueries:
         one is ``assemble="induced"`` (only with ``prune``): one ``induced_query_graphs`` call builds the induced subgraph of every query's
         kept set on the device, from the rows of its kept regions alone -- csrc/induced_graph_core.h --, where ``"host"`` masks and
         renumbers the whole region edge list per query; every field of every graph is the host path's."""
-        return self._graphs(starts, goals, eps, tol, assemble, prune, restrict)[0]
+        return self._graphs(starts, goals, eps, tol, assemble, prune, restrict, start_boxes, goal_boxes)[0]
 
-    def _graphs(self, starts, goals, eps, tol, assemble, prune, restrict):
+    def _graphs(self, starts, goals, eps, tol, assemble, prune, restrict, start_boxes=None, goal_boxes=None):
         """(the graphs of ``graphs``, the records of ``informed`` or None)"""
         if assemble not in ("host", "device", "induced"):
             raise ValueError(f"assemble must be 'host' or 'device', or 'induced' with prune, not {assemble!r}")
@@ -370,17 +439,21 @@ class SceneQueries:
             raise ValueError("prune needs assemble='host' or 'induced': 'device' assembles the graphs of the whole scene")
         if prune is None and assemble == "induced":
             raise ValueError("assemble='induced' needs prune")
-        S, G, regs = self._located(starts, goals, eps, tol)
+        if prune is not None and (start_boxes is not None or goal_boxes is not None):
+            raise ValueError("prune='informed' takes point terminals: its bound is measured from the start and goal points")
+        S, G, regs, sb, gb = self._located(starts, goals, eps, tol, start_boxes, goal_boxes)
         B = len(S)
         if assemble == "device":
-            return self._assemble_on_device(S, G, regs, eps), None
+            return self._assemble_on_device(S, G, regs, eps, sb, gb), None
         info = self._informed(S, G, regs, eps, restrict) if prune else None
         if assemble == "induced":
             return (self._assemble_induced(S, G, regs, eps, info) if B else []), info
-        return [self._host_graph(S[i], G[i], regs[i], regs[B + i], eps, info[i]["keep"] if prune else None) for i in range(B)], info
+        return [self._host_graph(S[i], G[i], regs[i], regs[B + i], eps, info[i]["keep"] if prune else None, self._box_of(sb, i), self._box_of(gb, i))
+                for i in range(B)], info
 
-    def solve(self, starts, goals, state_dtype: str = "f64", N: int = 5, M: int = 20, seeds=None, params=None, return_state: bool = False,
-              walk: str = "host", assemble: str = "host", prune=None, restrict=None, large: bool = False, **common):
+    def solve(self, starts=None, goals=None, state_dtype: str = "f64", N: int = 5, M: int = 20, seeds=None, params=None, return_state: bool = False,
+              walk: str = "host", assemble: str = "host", prune=None, restrict=None, large: bool = False, start_boxes=None, goal_boxes=None,
+              **common):
         """Every query to its stop test in one ``BatchSolver`` (``params``: one dict per query, ``common``: parameters of all, as
         ``BatchSolver.solve``), then rounded by ``rounding_many`` (``N``, ``M``: as ``rounding``; ``seeds``: one per query, default 0).
         ``walk``: ``"host"`` (the default: the walks of ``rounding``, on a host copy of every query's activations) or ``"device"``
@@ -390,6 +463,7 @@ class SceneQueries:
         gains ``informed_bound`` and ``kept_regions``, and the bound's path is one more candidate of the rounding step, so that
         ``rounded_cost <= informed_bound`` whenever the bound is finite.  ``large``: as ``BatchSolver`` -- query graphs a plain batch
         refuses (unpruned queries on a scene of a thousand regions) run as wavefront members; small ones take the path they always took.
+        ``start_boxes``, ``goal_boxes``: as ``graphs``; with a box terminal the batch is made with ``region_terminals`` (otherwise not).
         Returns one record per query: that of ``DeviceSolver.solve`` plus ``rounded_cost``, ``x_v_rounded``, ``y_v_rounded`` and
         ``graph``; with ``return_state`` also ``trace`` and ``state``, host copies of the member's trace and of its six state arrays (the
         batch and its members are closed on return)."""
@@ -398,13 +472,13 @@ class SceneQueries:
         from .rounding import rounding_many, rounding_members, rounding_problem
         if walk not in ("host", "device"):
             raise ValueError(f"walk must be 'host' or 'device', not {walk!r}")
-        graphs, info = self._graphs(starts, goals, 1e-6, 1e-9, assemble, prune, restrict)
+        graphs, info = self._graphs(starts, goals, 1e-6, 1e-9, assemble, prune, restrict, start_boxes, goal_boxes)
         seeds = [0] * len(graphs) if seeds is None else list(seeds)
         if len(seeds) != len(graphs):
             raise ValueError("one seed per query")
         # the bound's path with its restriction: one more candidate of the rounding step
         extra = info and [[(r["bound"], list(r["restriction"]), r["restriction"])] if r["restriction"] is not None else [] for r in info]
-        batch = BatchSolver(graphs, state_dtype, device=self.device, large=large)
+        batch = BatchSolver(graphs, state_dtype, device=self.device, large=large, region_terminals=start_boxes is not None or goal_boxes is not None)
 
         def close():
             batch.close()

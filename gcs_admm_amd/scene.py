@@ -239,6 +239,21 @@ class DeviceScene:
         self._call("gcsadmm_scene_read_hits", hit_ptr.ctypes.data, hit_region.ctypes.data, hit_class.ctypes.data)
         return hit_ptr, hit_region, hit_class
 
+    def locate_boxes(self, lo, hi, tol: float = 1e-9):
+        """The regions that each of the boxes ``[lo[q], hi[q]]`` ([Q, n] each) meets (``gcsadmm_scene_locate_boxes``,
+        csrc/box_locate_core.h has the rule).  Returns what ``locate`` returns: ``(hit_ptr int64 [Q + 1], hit_region int32, hit_class
+        uint8)``, class 1 (IN: the box's centre lies in the region) or 2 (UNDECIDED: a pair LP decides it); a region that is not listed
+        does not meet the box.  ``lo > hi`` in a coordinate or a non-finite bound is refused."""
+        lo = np.ascontiguousarray(lo, float).reshape(-1, self.n); hi = np.ascontiguousarray(hi, float).reshape(-1, self.n)
+        if lo.shape != hi.shape:
+            raise ValueError("lo and hi must have one shape")
+        Q = lo.shape[0]
+        num = C.c_int64(0)
+        self._call("gcsadmm_scene_locate_boxes", Q, lo.ctypes.data, hi.ctypes.data, float(tol), C.addressof(num))
+        hit_ptr = np.empty(Q + 1, np.int64); hit_region = np.empty(int(num.value), np.int32); hit_class = np.empty(int(num.value), np.uint8)
+        self._call("gcsadmm_scene_read_hits", hit_ptr.ctypes.data, hit_region.ctypes.data, hit_class.ctypes.data)
+        return hit_ptr, hit_region, hit_class
+
     def regions(self):
         """The resident results per region as they are, no LP run (``gcsadmm_scene_read_regions``; after ``centers`` and ``bounds``):
         ``(centres [P, n], radii [P], LP status [P], lo [P, n], hi [P, n], LP status [P, 2n])``."""

@@ -240,15 +240,25 @@ gcsadmm_status gcsadmm_run_timed(gcsadmm_handle h, const gcsadmm_state *st, int3
  * member may have any number of workgroup-program vertices, or both kinds: a batch does no slowest-first reorder, which changes the
  * order of dispatch and never a result.  Per iteration: the workgroup launch over the members that have something in it, one wave
  * launch per group, the edge + control launch.  Everything else above holds, the bit-for-bit statement included.
+ *
+ * GCSADMM_BATCH_TERMINALS (gcsadmm_batch_create_ex; may be combined with GCSADMM_BATCH_LARGE) lifts "no terminal that is a region".  The
+ * region terminals of all members are grouped by the thread count of their solve (64 or 256) and by where its work arrays live (LDS or
+ * the handle's workspace), at most four groups, and every group is one launch of terminal_region_batch_kernel per iteration, one
+ * workgroup per terminal, on a stream of the batch's own beside the vertex launches.  Each terminal keeps its handle's workspace and
+ * warm-start records (none under cold_start, as the parameters at bind say).  Every other rule stands, and so does bit for bit.
  */
 typedef struct gcsadmm_batch_s gcsadmm_batch_s;
-enum { GCSADMM_BATCH_LARGE = 1 };
+/* GCSADMM_BATCH_TERMINALS is 4, not 2: flags 2 and 3 have been refused as "unknown batch flag" since gcsadmm_batch_create_ex exists
+ * and stay refused, so bit 1 stays undefined. */
+enum { GCSADMM_BATCH_LARGE = 1, GCSADMM_BATCH_TERMINALS = 4 };
 
 gcsadmm_status gcsadmm_batch_create(const gcsadmm_handle *members, int32_t count, struct gcsadmm_batch_s **out);
-/* gcsadmm_batch_create is this call with flags 0; a bit other than GCSADMM_BATCH_LARGE is GCSADMM_ERR_BAD_ARG */
+/* gcsadmm_batch_create is this call with flags 0; a bit other than GCSADMM_BATCH_LARGE and GCSADMM_BATCH_TERMINALS is GCSADMM_ERR_BAD_ARG */
 gcsadmm_status gcsadmm_batch_create_ex(const gcsadmm_handle *members, int32_t count, int32_t flags, struct gcsadmm_batch_s **out);
 /* the launches of an iteration (any pointer may be NULL): members in the workgroup launch, wave launches, members over all wave launches */
 gcsadmm_status gcsadmm_batch_query(struct gcsadmm_batch_s *b, int32_t *wg_members, int32_t *wave_groups, int32_t *wave_members);
+/* ... and its terminal launches (GCSADMM_BATCH_TERMINALS; either pointer may be NULL): launches, region terminals over all of them */
+gcsadmm_status gcsadmm_batch_query_terminals(struct gcsadmm_batch_s *b, int32_t *term_groups, int32_t *terminals);
 void gcsadmm_batch_destroy(struct gcsadmm_batch_s *b);
 const char *gcsadmm_batch_last_error(struct gcsadmm_batch_s *b);   /* b may be NULL: error of the calling thread's last failed create */
 
@@ -260,7 +270,7 @@ gcsadmm_status gcsadmm_batch_bind(struct gcsadmm_batch_s *b, const gcsadmm_state
 
 /* Enqueue up to k iterations of every member that is still RUNNING, with no host synchronisation: per iteration ONE vertex launch and
  * ONE edge + control launch for the whole batch (GCSADMM_BATCH_LARGE: the vertex step is the workgroup launch, if any member has
- * something in it, and one wave launch per group).  A member whose stop test has fired is left exactly as it stopped. */
+ * something in it, and one wave launch per group; GCSADMM_BATCH_TERMINALS: and one terminal launch per group).  A member whose stop test has fired is left exactly as it stopped. */
 gcsadmm_status gcsadmm_batch_run(struct gcsadmm_batch_s *b, int32_t k, void *stream);
 
 /* status[count] and it[count] of the members' control blocks in one copy (either may be NULL; synchronises `stream`). */
@@ -435,8 +445,19 @@ int gcsadmm_scene_restrict_paths(gcsadmm_scene s, int num_paths, const int *path
  * GCSADMM_ERR_UNSUPPORTED, before the list is allocated.  num_points = 0 gives an empty list. */
 int gcsadmm_scene_locate_points(gcsadmm_scene s, int num_points, const double *points, double eps, double tol, int64_t *num_hits);
 
-/* The resident hit list: the hits of point q are hit_region / hit_class [hit_ptr[q] .. hit_ptr[q + 1]).  Before a
- * gcsadmm_scene_locate_points call has produced a list: GCSADMM_ERR_BAD_ARG. */
+/* The same query for BOXES (a start or goal that is a set): the regions that each of the boxes [lo_q, hi_q] meets, as the same resident
+ * hit list (it replaces the one of an earlier locate call of either kind), ordered by box, then by region index, the same on every run.
+ * With c = (lo + hi) / 2 and h = (hi - lo) / 2, region r is listed for a box unless some row a_i x <= b_i has
+ * a_i.c - b_i > sum_k |a_ik| (h_k + 2 tol) + 2^-40 (sum_k |a_ik c_k| + |b_i|), which puts the pair LP's r* below -tol.  A listed hit is
+ * of class 1 (IN: the centre lies in the region) or 2 (UNDECIDED: the region may reach into the box without holding its centre -- decide
+ * these with gcsadmm_polytope_overlaps).  locate_box_kernel (csrc/box_locate_core.h), in the shape of locate_kernel.  lo, hi
+ * [num_boxes][n] are host doubles.  lo > hi in a coordinate, a NaN or inf bound, a negative num_boxes, tol < 0 or a null pointer:
+ * GCSADMM_ERR_BAD_ARG (a list made earlier stays); more than 2^31 - 1 hits: GCSADMM_ERR_UNSUPPORTED, before the list is allocated.
+ * num_boxes = 0 gives an empty list. */
+int gcsadmm_scene_locate_boxes(gcsadmm_scene s, int num_boxes, const double *lo, const double *hi, double tol, int64_t *num_hits);
+
+/* The resident hit list: the hits of point (or box) q are hit_region / hit_class [hit_ptr[q] .. hit_ptr[q + 1]).  Before a
+ * gcsadmm_scene_locate_points or gcsadmm_scene_locate_boxes call has produced a list: GCSADMM_ERR_BAD_ARG. */
 int gcsadmm_scene_read_hits(gcsadmm_scene s, int64_t *hit_ptr, int *hit_region, unsigned char *hit_class);
 
 /* Edits of a scene whose graph is decided (csrc/scene_edit_core.h has the contract): afterwards every resident result -- centres, radii,
