@@ -147,5 +147,12 @@ GCS_HD bool mu_converged(double mu, double tol, bool stalled, bool first_warm)
 // status of a solve whose cone pair has reached the boundary: accepted (0) when a cold solve is within 1e3 of the tolerance, failed
 // (-4) otherwise
 GCS_HD int boundary_status(double mu, double tol, bool warm) { return (mu <= 1e3 * tol && !warm) ? 0 : -4; }
+// a non-finite step is precision exhausted too: at the last digits of a solve the Newton system can return NaN / Inf, which the ratio
+// test does not see (fmin / fmax drop a NaN, so the step bound stays 1e300 and a full step of NaNs would be taken).  Such a step is
+// not applied and counts as a stalled step, of length zero: the iterate stays as it is and mu_converged decides at the next stop test.
+// probe: a sum of finite_probe(x) over entries x of the direction -- 0.0 when all are finite, NaN otherwise (a sum carries a NaN, a
+// minimum or maximum does not)
+GCS_HD double finite_probe(double x) { return x * 0.0; }
+GCS_HD bool step_finite(double sigmu, double probe) { return sigmu - sigmu == 0.0 && probe == 0.0; }
 
 } // namespace gcs_math

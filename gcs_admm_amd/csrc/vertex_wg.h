@@ -1664,6 +1664,12 @@ GCS_HD void wg_solve_vertex(const WgArgs<T> &a, int v, double rho, double mu_sca
         WG_STAMP(18);
         // ================= final direction: dual directions, step bound =================
         rmax = 0.0;
+        // 0.0 while every row's slack direction is finite, NaN otherwise (gcs_math::finite_probe): rides the reduction's sums.  Dense rows
+        // in R^3 and above only (FINITE_RULE): on canonical boxes, where the products that cancel on dense rows are exact zeros, and at
+        // n <= 2 no non-finite direction occurs (tests/test_rotated_steps.py, the census), and a live sum in this reduction costs the
+        // n = 2 launch of benchmark4 2 % (10 480 -> 10 270 iterations/s): those instantiations stay as they were
+        constexpr bool FINITE_RULE = !BOX && N >= 3;
+        double nonfin = 0.0;
         Place pld;
         WG_ROWS_BEGIN_DS(pld)
             const double l = un[oLAM + ro];
@@ -1671,6 +1677,7 @@ GCS_HD void wg_solve_vertex(const WgArgs<T> &a, int v, double rho, double mu_sca
             const double dl = (sigmu - un[oR1 + ro]) * un[oR2 + ro] - l - (l * is) * ds;      // kappa - l - (l / s) ds
             un[oR2 + ro] = dl;
             rmax = fmax(rmax, fmax(-ds * is, -dl * il));
+            if constexpr (FINITE_RULE) nonfin += gcs_math::finite_probe(ds);
         WG_ROWS_END()
         WG_FOR_AT(u, U, pld.at(U)) {
             double *un = UN(u);
@@ -1684,7 +1691,7 @@ GCS_HD void wg_solve_vertex(const WgArgs<T> &a, int v, double rho, double mu_sca
         amax_cone = 1e300;
         WG_CONE() amax_cone = fmin(SC[SC_AMAXC], SC[SC_AMAXC2]);
         WG_ARRIVE(19);
-        const Red3 rd = wg_reduce<WG_VM>(Red3{fmin(rmax > 0.0 ? rcp1(rmax) : 1e300, amax_cone), 0.0, 0.0}, sm + W::RED, red_phase);
+        const Red3 rd = wg_reduce<WG_VM>(Red3{fmin(rmax > 0.0 ? rcp1(rmax) : 1e300, amax_cone), nonfin, 0.0}, sm + W::RED, red_phase);
         WG_STAMP(19); WG_REGION();
         WG_CONE() {      // step length with the cone guard (round-off must not push either cone point outside)
             double al = gcs_math::step_length(rd.mn);
@@ -1695,14 +1702,19 @@ GCS_HD void wg_solve_vertex(const WgArgs<T> &a, int v, double rho, double mu_sca
                 if (gcs_math::soc_interior<Q>(s2) && gcs_math::soc_interior<Q>(l2)) break;
                 al *= 0.7;
             }
-            SC[SC_ALPHA] = al;
+            // a non-finite direction (fmin / fmax above dropped its NaNs: rd.mn does not show it) is precision exhausted: no step length
+            // (gcs_math::step_finite; oracle/gcs_oracle.c states the same rule)
+            SC[SC_ALPHA] = (!FINITE_RULE || gcs_math::step_finite(sigmu, rd.s1)) ? al : -1.0;
         }
         WG_ARRIVE(20);
         WG_SYNC();
         WG_STAMP(20); WG_REGION();
         const double alpha = wg_uniform(SC[SC_ALPHA]);
-        stalled = gcs_math::step_stalled(alpha);
+        stalled = gcs_math::step_stalled(alpha);      // (a non-finite step, alpha = -1, counts as stalled)
         // ================= update =================
+        // (a non-finite step is not applied: the iterate stays as the last finite step left it, and the stop test of the next pass, on the
+        //  same barrier parameter and with `stalled` set, ends the solve by the precision-exhausted rule)
+        if (!FINITE_RULE || alpha >= 0.0) {
         Place plu;
         WG_ROWS_BEGIN(plu)       // (the slack the macro offers is unused here: the compiler drops it)
             (void)s;
@@ -1724,6 +1736,7 @@ GCS_HD void wg_solve_vertex(const WgArgs<T> &a, int v, double rho, double mu_sca
         WG_CONE() {
             SC[SC_T] += alpha * SC[SC_DT];
             for (int k = 0; k < Q; ++k) SOC[SO::LS + k] += alpha * SOC[SO::DLS + k];
+        }
         }
         WG_ARRIVE(21);
         WG_SYNC();

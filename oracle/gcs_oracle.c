@@ -1288,6 +1288,14 @@ restart:
             B->k5 = dl5; B->k6 = dl6; /* reuse as storage of the dual step */
         }
         double al = fmin(1.0, 0.99 * amax);
+        {   /* A non-finite step is precision exhausted: at the last digits of a solve the Newton system can return NaN / Inf, and
+             * fmin / fmax in the ratio tests drop a NaN, so amax would stay 1e300 and a full step of NaNs be taken (the next slack
+             * test then reported -3).  The step is not applied and counts as a stalled step, of length zero: the stop test of the
+             * next pass, on the same mu, decides by the precision-exhausted rule. */
+            int finite = isfinite(sm);
+            for (int k = 0; k < NB; ++k) finite = finite && isfinite(db[k]);
+            if (!finite) { stalled = 1; continue; }
+        }
         if (getenv("GCS_ORACLE_DEBUG3") && (!getenv("GCS_ORACLE_DEBUG_V") || atoi(getenv("GCS_ORACLE_DEBUG_V")) == dbg_vertex)) fprintf(stderr, "  it %d mu %.3e rd %.2e rp %.2e sigma*mu %.2e amax %.4e yv %.4e t %.4e\n", it, mu, rdmax, rpmax, sm, amax, P.beta[4*n], P.beta[4*n+1]);
         for (int tries = 0; tries < 40; ++tries) {   /* keep both cone points strictly inside despite round-off */
             double s2[MAXN + 1] = {0}, l2[MAXN + 1] = {0};

@@ -56,6 +56,33 @@ MI355X (tests/test_gpu_scaled_steps.py prints every case): f64 under the schedul
 within 1e-7, worst 4.5e-5, warm totals -2 .. +1; f32 0.945 (benchmark3, schedule) - 1.0, 0.973 - 1.0, worst 1.4e-4 (star 40, schedule: the
 host build's figure), warm totals -1 .. +0; every step after a change of rho takes exactly the oracle's total; region scene with its
 terminals in the mask 0.932 / 0.990 / 1.1e-6.  Per case the device is within 0.025 of the host builds' near fraction (a few solves).
+
+Rotated polytopes in R^3 .. R^8 (tests/rotated_cases.py: the 4 x 3 lattice turned by one orthogonal Q, cases (n, lattice seed, rotation
+seed, cuts); tests/test_rotated_steps.py the workgroup host build, tests/test_gpu_rotated_steps.py the device): 12 steps at rho = 1, 144
+solves a run.  Same thresholds.  (a) against the oracle on the same rotated graph, (b) cold against the rotated solves of the oracle on
+the AXIS-ALIGNED lattice; near / close / worst, Newton total - oracle's, per-vertex counts equal (tasks ascending; descending within
+0.007 / 0.035 of these):
+  case                 (a) warm                               (a) cold                          (b) cold
+  (3, 1, 3, 0)         0.944 / 0.944 / 3.9e-4, -5, 0.951      0.951 / 0.965 / 3.9e-4, +0, 1.0   0.944 / 0.965 / 4.0e-4, +0, 1.0
+  (4, 1, 4, 0)         0.958 / 0.958 / 1.1e-5, +0, 1.0        0.944 / 0.958 / 2.7e-4, +0, 1.0   0.944 / 0.958 / 2.7e-4, +0, 1.0
+  (5, 7, 605, 0)       0.931 / 0.951 / 2.8e-4, +2, 0.979      0.924 / 0.958 / 5.9e-4, +0, 1.0   0.924 / 0.958 / 2.0e-4, +1, 0.993
+  (6, 2, 106, 0)       0.938 / 0.965 / 1.8e-4, +4, 0.986      0.944 / 0.958 / 2.1e-5, +0, 1.0   0.944 / 0.972 / 5.8e-5, +0, 1.0
+  (7, 3, 207, 0)       0.944 / 0.979 / 5.4e-4, -1, 0.993      0.931 / 0.965 / 2.3e-4, +0, 1.0   0.931 / 0.972 / 1.9e-4, +0, 1.0
+  (8, 4, 308, 0)       0.931 / 0.979 / 5.4e-4, +0, 1.0        0.944 / 0.979 / 4.4e-4, +0, 1.0   0.938 / 0.972 / 4.3e-4, +0, 1.0
+  (3, 1, 3, 2)         0.938 / 0.951 / 7.3e-4, -9, 0.965      0.938 / 0.979 / 1.9e-5, +0, 1.0   0.944 / 0.979 / 7.0e-6, +0, 1.0
+  (4, 1, 4, 3)         0.944 / 0.951 / 1.2e-4, +15, 0.951     0.944 / 0.993 / 1.1e-4, +0, 1.0   0.944 / 0.986 / 2.6e-7, +0, 1.0
+  (6, 2, 106, 4)       0.944 / 0.979 / 1.1e-5, +2, 0.986      0.924 / 0.965 / 2.6e-6, +0, 1.0   0.931 / 0.972 / 2.0e-6, +0, 1.0
+  (8, 4, 308, 5)       0.931 / 0.965 / 3.7e-6, +0, 1.0        0.924 / 0.972 / 7.2e-5, +0, 1.0   0.924 / 0.986 / 6.3e-7, +0, 1.0
+The closest to a threshold: warm per-vertex counts equal in 0.951 of the solves on (3, 1, 3, 0) and (4, 1, 4, 3) against
+WARM_VERTEX_EQUAL = 0.95 (seven solves of 144 one iteration apart: one warm / cold decision flipped).  No inner failure on either side
+(before gcs_math::step_finite the cases at n = 5 .. 8 had them: test_rotated_steps.py quotes the census).  Seeded error that is the
+identity on boxes -- ONE off-diagonal facet product of the K assembly (facet 0, entry (1, 0)) times 1 + 1e-3: bit for bit the clean build
+on the lattices at n = 3, 6; on (3, 1, 3, 0) / (6, 2, 106, 0) 0.10 - 0.16 / 0.10 within 1e-9 under (a) and (b), 9 / 25 inner failures.
+MI355X (tests/test_gpu_rotated_steps.py prints every case): (a) warm, cuts 0 at n = 3, 5, 6, 7, 8: 0.944 / 0.944 / 3.9e-4, +4;  0.931 / 0.958 /
+4.4e-4, +0;  0.938 / 0.951 / 1.9e-4, +4;  0.944 / 0.979 / 5.6e-4, -1;  0.931 / 0.979 / 5.1e-4, +0;  (4, 1, 4, 3): 0.944 / 0.951 / 1.1e-4, +15;
+(8, 4, 308, 5): 0.931 / 0.965 / 3.2e-6, +0.  (b) cold at n = 3, 6, 8: 0.944 / 0.972 / 3.8e-4;  0.944 / 0.965 / 4.8e-5;  0.938 / 0.972 / 3.1e-4, every
+per-step total the oracle's.  n = 6 from the device-memory workspace 0.938 / 0.958 / 1.2e-4, +0; with f32 state ("nearest") 0.944 / 0.965 /
+6.7e-5, +0.  The four seeds that failed before, cold and warm through step 8: no inner failure, totals -10 .. +0.
 """
 from __future__ import annotations
 
