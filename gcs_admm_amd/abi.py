@@ -129,6 +129,9 @@ PROTOTYPES = {
     # the informed region set of every query of a batch (csrc/informed_core.h)
     "gcsadmm_scene_region_paths": ([_p, _i, _p, _p, _p, _i] + [_p] * 4, _i),
     "gcsadmm_scene_informed_regions": ([_p, _i, _p, _p, _d, _p, _p], _i),
+    # ... between start and goal sets (csrc/informed_set_core.h)
+    "gcsadmm_scene_region_paths_sets": ([_p, _i, _p, _p, _p, _p, _i] + [_p] * 4, _i),
+    "gcsadmm_scene_informed_regions_sets": ([_p, _i, _p, _p, _p, _d, _p, _p], _i),
     # the query graphs of a batch on each query's kept regions (csrc/induced_graph_core.h)
     "gcsadmm_scene_induced_sizes": ([_p, _i] + [_p] * 6, _i),
     "gcsadmm_scene_induced_query_graphs": ([_p, _i, _p, _p, _p, _p, _i] + [_p] * 9, _i),

@@ -1188,6 +1188,16 @@ int gcsadmm_scene_query_graphs(gcsadmm_scene s, int B, const int64_t *term_ptr, 
 }
 
 // ---- the informed region set of every query of a batch (informed_core.h); like restrict_paths outside the table of scene_stage.h ----
+// the weights of the region graph's edges: made once per graph, by the first path call on it (region_paths or region_paths_sets)
+static int region_weights(const SceneRegions &r, SceneGraph &rg)
+{
+    if (rg.w) return GCSADMM_OK;
+    LPCHK(rg.w.alloc((size_t)rg.edges));
+    if (rg.edges > 0)
+        hipLaunchKernelGGL(region_weight_kernel, dim3(blocks_of((long)rg.edges)), dim3(TB), 0, 0, r.cen.get(), r.n, rg.tail.get(), rg.head.get(), rg.edges, rg.w.get());
+    LPCHK(hipGetLastError());
+    return GCSADMM_OK;
+}
 int gcsadmm_scene_region_paths(gcsadmm_scene s, int num_queries, const double *points, const int64_t *term_ptr, const int *term_region,
                                int max_len, int *path_region, int *path_len, double *path_cost, int *status)
 {
@@ -1202,12 +1212,7 @@ int gcsadmm_scene_region_paths(gcsadmm_scene s, int num_queries, const double *p
         if (B == 0) return GCSADMM_OK;
         if (!path_region || !path_len || !path_cost || !status) { g_err = "null output array"; return GCSADMM_ERR_BAD_ARG; }
         if ((long long)B * max_len > (long long)INT32_MAX) { g_err = "num_queries * max_len above 2^31 - 1"; return GCSADMM_ERR_UNSUPPORTED; }
-        if (!rg.w) {      // once per region graph
-            LPCHK(rg.w.alloc((size_t)rg.edges));
-            if (rg.edges > 0)
-                hipLaunchKernelGGL(region_weight_kernel, dim3(blocks_of((long)rg.edges)), dim3(TB), 0, 0, r.cen.get(), n, rg.tail.get(), rg.head.get(), rg.edges, rg.w.get());
-            LPCHK(hipGetLastError());
-        }
+        LPRUN(region_weights(r, rg));
         const size_t coords = 2 * (size_t)B * n, hits = (size_t)term_ptr[2 * (size_t)B], cells = (size_t)B * max_len;
         const int chunk = informed_chunk(P);
         LPCHK(q.points.reserve(coords)); LPCHK(q.term_ptr.reserve(2 * (size_t)B + 1)); LPCHK(q.term_region.reserve(hits));
@@ -1252,6 +1257,81 @@ int gcsadmm_scene_informed_regions(gcsadmm_scene s, int num_queries, const doubl
         for (int first = 0; first < B && P > 0; first += QUERY_CHUNK_MAX) {      // grid.y
             a.first = first;
             hipLaunchKernelGGL(informed_keep_kernel, dim3(blocks_of(P), (unsigned)std::min(QUERY_CHUNK_MAX, B - first)), dim3(TB), 0, 0, a);
+            LPCHK(hipGetLastError());
+        }
+        LPCHK(to_host(keep, q.keep.get(), cells));
+        LPCHK(hipStreamSynchronize(nullptr));
+        if (num_kept)
+            for (int i = 0; i < B; ++i) {
+                int64_t kept = 0;
+                for (int p = 0; p < P; ++p) kept += keep[(size_t)i * P + p];
+                num_kept[i] = kept;
+            }
+        return GCSADMM_OK;
+    });
+}
+
+// ---- the same for start and goal sets (informed_set_core.h): the two calls above with boxes in the place of the points ----
+int gcsadmm_scene_region_paths_sets(gcsadmm_scene s, int num_queries, const double *lo, const double *hi, const int64_t *term_ptr,
+                                    const int *term_region, int max_len, int *path_region, int *path_len, double *path_cost, int *status)
+{
+    return scene_entry(s, [&]() -> int {
+        for (const NeedRule &rule : {NEED_FRESH_GRAPH, NEED_CENTERS})
+            if (!has(s->have, rule.flags)) { g_err = rule.refusal; return GCSADMM_ERR_BAD_ARG; }
+        const SceneRegions &r = s->reg;
+        SceneGraph &rg = s->graph;
+        InformedScratch &q = s->inf;
+        const int B = num_queries, P = r.P, n = r.n;
+        LPRUN(set_check_paths(P, n, B, lo, hi, (const long long *)term_ptr, term_region, max_len, g_err));
+        if (B == 0) return GCSADMM_OK;
+        if (!path_region || !path_len || !path_cost || !status) { g_err = "null output array"; return GCSADMM_ERR_BAD_ARG; }
+        if ((long long)B * max_len > (long long)INT32_MAX) { g_err = "num_queries * max_len above 2^31 - 1"; return GCSADMM_ERR_UNSUPPORTED; }
+        LPRUN(region_weights(r, rg));
+        const size_t coords = 2 * (size_t)B * n, hits = (size_t)term_ptr[2 * (size_t)B], cells = (size_t)B * max_len;
+        const int chunk = informed_chunk(P);
+        LPCHK(q.points.reserve(2 * coords)); LPCHK(q.term_ptr.reserve(2 * (size_t)B + 1)); LPCHK(q.term_region.reserve(hits));      // points: lo, then hi
+        LPCHK(q.d.reserve((size_t)std::min(chunk, B) * P));
+        LPCHK(q.path_region.reserve(cells)); LPCHK(q.path_len.reserve((size_t)B)); LPCHK(q.status.reserve((size_t)B)); LPCHK(q.cost.reserve((size_t)B));
+        LPCHK(to_device(q.points.get(), lo, coords)); LPCHK(to_device(q.points.get() + coords, hi, coords));
+        LPCHK(to_device(q.term_ptr.get(), (const long long *)term_ptr, 2 * (size_t)B + 1));
+        if (hits > 0) LPCHK(to_device(q.term_region.get(), term_region, hits));
+        LPCHK(hipMemset(q.path_region.get(), 0xff, sizeof(int) * cells));      // entries beyond a path's length: -1
+        SetPathArgs a{};
+        a.g = PathGraph{P, n, rg.row_ptr.get(), rg.head.get(), rg.w.get(), r.cen.get()};
+        a.lo = q.points.get(); a.hi = q.points.get() + coords; a.term_ptr = q.term_ptr.get(); a.term_region = q.term_region.get();
+        a.B = B; a.max_len = max_len; a.d = q.d.get();
+        a.path_region = q.path_region.get(); a.path_len = q.path_len.get(); a.status = q.status.get(); a.path_cost = q.cost.get();
+        for (int first = 0; first < B; first += chunk) {
+            a.first = first;
+            hipLaunchKernelGGL(terminal_set_path_kernel, dim3((unsigned)std::min(chunk, B - first)), dim3(PATH_THREADS), 0, 0, a);
+            LPCHK(hipGetLastError());
+        }
+        LPCHK(to_host(path_region, q.path_region.get(), cells)); LPCHK(to_host(path_len, q.path_len.get(), (size_t)B));
+        LPCHK(to_host(path_cost, q.cost.get(), (size_t)B)); LPCHK(to_host(status, q.status.get(), (size_t)B));
+        LPCHK(hipStreamSynchronize(nullptr));
+        return GCSADMM_OK;
+    });
+}
+
+int gcsadmm_scene_informed_regions_sets(gcsadmm_scene s, int num_queries, const double *lo, const double *hi, const double *bound, double pad,
+                                        unsigned char *keep, int64_t *num_kept)
+{
+    return scene_entry(s, [&]() -> int {
+        if (!has(s->have, NEED_BOXES.flags)) { g_err = NEED_BOXES.refusal; return GCSADMM_ERR_BAD_ARG; }
+        const SceneRegions &r = s->reg;
+        InformedScratch &q = s->inf;
+        const int B = num_queries, P = r.P, n = r.n;
+        LPRUN(set_check_keep(n, B, lo, hi, bound, pad, g_err));
+        if (B == 0) return GCSADMM_OK;
+        if (!keep) { g_err = "null output array"; return GCSADMM_ERR_BAD_ARG; }
+        const size_t coords = 2 * (size_t)B * n, cells = (size_t)B * P;
+        LPCHK(q.points.reserve(2 * coords)); LPCHK(q.bound.reserve((size_t)B)); LPCHK(q.keep.reserve(cells));
+        LPCHK(to_device(q.points.get(), lo, coords)); LPCHK(to_device(q.points.get() + coords, hi, coords));
+        LPCHK(to_device(q.bound.get(), bound, (size_t)B));
+        SetKeepArgs a{P, n, B, 0, r.lo.get(), r.hi.get(), q.points.get(), q.points.get() + coords, q.bound.get(), pad, q.keep.get()};
+        for (int first = 0; first < B && P > 0; first += QUERY_CHUNK_MAX) {      // grid.y
+            a.first = first;
+            hipLaunchKernelGGL(terminal_set_keep_kernel, dim3(blocks_of(P), (unsigned)std::min(QUERY_CHUNK_MAX, B - first)), dim3(TB), 0, 0, a);
             LPCHK(hipGetLastError());
         }
         LPCHK(to_host(keep, q.keep.get(), cells));

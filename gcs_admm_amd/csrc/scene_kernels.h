@@ -11,6 +11,7 @@
 #include "query_graph_core.h"
 #include "induced_graph_core.h"
 #include "informed_core.h"
+#include "informed_set_core.h"
 #include "path_restrict_core.h"
 #include "restrict_plan.h"
 
@@ -514,6 +515,82 @@ __global__ __launch_bounds__(256) void informed_keep_kernel(KeepArgs a)
     if (r >= a.P) return;
     const double lb = informed_lower_bound(a.points + (size_t)i * a.n, a.points + (size_t)(a.B + i) * a.n, a.lo + (size_t)r * a.n, a.hi + (size_t)r * a.n, a.n, a.pad);
     a.keep[(size_t)i * a.P + r] = informed_keep(lb, a.bound[i]) ? 1 : 0;
+}
+
+// ---- the informed region set of a query between start and goal sets (informed_set_core.h) ----
+struct SetPathArgs {
+    PathGraph g;
+    const double *lo, *hi;          // [2 B][n] each: the start boxes, then the goal boxes
+    const long long *term_ptr;      // [2 B + 1]
+    const int *term_region;
+    int B, first, max_len;          // blockIdx.x counts queries from `first`
+    double *d;                      // [queries of the chunk][P]
+    int *path_region, *path_len, *status;      // [B][max_len], [B], [B]
+    double *path_cost;              // [B]
+};
+// region_path_kernel's rounds (one workgroup per query, lane t owns the vertices t, t + 256, ..., the same round boundary and the same
+// three flags) under the bound of informed_set_core.h.  `bound` holds the bits of U: a non-negative double or +inf, which order as
+// their bits do, so the cell takes an unsigned minimum and only ever falls -- it needs no clearing and no rotation.  Behind a round's
+// barrier the lanes stride over the goal list and fold the goal costs of what that round left in d into the cell; a lane reads the
+// cell once, ahead of its relaxations, and may still see the value of the round before: that one was the goal cost of a d already
+// written too, and only admits more.
+__global__ __launch_bounds__(PATH_THREADS) void terminal_set_path_kernel(SetPathArgs a)
+{
+    __shared__ int changed[3];
+    __shared__ unsigned long long bound;
+    const int i = a.first + (int)blockIdx.x, t = (int)threadIdx.x, P = a.g.P;
+    if (i >= a.B) return;
+    const SetQuery q = set_query(a.lo, a.hi, a.term_ptr, a.term_region, a.B, a.g.n, i);
+    double *d = a.d + (size_t)blockIdx.x * P;
+    auto sync = [] {
+        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+        __syncthreads();
+    };
+    // (the lane's first goal region and that region's distance to G do not change from round to round: a fold is then one load of d
+    // for all but the lists longer than the lanes)
+    const int r0 = t < q.b ? q.rt[t] : -1;
+    const double g0 = r0 >= 0 ? set_point_distance(a.g.centers + (size_t)r0 * a.g.n, q.glo, q.ghi, a.g.n) : 0.0;
+    auto lower = [&](double c) {
+        if (set_lowers(c, __longlong_as_double((long long)bound))) atomicMin(&bound, (unsigned long long)__double_as_longlong(c));
+    };
+    auto fold = [&] {
+        if (r0 >= 0) lower(d[r0] + g0);
+        for (int j = t + PATH_THREADS; j < q.b; j += PATH_THREADS) lower(set_goal_cost(a.g, q, d, q.rt[j]));
+    };
+    for (int v = t; v < P; v += PATH_THREADS) d[v] = set_init(a.g, q, v);
+    if (t < 3) changed[t] = 0;
+    if (t == 0) bound = (unsigned long long)__double_as_longlong(INFINITY);
+    sync();
+    fold();
+    for (int round = 0; round < P; ++round) {
+        const double U = __longlong_as_double((long long)bound);
+        bool fell = false;
+        for (int v = t; v < P; v += PATH_THREADS) fell |= set_relax(a.g, d, v, U);
+        if (fell) changed[round % 3] = 1;
+        sync();
+        if (!changed[round % 3]) break;      // (the same in every lane)
+        if (t == 0) changed[(round + 2) % 3] = 0;
+        fold();
+    }
+    if (t == 0)
+        a.status[i] = set_backtrack(a.g, q, d, a.max_len, a.path_region + (size_t)i * a.max_len, a.path_len + i, a.path_cost + i);
+}
+
+struct SetKeepArgs {
+    int P, n, B, first;             // blockIdx.y counts queries from `first`
+    const double *lo, *hi;          // [P][n]: the resident boxes
+    const double *tlo, *thi;        // [2 B][n] each: the start boxes, then the goal boxes
+    const double *bound;            // [B]
+    double pad;
+    unsigned char *keep;            // [B][P]
+};
+// one thread per (query, region)
+__global__ __launch_bounds__(256) void terminal_set_keep_kernel(SetKeepArgs a)
+{
+    const int i = a.first + (int)blockIdx.y, r = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (r >= a.P) return;
+    const SetQuery q = set_query(a.tlo, a.thi, nullptr, nullptr, a.B, a.n, i);
+    a.keep[(size_t)i * a.P + r] = informed_keep(set_lower_bound(q, a.lo + (size_t)r * a.n, a.hi + (size_t)r * a.n, a.n, a.pad), a.bound[i]) ? 1 : 0;
 }
 
 } // namespace gcsadmm_lp

@@ -8,7 +8,7 @@ from-scratch ``graph_from_sets_device`` on ``{'s', 't', regions}`` gives; ``solv
 ``rounding_many``.  By default the graphs are assembled on the host (a sort over all edges per query); ``assemble="device"`` takes them
 from one kernel call on the scene's own region graph (csrc/query_graph_core.h), the same arrays.  ``prune="informed"`` runs every query on
 its informed region set alone (``informed``, csrc/informed_core.h): the regions within the length of a feasible path of both terminals,
-which loses no optimal path; ``assemble="induced"`` builds those pruned graphs on the device too (csrc/induced_graph_core.h), in work
+which loses no optimal path (``prune="informed_sets"``: the same between start and goal sets, csrc/informed_set_core.h); ``assemble="induced"`` builds those pruned graphs on the device too (csrc/induced_graph_core.h), in work
 proportional to the kept set.  The scene is not frozen: ``add_regions`` and ``remove_regions`` edit it in place, and only the LPs of what is new run.  There is no CPU fallback: the LPs and the locate call run on the device (tests inject stand-ins).
 """
 from __future__ import annotations
@@ -271,7 +271,20 @@ class SceneQueries:
         S, G, regs, _, _ = self._located(starts, goals, eps, tol)
         return self._informed(S, G, regs, eps, restrict)
 
-    def _informed(self, S, G, regs, eps, restrict=None):
+    def informed_sets(self, starts=None, goals=None, start_boxes=None, goal_boxes=None, eps: float = 1e-6, tol: float = 1e-9, restrict=None):
+        """``informed`` for start and goal SETS (csrc/informed_set_core.h): exactly one of ``starts`` / ``start_boxes`` and of ``goals`` /
+        ``goal_boxes``, as ``graphs`` takes them, in every mix.  The records are those of ``informed``.  The path comes from one
+        ``region_paths_sets`` call and the flags from one ``informed_regions_sets`` call: a region is kept when the distances of its
+        padded box to the start set and to the goal set add up to at most the bound, which loses no optimal path between a point of the
+        one and a point of the other.  A point goes to the two calls as the box ``lo == hi == p`` and to the restriction as its box of
+        half-width ``eps``, a box to both as itself; the kernel's bound is ``bound + 2 k eps sqrt(n)`` with k the number of point
+        terminals of the query (a box is measured from the very set the restriction used).  The regions under both terminals are kept
+        whatever the flags say.  On point queries the records equal ``informed``'s."""
+        S, G, regs, sb, gb = self._located(starts, goals, eps, tol, start_boxes, goal_boxes)
+        return self._informed(S, G, regs, eps, restrict, sets=True, sb=sb, gb=gb)
+
+    def _informed(self, S, G, regs, eps, restrict=None, sets=False, sb=None, gb=None):
+        """the records of ``informed``, or (``sets``; ``sb``, ``gb``: the (lo, hi) of a side given as boxes) of ``informed_sets``"""
         from .rounding import solve_path_restrictions_device
         B = len(S)
         if B == 0:
@@ -279,13 +292,18 @@ class SceneQueries:
         restrict = restrict or (lambda As, bs, n, paths: solve_path_restrictions_device(As, bs, n, paths, self.device))
         self._region_graph_on_device()
         points = np.vstack([S, G])
-        paths, _, status = self.scene.region_paths(points, *self._term_lists(regs))
+        if sets:      # what the kernels measure from: the boxes, a point as the box lo == hi
+            lo = np.vstack([S if sb is None else sb[0], G if gb is None else gb[0]])
+            hi = np.vstack([S if sb is None else sb[1], G if gb is None else gb[1]])
+            paths, _, status = self.scene.region_paths_sets(lo, hi, *self._term_lists(regs))
+        else:
+            paths, _, status = self.scene.region_paths(points, *self._term_lists(regs))
         As, bs, jobs, owner = {}, {}, [], []
         for i in range(B):
             if status[i] != 0:
                 continue
-            for key, p in ((('s', i), S[i]), (('t', i), G[i])):
-                As[key], bs[key] = convert_pt_to_polytope(p, eps)
+            for key, p, box in ((('s', i), S[i], self._box_of(sb, i)), (('t', i), G[i], self._box_of(gb, i))):
+                As[key], bs[key] = convert_pt_to_polytope(p, eps) if box is None else self._box_polytope(*box)
             for r in paths[i]:
                 As[('r', int(r))], bs[('r', int(r))] = self.polys[r]
             jobs.append([('s', i)] + [('r', int(r)) for r in paths[i]] + [('t', i)])
@@ -296,8 +314,15 @@ class SceneQueries:
             for i, (cost, xs) in zip(owner, restrict(As, bs, self.n, jobs)):
                 if xs is not None and np.isfinite(cost):
                     bound[i], points_of[i] = float(cost), {name(k): x for k, x in xs.items()}
-        keep = self.scene.informed_regions(points, bound + 4.0 * eps * np.sqrt(self.n))
+        if sets:      # (the set call takes finite bounds: a query without one keeps every region, here)
+            finite = np.isfinite(bound)
+            widened = bound + (2.0 * ((sb is None) + (gb is None))) * eps * np.sqrt(self.n)
+            keep = self.scene.informed_regions_sets(lo, hi, np.where(finite, widened, 0.0))
+        else:
+            keep = self.scene.informed_regions(points, bound + 4.0 * eps * np.sqrt(self.n))
         keep = np.array(keep, dtype=bool, copy=True)
+        if sets:
+            keep[~finite] = True
         for i in range(B):
             keep[i, regs[i]] = True
             keep[i, regs[B + i]] = True
@@ -355,7 +380,7 @@ class SceneQueries:
         return (np.concatenate([np.asarray(A_s, float).reshape(-1, self.n), np.asarray(A_t, float).reshape(-1, self.n)]),
                 np.concatenate([np.asarray(b_s, float).ravel(), np.asarray(b_t, float).ravel()]))
 
-    def _assemble_induced(self, S, G, regs, eps, info):
+    def _assemble_induced(self, S, G, regs, eps, info, sb=None, gb=None):
         """the pruned graphs of ``graphs`` from ONE ``induced_query_graphs`` call on the keep flags of ``_informed``: the induced subgraph
         of every query's kept set is built on the device from the rows of its kept regions (csrc/induced_graph_core.h), the arrays taken
         as they come; per query the host reads the P flags, and gathers the kept regions' rows of the stacked polytope CSR"""
@@ -364,14 +389,14 @@ class SceneQueries:
         rows, A_all, b_all = self._stack()
         term_ptr, term_region = self._term_lists(regs)
         keep = np.array([r["keep"] for r in info], np.uint8).reshape(B, len(self.keys))
-        arrays = self.scene.induced_query_graphs(keep, term_ptr, term_region, self._adjacent(S, G, eps))
+        arrays = self.scene.induced_query_graphs(keep, term_ptr, term_region, self._adjacent(S, G, eps, sb, gb))
         out = []
         for i in range(B):
             idx = np.nonzero(keep[i])[0]
             counts = rows[idx + 1] - rows[idx]
             ends = np.cumsum(counts)
             take = np.repeat(rows[idx] - (ends - counts), counts) + np.arange(int(ends[-1]) if len(ends) else 0)      # the kept regions' rows
-            A_pts, b_pts = self._point_rows(S[i], G[i], eps)
+            A_pts, b_pts = self._point_rows(S[i], G[i], eps, self._box_of(sb, i), self._box_of(gb, i))
             tail, head, inc_ptr, inc_edge, inc_out, inc_tail, inc_head = arrays[i]
             out.append(GcsGraph(n=self.n, keys=['s', 't'] + [self.keys[r] for r in idx], edge_tail=tail, edge_head=head, inc_ptr=inc_ptr,
                                 inc_edge=inc_edge, inc_out=inc_out, edge_inc_tail=inc_tail, edge_inc_head=inc_head,
@@ -415,7 +440,8 @@ class SceneQueries:
         a point).  The terminal's polytope is ``[I; -I] x <= [hi; -lo]``, its ``interior`` the box's centre, its edges those of
         ``regions_meeting``, and s-t is decided by the interval rule on the two boxes: the graph is what ``graph_from_sets`` makes of
         ``{'s': box, 't': box, regions}``, field for field.  Such a graph has a terminal that is a region: ``solve`` runs it in a
-        batch made with ``region_terminals``.  Not with ``prune``: the ellipsoid bound of csrc/informed_core.h is measured from points.
+        batch made with ``region_terminals``.  Not with ``prune="informed"``, whose bound is measured from points (csrc/informed_core.h);
+        ``prune="informed_sets"`` measures from the sets.
 
         ``assemble``: ``"host"`` (the default: one ``lexsort`` over all edges and ``graph._finish_graph`` per query) or ``"device"`` (the
         region graph is built once on the scene, where the pair list lives, and ONE kernel call writes the index arrays of all queries
@@ -426,28 +452,30 @@ class SceneQueries:
         't', *kept keys]``.  No optimal path is lost.  Not with ``assemble="device"``, which is the assembly of the WHOLE scene; the pruned
         one is ``assemble="induced"`` (only with ``prune``): one ``induced_query_graphs`` call builds the induced subgraph of every query's
         kept set on the device, from the rows of its kept regions alone -- csrc/induced_graph_core.h --, where ``"host"`` masks and
-        renumbers the whole region edge list per query; every field of every graph is the host path's."""
+        renumbers the whole region edge list per query; every field of every graph is the host path's.  ``"informed_sets"``: the same
+        with the set of ``informed_sets`` -- point or box terminals, in every mix, with ``assemble="host"`` or ``"induced"``."""
         return self._graphs(starts, goals, eps, tol, assemble, prune, restrict, start_boxes, goal_boxes)[0]
 
     def _graphs(self, starts, goals, eps, tol, assemble, prune, restrict, start_boxes=None, goal_boxes=None):
         """(the graphs of ``graphs``, the records of ``informed`` or None)"""
         if assemble not in ("host", "device", "induced"):
             raise ValueError(f"assemble must be 'host' or 'device', or 'induced' with prune, not {assemble!r}")
-        if prune not in (None, "informed"):
-            raise ValueError(f"prune must be None or 'informed', not {prune!r}")
+        if prune not in (None, "informed", "informed_sets"):
+            raise ValueError(f"prune must be None or 'informed' or 'informed_sets', not {prune!r}")
         if prune is not None and assemble == "device":
             raise ValueError("prune needs assemble='host' or 'induced': 'device' assembles the graphs of the whole scene")
         if prune is None and assemble == "induced":
             raise ValueError("assemble='induced' needs prune")
-        if prune is not None and (start_boxes is not None or goal_boxes is not None):
-            raise ValueError("prune='informed' takes point terminals: its bound is measured from the start and goal points")
+        if prune == "informed" and (start_boxes is not None or goal_boxes is not None):
+            raise ValueError("prune='informed' takes point terminals: its bound is measured from the start and goal points "
+                             "(prune='informed_sets' measures from sets)")
         S, G, regs, sb, gb = self._located(starts, goals, eps, tol, start_boxes, goal_boxes)
         B = len(S)
         if assemble == "device":
             return self._assemble_on_device(S, G, regs, eps, sb, gb), None
-        info = self._informed(S, G, regs, eps, restrict) if prune else None
+        info = self._informed(S, G, regs, eps, restrict, sets=prune == "informed_sets", sb=sb, gb=gb) if prune else None
         if assemble == "induced":
-            return (self._assemble_induced(S, G, regs, eps, info) if B else []), info
+            return (self._assemble_induced(S, G, regs, eps, info, sb, gb) if B else []), info
         return [self._host_graph(S[i], G[i], regs[i], regs[B + i], eps, info[i]["keep"] if prune else None, self._box_of(sb, i), self._box_of(gb, i))
                 for i in range(B)], info
 
@@ -461,7 +489,7 @@ class SceneQueries:
         ``walks.walk_reference`` -- other draws than the host's for the same seed).  ``assemble``: as ``graphs`` (the same graphs whichever way; ``"induced"`` only with ``prune``).
         ``prune``, ``restrict``: as ``graphs``; with ``prune="informed"`` every query runs on its informed region set alone, each record
         gains ``informed_bound`` and ``kept_regions``, and the bound's path is one more candidate of the rounding step, so that
-        ``rounded_cost <= informed_bound`` whenever the bound is finite.  ``large``: as ``BatchSolver`` -- query graphs a plain batch
+        ``rounded_cost <= informed_bound`` whenever the bound is finite; ``prune="informed_sets"`` does the same for box terminals too.  ``large``: as ``BatchSolver`` -- query graphs a plain batch
         refuses (unpruned queries on a scene of a thousand regions) run as wavefront members; small ones take the path they always took.
         ``start_boxes``, ``goal_boxes``: as ``graphs``; with a box terminal the batch is made with ``region_terminals`` (otherwise not).
         Returns one record per query: that of ``DeviceSolver.solve`` plus ``rounded_cost``, ``x_v_rounded``, ``y_v_rounded`` and

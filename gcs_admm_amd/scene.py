@@ -346,6 +346,21 @@ class DeviceScene:
         the length of a feasible path of each query, or ``inf`` (keeps every region)."""
         return informed_keep_array(self.n, self.P, points, bound, pad, lambda *arrays: self._call("gcsadmm_scene_informed_regions", *arrays))
 
+    def region_paths_sets(self, lo, hi, term_ptr, term_region, max_len=None):
+        """``region_paths`` between start and goal SETS (``gcsadmm_scene_region_paths_sets``; csrc/informed_set_core.h has the rule).
+        ``lo``, ``hi`` [2 B, n]: the start boxes, then the goal boxes (a point: ``lo == hi``, and the results have the bits of
+        ``region_paths``); ``term_ptr``, ``term_region``: the regions that meet each box.  The distance of a centre to the box takes the
+        place of the distance to the point, and the search ends once nothing below the cheapest goal cost moves.  Returns what
+        ``region_paths`` returns."""
+        return region_path_set_views(self.n, self.P, lo, hi, term_ptr, term_region, max_len,
+                                     lambda *arrays: self._call("gcsadmm_scene_region_paths_sets", *arrays))
+
+    def informed_regions_sets(self, lo, hi, bound, pad: float = SWEEP_PAD):
+        """bool [B, P]: ``keep[i, r]`` iff ``gap(S_i, box_r) + gap(G_i, box_r) <= bound[i] (1 + 1e-9)``, the distances between the
+        terminal boxes and the resident boxes, every side of those moved out by ``pad`` (``gcsadmm_scene_informed_regions_sets``).
+        ``lo``, ``hi`` [2 B, n]: as ``region_paths_sets``; ``bound`` [B]: the length of a feasible path of each query, finite."""
+        return informed_keep_set_array(self.n, self.P, lo, hi, bound, pad, lambda *arrays: self._call("gcsadmm_scene_informed_regions_sets", *arrays))
+
     def induced_sizes(self, keep, term_ptr, term_region, st_adjacent):
         """``(num_kept int32 [B], num_edges int64 [B])`` of the graphs ``induced_query_graphs`` would write (``gcsadmm_scene_induced_sizes``:
         the counts alone)"""
@@ -387,6 +402,26 @@ def informed_keep_array(n, P, points, bound, pad, call):
     keep = np.zeros((B, P), np.uint8)
     call(B, pts.ctypes.data, bnd.ctypes.data, float(pad), keep.ctypes.data, None)
     return keep != 0
+
+
+def _terminal_boxes(n, lo, hi):
+    lo = np.ascontiguousarray(lo, float).reshape(-1, n); hi = np.ascontiguousarray(hi, float).reshape(-1, n)
+    if lo.shape != hi.shape or lo.shape[0] % 2:
+        raise ValueError("lo and hi need 2 B rows each: the start boxes, then the goal boxes")
+    return lo, hi
+
+
+def region_path_set_views(n, P, lo, hi, term_ptr, term_region, max_len, call):
+    """the arrays of ``gcsadmm_scene_region_paths_sets`` around ``call(num_queries, lo, hi, term_ptr, term_region, max_len, *four
+    outputs)`` (addresses): ``region_path_views`` with the two box arrays in the place of the points"""
+    lo, hi = _terminal_boxes(n, lo, hi)
+    return region_path_views(n, P, lo, term_ptr, term_region, max_len, lambda B, _, *rest: call(B, lo.ctypes.data, hi.ctypes.data, *rest))
+
+
+def informed_keep_set_array(n, P, lo, hi, bound, pad, call):
+    """the arrays of ``gcsadmm_scene_informed_regions_sets`` around ``call(num_queries, lo, hi, bound, pad, keep, num_kept)`` (addresses)"""
+    lo, hi = _terminal_boxes(n, lo, hi)
+    return informed_keep_array(n, P, lo, bound, pad, lambda B, _, *rest: call(B, lo.ctypes.data, hi.ctypes.data, *rest))
 
 
 def query_graph_views(P, region_edges, term_ptr, term_region, st_adjacent, call, chunk_queries=0):

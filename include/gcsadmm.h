@@ -551,6 +551,26 @@ int gcsadmm_scene_region_paths(gcsadmm_scene s, int num_queries, const double *p
 int gcsadmm_scene_informed_regions(gcsadmm_scene s, int num_queries, const double *points, const double *bound, double pad,
                                    unsigned char *keep, int64_t *num_kept);
 
+/* The two calls above for start and goal SETS (csrc/informed_set_core.h has the rule and why it is safe).  A terminal is a box: lo and
+ * hi are [2 num_queries][n] each, the start boxes and then the goal boxes, finite, lo <= hi; a point is the box with lo == hi, and on
+ * such boxes every output has the bits of the point call.  term_ptr and term_region list the regions that meet each box.
+ *
+ * region_paths_sets: the path of region_paths with the distance of a centre to the box, sqrt(sum_k max(lo_k - c_k, 0, c_k - hi_k)^2), in
+ * the place of |s - c_r| and |c_r - g|.  Its rounds stop early: a relaxation is stored only while it is not above the cheapest goal
+ * cost seen so far, so a local query settles in the rounds its own path needs.  Status, path, length and cost are those of the search
+ * that runs to the end.
+ *
+ * informed_regions_sets: keep[i][r] = 1 iff gap(S_i, box_r) + gap(G_i, box_r) <= bound[i] (1 + 1e-9), gap the distance between two
+ * boxes, the region's sides moved out by pad.  No region of an optimal path from a point of S_i to a point of G_i is dropped when
+ * bound[i] is the length of a feasible one.
+ *
+ * GCSADMM_ERR_BAD_ARG: what the point calls refuse, and a null lo or hi, lo > hi in a coordinate, a bound that is not finite.
+ * num_queries = 0 does nothing.  A refused call writes no output and changes nothing resident. */
+int gcsadmm_scene_region_paths_sets(gcsadmm_scene s, int num_queries, const double *lo, const double *hi, const int64_t *term_ptr,
+                                    const int *term_region, int max_len, int *path_region, int *path_len, double *path_cost, int *status);
+int gcsadmm_scene_informed_regions_sets(gcsadmm_scene s, int num_queries, const double *lo, const double *hi, const double *bound, double pad,
+                                        unsigned char *keep, int64_t *num_kept);
+
 /* The query graphs of a batch, each on its own kept regions, assembled on the device (csrc/induced_graph_core.h has the contract): what
  * gcs_admm_amd.queries.SceneQueries.graphs(prune="informed") builds on the host by masking and renumbering the whole edge list per
  * query.  keep[num_queries][P]: any non-zero byte keeps region r for query i; the kept regions are renumbered in scene order (new[r] =
