@@ -5,6 +5,7 @@ from .graph import (GcsGraph, build_graph, convert_pt_to_polytope, delta, graph_
 from .cases import load_fixture  # noqa: F401
 from .batch import BatchSolver  # noqa: F401  (many small problems in one set of launches; needs the GPU only when one is made)
 from .queries import SceneQueries  # noqa: F401  (many start / goal queries on one resident scene)
+from .transfer import StateSnapshot  # noqa: F401  (replanning: a solved state kept to seed the next query)
 
 # Barrier parameter at which a vertex solve stops (gcsadmm_params.ipm_tol).  MOSEK's default relative gap behind the reference's
 # SolveInParallel (admm_solver_v3.py:490) is ~1e-8.  Swept on the oracle in round 4 (profiles/r04/README.md): 1e-9, 3e-9 and 5e-9 keep
@@ -14,4 +15,4 @@ from .queries import SceneQueries  # noqa: F401  (many start / goal queries on o
 IPM_TOL = 3e-9
 
 __all__ = ["GcsGraph", "build_graph", "convert_pt_to_polytope", "delta", "graph_from_sets", "lattice_boxes",
-           "polytopes_overlap", "load_fixture", "BatchSolver", "SceneQueries", "IPM_TOL"]
+           "polytopes_overlap", "load_fixture", "BatchSolver", "SceneQueries", "StateSnapshot", "IPM_TOL"]

@@ -55,6 +55,13 @@ class ControlBlock(C.Structure):
                 ("it", C.c_int32), ("status", C.c_int32), ("inner_failures", C.c_int32), ("inner_iters", C.c_int32)]
 
 
+class Snapshot(C.Structure):
+    """gcsadmm_snapshot: device pointers the caller allocates (gcs_admm_amd/transfer.py)"""
+    _fields_ = [("n", C.c_int32), ("state_dtype", C.c_int32), ("V", C.c_int32), ("E", C.c_int32),
+                ("edge_key", C.c_void_p), ("edge_words", C.c_void_p), ("vertex_id", C.c_void_p), ("vertex_words", C.c_void_p),
+                ("rho", C.c_void_p)]
+
+
 _p, _i, _d = C.c_void_p, C.c_int32, C.c_double
 _run, _run_timed = [_p, _p, _i, _p, _p], [_p, _p, _i, _p, _p] + [_p] * 4
 _csr = [_i, _i, _p, _p, _p]
@@ -86,6 +93,11 @@ PROTOTYPES = {
     "gcsadmm_batch_bind": ([_p] * 4, _i),
     "gcsadmm_batch_run": ([_p, _i, _p], _i),
     "gcsadmm_batch_poll": ([_p] * 4, _i),
+    # replanning: the state of a solved handle carried to another query graph (gcs_admm_amd/transfer.py)
+    "gcsadmm_export_state": ([_p] * 5, _i),
+    "gcsadmm_import_state": ([_p] * 5, _i),
+    "gcsadmm_batch_export_state": ([_p] * 4, _i),
+    "gcsadmm_batch_import_state": ([_p] * 4, _i),
     "gcsadmm_vertex_prox": ([_p] * 6 + [_d, _i, _p, _p], _i),
     # vertex partitions across GPUs (RCCL)
     "gcsadmm_comm_unique_id": ([_p], _i),

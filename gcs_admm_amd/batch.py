@@ -160,11 +160,50 @@ class BatchSolver:
         self._call("gcsadmm_batch_poll", status, it, self._stream())
         return list(status), list(it)
 
-    def solve(self, chunk: int = 25, params=None, **common):
+    # ------------------------------------------------------------------ replanning (gcs_admm_amd/transfer.py)
+    def _id_table(self, vertex_ids, active):
+        """(the checked id arrays, the host array of their addresses) for the members ``active`` says take part"""
+        from .transfer import check_vertex_ids
+        if vertex_ids is None or len(vertex_ids) != len(self.members):
+            raise ValueError("one vertex id list per member")
+        ids = [check_vertex_ids(v, m.g.num_vertices) if a else None for v, m, a in zip(vertex_ids, self.members, active)]
+        return ids, (C.c_void_p * len(ids))(*[None if a is None else a.ctypes.data for a in ids])
+
+    def export_state(self, vertex_ids):
+        """One ``StateSnapshot`` per member of the state it holds now -- typically after ``solve`` --, keyed by ``vertex_ids[i]`` (int32,
+        >= 0, strictly ascending with the vertex index of member i): one launch for the whole batch (gcsadmm_batch_export_state).  The
+        batch must be bound (``reset`` or ``solve`` has run)."""
+        from .transfer import StateSnapshot
+        state_dtype = "f64" if not self.members or self.members[0].dtype_code == abi.F64 else "f32"
+        ids, table = self._id_table(vertex_ids, [True] * len(self.members))
+        snaps = [StateSnapshot(m.g.n, state_dtype, m.g.num_vertices, m.g.num_edges, self.device) for m in self.members]
+        self._call("gcsadmm_batch_export_state", table, (C.c_void_p * len(snaps))(*[C.addressof(s.c) for s in snaps]), self._stream())
+        return snaps
+
+    def import_state(self, seed, vertex_ids):
+        """Write ``seed[i]`` (a ``StateSnapshot`` or None: member i keeps its state) into the state of member i, matched by
+        ``vertex_ids[i]``; what the snapshot does not have becomes zero: one launch (gcsadmm_batch_import_state), after ``reset``."""
+        if len(seed) != len(self.members):
+            raise ValueError("one snapshot or None per member")
+        ids, table = self._id_table(vertex_ids, [s is not None for s in seed])
+        self._call("gcsadmm_batch_import_state", table, (C.c_void_p * len(seed))(*[None if s is None else C.addressof(s.c) for s in seed]), self._stream())
+
+    def solve(self, chunk: int = 25, params=None, seed=None, vertex_ids=None, **common):
         """Every member to its stop test (or its max_it) as ``DeviceSolver.solve`` runs one: enqueue ``chunk`` iterations, poll once, stop
         when no member is running.  Returns one result per member in the shape ``DeviceSolver.solve`` returns; ``wall_time_s`` is the
-        wall time of the whole batch."""
+        wall time of the whole batch.  ``seed``: one ``StateSnapshot`` or None per member, with ``vertex_ids`` (as ``export_state``):
+        after the reset the seeded members start from their snapshot (``import_state``) at the rho their parameters say, the others
+        from zero as always; the import is part of ``wall_time_s``."""
+        if seed is not None and len(seed) != len(self.members):
+            raise ValueError("one snapshot or None per member")
         self.reset(params, **common)
+        if seed is not None and any(s is not None for s in seed):
+            self.torch.cuda.synchronize(self.device)
+            t_import = time.perf_counter()
+            self.import_state(seed, vertex_ids)
+            t_import = time.perf_counter() - t_import
+        else:
+            t_import = 0.0
         max_it, done = max(m.params.max_it for m in self.members), 0
         self.torch.cuda.synchronize(self.device)
         t0 = time.perf_counter()
@@ -176,5 +215,5 @@ class BatchSolver:
             status, _ = self.poll()
             if all(s != RUNNING for s in status) or done >= max_it:
                 break
-        wall = time.perf_counter() - t0
+        wall = time.perf_counter() - t0 + t_import
         return [m.record(m.read_control(), wall) for m in self.members]

@@ -9,6 +9,7 @@
 
 #include "canonical_box.h"
 #include "gcsadmm.h"
+#include "state_transfer_core.h"
 #include "step_args.h"
 #include "vertex_program.h"
 #include "warm_start.h"
@@ -70,6 +71,11 @@ struct CreatePlan {
     // gcsadmm_run may run the edge and control steps as the tail of the workgroup program's launch (vertex_wg_kernel.h): one launch
     // per iteration instead of two
     int fused_tail = 0;
+    // state transfer (state_transfer_core.h): both ends of every edge as vertices of this handle, from the CSR (-1: an end that is not
+    // among them, a cut edge of a partition), and whether the edge list ascends strictly in (tail, head) -- the edge keys of a snapshot
+    // then ascend too, which gcsadmm_export_state / gcsadmm_import_state need
+    std::vector<int> edge_tail, edge_head;
+    int edges_ascending = 0;
     int n_waves() const { return (int)wave_slot_ptr.size() - 1; }
 };
 
@@ -124,6 +130,10 @@ inline gcsadmm_status make_create_plan(const gcsadmm_graph_desc &g, CreatePlan &
             if (g.edge_inc_tail[e] != e || g.edge_inc_head[e] != E + e)
                 return fail(GCSADMM_ERR_BAD_ARG, "edge-major columns: edge_inc_tail[e] must be e and edge_inc_head[e] num_edges + e");
     }
+    p.edge_tail.assign(E, -1); p.edge_head.assign(E, -1);
+    for (int v = 0; v < V; ++v)
+        for (int k = g.inc_ptr[v]; k < g.inc_ptr[v + 1]; ++k) (g.inc_out[k] ? p.edge_tail : p.edge_head)[g.inc_edge[k]] = v;
+    p.edges_ascending = transfer_edges_ascend(E, p.edge_tail.data(), p.edge_head.data());
     auto poly_A = [&](int v) { return g.poly_A + (size_t)g.poly_ptr[v] * n; };
 
     // centred right-hand sides b - A c

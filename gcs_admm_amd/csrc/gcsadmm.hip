@@ -22,6 +22,8 @@
 //                        GCSADMM_BATCH_LARGE: one launch per group of members that run the same instantiation
 //   terminal_region_batch_kernel<N,T,LDSWS> (terminal_region.hip)   the same for terminal_region_kernel, in batches made with
 //                        GCSADMM_BATCH_TERMINALS: one launch per group of terminals, on the batch's auxiliary stream
+//   state_export_kernel<T> / state_import_kernel<T> (state_transfer_core.h)   replanning: the state of a solved handle written to a snapshot
+//                        keyed by stable vertex ids, and read into the state of another graph of the scene; all members of a call in one launch
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -112,6 +114,8 @@ struct gcsadmm_handle_s {
     // the graph and what the plan made of it: from create to destroy
     struct Graph {
         DevBuf<int> d_inc_ptr, d_deg_in, d_inc_edge, d_poly_ptr, d_edge_inc_tail, d_edge_inc_head;
+        DevBuf<int> d_edge_tail, d_edge_head;      // both ends of every edge as vertices (plan.edge_tail / edge_head), uploaded by the first
+                                                   // state transfer of the handle: create allocates what it always did
         DevBuf<int> d_wave_slot_ptr, d_wave_vtx, d_special_vtx, d_special_kind, d_wg_vtx;
         DevBuf<double> d_poly_A, d_poly_bc, d_center;
         DevBuf<uint8_t> d_inc_counted, d_edge_counted;      // may stay empty
@@ -131,6 +135,7 @@ struct gcsadmm_handle_s {
         DevBuf<int> d_counters;
         DevBuf<double> d_partials, d_sums;
         DevBuf<unsigned> d_ticket;      // arrival counter of the single-launch edge step (edge_kernel MODE 2)
+        DevBuf<char> d_transfer;        // table and vertex ids of the last gcsadmm_export_state / gcsadmm_import_state (grows, is kept)
     } loop;
     struct Prox { DevBuf<int> d_prox_vtx, d_prox_counters; } prox;      // gcsadmm_vertex_prox: every non-terminal vertex, own counters
     Halo halo;
@@ -153,6 +158,8 @@ struct gcsadmm_batch_s {
     std::string err;
     std::vector<gcsadmm_handle> members;
     std::vector<unsigned> resets;       // members' reset counts at bind
+    std::vector<gcsadmm_state> states;  // members' state pointers at bind (gcsadmm_batch_export_state / _import_state work on them)
+    DevBuf<char> d_transfer;            // table and vertex ids of the last of those calls (grows, is kept)
     BatchPlan plan;
     bool bound = false;
     unsigned flags = 0;                 // GCSADMM_BATCH_LARGE | GCSADMM_BATCH_TERMINALS or 0 (gcsadmm_batch_create_ex)
@@ -634,6 +641,82 @@ static gcsadmm_status need_bound(gcsadmm_batch_s *b)
     if (!b->bound) b->err = "gcsadmm_batch_bind has not been called";
     return bad_unless(b->bound);
 }
+
+// ---- state transfer (state_transfer_core.h): host-side helpers of the four export / import entry points ----
+// the checks and the table of a call are the header's (transfer_add on a TransferHandle): what it reads of a handle.  The two arrays of
+// edge ends are uploaded by the handle's first transfer (transfer_ends), so the entries take their pointers there
+static TransferHandle transfer_handle(const gcsadmm_handle_s *h)
+{
+    return TransferHandle{h->n, h->dtype, h->V, h->E, h->NI, h->edge_major, h->plan.edges_ascending, h->params_set, h->g.d_edge_tail.get(), h->g.d_edge_head.get(),
+                          h->g.d_edge_inc_tail.get(), h->g.d_edge_inc_head.get(), h->loop.d_cb.get()};
+}
+
+// one call: its table, and the handle of every entry
+struct TransferJob {
+    TransferCall call;
+    std::vector<gcsadmm_handle> handles;
+};
+// under the guard, before the launch: the edge ends of every handle of the job are on the device and in its entry
+template <class O> static gcsadmm_status transfer_ends(O *obj, TransferJob &job)
+{
+    for (size_t i = 0; i < job.handles.size(); ++i) {
+        gcsadmm_handle h = job.handles[i];
+        if (!h->g.d_edge_tail) HIPCHK(obj, h->g.d_edge_tail.upload(h->plan.edge_tail.data(), (size_t)h->E));
+        if (!h->g.d_edge_head) HIPCHK(obj, h->g.d_edge_head.upload(h->plan.edge_head.data(), (size_t)h->E));
+        job.call.table[i].edge_tail = h->g.d_edge_tail.get(); job.call.table[i].edge_head = h->g.d_edge_head.get();
+    }
+    return GCSADMM_OK;
+}
+
+// Upload the table and the ids into `buf` (the object's, kept from call to call), one launch for all members, then wait for it: the
+// host arrays of `call` end with the call.  `obj`: the handle or batch whose err takes the text.
+template <class O> static gcsadmm_status transfer_launch(O *obj, DevBuf<char> &buf, TransferJob &job, int dtype, bool exporting, hipStream_t s)
+{
+    TransferCall &call = job.call;
+    if (call.table.empty()) return GCSADMM_OK;
+    const gcsadmm_status ends = transfer_ends(obj, job);
+    if (ends != GCSADMM_OK) return ends;
+    const size_t table_bytes = sizeof(TransferEntry) * call.table.size(), id_bytes = sizeof(int32_t) * call.ids.size();
+    HIPCHK(obj, buf.reserve(table_bytes + std::max<size_t>(id_bytes, 4)));
+    const int32_t *d_ids = (const int32_t *)(buf.get() + table_bytes);
+    for (size_t i = 0; i < call.table.size(); ++i) call.table[i].vertex_id = d_ids + call.ids_at[i];
+    HIPCHK(obj, hipMemcpyAsync(buf.get(), call.table.data(), table_bytes, hipMemcpyHostToDevice, s));
+    if (id_bytes) HIPCHK(obj, hipMemcpyAsync(buf.get() + table_bytes, call.ids.data(), id_bytes, hipMemcpyHostToDevice, s));
+    const TransferEntry *table = (const TransferEntry *)buf.get();
+    with_state_type(dtype == GCSADMM_F64, [&](auto t) {
+        using T = decltype(t);
+        if (exporting) hipLaunchKernelGGL((state_export_kernel<T>), dim3(call.blocks), dim3(TRANSFER_BLOCK), 0, s, table, (int)call.table.size());
+        else hipLaunchKernelGGL((state_import_kernel<T>), dim3(call.blocks), dim3(TRANSFER_BLOCK), 0, s, table, (int)call.table.size());
+    });
+    HIPCHK(obj, hipGetLastError());
+    HIPCHK(obj, hipStreamSynchronize(s));
+    return GCSADMM_OK;
+}
+
+// the members of a batch call that have a snapshot, checked and entered; nothing is entered unless all pass
+template <class S> static gcsadmm_status transfer_add_batch(gcsadmm_batch_s *b, TransferJob &job, const int32_t *const *vertex_ids, S *const *snapshots, bool exporting)
+{
+    if (need_bound(b) != GCSADMM_OK) return GCSADMM_ERR_BAD_ARG;
+    if (!vertex_ids || !snapshots) { b->err = "null vertex_ids or snapshots"; return GCSADMM_ERR_BAD_ARG; }
+    for (size_t i = 0; i < b->members.size(); ++i) {
+        if (!snapshots[i]) continue;
+        const gcsadmm_status st = transfer_add(job.call, transfer_handle(b->members[i]), &b->states[i], vertex_ids[i], snapshots[i], exporting, "member " + std::to_string(i) + ": ", b->err);
+        if (st != GCSADMM_OK) return st;
+        job.handles.push_back(b->members[i]);
+    }
+    return GCSADMM_OK;
+}
+
+// the one member of a solo call
+static gcsadmm_status transfer_add_solo(TransferJob &job, gcsadmm_handle h, const gcsadmm_state *st, const int32_t *vertex_id, const gcsadmm_snapshot *snap, bool exporting)
+{
+    const gcsadmm_status r = transfer_add(job.call, transfer_handle(h), st, vertex_id, snap, exporting, "", h->err);
+    if (r == GCSADMM_OK) job.handles.push_back(h);
+    return r;
+}
+
+// what an export reports back: the sizes it wrote
+static void transfer_exported(const gcsadmm_handle_s *h, gcsadmm_snapshot *snap) { snap->V = h->V; snap->E = h->E; }
 
 // one vertex launch of the workgroup program over the members that have something in it, one of the wavefront program per group
 // (GCSADMM_BATCH_LARGE alone has any) and one edge + control launch for the whole batch.  GCSADMM_BATCH_TERMINALS: the terminal launches,
@@ -1256,6 +1339,7 @@ gcsadmm_status gcsadmm_batch_bind(struct gcsadmm_batch_s *b, const gcsadmm_state
         std::vector<char> vtab(vbytes * bp.wg_members.size());
         std::vector<const gcsadmm_control_block *> cbs((size_t)count);
         b->resets.assign((size_t)count, 0u);
+        b->states.assign(states, states + count);
         for (int i = 0; i < count; ++i) {
             cbs[i] = b->members[i]->loop.d_cb.get();
             b->resets[i] = b->members[i]->resets;
@@ -1336,6 +1420,44 @@ gcsadmm_status gcsadmm_batch_poll(struct gcsadmm_batch_s *b, int32_t *status, in
         }
         return GCSADMM_OK;
     });
+}
+
+// =================================================================================================
+// state transfer (include/gcsadmm.h): a solved state written to a snapshot keyed by stable vertex ids, and read into another graph
+// =================================================================================================
+gcsadmm_status gcsadmm_export_state(gcsadmm_handle h, const gcsadmm_state *state, const int32_t *vertex_id, gcsadmm_snapshot *snapshot, void *stream)
+{
+    TransferJob job;
+    return handle_entry(h, [&] { return transfer_add_solo(job, h, state, vertex_id, snapshot, true); }, [&] {
+        const gcsadmm_status st = transfer_launch(h, h->loop.d_transfer, job, h->dtype, true, (hipStream_t)stream);
+        if (st == GCSADMM_OK) transfer_exported(h, snapshot);
+        return st;
+    });
+}
+
+gcsadmm_status gcsadmm_import_state(gcsadmm_handle h, const gcsadmm_state *state, const int32_t *vertex_id, const gcsadmm_snapshot *snapshot, void *stream)
+{
+    TransferJob job;
+    return handle_entry(h, [&] { return transfer_add_solo(job, h, state, vertex_id, snapshot, false); },
+                        [&] { return transfer_launch(h, h->loop.d_transfer, job, h->dtype, false, (hipStream_t)stream); });
+}
+
+gcsadmm_status gcsadmm_batch_export_state(struct gcsadmm_batch_s *b, const int32_t *const *vertex_ids, gcsadmm_snapshot *const *snapshots, void *stream)
+{
+    TransferJob job;
+    return batch_entry(b, [&] { return transfer_add_batch(b, job, vertex_ids, snapshots, true); }, [&] {
+        const gcsadmm_status st = transfer_launch(b, b->d_transfer, job, b->plan.dtype, true, (hipStream_t)stream);
+        for (size_t i = 0; st == GCSADMM_OK && i < b->members.size(); ++i)
+            if (snapshots[i]) transfer_exported(b->members[i], snapshots[i]);
+        return st;
+    });
+}
+
+gcsadmm_status gcsadmm_batch_import_state(struct gcsadmm_batch_s *b, const int32_t *const *vertex_ids, const gcsadmm_snapshot *const *snapshots, void *stream)
+{
+    TransferJob job;
+    return batch_entry(b, [&] { return transfer_add_batch(b, job, vertex_ids, snapshots, false); },
+                       [&] { return transfer_launch(b, b->d_transfer, job, b->plan.dtype, false, (hipStream_t)stream); });
 }
 
 } // extern "C"

@@ -6,6 +6,7 @@
 
 #include "gcsadmm.h"
 #include "edge_step.h"
+#include "state_transfer_core.h"
 
 namespace {
 
@@ -66,6 +67,22 @@ __global__ __launch_bounds__(256) void batch_poll_kernel(const gcsadmm_control_b
     if (i >= count) return;
     out[i] = cbs[i]->status;
     out[count + i] = cbs[i]->it;
+}
+
+// STATE TRANSFER (gcsadmm_export_state / gcsadmm_import_state and their batch forms): the bodies are state_transfer_core.h's.  One launch
+// for all members of a call; a workgroup finds its member in the table's prefix of workgroup counts (uniform per workgroup) and runs
+// the lanes of one tile of that member's edges or, in the member's trailing workgroups, vertices.
+template <class T>
+__global__ __launch_bounds__(TRANSFER_BLOCK) void state_export_kernel(const TransferEntry *__restrict__ table, int count)
+{
+    const TransferEntry e = table[transfer_member(table, count, (int)blockIdx.x)];
+    transfer_export_lane<T>(e, (int)blockIdx.x - e.block_first, (int)threadIdx.x);
+}
+template <class T>
+__global__ __launch_bounds__(TRANSFER_BLOCK) void state_import_kernel(const TransferEntry *__restrict__ table, int count)
+{
+    const TransferEntry e = table[transfer_member(table, count, (int)blockIdx.x)];
+    transfer_import_lane<T>(e, (int)blockIdx.x - e.block_first, (int)threadIdx.x);
 }
 
 // SLOWEST-FIRST DISPATCH.  A vertex-step launch ends when its slowest workgroup does, and with the warm start most solves take 3-5

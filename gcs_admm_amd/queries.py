@@ -50,6 +50,9 @@ class SceneQueries:
             self.close()
             raise
         self.centers = np.ascontiguousarray(self.centers, float)
+        # replanning: a serial number per region that survives every edit -- 0 .. P-1 now, the next free ones in add_regions, never
+        # reused after remove_regions; a query graph's vertex ids are made of them (vertex_ids)
+        self.serials, self._next_serial = list(range(len(self.keys))), len(self.keys)
         self.last = {}      # counts of the last regions_at call: hits, undecided, redone_on_host
         # assemble="device" / "induced" and informed: is the scene's region graph that of _pairs?  The two assemblies: the regions' stacked
         # polytope CSR (rows int64, A, b)
@@ -112,6 +115,8 @@ class SceneQueries:
             flags[t] = 1 if polytopes_overlap(A1, b1, A2, b2) else 0
         self.keys = self.keys + new_keys
         self.polys = self.polys + polys
+        self.serials = self.serials + list(range(self._next_serial, self._next_serial + len(new_keys)))
+        self._next_serial += len(new_keys)
         if self._stacked is not None:      # extended by the new rows
             rows, A, b = self._stacked
             self._stacked = (np.concatenate([rows, rows[-1] + np.cumsum([len(q) for _, q in polys], dtype=np.int64)]),
@@ -141,6 +146,7 @@ class SceneQueries:
         if not (np.array_equal(pa, newidx[old["pa"][keep]]) and np.array_equal(pb, newidx[old["pb"][keep]])):
             raise RuntimeError("the scene's pair list lost its order")
         self.keys = [k for k, s in zip(self.keys, stays) if s]
+        self.serials = [r for r, s in zip(self.serials, stays) if s]
         self.polys = [p for p, s in zip(self.polys, stays) if s]
         if self._stacked is not None:      # compacted: the rows of the regions that stay
             rows, A, b = self._stacked
@@ -479,9 +485,25 @@ class SceneQueries:
         return [self._host_graph(S[i], G[i], regs[i], regs[B + i], eps, info[i]["keep"] if prune else None, self._box_of(sb, i), self._box_of(gb, i))
                 for i in range(B)], info
 
+    def vertex_ids(self, graph):
+        """The stable vertex ids of a query graph of this scene (``graphs``, or the ``graph`` of a ``solve`` record), int32: 0 for 's', 1
+        for 't' and serial + 2 for a region, the serial being the number the region got when it entered the scene -- the same for
+        every graph it appears in, pruned or not, before and after ``add_regions`` / ``remove_regions`` of others.  What
+        ``StateSnapshot``s of this scene are keyed by.  Ids must ascend with the vertex index: a scene whose order of regions
+        disagrees with their serials is refused, not sorted."""
+        serial = dict(zip(self.keys, self.serials))
+        try:
+            ids = np.array([0, 1] + [serial[k] + 2 for k in graph.keys[2:]], np.int64)
+        except KeyError as e:
+            raise ValueError(f"region {e.args[0]!r} of the graph is not in the scene (any more)") from None
+        if list(graph.keys[:2]) != ['s', 't'] or np.any(np.diff(ids) <= 0):
+            raise RuntimeError("the order of the graph's regions and their serial numbers disagree: the vertex ids of a snapshot must "
+                               "ascend with the vertex index")
+        return ids.astype(np.int32)
+
     def solve(self, starts=None, goals=None, state_dtype: str = "f64", N: int = 5, M: int = 20, seeds=None, params=None, return_state: bool = False,
               walk: str = "host", assemble: str = "host", prune=None, restrict=None, large: bool = False, start_boxes=None, goal_boxes=None,
-              **common):
+              keep: bool = False, seed=None, **common):
         """Every query to its stop test in one ``BatchSolver`` (``params``: one dict per query, ``common``: parameters of all, as
         ``BatchSolver.solve``), then rounded by ``rounding_many`` (``N``, ``M``: as ``rounding``; ``seeds``: one per query, default 0).
         ``walk``: ``"host"`` (the default: the walks of ``rounding``, on a host copy of every query's activations) or ``"device"``
@@ -494,7 +516,14 @@ class SceneQueries:
         ``start_boxes``, ``goal_boxes``: as ``graphs``; with a box terminal the batch is made with ``region_terminals`` (otherwise not).
         Returns one record per query: that of ``DeviceSolver.solve`` plus ``rounded_cost``, ``x_v_rounded``, ``y_v_rounded`` and
         ``graph``; with ``return_state`` also ``trace`` and ``state``, host copies of the member's trace and of its six state arrays (the
-        batch and its members are closed on return)."""
+        batch and its members are closed on return).
+
+        Replanning (gcs_admm_amd/transfer.py).  ``keep=True``: every record gains ``"snapshot"``, a ``StateSnapshot`` of the member's final
+        state keyed by ``vertex_ids``, exported -- one launch for the batch -- before the members are closed; it is the caller's to
+        ``close()``.  ``seed``: one snapshot or None per query; a seeded query starts its loop from the snapshot's state, matched by
+        region serial (what the snapshot lacks starts at zero), at the rho its parameters say, and stops in a fraction of the
+        iterations when the query moved a little.  Both work with every ``assemble``, ``prune``, ``large``, ``walk`` and terminal
+        combination and across ``add_regions`` / ``remove_regions``.  Without them the call is what it always was."""
         from .batch import BatchSolver
         from .graph import sets_of_graph
         from .rounding import rounding_many, rounding_members, rounding_problem
@@ -504,6 +533,9 @@ class SceneQueries:
         seeds = [0] * len(graphs) if seeds is None else list(seeds)
         if len(seeds) != len(graphs):
             raise ValueError("one seed per query")
+        if seed is not None and len(seed) != len(graphs):
+            raise ValueError("one snapshot or None per query")
+        ids = [self.vertex_ids(g) for g in graphs] if keep or seed is not None else None
         # the bound's path with its restriction: one more candidate of the rounding step
         extra = info and [[(r["bound"], list(r["restriction"]), r["restriction"])] if r["restriction"] is not None else [] for r in info]
         batch = BatchSolver(graphs, state_dtype, device=self.device, large=large, region_terminals=start_boxes is not None or goal_boxes is not None)
@@ -513,21 +545,24 @@ class SceneQueries:
             for m in batch.members:
                 m.close()
 
-        def keep(records):
-            for rec, m, g in zip(records, batch.members, graphs):
+        def attach(records):
+            snapshots = batch.export_state(ids) if keep else [None] * len(graphs)
+            for rec, m, g, snap in zip(records, batch.members, graphs, snapshots):
+                if keep:
+                    rec["snapshot"] = snap
                 rec["graph"] = g
                 if return_state:
                     rec["trace"] = m.trace.cpu().numpy()
                     rec["state"] = {k: getattr(m, k).cpu().numpy() for k in ("copy", "mu", "zedge", "xv", "zv", "yv")}
         with contextlib.ExitStack() as members_open:
             members_open.callback(close)
-            records = batch.solve(params=params, **common)
+            records = batch.solve(params=params, **common) if seed is None else batch.solve(params=params, seed=list(seed), vertex_ids=ids, **common)
             if walk == "device":         # the walks read the activations where the members hold them
                 rounded = rounding_members(batch.members, graphs, N=N, M=M, seeds=seeds, device=self.device, extra=extra)
-                keep(records)
+                attach(records)
             else:                        # the host walks read a copy of them; the batch is closed before the rounding
                 problems = [rounding_problem(m, *sets_of_graph(g), seed=s) for m, g, s in zip(batch.members, graphs, seeds)]
-                keep(records)
+                attach(records)
                 members_open.close()
                 rounded = rounding_many(problems, N=N, M=M, device=self.device, extra=extra)
         for i, (rec, (cost, x_v, y_v)) in enumerate(zip(records, rounded)):

@@ -266,6 +266,23 @@ class DeviceSolver:
             self._call("gcsadmm_unit_iterations", out.ctypes.data, n.value, C.byref(n), self._stream())
         return out
 
+    # ---- replanning (gcs_admm_amd/transfer.py) ------------------------------------------
+    def export_state(self, vertex_ids):
+        """a ``StateSnapshot`` of the state this solver holds, keyed by ``vertex_ids`` (int32, >= 0, strictly ascending with the vertex
+        index): gcsadmm_export_state, after ``reset``"""
+        from .transfer import StateSnapshot, check_vertex_ids
+        ids = check_vertex_ids(vertex_ids, self.g.num_vertices)
+        snap = StateSnapshot(self.g.n, "f64" if self.dtype_code == F64 else "f32", self.g.num_vertices, self.g.num_edges, self.device)
+        self._call("gcsadmm_export_state", C.byref(self.state), ids.ctypes.data, C.byref(snap.c), self._stream())
+        return snap
+
+    def import_state(self, snapshot, vertex_ids):
+        """every word of the state from ``snapshot``, matched by ``vertex_ids``; what it does not have becomes zero (gcsadmm_import_state,
+        after ``reset(zero_state=...)`` either way: the import writes all six arrays)"""
+        from .transfer import check_vertex_ids
+        ids = check_vertex_ids(vertex_ids, self.g.num_vertices)
+        self._call("gcsadmm_import_state", C.byref(self.state), ids.ctypes.data, C.byref(snapshot.c), self._stream())
+
     def cost(self) -> float:
         eps = self.params.eps_edge if self.params is not None else 1e-4
         self._call("gcsadmm_cost", C.byref(self.state), eps, self._cost.data_ptr(), self._stream(), select=False)

@@ -277,6 +277,50 @@ gcsadmm_status gcsadmm_batch_run(struct gcsadmm_batch_s *b, int32_t k, void *str
 gcsadmm_status gcsadmm_batch_poll(struct gcsadmm_batch_s *b, int32_t *status, int32_t *it, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Replanning: the state of a solved handle, carried to another query graph of the same scene (csrc/state_transfer_core.h has the
+ * kernels' contract).  A planner asks almost the same query again every tick; the relaxation is convex, so the loop converges from any
+ * state, and from the state of the query before it does so in a fraction of the iterations.  Two graphs of a scene number vertices,
+ * edges and state columns differently, so a SNAPSHOT names everything by stable ids the caller gives: vertex_id[V] per handle, int32
+ * HOST memory, every id >= 0, strictly ascending with the vertex index.  Edge (u, w) has the key (int64(id[u]) << 32) | id[w]; the keys
+ * ascend along the edge list exactly when it ascends in (tail, head), which is decided once, at create.
+ *
+ * A snapshot is plain DEVICE pointers the caller allocates (as for the state); n and state_dtype are the caller's statement of what it
+ * is for.  edge_words holds, word-major, zedge, copy at the tail column, copy at the head column, mu at the tail column, mu at the
+ * head column (c = 2n + 1 words each) in the state's element type; the mu words hold fl(mu_scale * mu) with the control block's pending
+ * rescale applied (f64 product, rounded once for f32 state).  vertex_words holds xv[2n], zv[2n], yv.  rho[0] is the control block's
+ * rho.  Everything else is a copy.
+ *
+ * export: on entry V and E are the capacities of the snapshot's arrays (each at least the handle's); on return they are the handle's
+ * num_vertices and num_edges, the lengths of the two key lists and the strides of the word-major arrays.  One launch writes all of it.
+ * import: after gcsadmm_reset (batch: after gcsadmm_batch_bind, before gcsadmm_batch_run).  One launch writes EVERY word of the six state
+ * arrays: a destination edge whose key is in the snapshot gets its five groups of words, the mu words as fl(word * r) with
+ * r = fl(rho_snapshot / rho_handle), the handle's rho read from its control block as gcsadmm_reset left it (r = 1 is a copy); an edge
+ * that is not gets zeros; vertices alike by id.  Not carried: the vertex solves' warm-start records (gcsadmm_reset clears them; the first
+ * vertex step of a seeded run starts cold), the trace, the iteration counter, rho itself.
+ * The batch calls take vertex_ids[count] and snapshots[count], host arrays of pointers; a null snapshots[i] leaves member i untouched
+ * (its vertex_ids[i] may then be null too), and all members are served by one launch, on the states the last bind recorded.
+ * Each call uploads its table and the ids, enqueues its one launch on `stream` and synchronises it.
+ *
+ * GCSADMM_ERR_BAD_ARG, with a text, nothing written, nothing launched: ids that are negative or not strictly ascending; a handle
+ * whose edge list is not strictly ascending in (tail, head) or that has ghost columns (num_incidences != 2 num_edges); n or
+ * state_dtype of snapshot and handle that differ; on export a snapshot smaller than the handle; a null pointer; a handle that has
+ * not been reset, a batch that is not bound. */
+typedef struct gcsadmm_snapshot {
+    int32_t n, state_dtype;
+    int32_t V, E;
+    int64_t *edge_key;       /* [E] ascending */
+    void *edge_words;        /* [5][c][E] */
+    int32_t *vertex_id;      /* [V] ascending */
+    double *vertex_words;    /* [4n + 1][V] */
+    double *rho;             /* [1] */
+} gcsadmm_snapshot;
+
+gcsadmm_status gcsadmm_export_state(gcsadmm_handle h, const gcsadmm_state *state, const int32_t *vertex_id, gcsadmm_snapshot *snapshot, void *stream);
+gcsadmm_status gcsadmm_import_state(gcsadmm_handle h, const gcsadmm_state *state, const int32_t *vertex_id, const gcsadmm_snapshot *snapshot, void *stream);
+gcsadmm_status gcsadmm_batch_export_state(struct gcsadmm_batch_s *b, const int32_t *const *vertex_ids, gcsadmm_snapshot *const *snapshots, void *stream);
+gcsadmm_status gcsadmm_batch_import_state(struct gcsadmm_batch_s *b, const int32_t *const *vertex_ids, const gcsadmm_snapshot *const *snapshots, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * The x-update of the reference's OTHER splittings: admm_solver_v1.py:334-383 (shared by v2) solves,
  * per vertex, the border-only problem -- no edge blocks -- whose consensus penalty (:350-367) is a separable quadratic in the
  * vertex's own unknowns:
