@@ -92,6 +92,9 @@ struct SceneHits {                                     // the hit list of the la
     DevBuf<int> region;
     DevBuf<unsigned char> cls;
     std::vector<int64_t> ptr;                          //   its segments per point (host: the scan runs there)
+    bool projected = false;                            //   which kind of call made it: project_points (true) or a locate call
+    DevBuf<double> distance, nearest;                  //   project_points: per hit the distance, the nearest point [n],
+    DevBuf<int> status, iterations;                    //   the status and the iterations of its solve
 };
 struct SceneGraph {                                    // region graph of the decided pairs (HAVE_GRAPH; query_graph_core.h): rows [P + 1],
     DevBuf<long long> row_ptr;
@@ -103,6 +106,8 @@ struct LocateScratch {                                 // locate_points / locate
     DevBuf<double> points;
     DevBuf<int> count;                                 //   counts and
     DevBuf<long long> offset;                          //   offsets per (point, chunk)
+    DevBuf<double> radius;                             //   project_points: the radii [num_points] and the segments of the list
+    DevBuf<long long> hit_ptr;                         //   [num_points + 1]
 };
 struct QueryScratch {                                  // query_graphs, kept and grown from call to call: the caller's arrays,
     DevBuf<long long> term_ptr, edge_off;
@@ -326,6 +331,33 @@ template <int N> int launch_locate_boxes(const LocateBoxArgs &args, long long nu
         const dim3 grid((unsigned)a.chunks, (unsigned)std::min(SLAB, num_boxes - q0));
         if (fill) hipLaunchKernelGGL((locate_box_kernel<N, true>), grid, dim3(LOCATE_WAVE), 0, 0, a);
         else hipLaunchKernelGGL((locate_box_kernel<N, false>), grid, dim3(LOCATE_WAVE), 0, 0, a);
+        LPCHK(hipGetLastError());
+    }
+    return GCSADMM_OK;
+}
+
+template <int N> int launch_project_list(const ProjectArgs &args, long long num_points, bool fill)
+{
+    constexpr long long SLAB = 65535;      // grid.y
+    for (long long q0 = 0; q0 < num_points; q0 += SLAB) {
+        ProjectArgs a = args;
+        a.first_point = (int)q0;
+        const dim3 grid((unsigned)a.chunks, (unsigned)std::min(SLAB, num_points - q0));
+        if (fill) hipLaunchKernelGGL((project_list_kernel<N, true>), grid, dim3(LOCATE_WAVE), 0, 0, a);
+        else hipLaunchKernelGGL((project_list_kernel<N, false>), grid, dim3(LOCATE_WAVE), 0, 0, a);
+        LPCHK(hipGetLastError());
+    }
+    return GCSADMM_OK;
+}
+
+template <int N> int launch_project_solve(const ProjectSolveArgs &args)
+{
+    constexpr long long SLAB = 1LL << 30;      // workgroups of one launch (grid.x)
+    const long long groups = (args.total + PROJECT_LANES - 1) / PROJECT_LANES;
+    for (long long g0 = 0; g0 < groups; g0 += SLAB) {
+        ProjectSolveArgs a = args;
+        a.first = g0 * PROJECT_LANES;
+        hipLaunchKernelGGL(project_solve_kernel<N>, dim3((unsigned)std::min(SLAB, groups - g0)), dim3(PROJECT_LANES), 0, 0, a);
         LPCHK(hipGetLastError());
     }
     return GCSADMM_OK;
@@ -766,6 +798,7 @@ int gcsadmm_scene_locate_points(gcsadmm_scene s, int num_points, const double *p
         }
         LPCHK(hipStreamSynchronize(nullptr));
         s->hits.ptr.swap(hit_ptr);
+        s->hits.projected = false;
         stage_finish(s->have, CALL_LOCATE_POINTS);
         if (num_hits) *num_hits = total;
         return GCSADMM_OK;
@@ -817,6 +850,7 @@ int gcsadmm_scene_locate_boxes(gcsadmm_scene s, int num_boxes, const double *lo,
         }
         LPCHK(hipStreamSynchronize(nullptr));
         s->hits.ptr.swap(hit_ptr);
+        s->hits.projected = false;
         stage_finish(s->have, CALL_LOCATE_POINTS);
         if (num_hits) *num_hits = total;
         return GCSADMM_OK;
@@ -832,6 +866,81 @@ int gcsadmm_scene_read_hits(gcsadmm_scene s, int64_t *hit_ptr, int *hit_region, 
         const size_t total = (size_t)h.ptr.back();      // (the buffers may be longer: they are kept from call to call)
         LPCHK(to_host(hit_region, h.region.get(), total));
         LPCHK(to_host(hit_class, h.cls.get(), total));
+        return GCSADMM_OK;
+    });
+}
+
+// The nearest regions of points that may lie in none (point_project_core.h): the candidates of every point as the resident hit list
+// (the stage rule of locate_points: it replaces the list of a locate call and is replaced by one), then one solve per entry
+int gcsadmm_scene_project_points(gcsadmm_scene s, int num_points, const double *points, const double *radius, int max_iter, int64_t *num_hits)
+{
+    return scene_entry(s, [&]() -> int {
+        const SceneRegions &r = s->reg;
+        LocateScratch &lq = s->lq;
+        SceneHits &h = s->hits;
+        if (num_points < 0 || (num_points > 0 && !points)) { g_err = "negative number of points or null points"; return GCSADMM_ERR_BAD_ARG; }
+        if (max_iter < 0) { g_err = "max_iter must not be negative"; return GCSADMM_ERR_BAD_ARG; }
+        const size_t coords = (size_t)num_points * r.n;
+        for (size_t i = 0; i < coords; ++i)
+            if (!std::isfinite(points[i])) { g_err = "point with a NaN or an inf coordinate"; return GCSADMM_ERR_BAD_ARG; }
+        for (int q = 0; radius && q < num_points; ++q)
+            if (!(radius[q] >= 0.0)) { g_err = "radius of point " + std::to_string(q) + " is NaN or negative"; return GCSADMM_ERR_BAD_ARG; }
+        stage_start(s->have, CALL_LOCATE_POINTS);
+        const long long Q = num_points, chunks = locate_chunks(r.P);
+        const size_t cells = (size_t)(Q * chunks);
+        std::vector<int> count(cells);
+        std::vector<long long> offset(cells);
+        std::vector<int64_t> hit_ptr((size_t)Q + 1, 0);
+        std::vector<double> rad((size_t)Q, INFINITY);      // (a null radius: +inf for every point)
+        if (radius) rad.assign(radius, radius + Q);
+        ProjectArgs a{};
+        a.R = LocateRegions{r.P, r.ptr.get(), r.A.get(), r.b.get()};
+        a.chunks = chunks;
+        long long total = 0;
+        if (cells > 0) {
+            LPCHK(lq.points.reserve(coords)); LPCHK(lq.radius.reserve((size_t)Q)); LPCHK(lq.count.reserve(cells));
+            LPCHK(to_device(lq.points.get(), points, coords)); LPCHK(to_device(lq.radius.get(), rad.data(), (size_t)Q));
+            a.points = lq.points.get(); a.radius = lq.radius.get(); a.count = lq.count.get();
+            LPRUN(for_dim(r.n, [&](auto N) { return launch_project_list<decltype(N)::value>(a, Q, false); }));
+            LPCHK(to_host(count.data(), lq.count.get(), cells));
+            if (!locate_scan(count.data(), Q, chunks, offset.data(), hit_ptr.data())) {      // before the list is allocated
+                g_err = "more than 2^31 - 1 candidates"; return GCSADMM_ERR_UNSUPPORTED;
+            }
+            total = hit_ptr[(size_t)Q];
+        }
+        if (total > 0) {
+            const size_t T = (size_t)total;
+            LPCHK(h.region.reserve(T)); LPCHK(h.cls.reserve(T)); LPCHK(lq.offset.reserve(cells)); LPCHK(lq.hit_ptr.reserve((size_t)Q + 1));
+            LPCHK(h.distance.reserve(T)); LPCHK(h.nearest.reserve(T * r.n)); LPCHK(h.status.reserve(T)); LPCHK(h.iterations.reserve(T));
+            const std::vector<long long> segments(hit_ptr.begin(), hit_ptr.end());
+            LPCHK(to_device(lq.offset.get(), offset.data(), cells)); LPCHK(to_device(lq.hit_ptr.get(), segments.data(), (size_t)Q + 1));
+            a.offset = lq.offset.get(); a.limit = total;
+            a.hit_region = h.region.get(); a.hit_class = h.cls.get();
+            LPRUN(for_dim(r.n, [&](auto N) { return launch_project_list<decltype(N)::value>(a, Q, true); }));
+            ProjectSolveArgs v{};
+            v.R = a.R; v.points = a.points; v.radius = a.radius; v.hit_ptr = lq.hit_ptr.get(); v.num_points = Q; v.total = total;
+            v.hit_region = h.region.get(); v.max_iter = max_iter;
+            v.out = ProjectOut{h.distance.get(), h.nearest.get(), h.status.get(), h.iterations.get()};
+            LPRUN(for_dim(r.n, [&](auto N) { return launch_project_solve<decltype(N)::value>(v); }));
+        }
+        LPCHK(hipStreamSynchronize(nullptr));
+        h.ptr.swap(hit_ptr);
+        h.projected = true;
+        stage_finish(s->have, CALL_LOCATE_POINTS);
+        if (num_hits) *num_hits = total;
+        return GCSADMM_OK;
+    });
+}
+
+int gcsadmm_scene_read_projections(gcsadmm_scene s, double *distance, double *nearest, int *status, int *iterations)
+{
+    return scene_entry(s, [&]() -> int {
+        NEED(s, CALL_READ_HITS);
+        const SceneHits &h = s->hits;
+        if (!h.projected) { g_err = "the resident hit list is a locate call's: call gcsadmm_scene_project_points first"; return GCSADMM_ERR_BAD_ARG; }
+        const size_t total = (size_t)h.ptr.back();      // (the buffers may be longer: they are kept from call to call)
+        LPCHK(to_host(distance, h.distance.get(), total)); LPCHK(to_host(nearest, h.nearest.get(), total * s->reg.n));
+        LPCHK(to_host(status, h.status.get(), total)); LPCHK(to_host(iterations, h.iterations.get(), total));
         return GCSADMM_OK;
     });
 }

@@ -7,6 +7,7 @@
 #include "box_sweep_core.h"
 #include "point_locate_core.h"
 #include "box_locate_core.h"
+#include "point_project_core.h"
 #include "scene_edit_core.h"
 #include "query_graph_core.h"
 #include "induced_graph_core.h"
@@ -267,6 +268,66 @@ __global__ __launch_bounds__(LOCATE_WAVE) void locate_box_kernel(LocateBoxArgs a
         }
     }
     if (!FILL && lane == 0) a.count[cell] = total;
+}
+
+// ---- the nearest regions of query points (point_project_core.h) ----
+struct ProjectArgs {
+    LocateRegions R;
+    const double *points;      // [num_points][N]
+    const double *radius;      // [num_points], +inf allowed
+    int first_point;           // blockIdx.y counts from here (one launch takes at most 65 535 points)
+    long long chunks, limit;   // chunks of the P regions; length of the list
+    int *count;                // [num_points][chunks]
+    const long long *offset;   // [num_points][chunks]
+    int *hit_region;
+    unsigned char *hit_class;
+};
+
+// locate_kernel's shape with the candidate test of a projection: one 64-lane workgroup per (chunk of regions, point), one region per
+// lane, a count pass (FILL = false) and a fill pass that runs the same tests again and writes the candidates from offset[point][chunk] on
+template <int N, bool FILL>
+__global__ __launch_bounds__(LOCATE_WAVE) void project_list_kernel(ProjectArgs a)
+{
+    const long long chunk = blockIdx.x, q = (long long)a.first_point + blockIdx.y;
+    const int lane = threadIdx.x;
+    double p[N];
+#pragma unroll
+    for (int k = 0; k < N; ++k) p[k] = a.points[(size_t)q * N + k];      // the same address in every lane
+    const double radius = a.radius[q];
+    const size_t cell = (size_t)(q * a.chunks + chunk);
+    long long pos = FILL ? a.offset[cell] : 0;
+    int total = 0;
+    for (int stride = 0; stride < LOCATE_CHUNK / LOCATE_WAVE; ++stride) {
+        const int region = locate_region(a.R.P, chunk, stride, lane);
+        const int cls = project_lane<N>(a.R, region, p, radius);
+        const unsigned long long mask = __ballot(cls != PROJECT_OUT);
+        if (FILL) {
+            locate_store(a.hit_region, a.hit_class, pos, a.limit, mask, lane, region, cls);
+            pos += locate_hits(mask);
+        } else {
+            total += locate_hits(mask);
+        }
+    }
+    if (!FILL && lane == 0) a.count[cell] = total;
+}
+
+struct ProjectSolveArgs {
+    LocateRegions R;
+    const double *points, *radius;
+    const long long *hit_ptr;  // [num_points + 1]
+    long long num_points, total;
+    const int *hit_region;
+    int max_iter;
+    long long first;           // blockIdx.x counts workgroups from this list entry on
+    ProjectOut out;
+};
+
+// one lane per candidate pair in list order, 64 pairs per workgroup; the working set of a lane stays in its registers
+template <int N>
+__global__ __launch_bounds__(PROJECT_LANES) void project_solve_kernel(ProjectSolveArgs a)
+{
+    const long long t = a.first + (long long)blockIdx.x * PROJECT_LANES + threadIdx.x;
+    if (t < a.total) project_entry<N>(a.R, a.points, a.radius, a.hit_ptr, a.num_points, a.hit_region, a.max_iter, t, a.out);
 }
 
 // ---- edits of a decided scene (scene_edit_core.h) ----

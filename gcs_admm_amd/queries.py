@@ -54,6 +54,7 @@ class SceneQueries:
         # reused after remove_regions; a query graph's vertex ids are made of them (vertex_ids)
         self.serials, self._next_serial = list(range(len(self.keys))), len(self.keys)
         self.last = {}      # counts of the last regions_at call: hits, undecided, redone_on_host
+        self.snapped = []   # per query of the last graphs / solve call: what outside="snap" replaced (_snap)
         # assemble="device" / "induced" and informed: is the scene's region graph that of _pairs?  The two assemblies: the regions' stacked
         # polytope CSR (rows int64, A, b)
         self._graph_resident, self._stacked = False, None
@@ -206,6 +207,78 @@ class SceneQueries:
         counts = np.bincount(np.repeat(np.arange(Q), np.diff(hit_ptr))[keep], minlength=Q)
         return np.split(hit_region[keep].astype(np.int32), np.cumsum(counts)[:-1]) if Q else []
 
+    def nearest_regions(self, points, radius=None):
+        """For points that may lie in NO region: per point ``(region index, distance, projected point)`` of the nearest region -- the
+        Euclidean projection of the point onto it, the point itself at distance 0 when it lies in a region -- or ``(-1, inf, None)``
+        when no region is within ``radius`` of it.  One ``project`` call for all points (csrc/point_project_core.h).  ``radius``: one
+        value or one per point; default per point ``min_r |p - c_r|`` over the resident Chebyshev centres -- a centre lies in its
+        region, so the nearest region is always within it.  The nearest region is the solved hit within the radius of least distance,
+        the lowest region index among equals.  A pair whose solve failed on the device (status -1) is solved again on the host by
+        ``scipy.optimize.minimize(method="SLSQP")`` from the region's centre; ``last`` counts them (``redone_on_host``)."""
+        if self.scene is None:
+            raise RuntimeError("the scene is closed")
+        pts = np.ascontiguousarray(points, float).reshape(-1, self.n)
+        Q = pts.shape[0]
+        if radius is None:
+            rad = np.array([np.sqrt(((self.centers - p) ** 2).sum(axis=1)).min() for p in pts]) if len(self.keys) else np.full(Q, np.inf)
+        else:
+            rad = np.ascontiguousarray(np.broadcast_to(np.asarray(radius, float), (Q,)))
+        hit_ptr, hit_region, _, distance, nearest, status, _ = self.scene.project(pts, rad)
+        distance, nearest, status = np.array(distance, float), np.array(nearest, float).reshape(-1, self.n), np.array(status, np.int32)
+        point_of = np.repeat(np.arange(Q), np.diff(hit_ptr))
+        failed = np.nonzero(status < 0)[0]
+        for t in failed:
+            p = pts[point_of[t]]
+            x = self._project_on_host(int(hit_region[t]), p)
+            nearest[t], distance[t] = x, float(np.sqrt(((x - p) ** 2).sum()))
+            status[t] = 0 if distance[t] <= rad[point_of[t]] else 1
+        self.last = dict(hits=int(len(hit_region)), undecided=int(len(failed)), redone_on_host=int(len(failed)))
+        out = []
+        for q in range(Q):
+            seg = np.arange(hit_ptr[q], hit_ptr[q + 1])
+            seg = seg[status[seg] == 0]
+            if len(seg) == 0:
+                out.append((-1, np.inf, None))
+                continue
+            t = seg[np.argmin(distance[seg])]      # (region indices ascend: the first of equals is the lowest)
+            out.append((int(hit_region[t]), float(distance[t]), nearest[t].copy()))
+        return out
+
+    def _project_on_host(self, r, p):
+        """the projection of p onto region r by SLSQP, started at the region's centre: what a failed device solve falls back to"""
+        from scipy.optimize import minimize
+        A, b = self.polys[r]
+        res = minimize(lambda x: 0.5 * float((x - p) @ (x - p)), self.centers[r], jac=lambda x: x - p, method="SLSQP",
+                       constraints=[dict(type="ineq", fun=lambda x: b - A @ x, jac=lambda x: -A)], options=dict(ftol=1e-15, maxiter=200))
+        return np.asarray(res.x, float)
+
+    def _snap(self, S, G, regs, eps, tol, snap_radius, sb=None, gb=None):
+        """``outside="snap"``: every point terminal that lies in no region is replaced, in S / G and in ``regs``, by its projection onto
+        its nearest region -- one ``project`` call for all of them, one more ``regions_at`` call for the replaced points alone.  Returns
+        the ``snapped`` records, one dict(start=, goal=) per query"""
+        B = len(S)
+        snapped = [dict(start=None, goal=None) for _ in range(B)]
+        out = [(which, i) for i in range(B) for which, r, boxes in (("start", regs[i], sb), ("goal", regs[B + i], gb)) if len(r) == 0 and boxes is None]
+        if not out:
+            return snapped
+        side = lambda which: S if which == "start" else G
+        counts = dict(self.last)
+        found = self.nearest_regions(np.array([side(which)[i] for which, i in out]), snap_radius)
+        counts = {k: v + self.last[k] for k, v in counts.items()}
+        for (which, i), (r, d, x) in zip(out, found):
+            if r < 0:
+                raise ValueError(f"query {i}: the {which} lies in no region"
+                                 + ("" if snap_radius is None else f", and no region is within {np.ravel(snap_radius)[0]:g} of it"))
+            snapped[i][which] = dict(original=side(which)[i].copy(), point=x, region=self.keys[r], distance=d)
+        again = self.regions_at(np.array([x for _, _, x in found]), eps, tol)
+        self.last = {k: v + self.last[k] for k, v in counts.items()}
+        for (which, i), (r, _, x), lst in zip(out, found, again):
+            if r not in lst.tolist():
+                raise RuntimeError(f"query {i}: the projected {which} is not found in its nearest region {self.keys[r]!r}")
+            side(which)[i] = x
+            regs[i if which == "start" else B + i] = lst
+        return snapped
+
     def _region_graph_on_device(self):
         """the scene's region graph is that of ``_pairs``: built on first use and after an edit, with the host's decisions in it when an
         LP left a pair undecided"""
@@ -232,17 +305,20 @@ class SceneQueries:
             raise ValueError(f"{which}_boxes: every half-width must exceed {self.MIN_HALF_WIDTH:g}: give a point as a point ({which}s)")
         return lo, hi
 
-    def _located(self, starts, goals, eps, tol, start_boxes=None, goal_boxes=None):
+    def _located(self, starts, goals, eps, tol, start_boxes=None, goal_boxes=None, outside="raise", snap_radius=None):
         """(S [B, n], G [B, n], the region lists of ``regions_at`` / ``regions_meeting`` for the starts, then the goals, (lo, hi) of the
-        start boxes or None, (lo, hi) of the goal boxes or None); S, G: the points, or the centres of the boxes.  A terminal that meets
-        no region raises"""
+        start boxes or None, (lo, hi) of the goal boxes or None); S, G: the points, or the centres of the boxes.
+        A terminal that meets no region raises -- with ``outside="snap"`` a point terminal is first replaced by its projection onto
+        its nearest region (``_snap``); ``snapped`` has one record dict(start=, goal=) per query of what was replaced"""
+        if outside not in ("raise", "snap"):
+            raise ValueError(f"outside must be 'raise' or 'snap', not {outside!r}")
         for which, pts, boxes in (("start", starts, start_boxes), ("goal", goals, goal_boxes)):
             if (pts is None) == (boxes is None):
                 raise ValueError(f"give exactly one of {which}s and {which}_boxes")
         sb = self._box_terminals(start_boxes, "start") if start_boxes is not None else None
         gb = self._box_terminals(goal_boxes, "goal") if goal_boxes is not None else None
-        S = np.ascontiguousarray(starts, float).reshape(-1, self.n) if sb is None else 0.5 * (sb[0] + sb[1])
-        G = np.ascontiguousarray(goals, float).reshape(-1, self.n) if gb is None else 0.5 * (gb[0] + gb[1])
+        S = np.array(starts, float).reshape(-1, self.n) if sb is None else 0.5 * (sb[0] + sb[1])      # (copies: a snap writes into them)
+        G = np.array(goals, float).reshape(-1, self.n) if gb is None else 0.5 * (gb[0] + gb[1])
         if len(S) != len(G):
             raise ValueError("one goal for every start")
         B = len(S)
@@ -255,6 +331,7 @@ class SceneQueries:
             counts = dict(self.last)
             regs = first + (self.regions_at(G, eps, tol) if gb is None else self.regions_meeting(*gb, tol))
             self.last = {k: v + counts[k] for k, v in self.last.items()}
+        self.snapped = self._snap(S, G, regs, eps, tol, snap_radius, sb, gb) if outside == "snap" else [dict(start=None, goal=None) for _ in range(B)]
         for i in range(B):
             for which, r in (("start", regs[i]), ("goal", regs[B + i])):
                 if len(r) == 0:
@@ -433,7 +510,7 @@ class SceneQueries:
         return out
 
     def graphs(self, starts=None, goals=None, eps: float = 1e-6, tol: float = 1e-9, assemble: str = "host", prune=None, restrict=None,
-               start_boxes=None, goal_boxes=None):
+               start_boxes=None, goal_boxes=None, outside: str = "raise", snap_radius=None):
         """One ``GcsGraph`` per query ``(starts[i], goals[i])``, keys ``['s', 't', *region keys]``: what ``graph_from_sets`` makes of the
         sets ``{'s': box of the start, 't': box of the goal, regions}`` -- the region edges shifted by two, both directions of every
         terminal-region hit, and both directions of s-t when the two boxes meet (the interval rule of ``graph.polytopes_overlap``), in
@@ -459,11 +536,18 @@ class SceneQueries:
         one is ``assemble="induced"`` (only with ``prune``): one ``induced_query_graphs`` call builds the induced subgraph of every query's
         kept set on the device, from the rows of its kept regions alone -- csrc/induced_graph_core.h --, where ``"host"`` masks and
         renumbers the whole region edge list per query; every field of every graph is the host path's.  ``"informed_sets"``: the same
-        with the set of ``informed_sets`` -- point or box terminals, in every mix, with ``assemble="host"`` or ``"induced"``."""
-        return self._graphs(starts, goals, eps, tol, assemble, prune, restrict, start_boxes, goal_boxes)[0]
+        with the set of ``informed_sets`` -- point or box terminals, in every mix, with ``assemble="host"`` or ``"induced"``.
 
-    def _graphs(self, starts, goals, eps, tol, assemble, prune, restrict, start_boxes=None, goal_boxes=None):
-        """(the graphs of ``graphs``, the records of ``informed`` or None)"""
+        ``outside``: ``"raise"`` (the default: a terminal in no region raises) or ``"snap"``: a POINT terminal whose ``regions_at`` list
+        is empty is replaced by its projection onto its nearest region (``nearest_regions``: all such points of the call in one
+        ``project`` call, then ``regions_at`` again for the replaced points alone, whose list must hold the nearest region), and the
+        graphs are those of the call with the replaced points, field for field: every later stage sees them and nothing else.
+        ``snap_radius``: the farthest a point may be moved (default: as far as the nearest region is); a point with no region within
+        it raises the ValueError.  Box terminals are untouched: a box that meets no region raises as before."""
+        return self._graphs(starts, goals, eps, tol, assemble, prune, restrict, start_boxes, goal_boxes, outside, snap_radius)[0]
+
+    def _graphs(self, starts, goals, eps, tol, assemble, prune, restrict, start_boxes=None, goal_boxes=None, outside="raise", snap_radius=None):
+        """(the graphs of ``graphs``, the records of ``informed`` or None); ``snapped`` has the records of what ``outside="snap"`` replaced"""
         if assemble not in ("host", "device", "induced"):
             raise ValueError(f"assemble must be 'host' or 'device', or 'induced' with prune, not {assemble!r}")
         if prune not in (None, "informed", "informed_sets"):
@@ -475,7 +559,7 @@ class SceneQueries:
         if prune == "informed" and (start_boxes is not None or goal_boxes is not None):
             raise ValueError("prune='informed' takes point terminals: its bound is measured from the start and goal points "
                              "(prune='informed_sets' measures from sets)")
-        S, G, regs, sb, gb = self._located(starts, goals, eps, tol, start_boxes, goal_boxes)
+        S, G, regs, sb, gb = self._located(starts, goals, eps, tol, start_boxes, goal_boxes, outside, snap_radius)
         B = len(S)
         if assemble == "device":
             return self._assemble_on_device(S, G, regs, eps, sb, gb), None
@@ -503,7 +587,7 @@ class SceneQueries:
 
     def solve(self, starts=None, goals=None, state_dtype: str = "f64", N: int = 5, M: int = 20, seeds=None, params=None, return_state: bool = False,
               walk: str = "host", assemble: str = "host", prune=None, restrict=None, large: bool = False, start_boxes=None, goal_boxes=None,
-              keep: bool = False, seed=None, **common):
+              keep: bool = False, seed=None, outside: str = "raise", snap_radius=None, **common):
         """Every query to its stop test in one ``BatchSolver`` (``params``: one dict per query, ``common``: parameters of all, as
         ``BatchSolver.solve``), then rounded by ``rounding_many`` (``N``, ``M``: as ``rounding``; ``seeds``: one per query, default 0).
         ``walk``: ``"host"`` (the default: the walks of ``rounding``, on a host copy of every query's activations) or ``"device"``
@@ -523,13 +607,18 @@ class SceneQueries:
         ``close()``.  ``seed``: one snapshot or None per query; a seeded query starts its loop from the snapshot's state, matched by
         region serial (what the snapshot lacks starts at zero), at the rho its parameters say, and stops in a fraction of the
         iterations when the query moved a little.  Both work with every ``assemble``, ``prune``, ``large``, ``walk`` and terminal
-        combination and across ``add_regions`` / ``remove_regions``.  Without them the call is what it always was."""
+        combination and across ``add_regions`` / ``remove_regions``.  Without them the call is what it always was.
+
+        ``outside``, ``snap_radius``: as ``graphs``.  Every record has ``"snapped"``: ``{"start": None, "goal": None}``, or for a
+        terminal that ``outside="snap"`` replaced ``dict(original=the point given, point=its projection, region=the key of its nearest
+        region, distance=how far it moved)``.  The segment from the original point to its projection lies outside the cover: it is
+        reported here and is no part of the path or of the cost."""
         from .batch import BatchSolver
         from .graph import sets_of_graph
         from .rounding import rounding_many, rounding_members, rounding_problem
         if walk not in ("host", "device"):
             raise ValueError(f"walk must be 'host' or 'device', not {walk!r}")
-        graphs, info = self._graphs(starts, goals, 1e-6, 1e-9, assemble, prune, restrict, start_boxes, goal_boxes)
+        graphs, info = self._graphs(starts, goals, 1e-6, 1e-9, assemble, prune, restrict, start_boxes, goal_boxes, outside, snap_radius)
         seeds = [0] * len(graphs) if seeds is None else list(seeds)
         if len(seeds) != len(graphs):
             raise ValueError("one seed per query")
@@ -568,5 +657,5 @@ class SceneQueries:
         for i, (rec, (cost, x_v, y_v)) in enumerate(zip(records, rounded)):
             if info is not None:
                 rec.update(informed_bound=info[i]["bound"], kept_regions=int(info[i]["keep"].sum()))
-            rec.update(rounded_cost=cost, x_v_rounded=x_v, y_v_rounded=y_v)
+            rec.update(rounded_cost=cost, x_v_rounded=x_v, y_v_rounded=y_v, snapped=self.snapped[i])
         return records

@@ -254,6 +254,26 @@ class DeviceScene:
         self._call("gcsadmm_scene_read_hits", hit_ptr.ctypes.data, hit_region.ctypes.data, hit_class.ctypes.data)
         return hit_ptr, hit_region, hit_class
 
+    def project(self, points, radius=None, max_iter: int = 100):
+        """The regions within ``radius[q]`` of each of ``points`` [Q, n] (default: every region) with the Euclidean projection of the
+        point onto each (``gcsadmm_scene_project_points``, csrc/point_project_core.h has the rule): for a point that may lie in no
+        region.  Returns ``(hit_ptr int64 [Q + 1], hit_region int32, hit_class uint8, distance [T], nearest [T, n], status int32 [T],
+        iterations int32 [T])``: the entries of point q are ``hit_ptr[q]:hit_ptr[q + 1]``, region indices ascending, class 1 (INSIDE:
+        the nearest point is the point itself, distance 0) or 2; status 0: solved and within the radius, 1: solved and beyond it, -1:
+        failed (``distance`` and ``nearest`` are then no projection).  The list takes the place of the one ``locate`` or
+        ``locate_boxes`` left.  Needs none of the other calls to have run and leaves their resident results as they are."""
+        pts = np.ascontiguousarray(points, float).reshape(-1, self.n)
+        Q = pts.shape[0]
+        rad = None if radius is None else np.ascontiguousarray(np.broadcast_to(np.asarray(radius, float), (Q,)))
+        num = C.c_int64(0)
+        self._call("gcsadmm_scene_project_points", Q, pts.ctypes.data, rad.ctypes.data if rad is not None else None, int(max_iter), C.addressof(num))
+        T = int(num.value)
+        hit_ptr = np.empty(Q + 1, np.int64); hit_region = np.empty(T, np.int32); hit_class = np.empty(T, np.uint8)
+        distance = np.empty(T); nearest = np.empty((T, self.n)); status = np.empty(T, np.int32); iterations = np.empty(T, np.int32)
+        self._call("gcsadmm_scene_read_hits", hit_ptr.ctypes.data, hit_region.ctypes.data, hit_class.ctypes.data)
+        self._call("gcsadmm_scene_read_projections", distance.ctypes.data, nearest.ctypes.data, status.ctypes.data, iterations.ctypes.data)
+        return hit_ptr, hit_region, hit_class, distance, nearest, status, iterations
+
     def regions(self):
         """The resident results per region as they are, no LP run (``gcsadmm_scene_read_regions``; after ``centers`` and ``bounds``):
         ``(centres [P, n], radii [P], LP status [P], lo [P, n], hi [P, n], LP status [P, 2n])``."""

@@ -504,6 +504,26 @@ int gcsadmm_scene_locate_boxes(gcsadmm_scene s, int num_boxes, const double *lo,
  * gcsadmm_scene_locate_points or gcsadmm_scene_locate_boxes call has produced a list: GCSADMM_ERR_BAD_ARG. */
 int gcsadmm_scene_read_hits(gcsadmm_scene s, int64_t *hit_ptr, int *hit_region, unsigned char *hit_class);
 
+/* The nearest regions of points that may lie in NO region (a state estimate just outside the cover, a goal beyond a wall): for every
+ * point the regions within radius[q] of it (null radius: +inf for every point), each with the Euclidean projection of the point onto it.
+ * csrc/point_project_core.h has the rule.  With the rows normalised (a^_i = a_i / |a_i|_2, b^_i = b_i / |a_i|_2), region r is a candidate
+ * of point p unless some row has a^_i.p - b^_i > radius (1 + 1e-9) + 2^-40 (sum_k |a^_ik p_k| + |b^_i|): the distance to one half-space
+ * never exceeds the distance to the region.  The candidates are the resident hit list (project_list_kernel, in the shape of
+ * locate_kernel: ordered by point, then region index, the same on every run); it replaces the list of an earlier locate call, and such a
+ * call replaces it.  gcsadmm_scene_read_hits returns it with hit_class 1 (INSIDE: no row is violated; the nearest point is p itself,
+ * the distance 0) or 2 (everything else).  project_solve_kernel then projects p onto every candidate, one lane per pair, by the dual
+ * active-set method of Goldfarb and Idnani (finite, exact up to rounding; at most max_iter steps), and gcsadmm_scene_read_projections
+ * returns per hit distance[T], nearest[T][n], iterations[T] and status[T]: 0 solved and distance <= radius; 1 solved, beyond the radius
+ * (the entry stays in the list); -1 failed (iteration limit, a non-finite value, no step available: distance and nearest are then not
+ * a projection -- decide such a pair on the host).  One pair's status never affects another's.  points[num_points][n] and
+ * radius[num_points] are host doubles.  Needs none of the other scene calls to have run and disturbs none of their resident results.
+ * A NaN or inf coordinate, a NaN or negative radius (+inf is allowed), a negative num_points, max_iter < 0 or null points:
+ * GCSADMM_ERR_BAD_ARG (a list made earlier stays); more than 2^31 - 1 candidates: GCSADMM_ERR_UNSUPPORTED, before the list is
+ * allocated.  num_points = 0 gives an empty list.  read_projections on a list that a locate call made, or before any list:
+ * GCSADMM_ERR_BAD_ARG. */
+int gcsadmm_scene_project_points(gcsadmm_scene s, int num_points, const double *points, const double *radius, int max_iter, int64_t *num_hits);
+int gcsadmm_scene_read_projections(gcsadmm_scene s, double *distance, double *nearest, int *status, int *iterations);
+
 /* Edits of a scene whose graph is decided (csrc/scene_edit_core.h has the contract): afterwards every resident result -- centres, radii,
  * boxes, statuses, the pair list with its flags and statuses -- is what the call order above gives on a scene created from the edited
  * list of regions, element for element and bit for bit, and restrict_paths and locate_points see the edited regions.  A hit list made
