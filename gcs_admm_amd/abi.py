@@ -133,6 +133,10 @@ PROTOTYPES = {
     # ... and the nearest regions of points that may lie in none (csrc/point_project_core.h)
     "gcsadmm_scene_project_points": ([_p, _i, _p, _p, _i, _p], _i),
     "gcsadmm_scene_read_projections": ([_p] * 5, _i),
+    # ... and the regions segments run through, with the cover test (csrc/segment_clip_core.h)
+    "gcsadmm_scene_clip_segments": ([_p, _i, _p, _p, _d, _p, _p], _i),
+    "gcsadmm_scene_read_spans": ([_p] * 3, _i),
+    "gcsadmm_scene_read_cover": ([_p] * 5, _i),
     # edits of a decided scene
     "gcsadmm_scene_add_regions": ([_p, _i, _p, _p, _p, _d, _d] + [_p] * 6, _i),
     "gcsadmm_scene_remove_regions": ([_p, _i, _p, _p], _i),

@@ -95,6 +95,11 @@ struct SceneHits {                                     // the hit list of the la
     bool projected = false;                            //   which kind of call made it: project_points (true) or a locate call
     DevBuf<double> distance, nearest;                  //   project_points: per hit the distance, the nearest point [n],
     DevBuf<int> status, iterations;                    //   the status and the iterations of its solve
+    bool clipped = false;                              //   ... or clip_segments (projected and clipped both false: a locate call)
+    DevBuf<double> t_in, t_out;                        //   clip_segments: per hit its span; per segment the cover status, the reach
+    DevBuf<int> cover, chain_len, chain;               //   and the length of its chain, written at the segment's offset in `chain`
+    DevBuf<double> reach;
+    std::vector<int> h_chain_len;                      //   (host: read with the counts, the chain offsets of read_cover come from it)
 };
 struct SceneGraph {                                    // region graph of the decided pairs (HAVE_GRAPH; query_graph_core.h): rows [P + 1],
     DevBuf<long long> row_ptr;
@@ -108,6 +113,7 @@ struct LocateScratch {                                 // locate_points / locate
     DevBuf<long long> offset;                          //   offsets per (point, chunk)
     DevBuf<double> radius;                             //   project_points: the radii [num_points] and the segments of the list
     DevBuf<long long> hit_ptr;                         //   [num_points + 1]
+    DevBuf<double> ends;                               //   clip_segments: the far ends of the segments [num_segments][n]
 };
 struct QueryScratch {                                  // query_graphs, kept and grown from call to call: the caller's arrays,
     DevBuf<long long> term_ptr, edge_off;
@@ -358,6 +364,32 @@ template <int N> int launch_project_solve(const ProjectSolveArgs &args)
         ProjectSolveArgs a = args;
         a.first = g0 * PROJECT_LANES;
         hipLaunchKernelGGL(project_solve_kernel<N>, dim3((unsigned)std::min(SLAB, groups - g0)), dim3(PROJECT_LANES), 0, 0, a);
+        LPCHK(hipGetLastError());
+    }
+    return GCSADMM_OK;
+}
+
+template <int N> int launch_clip(const ClipArgs &args, long long num_segments, bool fill)
+{
+    constexpr long long SLAB = 65535;      // grid.y
+    for (long long q0 = 0; q0 < num_segments; q0 += SLAB) {
+        ClipArgs a = args;
+        a.first_segment = (int)q0;
+        const dim3 grid((unsigned)a.chunks, (unsigned)std::min(SLAB, num_segments - q0));
+        if (fill) hipLaunchKernelGGL((segment_clip_kernel<N, true>), grid, dim3(LOCATE_WAVE), 0, 0, a);
+        else hipLaunchKernelGGL((segment_clip_kernel<N, false>), grid, dim3(LOCATE_WAVE), 0, 0, a);
+        LPCHK(hipGetLastError());
+    }
+    return GCSADMM_OK;
+}
+
+int launch_chain(const ChainArgs &args, long long num_segments)
+{
+    constexpr long long SLAB = 1LL << 30;      // workgroups of one launch (grid.x)
+    for (long long q0 = 0; q0 < num_segments; q0 += SLAB) {
+        ChainArgs a = args;
+        a.first_segment = q0;
+        hipLaunchKernelGGL(segment_chain_kernel, dim3((unsigned)std::min(SLAB, num_segments - q0)), dim3(LOCATE_WAVE), 0, 0, a);
         LPCHK(hipGetLastError());
     }
     return GCSADMM_OK;
@@ -799,6 +831,7 @@ int gcsadmm_scene_locate_points(gcsadmm_scene s, int num_points, const double *p
         LPCHK(hipStreamSynchronize(nullptr));
         s->hits.ptr.swap(hit_ptr);
         s->hits.projected = false;
+        s->hits.clipped = false;
         stage_finish(s->have, CALL_LOCATE_POINTS);
         if (num_hits) *num_hits = total;
         return GCSADMM_OK;
@@ -851,6 +884,7 @@ int gcsadmm_scene_locate_boxes(gcsadmm_scene s, int num_boxes, const double *lo,
         LPCHK(hipStreamSynchronize(nullptr));
         s->hits.ptr.swap(hit_ptr);
         s->hits.projected = false;
+        s->hits.clipped = false;
         stage_finish(s->have, CALL_LOCATE_POINTS);
         if (num_hits) *num_hits = total;
         return GCSADMM_OK;
@@ -926,6 +960,7 @@ int gcsadmm_scene_project_points(gcsadmm_scene s, int num_points, const double *
         LPCHK(hipStreamSynchronize(nullptr));
         h.ptr.swap(hit_ptr);
         h.projected = true;
+        h.clipped = false;
         stage_finish(s->have, CALL_LOCATE_POINTS);
         if (num_hits) *num_hits = total;
         return GCSADMM_OK;
@@ -941,6 +976,109 @@ int gcsadmm_scene_read_projections(gcsadmm_scene s, double *distance, double *ne
         const size_t total = (size_t)h.ptr.back();      // (the buffers may be longer: they are kept from call to call)
         LPCHK(to_host(distance, h.distance.get(), total)); LPCHK(to_host(nearest, h.nearest.get(), total * s->reg.n));
         LPCHK(to_host(status, h.status.get(), total)); LPCHK(to_host(iterations, h.iterations.get(), total));
+        return GCSADMM_OK;
+    });
+}
+
+// The regions every segment runs through with their spans, and the cover test (segment_clip_core.h): the hits as the resident hit list
+// (the stage rule of locate_points: it replaces the list of a locate or project call and is replaced by one), then one wavefront per
+// segment for its chain
+int gcsadmm_scene_clip_segments(gcsadmm_scene s, int num_segments, const double *from, const double *to, double tol, int64_t *num_hits,
+                                int64_t *num_chain)
+{
+    return scene_entry(s, [&]() -> int {
+        const SceneRegions &r = s->reg;
+        LocateScratch &lq = s->lq;
+        SceneHits &h = s->hits;
+        if (num_segments < 0 || (num_segments > 0 && (!from || !to))) { g_err = "negative number of segments or null end points"; return GCSADMM_ERR_BAD_ARG; }
+        if (!(tol >= 0.0) || std::isinf(tol)) { g_err = "tol must be finite and non-negative"; return GCSADMM_ERR_BAD_ARG; }
+        const size_t coords = (size_t)num_segments * r.n;
+        for (size_t i = 0; i < coords; ++i)
+            if (!std::isfinite(from[i]) || !std::isfinite(to[i])) { g_err = "segment with a NaN or an inf coordinate"; return GCSADMM_ERR_BAD_ARG; }
+        stage_start(s->have, CALL_LOCATE_POINTS);
+        const long long Q = num_segments, chunks = locate_chunks(r.P);
+        const size_t cells = (size_t)(Q * chunks);
+        std::vector<int> count(cells), chain_len((size_t)Q, 0);
+        std::vector<long long> offset(cells);
+        std::vector<int64_t> hit_ptr((size_t)Q + 1, 0);
+        ClipArgs a{};
+        a.R = LocateRegions{r.P, r.ptr.get(), r.A.get(), r.b.get()};
+        a.tol = tol;
+        a.chunks = chunks;
+        long long total = 0, links = 0;
+        if (cells > 0) {
+            LPCHK(lq.points.reserve(coords)); LPCHK(lq.ends.reserve(coords)); LPCHK(lq.count.reserve(cells));
+            LPCHK(to_device(lq.points.get(), from, coords)); LPCHK(to_device(lq.ends.get(), to, coords));
+            a.from = lq.points.get(); a.to = lq.ends.get(); a.count = lq.count.get();
+            LPRUN(for_dim(r.n, [&](auto N) { return launch_clip<decltype(N)::value>(a, Q, false); }));
+            LPCHK(to_host(count.data(), lq.count.get(), cells));
+            if (!locate_scan(count.data(), Q, chunks, offset.data(), hit_ptr.data())) {      // before the list is allocated
+                g_err = "more than 2^31 - 1 hits"; return GCSADMM_ERR_UNSUPPORTED;
+            }
+            total = hit_ptr[(size_t)Q];
+        }
+        if (Q > 0) {
+            const size_t T = (size_t)total;
+            LPCHK(h.region.reserve(T)); LPCHK(h.cls.reserve(T)); LPCHK(h.t_in.reserve(T)); LPCHK(h.t_out.reserve(T)); LPCHK(h.chain.reserve(T));
+            LPCHK(h.cover.reserve((size_t)Q)); LPCHK(h.reach.reserve((size_t)Q)); LPCHK(h.chain_len.reserve((size_t)Q));
+            LPCHK(lq.hit_ptr.reserve((size_t)Q + 1));
+            const std::vector<long long> segments(hit_ptr.begin(), hit_ptr.end());
+            LPCHK(to_device(lq.hit_ptr.get(), segments.data(), (size_t)Q + 1));
+            if (total > 0) {
+                LPCHK(lq.offset.reserve(cells));
+                LPCHK(to_device(lq.offset.get(), offset.data(), cells));
+                a.offset = lq.offset.get(); a.limit = total;
+                a.hit_region = h.region.get(); a.hit_class = h.cls.get(); a.hit_in = h.t_in.get(); a.hit_out = h.t_out.get();
+                LPRUN(for_dim(r.n, [&](auto N) { return launch_clip<decltype(N)::value>(a, Q, true); }));
+            }
+            ChainArgs c{};      // (a segment without hits: a gap at 0, written by its wavefront)
+            c.hit_ptr = lq.hit_ptr.get(); c.hit_in = h.t_in.get(); c.hit_out = h.t_out.get();
+            c.status = h.cover.get(); c.reach = h.reach.get(); c.chain_len = h.chain_len.get(); c.chain_hit = h.chain.get();
+            LPRUN(launch_chain(c, Q));
+            LPCHK(to_host(chain_len.data(), h.chain_len.get(), (size_t)Q));
+            for (int len : chain_len) links += len;
+        }
+        LPCHK(hipStreamSynchronize(nullptr));
+        h.ptr.swap(hit_ptr);
+        h.h_chain_len.swap(chain_len);
+        h.projected = false;
+        h.clipped = true;
+        stage_finish(s->have, CALL_LOCATE_POINTS);
+        if (num_hits) *num_hits = total;
+        if (num_chain) *num_chain = links;
+        return GCSADMM_OK;
+    });
+}
+
+int gcsadmm_scene_read_spans(gcsadmm_scene s, double *t_in, double *t_out)
+{
+    return scene_entry(s, [&]() -> int {
+        NEED(s, CALL_READ_HITS);
+        const SceneHits &h = s->hits;
+        if (!h.clipped) { g_err = "the resident hit list is not a clip call's: call gcsadmm_scene_clip_segments first"; return GCSADMM_ERR_BAD_ARG; }
+        const size_t total = (size_t)h.ptr.back();      // (the buffers may be longer: they are kept from call to call)
+        LPCHK(to_host(t_in, h.t_in.get(), total)); LPCHK(to_host(t_out, h.t_out.get(), total));
+        return GCSADMM_OK;
+    });
+}
+
+int gcsadmm_scene_read_cover(gcsadmm_scene s, int *status, double *reach, int64_t *chain_ptr, int *chain_hit)
+{
+    return scene_entry(s, [&]() -> int {
+        NEED(s, CALL_READ_HITS);
+        const SceneHits &h = s->hits;
+        if (!h.clipped) { g_err = "the resident hit list is not a clip call's: call gcsadmm_scene_clip_segments first"; return GCSADMM_ERR_BAD_ARG; }
+        const size_t Q = h.ptr.size() - 1, total = (size_t)h.ptr.back();
+        LPCHK(to_host(status, h.cover.get(), Q)); LPCHK(to_host(reach, h.reach.get(), Q));
+        std::vector<int> chain(total);      // every chain at its segment's offset in the list: packed here, segment by segment
+        LPCHK(to_host(chain.data(), h.chain.get(), total));
+        int64_t at = 0;
+        for (size_t q = 0; q < Q; ++q) {
+            if (chain_ptr) chain_ptr[q] = at;
+            if (chain_hit) std::copy_n(chain.begin() + h.ptr[q], h.h_chain_len[q], chain_hit + at);
+            at += h.h_chain_len[q];
+        }
+        if (chain_ptr) chain_ptr[Q] = at;
         return GCSADMM_OK;
     });
 }

@@ -8,6 +8,7 @@
 #include "point_locate_core.h"
 #include "box_locate_core.h"
 #include "point_project_core.h"
+#include "segment_clip_core.h"
 #include "scene_edit_core.h"
 #include "query_graph_core.h"
 #include "induced_graph_core.h"
@@ -328,6 +329,94 @@ __global__ __launch_bounds__(PROJECT_LANES) void project_solve_kernel(ProjectSol
 {
     const long long t = a.first + (long long)blockIdx.x * PROJECT_LANES + threadIdx.x;
     if (t < a.total) project_entry<N>(a.R, a.points, a.radius, a.hit_ptr, a.num_points, a.hit_region, a.max_iter, t, a.out);
+}
+
+// ---- the regions a segment runs through, and whether they cover it (segment_clip_core.h) ----
+struct ClipArgs {
+    LocateRegions R;
+    const double *from, *to;   // [num_segments][N] each
+    double tol;
+    int first_segment;         // blockIdx.y counts from here (one launch takes at most 65 535 segments)
+    long long chunks, limit;   // chunks of the P regions; length of the list
+    int *count;                // [num_segments][chunks]
+    const long long *offset;   // [num_segments][chunks]
+    int *hit_region;
+    unsigned char *hit_class;
+    double *hit_in, *hit_out;  // the span of every hit
+};
+
+// locate_kernel's shape with a segment in the place of the point: one 64-lane workgroup per (chunk of regions, segment), one region per
+// lane, a count pass (FILL = false) and a fill pass that runs the same tests again and writes the hits and their spans from
+// offset[segment][chunk] on
+template <int N, bool FILL>
+__global__ __launch_bounds__(LOCATE_WAVE) void segment_clip_kernel(ClipArgs a)
+{
+    const long long chunk = blockIdx.x, q = (long long)a.first_segment + blockIdx.y;
+    const int lane = threadIdx.x;
+    double p[N], e[N], d[N];
+#pragma unroll
+    for (int k = 0; k < N; ++k) {      // the same addresses in every lane
+        p[k] = a.from[(size_t)q * N + k];
+        e[k] = a.to[(size_t)q * N + k];
+    }
+    clip_direction<N>(p, e, d);
+    const size_t cell = (size_t)(q * a.chunks + chunk);
+    long long pos = FILL ? a.offset[cell] : 0;
+    int total = 0;
+    for (int stride = 0; stride < LOCATE_CHUNK / LOCATE_WAVE; ++stride) {
+        const int region = locate_region(a.R.P, chunk, stride, lane);
+        double t_in = 0.0, t_out = 0.0;
+        const int cls = clip_lane<N>(a.R, region, p, d, a.tol, &t_in, &t_out);
+        const unsigned long long mask = __ballot(cls != CLIP_OUT);
+        if (FILL) {
+            clip_store(a.hit_region, a.hit_class, a.hit_in, a.hit_out, pos, a.limit, mask, lane, region, cls, t_in, t_out);
+            pos += locate_hits(mask);
+        } else {
+            total += locate_hits(mask);
+        }
+    }
+    if (!FILL && lane == 0) a.count[cell] = total;
+}
+
+struct ChainArgs {
+    const long long *hit_ptr;      // [num_segments + 1]
+    const double *hit_in, *hit_out;
+    long long first_segment;       // blockIdx.x counts from here
+    int *status;                   // [num_segments] COVER_COVERED / COVER_GAP
+    double *reach;                 // [num_segments]
+    int *chain_len;                // [num_segments]
+    int *chain_hit;                // [length of the list]: the chain of segment q from hit_ptr[q] on, as positions in the list
+};
+
+// the cover test: one 64-lane wavefront per segment.  A step is chain_lane_best over the hits lane, lane + 64, ... and one butterfly of
+// shuffles on (t_out, position), after which every lane holds the same best: no LDS, no barrier, no atomics.  The span at position
+// `lane` stays in two registers across the steps
+__global__ __launch_bounds__(LOCATE_WAVE) void segment_chain_kernel(ChainArgs a)
+{
+    const long long q = a.first_segment + blockIdx.x;
+    const int lane = threadIdx.x;
+    const long long first = a.hit_ptr[q];
+    const int count = (int)(a.hit_ptr[q + 1] - first);
+    const double *t_in = a.hit_in + first, *t_out = a.hit_out + first;
+    const double first_in = lane < count ? t_in[lane] : 0.0, first_out = lane < count ? t_out[lane] : 0.0;
+    double cur = 0.0;
+    int len = 0, status = COVER_COVERED;
+    while (cur < 1.0) {
+        double best_out;
+        int best_pos;
+        chain_lane_best(t_in, t_out, count, lane, first_in, first_out, cur, &best_out, &best_pos);
+#pragma unroll
+        for (int off = LOCATE_WAVE / 2; off > 0; off >>= 1) {
+            const double other_out = __shfl_xor(best_out, off);
+            const int other_pos = __shfl_xor(best_pos, off);
+            if (chain_better(other_out, other_pos, best_out, best_pos)) { best_out = other_out; best_pos = other_pos; }
+        }
+        if (best_pos == CHAIN_NONE || len >= count) { status = COVER_GAP; break; }      // (len < count always: a hit is taken once)
+        if (lane == 0) a.chain_hit[first + len] = (int)(first + best_pos);
+        ++len;
+        cur = best_out;
+    }
+    if (lane == 0) { a.status[q] = status; a.reach[q] = cur; a.chain_len[q] = len; }
 }
 
 // ---- edits of a decided scene (scene_edit_core.h) ----

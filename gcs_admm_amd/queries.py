@@ -20,9 +20,42 @@ import numpy as np
 
 from .graph import GcsGraph, _finish_graph, convert_pt_to_polytope, polytopes_overlap
 
-__all__ = ["SceneQueries"]
+__all__ = ["SceneQueries", "rounded_path", "rounded_polyline"]
 
 IN, UNDECIDED = 1, 2      # hit classes of gcsadmm_scene_locate_points
+
+
+def rounded_path(record):
+    """The vertex keys of the rounded path of a ``SceneQueries.solve`` record, from ``'s'`` to ``'t'``.  A vertex of the rounded path
+    holds one segment of it (``x_v_rounded[v]``: its two end points); the walk goes over the record's graph along the vertices with
+    ``y_v_rounded == 1``, at each step to the successor whose first point is the current vertex's second point.  ValueError: the
+    record has no rounded path."""
+    g, xs, ys = record["graph"], record.get("x_v_rounded"), record.get("y_v_rounded")
+    if xs is None or ys is None:
+        raise ValueError("the record has no rounded path")
+    n, keys = g.n, g.keys
+    cur = keys[g.src]
+    if not ys.get(cur) or not ys.get(keys[g.dst]):
+        raise ValueError("the record has no rounded path")
+    path = [cur]
+    while cur != keys[g.dst]:
+        heads = [keys[h] for h in g.edge_head[g.edge_tail == keys.index(cur)]]
+        nxt = [w for w in heads if ys.get(w) and w not in path and np.array_equal(xs[w][:n], xs[cur][n:])]
+        if not nxt:
+            raise ValueError(f"the rounded path ends at {cur!r}")
+        cur = nxt[0]
+        path.append(cur)
+    return path
+
+
+def rounded_polyline(record):
+    """The points q_0 .. q_k of the rounded path of a ``SceneQueries.solve`` record (``rounded_path``: the first point of ``'s'``, then
+    the second point of every vertex), as ``SceneQueries.path_cover`` takes them.  Consecutive equal points are dropped."""
+    xs, n = record["x_v_rounded"], record["graph"].n
+    path = rounded_path(record)
+    points = [np.asarray(xs[path[0]][:n], float)] + [np.asarray(xs[v][n:], float) for v in path]
+    keep = [0] + [i for i in range(1, len(points)) if not np.array_equal(points[i], points[i - 1])]
+    return np.array([points[i] for i in keep])
 
 
 class SceneQueries:
@@ -242,6 +275,43 @@ class SceneQueries:
                 continue
             t = seg[np.argmin(distance[seg])]      # (region indices ascend: the first of equals is the lowest)
             out.append((int(hit_region[t]), float(distance[t]), nearest[t].copy()))
+        return out
+
+    def path_cover(self, paths, tol: float = 1e-9):
+        """Is each of ``paths`` -- polylines ``[k + 1, n]`` -- inside the union of the resident regions, and through which regions does it
+        run?  All segments of all paths go into one ``clip_segments`` call (csrc/segment_clip_core.h: per segment the spans of the
+        regions it meets, inflated by ``tol``, and the shortest chain of them that covers it).  Per path a dict: ``covered``; ``gap``:
+        None, or for the first segment that is not covered ``dict(segment=j, t=reach, point=p + reach d)``, the first parameter no region
+        holds; ``corridor``: the region keys of the chains of its segments in order, consecutive repeats merged (the form
+        ``DeviceScene.restrict_paths`` takes); ``breaks``: the points ``x(t_out)`` at which the corridor passes from one region to the
+        next; ``adjacent``: whether every consecutive pair of the corridor is an edge of the resident region graph -- informative: two
+        regions that touch only within the inflation can share a break without being an edge."""
+        if self.scene is None:
+            raise RuntimeError("the scene is closed")
+        lines = [np.ascontiguousarray(p, float).reshape(-1, self.n) for p in paths]
+        if any(len(p) < 2 for p in lines):
+            raise ValueError("a polyline has at least two points")
+        start = np.concatenate([p[:-1] for p in lines]) if lines else np.zeros((0, self.n))
+        end = np.concatenate([p[1:] for p in lines]) if lines else np.zeros((0, self.n))
+        _, hit_region, _, _, t_out, status, reach, chain_ptr, chain_hit = self.scene.clip_segments(start, end, tol)
+        edges = set(zip(np.asarray(self.edge_tail).tolist(), np.asarray(self.edge_head).tolist()))
+        out, q = [], 0
+        for line in lines:
+            corridor, breaks, gap, last = [], [], None, None
+            for j in range(len(line) - 1):
+                d = end[q] - start[q]
+                for c in chain_hit[chain_ptr[q]:chain_ptr[q + 1]]:
+                    r = int(hit_region[c])
+                    if not corridor or corridor[-1] != r:
+                        if corridor:
+                            breaks.append(last)
+                        corridor.append(r)
+                    last = start[q] + t_out[c] * d
+                if status[q] != 0 and gap is None:
+                    gap = dict(segment=j, t=float(reach[q]), point=start[q] + reach[q] * d)
+                q += 1
+            out.append(dict(covered=gap is None, gap=gap, corridor=[self.keys[r] for r in corridor], breaks=breaks,
+                            adjacent=all((a, b) in edges or (b, a) in edges for a, b in zip(corridor, corridor[1:]))))
         return out
 
     def _project_on_host(self, r, p):

@@ -274,6 +274,32 @@ class DeviceScene:
         self._call("gcsadmm_scene_read_projections", distance.ctypes.data, nearest.ctypes.data, status.ctypes.data, iterations.ctypes.data)
         return hit_ptr, hit_region, hit_class, distance, nearest, status, iterations
 
+    def clip_segments(self, start, end, tol: float = 1e-9):
+        """The regions each segment ``start[q] + t (end[q] - start[q])``, t in [0, 1], runs through, and whether they cover it
+        (``gcsadmm_scene_clip_segments``, csrc/segment_clip_core.h has the rule).  Returns ``(hit_ptr int64 [Q + 1], hit_region int32,
+        hit_class uint8, t_in [T], t_out [T], status int32 [Q], reach [Q], chain_ptr int64 [Q + 1], chain_hit int32)``: the hits of
+        segment q are ``hit_ptr[q]:hit_ptr[q + 1]``, region indices ascending, each with the span ``[t_in, t_out]`` of the parameters at
+        which the segment lies in the region inflated by ``tol``, class 1 (WHOLE: the span is [0, 1]) or 2 (PART); status 0 (COVERED,
+        ``reach == 1.0``) or 1 (GAP: no hit holds ``t = reach``); ``chain_hit[chain_ptr[q]:chain_ptr[q + 1]]`` are the positions in the
+        hit list of the shortest sequence of hits that covers the segment up to ``reach``.  The list takes the place of the one
+        ``locate``, ``locate_boxes`` or ``project`` left.  Needs none of the other calls to have run and leaves their resident results
+        as they are."""
+        p = np.ascontiguousarray(start, float).reshape(-1, self.n)
+        q = np.ascontiguousarray(end, float).reshape(-1, self.n)
+        if p.shape != q.shape:
+            raise ValueError("one end for every start")
+        Q = p.shape[0]
+        num, links = C.c_int64(0), C.c_int64(0)
+        self._call("gcsadmm_scene_clip_segments", Q, p.ctypes.data, q.ctypes.data, float(tol), C.addressof(num), C.addressof(links))
+        T = int(num.value)
+        hit_ptr = np.empty(Q + 1, np.int64); hit_region = np.empty(T, np.int32); hit_class = np.empty(T, np.uint8)
+        t_in = np.empty(T); t_out = np.empty(T); status = np.empty(Q, np.int32); reach = np.empty(Q)
+        chain_ptr = np.empty(Q + 1, np.int64); chain_hit = np.empty(int(links.value), np.int32)
+        self._call("gcsadmm_scene_read_hits", hit_ptr.ctypes.data, hit_region.ctypes.data, hit_class.ctypes.data)
+        self._call("gcsadmm_scene_read_spans", t_in.ctypes.data, t_out.ctypes.data)
+        self._call("gcsadmm_scene_read_cover", status.ctypes.data, reach.ctypes.data, chain_ptr.ctypes.data, chain_hit.ctypes.data)
+        return hit_ptr, hit_region, hit_class, t_in, t_out, status, reach, chain_ptr, chain_hit
+
     def regions(self):
         """The resident results per region as they are, no LP run (``gcsadmm_scene_read_regions``; after ``centers`` and ``bounds``):
         ``(centres [P, n], radii [P], LP status [P], lo [P, n], hi [P, n], LP status [P, 2n])``."""

@@ -524,6 +524,28 @@ int gcsadmm_scene_read_hits(gcsadmm_scene s, int64_t *hit_ptr, int *hit_region, 
 int gcsadmm_scene_project_points(gcsadmm_scene s, int num_points, const double *points, const double *radius, int max_iter, int64_t *num_hits);
 int gcsadmm_scene_read_projections(gcsadmm_scene s, double *distance, double *nearest, int *status, int *iterations);
 
+/* Through which regions segments run, and whether the regions cover them: is a path still inside the free space after an edit, and
+ * which corridor of regions does it take?  Segment q is x(t) = from[q] + t (to[q] - from[q]), t in [0, 1].  csrc/segment_clip_core.h has
+ * the rule: per (segment, region) pair the span [t_in, t_out] of the parameters at which the segment lies in the region, every row
+ * a_i x <= b_i relaxed by tol sum_k |a_ik| (>= tol |a_i|_2) plus an allowance of 2^-40 (|b_i| + sum_k |a_ik| (|p_k| + |d_k|)) for the rounding
+ * of the rule itself; the header derives between which two exact spans every reported span lies.  A pair with a non-empty span is a hit.
+ * The hits are the resident hit list (segment_clip_kernel, in the shape of locate_kernel: ordered by segment, then region index, the
+ * same on every run); it replaces the list of an earlier locate or project call, and such a call replaces it.  gcsadmm_scene_read_hits
+ * returns it with hit_class 1 (WHOLE: t_in == 0 and t_out == 1) or 2 (PART), gcsadmm_scene_read_spans t_in[T] and t_out[T].
+ * segment_chain_kernel then sweeps every segment from t = 0: among the hits with t_in <= t < t_out it takes the one of largest t_out
+ * (the first in the list among equals) and goes on from there.  gcsadmm_scene_read_cover returns per segment status[q] 0 (COVERED:
+ * reach[q] == 1.0 exactly) or 1 (GAP: no hit holds reach[q]) and the chain, the hits taken in order, as positions in the hit list:
+ * chain_hit[chain_ptr[q] .. chain_ptr[q + 1]), num_chain entries in all -- the shortest sequence of regions that covers the segment.
+ * from[num_segments][n] and to[num_segments][n] are host doubles; a segment with from == to is a point.  Needs none of the other scene
+ * calls to have run and disturbs none of their resident results.  A NaN or inf coordinate, a negative num_segments, tol < 0 (or NaN or
+ * inf) or a null from / to: GCSADMM_ERR_BAD_ARG (a list made earlier stays); more than 2^31 - 1 hits: GCSADMM_ERR_UNSUPPORTED, before
+ * the list is allocated.  num_segments = 0 gives empty lists.  read_spans and read_cover on a list that another kind of call made, or
+ * before any list, and read_projections on a clip list: GCSADMM_ERR_BAD_ARG. */
+int gcsadmm_scene_clip_segments(gcsadmm_scene s, int num_segments, const double *from, const double *to, double tol, int64_t *num_hits,
+                                int64_t *num_chain);
+int gcsadmm_scene_read_spans(gcsadmm_scene s, double *t_in, double *t_out);
+int gcsadmm_scene_read_cover(gcsadmm_scene s, int *status, double *reach, int64_t *chain_ptr, int *chain_hit);
+
 /* Edits of a scene whose graph is decided (csrc/scene_edit_core.h has the contract): afterwards every resident result -- centres, radii,
  * boxes, statuses, the pair list with its flags and statuses -- is what the call order above gives on a scene created from the edited
  * list of regions, element for element and bit for bit, and restrict_paths and locate_points see the edited regions.  A hit list made
